@@ -6,13 +6,21 @@ One step = scene.render(material, res, spp, seed=random) followed by I.sum().bac
 (2 * W * H * spp per step), inputs resident in HBM.
 
   --gpus 1 (default)  BASELINE configs[2]: cbox, path integrator, 512x512, spp 256, textures cboxd/cboxr — the headline
-                      line — and, in the same JSON line under "configs", the other configurations that fit one GPU, each
-                      timed the same way on its own scene: c2 (direct 512^2 spp 64), c4_one_gpu (path 1024^2 spp 1024, the
-                      8-GPU workload on one GPU) and c5 (1,004,672-triangle tessellated cbox, path 1024^2 spp 256)
   --gpus N > 1        BASELINE configs[3]: cbox path 1024x1024 spp 1024, ONE render pixel-tiled over the N ranks
                       (8x8 tiles dealt round-robin, one launch per rank and pass) and one RCCL all_reduce of the image
                       and of the gradient per step: fixed total work, "scaling": "strong"
   --config c5         BASELINE configs[4] as the headline, on 1 or N GPUs (tiled like c4)
+  --full              everything beyond the headline, in the same JSON line: HIP-event times of the forward and backward
+                      calls, path statistics and roofline, counter and FD figures from profiles/, per-rank and all-reduce
+                      times and the shard union check (N > 1), the CPU baseline (1 GPU) and, for the c3 headline, the
+                      other configurations that fit one GPU, each timed the same way on its own scene under "configs":
+                      c2 (direct 512^2 spp 64), c4_one_gpu (path 1024^2 spp 1024, the 8-GPU workload on one GPU) and
+                      c5 (1,004,672-triangle tessellated cbox, path 1024^2 spp 256).  A plain run sets up, warms up,
+                      times --steps steps and prints the headline line only.
+  --dump-outputs DIR  after the timed steps: what the last timed step returned to its caller, DIR/image.npy (H, W, 4)
+                      and DIR/material_grad.npy (the material's gradient), float32.  Step seeds are a fixed sequence, so
+                      the same arguments give the same inputs in every run.  Above DUMP_BYTES in all, each array is
+                      replaced by a fixed, seeded sample of its flattened elements (in index order).
 
 Launch: `python bench.py --gpus N ...` starts its N ranks itself (torch.distributed.run as a child process; the parent
 never loads torch or touches a GPU); under torchrun (WORLD_SIZE set) it is one of the ranks.
@@ -33,6 +41,21 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 NAMES = {"c2": "cbox direct", "c3": "cbox path", "c4": "cbox path", "c5": "1,004,672-triangle tessellated cbox, path"}
+DUMP_BYTES = 60 << 20          # --dump-outputs stays under 64 MB with the .npy headers
+
+
+def dump_outputs(path, arrays):
+    """Writes each tensor of `arrays` as path/<name>.npy in float32; above DUMP_BYTES in all, a fixed, seeded sample of each
+    (a share of DUMP_BYTES in proportion to its size, flattened elements in index order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    for i, (name, t) in enumerate(arrays.items()):
+        a = t.detach().float().cpu().numpy()
+        if total > DUMP_BYTES:
+            k = a.size * DUMP_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(i).choice(a.size, k, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def parse_args():
@@ -44,8 +67,10 @@ def parse_args():
     ap.add_argument("--res", type=int, default=0, help="override the configuration's resolution")
     ap.add_argument("--spp", type=int, default=0, help="override the configuration's samples per pixel")
     ap.add_argument("--shard", default="tiles", choices=["tiles", "rows", "samples", "seeds"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="headline line only (skip the c2 / c4_one_gpu / c5 legs of the default run)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's image and material gradient as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra-configs", action="store_true", help="with --full: skip the c2 / c4_one_gpu / c5 legs")
     ap.add_argument("--cpu-spp", type=int, default=16)
     return ap.parse_args()
 
@@ -199,16 +224,19 @@ def shard_union_check(scene, renderer, material, rank, world, W=256, spp=16, see
 
 
 class Leg:
-    """One timed workload: `steps` steps of render + backward on one scene, HIP events around the native calls."""
+    """One timed workload: `steps` steps of render + backward on one scene; with `events`, HIP events around the native calls."""
 
-    def __init__(self, scene, material, W, spp, renderer=None, world=1):
+    def __init__(self, scene, material, W, spp, renderer=None, world=1, events=True):
         import torch
         self.torch, self.scene, self.material, self.W, self.spp, self.renderer, self.world = torch, scene, material, W, spp, renderer, world
         self.ev = {"fwd": [], "bwd": []}
         self.timing = False
         self.seeds = random.Random(0)
-        scene.render_forward = self._timed("fwd", scene.render_forward)
-        scene.render_backward = self._timed("bwd", scene.render_backward)
+        self.img = None                                         # the image the last step returned
+        self.events = events
+        if events:
+            scene.render_forward = self._timed("fwd", scene.render_forward)
+            scene.render_backward = self._timed("bwd", scene.render_backward)
 
     def _timed(self, name, fn):
         # HIP events directly around the native calls, on the stream the kernels are enqueued on (torch's current one)
@@ -227,6 +255,7 @@ class Leg:
         res = (self.W, self.W)
         img = self.renderer.render(self.material, res=res, spp=self.spp, seed=seed) if self.world > 1 else self.scene.render(self.material, res=res, spp=self.spp, seed=seed)
         img.sum().backward()
+        self.img = img.detach()
 
     def run(self, steps, warmup):
         import torch.distributed as dist
@@ -236,7 +265,7 @@ class Leg:
         if self.world > 1: dist.barrier()
         torch.cuda.synchronize()
         self.timing = True
-        if self.renderer is not None: self.renderer.reduce_events = []
+        if self.renderer is not None and self.events: self.renderer.reduce_events = []
         t0 = time.perf_counter()
         for _ in range(steps):
             self.step()
@@ -370,8 +399,8 @@ def main():
     mat_np = scenes.cbox_material_np()
     material = torch.from_numpy(mat_np).to(dev).requires_grad_()
     renderer = zd.attach(scene, mode=args.shard)
-    union = shard_union_check(scene, renderer, material, rank, world) if (world > 1 and integrator == "path" and args.shard != "seeds") else None
-    leg = Leg(scene, material, W, spp, renderer, world)
+    union = shard_union_check(scene, renderer, material, rank, world) if (args.full and world > 1 and integrator == "path" and args.shard != "seeds") else None
+    leg = Leg(scene, material, W, spp, renderer, world, events=args.full)
     dt_rank = leg.run(args.steps, args.warmup)
     dt = dt_rank
     per_rank = None
@@ -379,22 +408,22 @@ def main():
         t = torch.tensor([dt_rank], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        # outside the timed region: what every rank measured, so that a shortfall can be attributed to imbalance
-        # (kernel time differs between ranks) or to communication (all-reduce time)
-        red = renderer.reduce_ms()
-        mine = torch.tensor([dt_rank / args.steps * 1e3, leg.fwd_ms, leg.bwd_ms, red["image"] / args.steps, red["gradient"] / args.steps], dtype=torch.float64, device=dev)
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        per_rank = torch.stack(allr).cpu().numpy()
+        if args.full:
+            # outside the timed region: what every rank measured, so that a shortfall can be attributed to imbalance
+            # (kernel time differs between ranks) or to communication (all-reduce time)
+            red = renderer.reduce_ms()
+            mine = torch.tensor([dt_rank / args.steps * 1e3, leg.fwd_ms, leg.bwd_ms, red["image"] / args.steps, red["gradient"] / args.steps], dtype=torch.float64, device=dev)
+            allr = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(allr, mine)
+            per_rank = torch.stack(allr).cpu().numpy()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"image": leg.img, "material_grad": material.grad})
 
     n_per_pass = W * W * spp                                # camera samples of one whole pass (all ranks together)
     weak = world > 1 and args.shard == "seeds"
 
     if rank == 0:
-        stats = leg.stats(zd.plan(args.shard, 0, world, (W, W), spp, 0))
         accel = scene.info()["accel"]
-        roof, ps, n_rank = leg.roofline(stats, integrator, accel)
-        roof = pmc_fields(roof, "k_path_bwd", cfg, stats, (world, integrator) == (1, "path") and not (args.res or args.spp))
         out = {
             "metric": "Msamples/s fwd+PRB-bwd" + (", cbox 512x512 spp=256" if (cfg, W, spp) == ("c3", 512, 256) else f", {NAMES[cfg]} {W}x{W} spp={spp}"),
             "value": round(2 * n_per_pass * args.steps * (world if weak else 1) / dt / 1e6, 2),
@@ -403,42 +432,48 @@ def main():
             "vs_baseline": None, "dtype": "f32", "data": "synthetic (random seeds; cbox geometry + cboxd/cboxr textures" + ("; instance 0 tessellated and displaced, seed 0)" if cfg == "c5" else ")"),
             "config": {"workload": f"{NAMES[cfg]} integrator {W}x{W} spp={spp}, forward + PRB backward w.r.t. the 1024x1024x4 material (BASELINE configs[{cfg_index}])",
                        "sampler": "cmj", "shard": args.shard if world > 1 else "none", "accel": accel,
-                       "rccl_ranks": dist.get_world_size() if world > 1 else 1, "backend": dist.get_backend() if world > 1 else "none",
-                       "launches_per_step_per_rank": leg.launches},
-            "fwd_msamples_s": round(n_rank / (leg.fwd_ms * 1e-3) / 1e6, 2), "bwd_msamples_s": round(n_rank / (leg.bwd_ms * 1e-3) / 1e6, 2),
-            "fwd_ms": round(leg.fwd_ms, 3), "bwd_ms": round(leg.bwd_ms, 3),
-            "per_rank_note": "fwd/bwd figures are rank 0's kernels on its share of the pass (HIP events around the native calls)" if world > 1 else "HIP events around the native calls",
-            "path_stats": ps, "roofline": roof,
+                       "rccl_ranks": dist.get_world_size() if world > 1 else 1, "backend": dist.get_backend() if world > 1 else "none"},
         }
-        if per_rank is not None:
-            col = lambda i: {"min": round(float(per_rank[:, i].min()), 3), "max": round(float(per_rank[:, i].max()), 3)}
-            out["per_rank_ms"] = {"step": col(0), "fwd_kernels": col(1), "bwd_kernels": col(2),
-                                  "note": "per step; step = wall clock of the timed loop / steps on each rank, kernels = HIP events around the native calls"}
-            out["allreduce_ms"] = {"image": col(3), "gradient": col(4), "bytes": {"image": W * W * 16, "gradient": int(material.numel()) * 4},
-                                   "note": "per step, HIP events on the compute stream around torch.distributed.all_reduce (includes waiting for the slowest rank)"}
-        if union is not None:
-            out["shard_union_check"] = union
-        fd = fd_summary()
-        if fd: out["grad_rel_err_vs_fd"] = fd
-        if world == 1 and cfg == "c3" and not (args.res or args.spp) and not args.no_extra_configs:
-            # the other single-GPU BASELINE configurations, each on its own scene with its own statistics (c5: BVH built once, 2 steps)
-            scene.render_forward = scene.render_backward = None
-            del leg, renderer, scene
-            gc.collect()
-            torch.cuda.empty_cache()
-            out["configs"] = {}
-            for name, key, steps, warm in (("c2", "c2", 10, 2), ("c4_one_gpu", "c4", 2, 1), ("c5", "c5", 2, 1)):
-                try:                                            # a leg that fails is reported as such; the headline above stands on its own
-                    out["configs"][name] = extra_config(name, key, dev, mat_np, steps, warm)
-                except Exception as e:                          # noqa: BLE001
-                    out["configs"][name] = {"error": f"{type(e).__name__}: {e}"}
-            scene = scenes.make_scene(integrator)
-        if world == 1 and not args.no_cpu_baseline:
-            # only now is the CPU oracle loaded — after every timed region
-            try:
-                out["cpu_baseline"] = cpu_baseline(scene, mat_np, min(W, 512), args.cpu_spp)
-            except Exception as e:                              # noqa: BLE001
-                out["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
+        if args.full:
+            stats = leg.stats(zd.plan(args.shard, 0, world, (W, W), spp, 0))
+            roof, ps, n_rank = leg.roofline(stats, integrator, accel)
+            roof = pmc_fields(roof, "k_path_bwd", cfg, stats, (world, integrator) == (1, "path") and not (args.res or args.spp))
+            out["config"]["launches_per_step_per_rank"] = leg.launches
+            out.update({
+                "fwd_msamples_s": round(n_rank / (leg.fwd_ms * 1e-3) / 1e6, 2), "bwd_msamples_s": round(n_rank / (leg.bwd_ms * 1e-3) / 1e6, 2),
+                "fwd_ms": round(leg.fwd_ms, 3), "bwd_ms": round(leg.bwd_ms, 3),
+                "per_rank_note": "fwd/bwd figures are rank 0's kernels on its share of the pass (HIP events around the native calls)" if world > 1 else "HIP events around the native calls",
+                "path_stats": ps, "roofline": roof,
+            })
+            if per_rank is not None:
+                col = lambda i: {"min": round(float(per_rank[:, i].min()), 3), "max": round(float(per_rank[:, i].max()), 3)}
+                out["per_rank_ms"] = {"step": col(0), "fwd_kernels": col(1), "bwd_kernels": col(2),
+                                      "note": "per step; step = wall clock of the timed loop / steps on each rank, kernels = HIP events around the native calls"}
+                out["allreduce_ms"] = {"image": col(3), "gradient": col(4), "bytes": {"image": W * W * 16, "gradient": int(material.numel()) * 4},
+                                       "note": "per step, HIP events on the compute stream around torch.distributed.all_reduce (includes waiting for the slowest rank)"}
+            if union is not None:
+                out["shard_union_check"] = union
+            fd = fd_summary()
+            if fd: out["grad_rel_err_vs_fd"] = fd
+            if world == 1 and cfg == "c3" and not (args.res or args.spp) and not args.no_extra_configs:
+                # the other single-GPU BASELINE configurations, each on its own scene with its own statistics (c5: BVH built once, 2 steps)
+                scene.render_forward = scene.render_backward = None
+                del leg, renderer, scene
+                gc.collect()
+                torch.cuda.empty_cache()
+                out["configs"] = {}
+                for name, key, steps, warm in (("c2", "c2", 10, 2), ("c4_one_gpu", "c4", 2, 1), ("c5", "c5", 2, 1)):
+                    try:                                            # a leg that fails is reported as such; the headline above stands on its own
+                        out["configs"][name] = extra_config(name, key, dev, mat_np, steps, warm)
+                    except Exception as e:                          # noqa: BLE001
+                        out["configs"][name] = {"error": f"{type(e).__name__}: {e}"}
+                scene = scenes.make_scene(integrator)
+            if world == 1 and not args.no_cpu_baseline:
+                # only now is the CPU oracle loaded — after every timed region
+                try:
+                    out["cpu_baseline"] = cpu_baseline(scene, mat_np, min(W, 512), args.cpu_spp)
+                except Exception as e:                              # noqa: BLE001
+                    out["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

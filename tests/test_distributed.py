@@ -44,6 +44,8 @@ def _oracle_renderer(mode):
 
 def _worker(rank, world, port, mode, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    # CPU ranks: on a machine with fewer GPUs than ranks, init_from_env would otherwise bind rank r to cuda:r and fail
+    torch.cuda.is_available = lambda: False
     from zdr_amd import distributed as zd
     assert zd.init_from_env("gloo") == (rank, world, rank)
     r = _oracle_renderer(mode)
