@@ -47,6 +47,8 @@ enum { ZDR_SAMPLER_CMJ = 0, ZDR_SAMPLER_PMJ02BN = 1 };
 /* acceleration structure used for LuisaCompute's Accel (render.py:74,109,127) */
 enum { ZDR_ACCEL_AUTO = 0, ZDR_ACCEL_BRUTE = 1, ZDR_ACCEL_BVH = 2 };
 enum { ZDR_PRB_EXPECTATION = 0, ZDR_PRB_DETACHED = 1, ZDR_PRB_LITERAL = 2 };
+/* most materials one zdr_render_*_materials call takes */
+#define ZDR_MAX_MATERIALS 16
 
 typedef struct zdr_scene zdr_scene;
 
@@ -109,7 +111,8 @@ const char *zdr_last_error(void);
  *   inst_tri_begin  ninst + 1 int32     triangles [begin[i], begin[i+1]) belong to instance i
  *   inst_xform      ninst x 16 float32  row-major object->world 4x4 (NULL = identity)
  *   inst_emission   ninst x 3 float32   (render.py:85-91; a light is any emission component > 0)
- * Only instance 0 is textured; every other instance is an emitter or a blocker (prb.py:45). */
+ * zdr_render_forward / zdr_render_backward texture instance 0 only; every other instance is an emitter or a blocker (prb.py:45).
+ * To shade several instances, each with a material of its own, see zdr_scene_set_material_slots and zdr_render_*_materials. */
 int zdr_scene_create(const float *verts8, uint32_t nverts, const int32_t *tris, uint32_t ntris,
                      const int32_t *inst_tri_begin, const float *inst_xform, const float *inst_emission,
                      uint32_t ninst, int device, int accel, zdr_scene **out);
@@ -146,6 +149,28 @@ int zdr_render_forward(zdr_scene *scene, const zdr_render_params *params, const 
  * d_image: DEVICE (H, W, 4) cotangent of the image. */
 int zdr_render_backward(zdr_scene *scene, const zdr_render_params *params, const float *d_image,
                         const float *material, float *d_material, void *stream);
+
+/* Material slots (the reference shades one material only: its instances > 0 are lights or blockers, prb.py:45).  inst_slot (HOST,
+ * ninst int32) gives each instance a material index k >= 0 of the zdr_render_*_materials calls, or -1 for none; copied to the
+ * device (a cold path, like zdr_scene_set_emissions: the stream is synchronised).  What an instance does in those calls:
+ *   path        slot >= 0: shaded by material k (an emitting instance still ends the path as a light, prb.py:39-46);
+ *               -1: what instances > 0 do in zdr_render_forward (emitter or blocker)
+ *   direct      slot >= 0: shaded by material k;  -1: returns its emission (direct.py:30-32)
+ *   collocated  slot >= 0: shaded by material k;  -1: black
+ * zdr_render_forward / zdr_render_backward are not affected.  Until the first call every slot is -1. */
+int zdr_scene_set_material_slots(zdr_scene *scene, const int32_t *inst_slot, void *stream);
+
+/* zdr_render_forward with one material per slot.  materials: DEVICE float32, the nmat textures concatenated texel by texel
+ * (material k is dims[2k] x dims[2k+1] x 4, CLAMP bilinear as read_bsdf); dims: HOST int32 nmat x {h, w}, 1 <= nmat <=
+ * ZDR_MAX_MATERIALS, every dimension >= 1.  params->tex_h / tex_w are ignored.  A slot >= nmat is ZDR_E_INVALID.  The table of
+ * materials travels in the kernel arguments, so a captured call keeps the layout it was recorded with. */
+int zdr_render_forward_materials(zdr_scene *scene, const zdr_render_params *params, const float *materials, const int32_t *dims,
+                                 uint32_t nmat, float *image, void *stream);
+
+/* zdr_render_backward with one material per slot: d_materials (DEVICE, packed like materials) is ACCUMULATED into (+=); each
+ * material receives the gradient of the vertices shaded with it.  Staging cells are sized for all materials together. */
+int zdr_render_backward_materials(zdr_scene *scene, const zdr_render_params *params, const float *d_image, const float *materials,
+                                  const int32_t *dims, uint32_t nmat, float *d_materials, void *stream);
 
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,

@@ -4,7 +4,11 @@ assembly (hipcc -S, CPU only) and compares every kernel's instruction stream, la
 very same machine code: no timing is needed for it — and one that is NOT expected to change and does is the thing to time first.
 (Round 4: a sampler change meant for the direct kernels shifted the register allocation of the BVH forward kernel and moved five spill
 operations into its walk loop, +8 %; it had been A/B-timed on the Cornell box only.)
-    python tools/isa_diff.py [rev]        rev defaults to HEAD; prints one line per kernel: identical | DIFFERENT (instructions, VALU, scratch ops old -> new)"""
+    python tools/isa_diff.py [rev]        rev defaults to HEAD; prints one line per kernel: identical | DIFFERENT (instructions, VALU, scratch ops old -> new)
+    python tools/isa_diff.py --pair-appended-false [rev]
+        for a change that appends a bool template parameter to kernel templates (the material-table mode of k_path, k_path_bwd and k_simple):
+        a kernel of rev that is gone from the tree is compared with the instantiation whose template arguments end in one more `false`
+        (mangled Lb0E inserted before the end of the template argument list) — the kernel the old launch now runs."""
 import os
 import re
 import subprocess
@@ -35,7 +39,9 @@ def stats(body):
     return len(body), sum(l.startswith("v_") for l in body), sum(l.startswith("scratch_") for l in body)
 
 
-rev = sys.argv[1] if len(sys.argv) > 1 else "HEAD"
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+pair_appended_false = "--pair-appended-false" in sys.argv[1:]
+rev = args[0] if args else "HEAD"
 with tempfile.TemporaryDirectory() as tmp:
     old_tree = os.path.join(tmp, "old"); os.makedirs(old_tree)
     tar = subprocess.run(["git", "-C", ROOT, "archive", rev, "zdr_amd/csrc", "include"], check=True, capture_output=True).stdout
@@ -43,6 +49,21 @@ with tempfile.TemporaryDirectory() as tmp:
     old = assemble(old_tree, os.path.join(tmp, "old.s"))
     new = assemble(ROOT, os.path.join(tmp, "new.s"))
 demangle = lambda n: subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip().split("(")[0][:70]
+
+
+
+def appended_false(name):
+    """_Z6k_pathILi0E10BruteAccelLb0ELb0EEv... -> _Z6k_pathILi0E10BruteAccelLb0ELb0ELb0EEv...: the template argument list of a
+    function template that returns void ends at the first `Ev`."""
+    i = name.find("Ev")
+    return name[:i] + "Lb0E" + name[i:] if i > 0 else None
+
+
+if pair_appended_false:   # rename each old kernel the tree no longer has to its legacy-mode counterpart, when that exists
+    for name in [n for n in old if n not in new]:
+        twin = appended_false(name)
+        if twin in new and twin not in old:
+            old[twin] = old.pop(name)
 changed = 0
 for name in sorted(set(old) | set(new)):
     if name not in old or name not in new:

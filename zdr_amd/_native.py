@@ -15,6 +15,7 @@ COLLOCATED, DIRECT, PATH, UVGRAD = 0, 1, 2, 3
 SAMPLER_CMJ, SAMPLER_PMJ02BN = 0, 1
 ACCEL_AUTO, ACCEL_BRUTE, ACCEL_BVH = 0, 1, 2
 ABI_VERSION = 3                # ZDR_ABI_VERSION of the include/zdr.h this binding mirrors
+MAX_MATERIALS = 16             # ZDR_MAX_MATERIALS
 PRB_MODES = {"expectation": 0, "detached": 1, "literal": 2}
 INTEGRATORS = {"collocated": COLLOCATED, "direct": DIRECT, "path": PATH}   # render.py:65-69
 SAMPLERS = {"cmj": SAMPLER_CMJ, "corrmj": SAMPLER_CMJ, "pmj02bn": SAMPLER_PMJ02BN}
@@ -25,7 +26,8 @@ COUNTER_NAMES = ("samples", "closest_rays", "closest_hits", "shadow_rays", "shad
 # every symbol include/zdr.h declares
 EXPORTS = ("zdr_version", "zdr_abi_version", "zdr_last_error", "zdr_scene_create", "zdr_scene_destroy", "zdr_scene_info",
            "zdr_scene_set_emissions", "zdr_scene_set_envmap", "zdr_scene_set_pmj02bn_tables", "zdr_render_forward", "zdr_render_backward",
-           "zdr_render_stats", "zdr_scene_check", "zdr_trace_closest", "zdr_trace_any", "zdr_sampler_dump", "zdr_vertex_sampler_dump", "zdr_path_dump", "zdr_debug_build_accel", "zdr_debug_never_occluders")
+           "zdr_render_stats", "zdr_scene_check", "zdr_trace_closest", "zdr_trace_any", "zdr_sampler_dump", "zdr_vertex_sampler_dump", "zdr_path_dump", "zdr_debug_build_accel", "zdr_debug_never_occluders",
+           "zdr_scene_set_material_slots", "zdr_render_forward_materials", "zdr_render_backward_materials")
 
 
 class CameraPOD(C.Structure):
@@ -79,6 +81,9 @@ def lib():
     L.zdr_scene_set_pmj02bn_tables.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32]
     L.zdr_render_forward.argtypes = [vp, C.POINTER(RenderParams), fp, fp, vp]
     L.zdr_render_backward.argtypes = [vp, C.POINTER(RenderParams), fp, fp, fp, vp]
+    L.zdr_scene_set_material_slots.argtypes = [vp, ip, vp]
+    L.zdr_render_forward_materials.argtypes = [vp, C.POINTER(RenderParams), fp, ip, C.c_uint32, fp, vp]
+    L.zdr_render_backward_materials.argtypes = [vp, C.POINTER(RenderParams), fp, fp, ip, C.c_uint32, fp, vp]
     L.zdr_render_stats.argtypes = [vp, C.POINTER(RenderParams), fp, C.POINTER(C.c_uint64), vp]
     L.zdr_scene_check.argtypes = [vp, vp]
     L.zdr_trace_closest.argtypes = [vp, fp, C.c_uint32, ip, fp, vp]

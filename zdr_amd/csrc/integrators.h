@@ -44,15 +44,23 @@ ZD float4 brdf_grad(float cz_over_pi, float dfdr, f3 ct) {     // d(f cos)[ct] w
 // collocated.py:11-31 / 35-57: L = brdf(wo, wo) / t^2
 // BWD: the vertex gradient is returned through (guv, grad) — grad stays 0 when there is nothing to add —
 // and the caller queues it at a reconverged point (scene.h, ScatterQueue).
-template <class A, bool BWD, bool STATS>
-ZD f3 collocated_sample(const DScene &S, const RenderCfg &R, const KernelIO &io, int *lds, f3 o, f3 d, unsigned long long cam_mask, f3 le_grad, Counters &cnt, f2 &guv, float4 &grad) {
+// MT (material table, zdr_render_*_materials): an instance without a material is black; gmat receives the material of the gradient.
+template <class A, bool BWD, bool STATS, bool MT = false>
+ZD f3 collocated_sample(const DScene &S, const RenderCfg &R, const KernelIO &io, int *lds, f3 o, f3 d, unsigned long long cam_mask, f3 le_grad, Counters &cnt, f2 &guv, float4 &grad,
+                        int &gmat) {
     COUNT(C_CLOSEST);
     Hit h = A::closest_camera(S, lds, o, d, cam_mask);
     if (h.slot < 0) return mk3(0.0f);
     COUNT(C_HITS);
     Interaction it = surface_interact(S, h);
     if (dot(-d, it.ng) < 1e-4f || dot(-d, it.ns) < 1e-4f) return mk3(0.0f);
-    float4 m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w);
+    float4 m;
+    if constexpr (MT) {
+        const int slot = io.mt.inst_slot[it.inst];
+        if (slot < 0) return mk3(0.0f);
+        m = read_bsdf_in(io.material, io.mt.m[slot], it.uv);
+        gmat = slot;
+    } else m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w);
     COUNT(C_SHADED);
     Onb onb = make_onb(it.ns);
     f3 wo = to_local(onb, -d);
@@ -97,17 +105,26 @@ ZD float4 uvgrad_sample(const DScene &S, int *lds, f3 o, f3 d, f3 odx, f3 ddx, f
 
 // -------------------------------------------------------------------------------- direct
 // direct.py:21-85 (forward) / 89-167 (adjoint; gradient written once at the primary uv, App. B-11)
-template <int SK, class A, bool BWD, bool STATS, bool ENV>
+// MT: an instance with a material is shaded by it, one without returns its emission (zdr.h, zdr_scene_set_material_slots)
+template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false>
 ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int *lds,
-                    Sampler &smp, f3 o, f3 d, unsigned long long cam_mask, f3 le_grad, Counters &cnt, f2 &guv, float4 &grad) {
+                    Sampler &smp, f3 o, f3 d, unsigned long long cam_mask, f3 le_grad, Counters &cnt, f2 &guv, float4 &grad, int &gmat) {
     COUNT(C_CLOSEST);
     Hit h = A::closest_camera(S, lds, o, d, cam_mask);
     if (h.slot < 0) return (ENV && S.env_count > 0) ? env_lookup(S, direction_to_uv(d)) : mk3(0.0f);   // direct.py:23-24
     COUNT(C_HITS);
     Interaction it = surface_interact(S, h);
     if (dot(-d, it.ng) < 1e-4f || dot(-d, it.ns) < 1e-4f) return mk3(0.0f);
-    if (it.inst > 0) return xyz(S.emission4[it.inst]);                            // direct.py:30-32
-    float4 m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w);
+    float4 m;
+    if constexpr (MT) {
+        const int slot = io.mt.inst_slot[it.inst];
+        if (slot < 0) return xyz(S.emission4[it.inst]);
+        m = read_bsdf_in(io.material, io.mt.m[slot], it.uv);
+        gmat = slot;
+    } else {
+        if (it.inst > 0) return xyz(S.emission4[it.inst]);                        // direct.py:30-32
+        m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w);
+    }
     f3 diffuse = mk3(m.x, m.y, m.z); float roughness = m.w;
     COUNT(C_SHADED);
     float4 mat_grad = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -206,8 +223,10 @@ struct PathState {
 // path_arrive: what the ray (ps.o, ps.d) reached (prb.py:25-46).  Returns true when the path ends here
 // (miss, back face, emitter, untextured instance); otherwise `it` is the vertex to shade.  BWD: sets
 // term_Li (and the MIS-weight fraction of the terminal emitter) when the path ended on a light.
-template <bool BWD, bool STATS, bool ENV>
-ZD bool path_arrive(const DScene &S, PathState &ps, const Hit &h, Interaction &it, f3 &term_Li, Counters &cnt, float *term_plfrac = nullptr) {
+// MT: the instance's material slot decides (inst_slot: MaterialTable::inst_slot) and `it.mat` receives it.
+template <bool BWD, bool STATS, bool ENV, bool MT = false>
+ZD bool path_arrive(const DScene &S, PathState &ps, const Hit &h, Interaction &it, f3 &term_Li, Counters &cnt, float *term_plfrac = nullptr,
+                    const int32_t *inst_slot = nullptr) {
     if (h.slot < 0) {                                                             // prb.py:26-32, in the form of direct.py:70-83
         if (ENV && S.env_count > 0) {
             f3 em = env_lookup(S, direction_to_uv(ps.d));
@@ -232,6 +251,10 @@ ZD bool path_arrive(const DScene &S, PathState &ps, const Hit &h, Interaction &i
         if (STATS && ps.depth > 0) cnt.c[C_EMIT_BSDF]++;
         return true;
     }
+    if constexpr (MT) {
+        it.mat = inst_slot[it.inst];
+        return it.mat < 0;
+    }
     if (it.inst > 0) return true;                                                 // prb.py:45-46
     return false;
 }
@@ -252,10 +275,12 @@ struct ShadeCtx { f3 diffuse; float roughness; Onb onb; f3 wo, wil; LightSample 
 struct NeeTerms { f3 dL, bW, fLW, neeM; float cL, dfLdr; };
 
 // material, frame and the light sample of the vertex (prb.py:47-58); BWD: resets pv
-template <int SK, bool BWD, bool STATS, bool ENV>
+template <int SK, bool BWD, bool STATS, bool ENV, bool MT = false>
 ZD ShadeCtx shade_ctx(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, PathState &ps, const Interaction &it, PathVertex &pv, Counters &cnt) {
     ShadeCtx x;
-    float4 m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w);
+    float4 m;
+    if constexpr (MT) m = read_bsdf_in(io.material, io.mt.m[it.mat], it.uv);
+    else m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w);
     x.diffuse = mk3(m.x, m.y, m.z); x.roughness = m.w;
     COUNT(C_SHADED);
     if (BWD) {
@@ -359,10 +384,10 @@ ZD bool sample_bsdf(const RenderCfg &R, const SamplerCfg &C, const ShadeCtx &x, 
 // so the image and the gradients are the reference's bit for bit.  Returns the shadow segment (if any) and whether the
 // path stops at this vertex; the continuation ray is (ps.o, ps.d).
 struct VertexRays { bool shadow, stop; f3 sd; float stmax; };
-template <int SK, bool BWD, bool STATS, bool ENV>
+template <int SK, bool BWD, bool STATS, bool ENV, bool MT = false>
 ZD VertexRays path_vertex_begin(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io,
                                 PathState &ps, const Interaction &it, PathVertex &pv, NeeTerms &n, Counters &cnt) {
-    const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV>(S, R, C, io, ps, it, pv, cnt);
+    const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, cnt);
     VertexRays vr; vr.sd = x.light.wi; vr.stmax = x.light.dist;
     n.dL = n.bW = n.fLW = n.neeM = mk3(0.0f); n.cL = 0.0f; n.dfLdr = 0.0f;
     COUNT(C_SHADOW);
@@ -380,18 +405,18 @@ ZD VertexRays path_vertex_begin(const DScene &S, const RenderCfg &R, const Sampl
     return vr;
 }
 
-template <int SK, class A, bool BWD, bool STATS, bool ENV>
+template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false>
 ZD bool path_shade(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int *lds,
                    PathState &ps, const Interaction &it, PathVertex &pv, Hit &h, Counters &cnt) {
     if constexpr (A::kFuseRays) {
         NeeTerms n;
-        const VertexRays vr = path_vertex_begin<SK, BWD, STATS, ENV>(S, R, C, io, ps, it, pv, n, cnt);
+        const VertexRays vr = path_vertex_begin<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, n, cnt);
         bool occluded;
         A::shadow_and_closest(S, lds, vr.shadow, it.p, vr.sd, 1e-4f, vr.stmax, !vr.stop, ps.o, ps.d, occluded, h);
         if (vr.shadow && !occluded) nee_apply<BWD>(ps, pv, n);
         return vr.stop;
     } else {
-        const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV>(S, R, C, io, ps, it, pv, cnt);
+        const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, cnt);
         COUNT(C_SHADOW);
         const bool occluded = A::any_shadow(S, lds, it.p, x.light.wi, 1e-4f, x.light.dist);
         if (!occluded && x.wil.z >= 1e-4f) nee_apply<BWD>(ps, pv, nee_terms<BWD>(x, ps.beta));
@@ -431,9 +456,10 @@ ZD uint32_t lane_rank(unsigned long long mask) {               // number of set 
 // Generates ZDR_RING_BATCH camera samples for every pixel of the tile (lane = pixel here).  Samples that end
 // at the camera ray (miss, emitter, back face) are finished at once: their radiance goes to `sum`,
 // this lane's own pixel.
-template <int SK, class A, bool BWD, bool STATS, bool ENV>
+template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false>
 ZD void primary_refill(const DScene &S, const RenderCfg &R, const SamplerCfg &C, int *lds, int x, int y, bool valid, unsigned long long cam_mask,
-                       uint32_t perm_seed, int bank, uint32_t &next_sample, uint32_t s_end, PrimaryQueue &q, f3 &sum, Counters &cnt) {
+                       uint32_t perm_seed, int bank, uint32_t &next_sample, uint32_t s_end, PrimaryQueue &q, f3 &sum, Counters &cnt,
+                       const int32_t *inst_slot = nullptr) {
     for (int b = 0; b < ZDR_RING_BATCH && next_sample < s_end; b++, next_sample++) {   // wave-uniform
         bool park = false;
         float4 e0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), e1 = e0;
@@ -445,7 +471,7 @@ ZD void primary_refill(const DScene &S, const RenderCfg &R, const SamplerCfg &C,
             COUNT(C_SAMPLES); COUNT(C_CLOSEST);
             Hit h = A::closest_camera(S, lds, ps.o, ps.d, cam_mask);
             Interaction it; f3 tl;
-            if (path_arrive<false, STATS, ENV>(S, ps, h, it, tl, cnt)) {
+            if (path_arrive<false, STATS, ENV, MT>(S, ps, h, it, tl, cnt, nullptr, inst_slot)) {
                 if (!BWD) {                                                     // a path without vertices has no gradient
                     if (!any_nan(ps.L)) sum = sum + clamp_radiance(ps.L);       // integrator.py:27-28
                     else COUNT(C_NAN);
@@ -470,9 +496,10 @@ ZD void primary_refill(const DScene &S, const RenderCfg &R, const SamplerCfg &C,
 // An idle lane takes the oldest parked vertex that no lower idle lane takes: the path state as it is right
 // after the camera ray.  Returns bank * 64 + pixel (lane index within the tile) of the path, or -1.
 // lds_perm[bank * 64 + pixel]: CMJ seed of the pixel; lds_origin[bank * 2 + {0, 1}]: first pixel of the bank's tile.
-template <int SK>
+// MT: the vertex's material is looked up again (the entry has no room for it; primary_refill parked only instances that have one).
+template <int SK, bool MT = false>
 ZD int primary_pop(const DScene &S, const SamplerCfg &C, bool idle, const uint32_t *lds_perm, const int *lds_origin,
-                   PrimaryQueue &q, PathState &ps, Interaction &it) {
+                   PrimaryQueue &q, PathState &ps, Interaction &it, const int32_t *inst_slot = nullptr) {
     const unsigned long long m = __ballot(idle);
     const uint32_t avail = q.tail - q.head, rank = lane_rank(m), want = (uint32_t)__popcll(m);
     const bool take = idle && rank < avail;
@@ -483,6 +510,7 @@ ZD int primary_pop(const DScene &S, const SamplerCfg &C, bool idle, const uint32
         float4 a = e[0], b = e[1];
         Hit h; h.slot = __float_as_int(b.y); h.u = a.w; h.v = b.x; h.t = 0.0f;
         it = surface_interact(S, h);
+        if constexpr (MT) it.mat = inst_slot[it.inst];
         ps.d = mk3(a.x, a.y, a.z); ps.o = mk3(0.0f);
         ps.beta = mk3(1.0f); ps.L = mk3(0.0f); ps.pdf_bsdf = 1e30f; ps.depth = 0;
         const uint32_t key = __float_as_uint(b.w);

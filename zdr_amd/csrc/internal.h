@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "sampler.h"
 #include "scene.h"
+#include "zdr.h"
 
 #define ZDR_MAX_RECORDED_DEPTH 16     // prb.py:15 max_depth; vertex records kept per path in backward
 
@@ -16,6 +17,16 @@
 #endif
 
 #define ZDR_MAX_PERSISTENT_BLOCKS 8192   // 256 CUs x 4 SIMDs x 8 waves: upper bound of the path kernels' persistent grid
+
+// Material table of the zdr_render_*_materials calls (zdr.h), a kernel argument like the rest of KernelIO so that a captured graph
+// carries its own copy.  Material k is texels [texel, texel + h w) of the packed buffer and staging cells [cell, cell + (h + 1)(w + 1))
+// of one copy of the cell array (copies are ncells apart).  The texture base pointer stays scalar; only the entry is per lane.
+struct MaterialSlot { int32_t texel, h, w, cell; };
+struct MaterialTable {
+    const int32_t *inst_slot;         // ninst entries: material of each instance, -1 = none (zdr_scene_set_material_slots)
+    int32_t nmat, ncells;             // materials in use; cells of all of them (one copy)
+    MaterialSlot m[ZDR_MAX_MATERIALS];
+};
 
 // Wave-uniform launch configuration (kernel argument, lives in SGPRs).
 struct RenderCfg {
@@ -49,6 +60,7 @@ struct KernelIO {
     int32_t tile_masks_valid;               // the masks in the buffer already belong to this camera and shard: skip k_tile_masks
     unsigned int *work_counters;      // path integrator: 8 item counters, one per XCD, zeroed before the launch (fetch_item)
     float4 *ring;                     // path integrator: one FIFO of parked camera-ray vertices per persistent workgroup (integrators.h)
+    MaterialTable mt;                 // material-table calls only (zdr_render_*_materials): `material` is then the packed buffer, `cells` all materials' cells
 };
 
 int zdr_launch_render(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io,

@@ -74,7 +74,11 @@ ZD void raise_device_error(const DScene &S, unsigned int bit) { if (S.error_word
 struct Hit { int slot; float u, v, t; };   // slot < 0: miss (LuisaCompute Hit{inst, prim, bary, ray_t})
 
 struct Interaction {                       // interaction.py:6
-    f3 p; f2 uv; f3 ns, ng; int inst, prim;
+    f3 p; f2 uv; f3 ns, ng; int inst;
+    union {
+        int prim;
+        int mat;                           // material-table path kernels: material slot of the instance (path_arrive, primary_pop), in prim's place
+    };
 };
 
 ZD f3 xyz(float4 a) { return mk3(a.x, a.y, a.z); }
@@ -118,6 +122,30 @@ ZD float4 read_bsdf(const float4 *__restrict__ mat, f2 uv, int tex_h, int tex_w)
     return r;
 }
 
+// The same lookup in material `m` of a packed buffer (zdr_render_*_materials): the base stays scalar, only m is per lane.
+// px and py pass through an empty asm so that they are rounded as products: with the texture size in VGPRs instead of SGPRs
+// the backend otherwise contracts px * 1 - ix into one FMA for the offsets (as it does not in read_bsdf of the forward
+// kernels), and the material-table image would differ from render_forward's in the last bit.
+template <class M>
+ZD float4 read_bsdf_in(const float4 *__restrict__ mats, const M &m, f2 uv) {
+    float px = uv.x * (float)(m.w - 1), py = (1.0f - uv.y) * (float)(m.h - 1);
+    asm volatile("" : "+v"(px), "+v"(py));
+    int ix = (int)px, iy = (int)py;
+    TexFoot f;
+    f.ox = px - (float)ix; f.oy = py - (float)iy;
+    int x0 = clampi(ix, 0, m.w - 1), x1 = clampi(ix + 1, 0, m.w - 1);
+    int y0 = clampi(iy, 0, m.h - 1), y1 = clampi(iy + 1, 0, m.h - 1);
+    f.i00 = x0 + m.w * y0; f.i01 = x0 + m.w * y1; f.i10 = x1 + m.w * y0; f.i11 = x1 + m.w * y1;
+    const float4 *t = mats + m.texel;
+    float4 c00 = t[f.i00], c01 = t[f.i01], c10 = t[f.i10], c11 = t[f.i11];
+    float4 r;
+    r.x = lerpf(lerpf(c00.x, c01.x, f.oy), lerpf(c10.x, c11.x, f.oy), f.ox);
+    r.y = lerpf(lerpf(c00.y, c01.y, f.oy), lerpf(c10.y, c11.y, f.oy), f.ox);
+    r.z = lerpf(lerpf(c00.z, c01.z, f.oy), lerpf(c10.z, c11.z, f.oy), f.ox);
+    r.w = lerpf(lerpf(c00.w, c01.w, f.oy), lerpf(c10.w, c11.w, f.oy), f.ox);
+    return r;
+}
+
 // ---------------------------------------------------------------- gradient scatter (backward)
 // The reference adds k_ij * dmat to the four texels of the bilinear footprint with 16 float atomics
 // (interaction.py:63-89) — 16 scattered 4-byte requests to the memory-side atomic unit per shaded
@@ -152,6 +180,9 @@ static_assert(ZDR_SCATTER_CAP >= 64, "one push can add an entry per lane");
 //        wave adds into copy blockIdx % copies; k_cells_to_grad sums the copies (in float64);
 //      - at most ZDR_LDS_CELLS cells (textures up to 4x4): the wave keeps the WHOLE cell array in LDS (the queue's
 //        block), adds with ds_add_f32 and writes it out once, when the kernel ends.
+//  * Several materials (template MT, zdr_render_*_materials): the cell array is the concatenation of every material's cells
+//    (MaterialSlot::cell is the first), both rules above apply to the TOTAL, a push stores the entry's material in its cell word
+//    and the flush turns (uv, material) into that material's cell.
 #define ZDR_LDS_CELLS 28             // 28 cells x 16 floats = the 448 floats of the queue's LDS block
 #define ZDR_MAX_CELL_COPIES 1024
 struct ScatterQueue {                // pointers into this wave's LDS block
@@ -168,15 +199,15 @@ struct ScatterQueue {                // pointers into this wave's LDS block
 #define ZDR_SCATTER_LDS_FLOATS (7 * ZDR_SCATTER_CAP)
 static_assert(16 * ZDR_LDS_CELLS <= ZDR_SCATTER_LDS_FLOATS, "the LDS cell array aliases the queue's block");
 
-// must be called by the whole wave
-ZD ScatterQueue scatter_queue_init(float *lds, int tex_h, int tex_w, int cell_copies) {
+// must be called by the whole wave; ncells: cells of one copy of the staging array
+ZD ScatterQueue scatter_queue_init_cells(float *lds, int ncells, int cell_copies) {
     ScatterQueue q;
     q.cell = (int *)lds; q.g = lds + ZDR_SCATTER_CAP; q.ox = lds + 5 * ZDR_SCATTER_CAP; q.oy = lds + 6 * ZDR_SCATTER_CAP;
     q.count = 0;
 #ifdef ZDR_MEASURE_STATS
     q.st_flushes = q.st_entries = q.st_dups = 0;
 #endif
-    q.ncells = (tex_h + 1) * (tex_w + 1);
+    q.ncells = ncells;
     q.copy_base = (int)(blockIdx.x % (unsigned)cell_copies) * q.ncells;
     q.small = (unsigned long long)q.ncells * (unsigned long long)cell_copies * 16ull < (1ull << 30);
     q.lds_cells = (q.ncells <= ZDR_LDS_CELLS) ? lds : nullptr;
@@ -186,6 +217,9 @@ ZD ScatterQueue scatter_queue_init(float *lds, int tex_h, int tex_w, int cell_co
         __builtin_amdgcn_wave_barrier();
     }
     return q;
+}
+ZD ScatterQueue scatter_queue_init(float *lds, int tex_h, int tex_w, int cell_copies) {
+    return scatter_queue_init_cells(lds, (tex_h + 1) * (tex_w + 1), cell_copies);
 }
 
 // Footprint of a gradient at uv: base cell (clamped so that out-of-range bases fold onto the border cells) and the bilinear offsets.
@@ -200,14 +234,18 @@ ZD int scatter_cell(f2 uv, int tex_h, int tex_w, float &ox, float &oy) {
 // must be called by the whole wave (reconverged control flow).  The queue holds (g, uv) as pushed; the flush first turns the uv of
 // all its entries into (cell, ox, oy) — lane = entry, once per ~57 entries instead of once per push (5.45 pushes per trip of the
 // backward path kernel, each by the whole wave for the few lanes that hold a gradient) — then adds them, 16 lanes per entry.
-ZD void scatter_flush(ScatterQueue &q, float *__restrict__ cells, int tex_h, int tex_w, int ablate) {
+// MT: the cell word of an entry holds its material as pushed; mats = the launch's MaterialTable::m.
+template <bool MT = false, class M = int>
+ZD void scatter_flush(ScatterQueue &q, float *__restrict__ cells, int tex_h, int tex_w, int ablate, const M *mats = nullptr) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const int lane = threadIdx.x & 63, sub = lane >> 4, j = lane & 15;
     for (int e = lane; e < q.count; e += 64) {
         f2 uv; uv.x = q.ox[e]; uv.y = q.oy[e];
         float ox, oy;
-        const int cell = scatter_cell(uv, tex_h, tex_w, ox, oy);
+        int cell;
+        if constexpr (MT) { const M m = mats[q.cell[e]]; cell = m.cell + scatter_cell(uv, m.h, m.w, ox, oy); }
+        else cell = scatter_cell(uv, tex_h, tex_w, ox, oy);
         q.cell[e] = (ablate == 2) ? (cell & 1023) : (q.copy_base + cell);   // ablation 2: all atomics hit 64 KiB of L2
         q.ox[e] = ox; q.oy[e] = oy;
     }
@@ -242,8 +280,9 @@ ZD void scatter_flush(ScatterQueue &q, float *__restrict__ cells, int tex_h, int
 }
 
 // end of the kernel: whatever is still queued, and the LDS cell array if the wave kept one
-ZD void scatter_finish(ScatterQueue &q, float *__restrict__ cells, int tex_h, int tex_w, int ablate) {
-    scatter_flush(q, cells, tex_h, tex_w, ablate);
+template <bool MT = false, class M = int>
+ZD void scatter_finish(ScatterQueue &q, float *__restrict__ cells, int tex_h, int tex_w, int ablate, const M *mats = nullptr) {
+    scatter_flush<MT>(q, cells, tex_h, tex_w, ablate, mats);
     if (q.lds_cells) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -254,8 +293,10 @@ ZD void scatter_finish(ScatterQueue &q, float *__restrict__ cells, int tex_h, in
     }
 }
 
-// must be called by the whole wave; lanes with active == false push nothing
-ZD void scatter_push(ScatterQueue &q, float *__restrict__ cells, bool active, f2 uv, float4 g, int tex_h, int tex_w, int ablate) {
+// must be called by the whole wave; lanes with active == false push nothing.  MT: `mat` is the material the gradient belongs to.
+template <bool MT = false, class M = int>
+ZD void scatter_push(ScatterQueue &q, float *__restrict__ cells, bool active, f2 uv, float4 g, int tex_h, int tex_w, int ablate,
+                     int mat = 0, const M *mats = nullptr) {
     if (ablate == 1) { asm volatile("" ::"v"(g.x), "v"(g.y), "v"(g.z), "v"(g.w), "v"(uv.x), "v"(uv.y)); return; }
     unsigned long long mask = __ballot(active);
     int n = __popcll(mask);
@@ -263,7 +304,9 @@ ZD void scatter_push(ScatterQueue &q, float *__restrict__ cells, bool active, f2
     if (q.lds_cells) {                   // few texels: the cell array is in LDS, 16 ds_add_f32 per vertex
         if (active) {
             float ox, oy;
-            const int cell = scatter_cell(uv, tex_h, tex_w, ox, oy);
+            int cell;
+            if constexpr (MT) { const M m = mats[mat]; cell = m.cell + scatter_cell(uv, m.h, m.w, ox, oy); }
+            else cell = scatter_cell(uv, tex_h, tex_w, ox, oy);
             float *c = q.lds_cells + 16 * cell;
             const float k00 = (1.0f - ox) * (1.0f - oy), k01 = (1.0f - ox) * oy, k10 = ox * (1.0f - oy), k11 = ox * oy;   // corner m = 2 dx + dy
             const float gg[4] = {g.x, g.y, g.z, g.w}, kk[4] = {k00, k01, k10, k11};
@@ -274,14 +317,15 @@ ZD void scatter_push(ScatterQueue &q, float *__restrict__ cells, bool active, f2
         }
         return;
     }
-    if (q.count + n > ZDR_SCATTER_CAP) scatter_flush(q, cells, tex_h, tex_w, ablate);
+    if (q.count + n > ZDR_SCATTER_CAP) scatter_flush<MT>(q, cells, tex_h, tex_w, ablate, mats);
     if (active) {
         int slot = q.count + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
         *(float4 *)(q.g + 4 * slot) = g;
         q.ox[slot] = uv.x; q.oy[slot] = uv.y;      // raw uv: the flush turns it into cell and offsets
+        if constexpr (MT) q.cell[slot] = mat;      // (free until the flush)
     }
     q.count += n;
-    if (q.count >= ZDR_SCATTER_FLUSH_AT) scatter_flush(q, cells, tex_h, tex_w, ablate);
+    if (q.count >= ZDR_SCATTER_FLUSH_AT) scatter_flush<MT>(q, cells, tex_h, tex_w, ablate, mats);
 }
 
 // ------------------------------------------------------------------------------------ lights

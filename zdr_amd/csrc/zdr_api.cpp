@@ -484,6 +484,8 @@ struct zdr_scene {
     float4 *d_ring = nullptr; size_t ring_bytes = 0;     // primary rings of the path kernels (integrators.h)
     float *d_cells = nullptr; size_t cells_bytes = 0;       // backward staging cells, (tex_h+1) x (tex_w+1) x 16 floats
     unsigned long long *d_counters = nullptr;
+    std::vector<int32_t> inst_slot;                         // material slot of each instance (zdr_scene_set_material_slots), -1 = none; empty = never set
+    int32_t *d_inst_slot = nullptr;                         // its device copy, allocated by the first call that needs it
     unsigned int *d_error = nullptr;                        // device error word (scene.h, ZDR_DEVERR_*), sticky until read
     uint64_t device_bytes = 0;
     // A render call recorded while its stream was CAPTURING (hipStreamBeginCapture; torch.cuda.graph) bakes this handle's workspace
@@ -781,7 +783,7 @@ extern "C" int zdr_scene_destroy(zdr_scene *s) {
     if (!s) return ZDR_OK;
     (void)hipSetDevice(s->device);
     if (!s->isect_in_nodes) (void)hipFree(s->d_isect); (void)hipFree(s->d_pairs); (void)hipFree(s->d_ppairs); (void)hipFree(s->d_shade); (void)hipFree(s->d_nodes); (void)hipFree(s->d_emission); (void)hipFree(s->d_light_insts); (void)hipFree(s->d_light_tris); (void)hipFree(s->d_light_range); (void)hipFree(s->d_emission4);
-    (void)hipFree(s->d_inst_tri_begin); (void)hipFree(s->d_slot_of_tri); (void)hipFree(s->d_pmj); (void)hipFree(s->d_bn); (void)hipFree(s->d_env_tex); (void)hipFree(s->d_alias_prob); (void)hipFree(s->d_alias_idx); (void)hipFree(s->d_env_pdf); (void)hipFree(s->d_partial); (void)hipFree(s->d_ring); (void)hipFree(s->d_work_counters); (void)hipFree(s->d_tile_masks); (void)hipFree(s->d_cells); (void)hipFree(s->d_counters); (void)hipFree(s->d_error);
+    (void)hipFree(s->d_inst_tri_begin); (void)hipFree(s->d_slot_of_tri); (void)hipFree(s->d_pmj); (void)hipFree(s->d_bn); (void)hipFree(s->d_env_tex); (void)hipFree(s->d_alias_prob); (void)hipFree(s->d_alias_idx); (void)hipFree(s->d_env_pdf); (void)hipFree(s->d_partial); (void)hipFree(s->d_ring); (void)hipFree(s->d_work_counters); (void)hipFree(s->d_tile_masks); (void)hipFree(s->d_cells); (void)hipFree(s->d_counters); (void)hipFree(s->d_error); (void)hipFree(s->d_inst_slot);
     for (void *p : s->retired) (void)hipFree(p);
     delete s;
     return ZDR_OK;
@@ -808,6 +810,24 @@ extern "C" int zdr_scene_set_emissions(zdr_scene *s, const float *inst_emission,
     HIPCHK(hipStreamSynchronize(st));
     s->ds.light_count = count;
     return upload_light_table(s, lights, count, st);
+}
+
+extern "C" int zdr_scene_set_material_slots(zdr_scene *s, const int32_t *inst_slot, void *stream) {
+    if (!s || !inst_slot) return fail(ZDR_E_INVALID, "null argument");
+    for (uint32_t i = 0; i < s->ninst; i++)
+        if (inst_slot[i] < -1 || inst_slot[i] >= ZDR_MAX_MATERIALS)
+            return fail(ZDR_E_INVALID, "instance " + std::to_string(i) + ": material slot " + std::to_string(inst_slot[i]) + " outside [-1, " + std::to_string(ZDR_MAX_MATERIALS) + ")");
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!s->d_inst_slot) {
+        if (stream_is_capturing(st)) return fail(ZDR_E_UNSUPPORTED, "the material-slot table would have to be allocated while the stream is capturing");
+        HIPCHK(hipMalloc((void **)&s->d_inst_slot, std::max<size_t>(16, (size_t)s->ninst * sizeof(int32_t))));
+        s->device_bytes += (size_t)s->ninst * sizeof(int32_t);
+    }
+    s->inst_slot.assign(inst_slot, inst_slot + s->ninst);
+    HIPCHK(hipMemcpyAsync(s->d_inst_slot, s->inst_slot.data(), (size_t)s->ninst * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZDR_OK;
 }
 
 extern "C" int zdr_scene_set_envmap(zdr_scene *s, const float *tex, uint32_t tex_h, uint32_t tex_w, const float *alias_prob,
@@ -884,6 +904,11 @@ static int check_params_abi(const zdr_render_params *p) {
     return ZDR_OK;
 }
 
+// few texels: replicate the staging cells so that the launch's atomics do not pile up on a handful of addresses (scene.h)
+static int32_t cell_copies_for(size_t ncells) {
+    return (ncells < (1u << 16)) ? (int32_t)std::min<size_t>(ZDR_MAX_CELL_COPIES, (1u << 20) / ncells) : 1;
+}
+
 static int make_render_cfg(const zdr_render_params *p, bool backward, RenderCfg &R) {
     { int rc = check_params_abi(p); if (rc) return rc; }
     if (p->integrator < 0 || p->integrator > ZDR_UVGRAD) return fail(ZDR_E_INVALID, "unknown integrator");
@@ -899,10 +924,7 @@ static int make_render_cfg(const zdr_render_params *p, bool backward, RenderCfg 
     R.width = p->width; R.height = p->height; R.x0 = p->x0; R.y0 = p->y0; R.x1 = p->x1; R.y1 = p->y1;
     R.sample_begin = p->sample_begin; R.sample_end = p->sample_end;
     R.use_tent = p->use_tent; R.max_depth = p->max_depth; R.rr_depth = p->rr_depth; R.tex_h = p->tex_h; R.tex_w = p->tex_w;
-    {   // few texels: replicate the staging cells so that the launch's atomics do not pile up on a handful of addresses (scene.h)
-        const size_t ncells = (size_t)(p->tex_h + 1) * (size_t)(p->tex_w + 1);
-        R.cell_copies = (ncells < (1u << 16)) ? (int32_t)std::min<size_t>(ZDR_MAX_CELL_COPIES, (1u << 20) / ncells) : 1;
-    }
+    R.cell_copies = cell_copies_for((size_t)(p->tex_h + 1) * (size_t)(p->tex_w + 1));
     R.two_over_w = 2.0f / (float)p->width; R.two_over_h = 2.0f / (float)p->height;
     R.aspect = (float)p->height / (float)p->width;
     R.inv_spp = 1.0f / (float)p->spp;
@@ -980,8 +1002,9 @@ static int ensure_ring(zdr_scene *s, hipStream_t st, bool capturing) {
     return ZDR_OK;
 }
 
-static int ensure_cells(zdr_scene *s, const RenderCfg &R, hipStream_t st, bool capturing) {
-    size_t need = (size_t)R.cell_copies * (size_t)(R.tex_h + 1) * (R.tex_w + 1) * 16 * sizeof(float);
+// ncells: cells of one copy ((tex_h + 1) x (tex_w + 1), or MaterialTable::ncells)
+static int ensure_cells(zdr_scene *s, const RenderCfg &R, size_t ncells, hipStream_t st, bool capturing) {
+    size_t need = (size_t)R.cell_copies * ncells * 16 * sizeof(float);
     if (need > s->cells_bytes) {
         if (int rc = may_allocate(capturing, "staging-cell")) return rc;
         release_buffer(s, s->d_cells); s->d_cells = nullptr; s->cells_bytes = 0;
@@ -1014,17 +1037,55 @@ extern "C" int zdr_scene_check(zdr_scene *s, void *stream) {
     return check_device_error(s, (hipStream_t)stream);
 }
 
+// The material table of a zdr_render_*_materials call (internal.h): materials packed in order, their cells likewise.
+static int make_material_table(zdr_scene *s, const int32_t *dims, uint32_t nmat, bool capturing, hipStream_t st, MaterialTable &mt) {
+    if (!dims) return fail(ZDR_E_INVALID, "null material dimensions");
+    if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
+    memset(&mt, 0, sizeof mt);
+    size_t texel = 0, cells = 0;
+    for (uint32_t k = 0; k < nmat; k++) {
+        const int32_t h = dims[2 * k], w = dims[2 * k + 1];
+        if (h < 1 || w < 1) return fail(ZDR_E_INVALID, "material " + std::to_string(k) + " is " + std::to_string(h) + " x " + std::to_string(w) + ": every dimension must be >= 1");
+        mt.m[k].texel = (int32_t)texel; mt.m[k].h = h; mt.m[k].w = w; mt.m[k].cell = (int32_t)cells;
+        texel += (size_t)h * (size_t)w; cells += (size_t)(h + 1) * (size_t)(w + 1);
+        if (texel >= (1ull << 31) || cells >= (1ull << 26)) return fail(ZDR_E_UNSUPPORTED, "materials too large for one material-table call (2^31 texels, 2^26 staging cells)");
+    }
+    for (size_t i = 0; i < s->inst_slot.size(); i++)
+        if (s->inst_slot[i] >= (int32_t)nmat)
+            return fail(ZDR_E_INVALID, "instance " + std::to_string(i) + " has material slot " + std::to_string(s->inst_slot[i]) + ", but only " + std::to_string(nmat) + " materials were passed");
+    if (!s->d_inst_slot) {                                  // never set: every slot is -1
+        if (int rc = may_allocate(capturing, "material-slot")) return rc;
+        std::vector<int32_t> none(s->ninst, -1);
+        if (int rc = zdr_scene_set_material_slots(s, none.data(), st)) return rc;
+    }
+    mt.inst_slot = s->d_inst_slot; mt.nmat = (int32_t)nmat; mt.ncells = (int32_t)cells;
+    return ZDR_OK;
+}
+
+// mt_dims / nmat: a material-table call (zdr_render_*_materials), else nullptr / 0
 static int render_common(zdr_scene *s, const zdr_render_params *p, const float *material, float *image, const float *d_image,
-                         float *d_material, int backward, int stats, void *stream) {
+                         float *d_material, int backward, int stats, void *stream, const int32_t *mt_dims = nullptr, uint32_t nmat = 0) {
     if (!s || !p || !material) return fail(ZDR_E_INVALID, "null argument");
     int rc = check_params_abi(p); if (rc) return rc;
     HIPCHK(hipSetDevice(s->device));
+    const bool use_mt = nmat > 0 || mt_dims;
+    zdr_render_params pm = *p;
+    if (use_mt) {                                       // the materials' sizes come from the table
+        if (p->integrator == ZDR_UVGRAD) return fail(ZDR_E_UNSUPPORTED, "render_duvdxy has no material-table form");
+        pm.tex_h = pm.tex_w = 1;
+    }
     RenderCfg R; SamplerCfg C;
-    rc = make_render_cfg(p, backward != 0, R); if (rc) return rc;
+    rc = make_render_cfg(&pm, backward != 0, R); if (rc) return rc;
     rc = make_sampler_cfg(s, p->sampler, p->seed, p->spp, C); if (rc) return rc;
     const bool capturing = stream_is_capturing((hipStream_t)stream);
+    MaterialTable mt; memset(&mt, 0, sizeof mt);
+    if (use_mt) {
+        rc = make_material_table(s, mt_dims, nmat, capturing, (hipStream_t)stream, mt); if (rc) return rc;
+        R.tex_h = R.tex_w = 0;                          // (unused in material-table mode)
+        R.cell_copies = cell_copies_for((size_t)mt.ncells);
+    }
     if (capturing) s->captured = true;                  // sticky: a graph may name this handle's buffers from now on (zdr_scene)
-    if (backward) { rc = ensure_cells(s, R, (hipStream_t)stream, capturing); if (rc) return rc; }
+    if (backward) { rc = ensure_cells(s, R, use_mt ? (size_t)mt.ncells : (size_t)(R.tex_h + 1) * (R.tex_w + 1), (hipStream_t)stream, capturing); if (rc) return rc; }
     else if (!stats) { rc = ensure_partial(s, R, capturing); if (rc) return rc; }
     if (p->integrator == ZDR_PATH) {
         if (p->spp > (1u << 25)) return fail(ZDR_E_UNSUPPORTED, "path integrator: spp above 2^25");   // queue entries pack pixel << 26 | bank << 25 | sample
@@ -1058,6 +1119,7 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
     }
     io.material = (const float4 *)material; io.image = (float4 *)image; io.partial = s->d_partial;
     io.d_image = (const float4 *)d_image; io.d_material = d_material; io.cells = s->d_cells; io.counters = s->d_counters;
+    io.mt = mt;
     // every pointer a kernel variant dereferences must be live before anything is launched
     if (backward && (!io.d_image || !io.d_material || !io.cells)) return fail(ZDR_E_INVALID, "backward needs d_image, d_material and the staging cells");
     if (!backward && !stats && !io.image) return fail(ZDR_E_INVALID, "forward needs an image");
@@ -1096,6 +1158,20 @@ extern "C" int zdr_render_backward(zdr_scene *s, const zdr_render_params *p, con
 #else
     return render_common(s, p, material, nullptr, d_image, d_material, 1, 0, stream);
 #endif
+}
+
+extern "C" int zdr_render_forward_materials(zdr_scene *s, const zdr_render_params *p, const float *materials, const int32_t *dims, uint32_t nmat,
+                                            float *image, void *stream) {
+    if (!image || !dims) return fail(ZDR_E_INVALID, "null argument");
+    if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
+    return render_common(s, p, materials, image, nullptr, nullptr, 0, 0, stream, dims, nmat);
+}
+
+extern "C" int zdr_render_backward_materials(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *materials,
+                                             const int32_t *dims, uint32_t nmat, float *d_materials, void *stream) {
+    if (!d_image || !d_materials || !dims) return fail(ZDR_E_INVALID, "null argument");
+    if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
+    return render_common(s, p, materials, nullptr, d_image, d_materials, 1, 0, stream, dims, nmat);
 }
 
 extern "C" int zdr_render_stats(zdr_scene *s, const zdr_render_params *p, const float *material, uint64_t counters[8], void *stream) {

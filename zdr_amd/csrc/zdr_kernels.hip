@@ -204,7 +204,8 @@ ZD const PathKArgs &kargs_fresh() {
 #define ZDR_ABLATE 0
 #endif
 
-template <int SK, class A, bool STATS, bool ENV>
+// MT: material-table mode (zdr_render_forward_materials): io.material is the packed buffer and io.mt says which material shades what
+template <int SK, class A, bool STATS, bool ENV, bool MT>
 __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) void k_path(ZDR_PATH_KERNEL_PARAMS) {
     ZDR_KARGS_BEGIN
 #define S (ka->S)
@@ -241,7 +242,8 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
             if (next_sample < s_end) {
                 progress = true;
                 const uint32_t t0 = q.tail;
-                primary_refill<SK, A, false, STATS, ENV>(S, R, C, lds, w.x, w.y, w.valid, cam_mask, perm_seed, bank, next_sample, s_end, q, sum, cnt);
+                primary_refill<SK, A, false, STATS, ENV, MT>(S, R, C, lds, w.x, w.y, w.valid, cam_mask, perm_seed, bank, next_sample, s_end, q, sum, cnt,
+                                                             MT ? io.mt.inst_slot : nullptr);
                 ib.inflight[bank] += q.tail - t0;
             } else if (more_items && ib.logical[bank ^ 1] < 0) {                // next item, into the free bank
                 if (ib.logical[bank] >= 0) {                                    // park the register part of the old item's sums
@@ -267,15 +269,15 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
                 continue;
             }
         }
-        const int took = primary_pop<SK>(S, C, !alive, lds_perm, lds_origin, q, ps, it);
+        const int took = primary_pop<SK, MT>(S, C, !alive, lds_perm, lds_origin, q, ps, it, MT ? io.mt.inst_slot : nullptr);
         if (took >= 0) { alive = true; pix = took; }
         if (__ballot(alive) != 0ull) {
             progress = true;
             bool done = false;
             if (alive) {
                 Hit h;
-                done = path_shade<SK, A, false, STATS, ENV>(S, R, C, io, lds, ps, it, pv, h, cnt);
-                if (!done) { path_continue<A, STATS>(S, lds, ps, h, cnt); done = path_arrive<false, STATS, ENV>(S, ps, h, it, term_Li, cnt); }
+                done = path_shade<SK, A, false, STATS, ENV, MT>(S, R, C, io, lds, ps, it, pv, h, cnt);
+                if (!done) { path_continue<A, STATS>(S, lds, ps, h, cnt); done = path_arrive<false, STATS, ENV, MT>(S, ps, h, it, term_Li, cnt, nullptr, MT ? io.mt.inst_slot : nullptr); }
                 if (done) {
                     alive = false;
                     if (!any_nan(ps.L)) {                   // integrator.py:27-28
@@ -323,8 +325,10 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
 // loads its cotangent from the image): that leaves room for the pool in 8 of gfx950's 1,280-byte LDS blocks, 16 waves per CU.
 // (The lane-owned record rows, the 12-wave layout with seeds and cotangents in LDS and the LDS padding experiment that preceded
 // this are kept as profiles/r4_pruned_experiment_branches.patch.)
+// MT (zdr_render_backward_materials): a record's material rides in its link word — the pool's links are 16 bits wide (two slots fewer keep the
+// LDS blocks), the scratch links are ints anyway — as `previous location | material << 8`; the 80-byte record itself is unchanged.
 typedef unsigned int zdr_u4 __attribute__((ext_vector_type(4)));
-template <int SK, class A, bool ENV>
+template <int SK, class A, bool ENV, bool MT>
 __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KERNEL_PARAMS) {
     ZDR_KARGS_BEGIN
 #define S (ka->S)
@@ -335,10 +339,12 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
     __shared__ __attribute__((aligned(16))) float lds_q[ZDR_SCATTER_LDS_FLOATS];   // the queue writes g as one float4
     // The records of all paths of the wave share ONE pool of NS slots (80 bytes + a link each): a lane takes its home slot
     // (slot == lane) when that is free and otherwise the lowest free one, and gives the slot back when the sweep has read it.
-    constexpr int NS = A::kPoolSlots;
+    constexpr int NS = MT ? A::kPoolSlots - 2 : A::kPoolSlots;
     static_assert(NS >= 16 && NS <= 128, "the free mask is two 64-bit words");
+    static_assert(ZDR_MAX_MATERIALS <= 256, "a material fits the upper byte of a link");
+    typedef typename std::conditional<MT, unsigned short, unsigned char>::type link_t;
     __shared__ float4 lds_pool[5 * NS];                     // [float4 f][slot]
-    __shared__ unsigned char lds_link[NS];                  // slot of the path's previous record (255: in scratch; a path's first record links to nothing and its link is never followed).  One byte: three more slots fit
+    __shared__ link_t lds_link[NS];                  // slot of the path's previous record (255: in scratch; a path's first record links to nothing and its link is never followed).  One byte: three more slots fit
     // bit s set: slot s is free.  The only state lanes share: lane 0 stores the mask after an allocation, the sweep's lanes OR freed
     // slots in, every lane reads it before the next allocation.  All three accesses are volatile or atomic and stand between
     // wavefront-scope fences, so the protocol does not rest on what the optimiser happens to do with plain LDS accesses.
@@ -362,7 +368,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
     uint32_t next_sample = 0, s_end = 0, perm_seed = 0;
     unsigned long long cam_mask = 0ull;
     f3 le_grad = mk3(0.0f);                                 // cotangent of the running path's pixel
-    ScatterQueue q = scatter_queue_init(lds_q, R.tex_h, R.tex_w, R.cell_copies);
+    ScatterQueue q = MT ? scatter_queue_init_cells(lds_q, io.mt.ncells, R.cell_copies) : scatter_queue_init(lds_q, R.tex_h, R.tex_w, R.cell_copies);
     PackedVertex deep[ZDR_MAX_RECORDED_DEPTH];
     int nrec = 0;
     PrimaryQueue pq = queue_init(io);
@@ -382,7 +388,8 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
         if (pq.tail - pq.head < (uint32_t)__popcll(__ballot(!alive))) {
             if (next_sample < s_end) {
                 const uint32_t t0 = pq.tail;
-                primary_refill<SK, A, true, false, ENV>(S, R, C, lds, w.x, w.y, w.valid, cam_mask, perm_seed, bank, next_sample, s_end, pq, unused_sum, cnt);
+                primary_refill<SK, A, true, false, ENV, MT>(S, R, C, lds, w.x, w.y, w.valid, cam_mask, perm_seed, bank, next_sample, s_end, pq, unused_sum, cnt,
+                                                            MT ? io.mt.inst_slot : nullptr);
                 ib.inflight[bank] += pq.tail - t0;
                 progress = true;
             } else if (more_items && ib.logical[bank ^ 1] < 0) {
@@ -402,7 +409,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
                 continue;
             }
         }
-        const int took = primary_pop<SK>(S, C, !alive, nullptr, lds_origin, pq, ps, it);
+        const int took = primary_pop<SK, MT>(S, C, !alive, nullptr, lds_origin, pq, ps, it, MT ? io.mt.inst_slot : nullptr);
         if (took >= 0) {
             {   // the pixel's cotangent / spp, straight from the image (load_le_grad; a popped path is inside the shard)
                 const float4 gi = io.d_image[ps.smp.px + ps.smp.py * (uint32_t)R.width];
@@ -422,15 +429,17 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
             f3 term_Li = mk3(0.0f);
             PackedVertex plast;                             // the vertex shaded this trip, as recorded
             plast.a = plast.b = plast.c = plast.d = plast.e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            int pmat = 0;                                   // MT: material of plast
             int sw_k = -1;                                  // next vertex the sweep consumes
             bool want_store = false, mute = false;
             SweepState sw; sw.A = mk3(0.0f); sw.Lv = mk3(0.0f); sw.s = 0.0f; sw.Z = 0.0f; sw.tw = 0.0f;
             if (alive) {
                 PathVertex pv; float term_plfrac = 0.0f;
                 Hit h;
-                done = path_shade<SK, A, true, false, ENV>(S, R, C, io, lds, ps, it, pv, h, cnt);
+                if (MT) pmat = it.mat;
+                done = path_shade<SK, A, true, false, ENV, MT>(S, R, C, io, lds, ps, it, pv, h, cnt);
                 plast = pack_vertex(pv, le_grad, R.prb_mode);
-                if (!done) { path_continue<A, false>(S, lds, ps, h, cnt); done = path_arrive<true, false, ENV>(S, ps, h, it, term_Li, cnt, &term_plfrac); }
+                if (!done) { path_continue<A, false>(S, lds, ps, h, cnt); done = path_arrive<true, false, ENV, MT>(S, ps, h, it, term_Li, cnt, &term_plfrac, MT ? io.mt.inst_slot : nullptr); }
                 // Only a vertex whose path goes on is put away: when the path ends here (52 % of the vertices) the sweep below starts
                 // from plast and nothing would read the record.  (5 LDS or scratch stores per vertex: 16.4 -> 15.5 ms for skipping
                 // the vertices that stop at the shading step alone.)
@@ -500,10 +509,10 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
                     if (slot >= 0) {
                         float4 *r = lds_pool + slot;
                         r[0] = plast.a; r[NS] = plast.b; r[2 * NS] = plast.c; r[3 * NS] = plast.d; r[4 * NS] = plast.e;
-                        lds_link[slot] = (unsigned char)last;
+                        lds_link[slot] = MT ? (link_t)((last & 255) | (pmat << 8)) : (link_t)last;
                         last = slot;
                     } else {
-                        deep[nrec - 1] = plast; deep_link[nrec - 1] = last;
+                        deep[nrec - 1] = plast; deep_link[nrec - 1] = MT ? ((last & 255) | (pmat << 8)) : last;
                         last = 255;
                     }
                 }
@@ -513,6 +522,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
             // wave-uniform: sweep every finished path to its first vertex.  The sweep starts from the vertex packed this
             // trip (still in registers).
             PackedVertex cur = plast;
+            int cur_mat = pmat;                             // MT: material of `cur`
             int loc = last;                                 // where the record of the sweep's next step lives
 #ifdef ZDR_MEASURE_STATS   // measurement build (tools/bwd_stats.sh): how full are the trips and the sweep iterations
             st_trips++; st_shaded += (unsigned long long)__popcll(__ballot(alive || done));
@@ -531,6 +541,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
 #endif
                 float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 f2 guv; guv.x = 0.0f; guv.y = 0.0f;
+                const int gmat = cur_mat;
                 if (swp) { g = sweep_vertex(cur, sw, guv, R.prb_mode); sw_k--; }
                 // everything that reads `cur` is finished here, before the fetch below overwrites it (left alone the compiler sinks
                 // part of the step below the fetch, loads into a second register set and copies — with a wait in front of the copies)
@@ -543,16 +554,20 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
                     const float4 *r = lds_pool + loc;
                     cur.a = r[0]; cur.b = r[NS]; cur.c = r[2 * NS]; cur.d = r[3 * NS]; cur.e = r[4 * NS];
                     nloc = (int)lds_link[loc];
+                    if (MT) { cur_mat = nloc >> 8; nloc &= 255; }
                 }
                 // LDS first: both kinds of fetch write the same registers (for different lanes), and the second kind waits for the
                 // first to land — an LDS read is back in ~100 cycles, a scratch read in ~500 and behind the flush's atomics
                 asm volatile("" ::: "memory");
-                if (fetch && loc == 255) { cur = deep[sw_k]; nloc = deep_link[sw_k]; }
+                if (fetch && loc == 255) {
+                    cur = deep[sw_k]; nloc = deep_link[sw_k];
+                    if (MT) { cur_mat = nloc >> 8; nloc &= 255; }
+                }
                 // the slots just read are free again: a wavefront-scope RELEASE or, so the reads of the record above are ordered before it
                 // (and this wave's LDS operations execute in order anyway: a later write cannot overtake the read)
                 if (pooled) __hip_atomic_fetch_or(&lds_free[loc >> 5], 1u << (loc & 31), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 if (fetch) loc = nloc;
-                scatter_push(q, io.cells, swp && !mute && any_nonzero4(g) && !any_nan4(g), guv, g, R.tex_h, R.tex_w, ZDR_ABLATE);   // prb.py:178-187
+                scatter_push<MT>(q, io.cells, swp && !mute && any_nonzero4(g) && !any_nan4(g), guv, g, R.tex_h, R.tex_w, ZDR_ABLATE, gmat, io.mt.m);   // prb.py:178-187
             }
         }
 #pragma unroll
@@ -562,7 +577,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
         stall = progress ? 0 : stall + 1;
         if (stall > 4) { raise_device_error(S, ZDR_DEVERR_STALL); break; }   // cannot happen (every branch above makes progress); never spin on the GPU, never end silently
     }
-    scatter_finish(q, io.cells, R.tex_h, R.tex_w, ZDR_ABLATE);
+    scatter_finish<MT>(q, io.cells, R.tex_h, R.tex_w, ZDR_ABLATE, io.mt.m);
     {   // every path has been swept, so every slot must be back: a leaked or doubly allocated slot is a protocol error, said aloud
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -584,7 +599,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
 }
 
 // ---------------------------------------------------------------------- direct / collocated
-template <int INTEG, int SK, class A, bool BWD, bool STATS, bool ENV>
+template <int INTEG, int SK, class A, bool BWD, bool STATS, bool ENV, bool MT>
 #ifndef ZDR_MIN_WAVES_DIRECT
 #define ZDR_MIN_WAVES_DIRECT 4   // brute-force direct kernels, cbox 512^2 spp 64: 153 VGPRs (3 waves per SIMD) 1.175 / 1.331 ms, 128 VGPRs (6 spilled) 1.110 / 1.267 ms
 #endif
@@ -604,26 +619,27 @@ __global__ __launch_bounds__(WAVE, (INTEG == ZDR_DIRECT && !A::kNeedsLds) ? (ENV
     for (int i = 0; i < 8; i++) cnt.c[i] = 0;
     f3 le_grad = mk3(0.0f);
     if (BWD) le_grad = load_le_grad(C, io, w);
-    ScatterQueue q = scatter_queue_init(lds_q, R.tex_h, R.tex_w, R.cell_copies);
+    ScatterQueue q = MT ? scatter_queue_init_cells(lds_q, io.mt.ncells, R.cell_copies) : scatter_queue_init(lds_q, R.tex_h, R.tex_w, R.cell_copies);
     const unsigned long long cam_mask = camera_mask(S, io, w);
     f3 sum = mk3(0.0f);
     for (uint32_t it = w.s_begin; it < w.s_end; it++) {     // integrator.py:15 (wave-uniform trip count)
         ZDR_KARGS_REFRESH
         float4 grad = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         f2 guv; guv.x = 0.0f; guv.y = 0.0f;
+        int gmat = 0;
         if (w.valid) {
             Sampler smp = sampler_make<SK>(C, (uint32_t)w.x, (uint32_t)w.y, perm_seed, it);
             f3 o, d;
             pixel_ray<SK, true>(R, C, smp, w.x, w.y, o, d);
             COUNT(C_SAMPLES);
             f3 rad;
-            if (INTEG == ZDR_COLLOCATED) rad = collocated_sample<A, BWD, STATS>(S, R, io, lds, o, d, cam_mask, le_grad, cnt, guv, grad);
-            else rad = direct_sample<SK, A, BWD, STATS, ENV>(S, R, C, io, lds, smp, o, d, cam_mask, le_grad, cnt, guv, grad);
+            if (INTEG == ZDR_COLLOCATED) rad = collocated_sample<A, BWD, STATS, MT>(S, R, io, lds, o, d, cam_mask, le_grad, cnt, guv, grad, gmat);
+            else rad = direct_sample<SK, A, BWD, STATS, ENV, MT>(S, R, C, io, lds, smp, o, d, cam_mask, le_grad, cnt, guv, grad, gmat);
             if (!any_nan(rad)) sum = sum + clamp_radiance(rad); else COUNT(C_NAN);
         }
-        if (BWD) scatter_push(q, io.cells, w.valid && any_nonzero4(grad) && !any_nan4(grad), guv, grad, R.tex_h, R.tex_w, ZDR_ABLATE);
+        if (BWD) scatter_push<MT>(q, io.cells, w.valid && any_nonzero4(grad) && !any_nan4(grad), guv, grad, R.tex_h, R.tex_w, ZDR_ABLATE, gmat, io.mt.m);
     }
-    if (BWD) scatter_finish(q, io.cells, R.tex_h, R.tex_w, ZDR_ABLATE);
+    if (BWD) scatter_finish<MT>(q, io.cells, R.tex_h, R.tex_w, ZDR_ABLATE, io.mt.m);
     if (!BWD && !STATS) store_pixel(R, C, io, w, sum);
     flush_counters<STATS>(io, cnt);
 #undef S
@@ -667,6 +683,35 @@ __global__ void k_cells_to_grad(const float4 *__restrict__ cells, float4 *__rest
     }
     float4 d = dmat[(size_t)x + (size_t)tex_w * y];
     dmat[(size_t)x + (size_t)tex_w * y] = make_float4(d.x + acc.x, d.y + acc.y, d.z + acc.z, d.w + acc.w);
+}
+// The same for every material of a material-table call in one launch (blockIdx.z = material): material k's range of the packed
+// gradient receives what its range of the cells holds (+=).
+__global__ void k_material_cells_to_grad(const float4 *__restrict__ cells, float4 *__restrict__ dmat, MaterialTable mt, int copies) {
+    const MaterialSlot m = mt.m[blockIdx.z];
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= m.w || y >= m.h) return;
+    const int tex_h = m.h, tex_w = m.w;
+    int ixs[3], dxs[3], nx = 0, iys[3], dys[3], ny = 0;         // (the footprint of k_cells_to_grad)
+    ixs[nx] = x - 1; dxs[nx++] = 1; ixs[nx] = x; dxs[nx++] = 0;
+    if (x == 0) { ixs[nx] = -1; dxs[nx++] = 0; }
+    if (x == tex_w - 1) { ixs[nx] = tex_w - 1; dxs[nx++] = 1; }
+    iys[ny] = y - 1; dys[ny++] = 1; iys[ny] = y; dys[ny++] = 0;
+    if (y == 0) { iys[ny] = -1; dys[ny++] = 0; }
+    if (y == tex_h - 1) { iys[ny] = tex_h - 1; dys[ny++] = 1; }
+    double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;              // (float64 for the copies, float32 order otherwise, as k_cells_to_grad)
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int k = 0; k < copies; k++)
+        for (int b = 0; b < ny; b++)
+            for (int a = 0; a < nx; a++) {
+                const size_t cell = (size_t)k * mt.ncells + (size_t)m.cell + (size_t)(ixs[a] + 1) + (size_t)(tex_w + 1) * (iys[b] + 1);
+                const float4 c = cells[4 * cell + 2 * dxs[a] + dys[b]];
+                if (copies == 1) { acc.x += c.x; acc.y += c.y; acc.z += c.z; acc.w += c.w; }
+                else { sx += c.x; sy += c.y; sz += c.z; sw += c.w; }
+            }
+    if (copies > 1) acc = make_float4((float)sx, (float)sy, (float)sz, (float)sw);
+    float4 *t = dmat + (size_t)m.texel + (size_t)x + (size_t)m.w * y;
+    const float4 d = *t;
+    *t = make_float4(d.x + acc.x, d.y + acc.y, d.z + acc.z, d.w + acc.w);
 }
 
 // render_duvdxy (uvgrad.py:76-98): mean over the samples of the screen->texture Jacobian, NaNs dropped
@@ -771,40 +816,46 @@ static dim3 persistent_grid(K kernel, size_t dyn, int nitems) {
     return dim3((unsigned)std::max<long>(1, std::min<long>(g, nitems)));
 }
 
-template <int SK, class A>
+// MT: material-table mode (io.mt.nmat > 0); it has no statistics variant (zdr_render_stats takes one material)
+template <int SK, class A, bool MT>
 static void launch_path(int nitems, size_t dyn, hipStream_t st, const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int backward, int stats) {
     // the environment-light code is a separate instantiation: inside the default kernels it cost 16 % (cbox forward)
 #define ZDR_LAUNCH_PERSISTENT(K) hipLaunchKernelGGL((K), persistent_grid((K), dyn, nitems), dim3(WAVE), dyn, st, S, R, C, io)
     if (S.env_count > 0) {
-        if (backward) ZDR_LAUNCH_PERSISTENT((k_path_bwd<SK, A, true>));
-        else if (stats) ZDR_LAUNCH_PERSISTENT((k_path<SK, A, true, true>));
-        else ZDR_LAUNCH_PERSISTENT((k_path<SK, A, false, true>));
+        if (backward) ZDR_LAUNCH_PERSISTENT((k_path_bwd<SK, A, true, MT>));
+        else if (stats && !MT) ZDR_LAUNCH_PERSISTENT((k_path<SK, A, true, true, false>));
+        else ZDR_LAUNCH_PERSISTENT((k_path<SK, A, false, true, MT>));
     } else {
-        if (backward) ZDR_LAUNCH_PERSISTENT((k_path_bwd<SK, A, false>));
-        else if (stats) ZDR_LAUNCH_PERSISTENT((k_path<SK, A, true, false>));
-        else ZDR_LAUNCH_PERSISTENT((k_path<SK, A, false, false>));
+        if (backward) ZDR_LAUNCH_PERSISTENT((k_path_bwd<SK, A, false, MT>));
+        else if (stats && !MT) ZDR_LAUNCH_PERSISTENT((k_path<SK, A, true, false, false>));
+        else ZDR_LAUNCH_PERSISTENT((k_path<SK, A, false, false, MT>));
     }
 #undef ZDR_LAUNCH_PERSISTENT
 }
 
-template <int INTEG, int SK, class A>
+template <int INTEG, int SK, class A, bool MT>
 static void launch_simple(dim3 grid, size_t dyn, hipStream_t st, const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int backward, int stats) {
     if (INTEG == ZDR_DIRECT && S.env_count > 0) {
-        if (backward) hipLaunchKernelGGL((k_simple<INTEG, SK, A, true, false, true>), grid, dim3(WAVE), dyn, st, S, R, C, io);
-        else if (stats) hipLaunchKernelGGL((k_simple<INTEG, SK, A, false, true, true>), grid, dim3(WAVE), dyn, st, S, R, C, io);
-        else hipLaunchKernelGGL((k_simple<INTEG, SK, A, false, false, true>), grid, dim3(WAVE), dyn, st, S, R, C, io);
+        if (backward) hipLaunchKernelGGL((k_simple<INTEG, SK, A, true, false, true, MT>), grid, dim3(WAVE), dyn, st, S, R, C, io);
+        else if (stats && !MT) hipLaunchKernelGGL((k_simple<INTEG, SK, A, false, true, true, false>), grid, dim3(WAVE), dyn, st, S, R, C, io);
+        else hipLaunchKernelGGL((k_simple<INTEG, SK, A, false, false, true, MT>), grid, dim3(WAVE), dyn, st, S, R, C, io);
     } else {
-        if (backward) hipLaunchKernelGGL((k_simple<INTEG, SK, A, true, false, false>), grid, dim3(WAVE), dyn, st, S, R, C, io);
-        else if (stats) hipLaunchKernelGGL((k_simple<INTEG, SK, A, false, true, false>), grid, dim3(WAVE), dyn, st, S, R, C, io);
-        else hipLaunchKernelGGL((k_simple<INTEG, SK, A, false, false, false>), grid, dim3(WAVE), dyn, st, S, R, C, io);
+        if (backward) hipLaunchKernelGGL((k_simple<INTEG, SK, A, true, false, false, MT>), grid, dim3(WAVE), dyn, st, S, R, C, io);
+        else if (stats && !MT) hipLaunchKernelGGL((k_simple<INTEG, SK, A, false, true, false, false>), grid, dim3(WAVE), dyn, st, S, R, C, io);
+        else hipLaunchKernelGGL((k_simple<INTEG, SK, A, false, false, false, MT>), grid, dim3(WAVE), dyn, st, S, R, C, io);
     }
+}
+template <int SK, class A, bool MT>
+static void launch_integ_mt(int integrator, dim3 grid, size_t dyn, hipStream_t st, const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int backward, int stats) {
+    if (integrator == ZDR_PATH) launch_path<SK, A, MT>(R.ntiles * R.nchunks, dyn, st, S, R, C, io, backward, stats);
+    else if (integrator == ZDR_DIRECT) launch_simple<ZDR_DIRECT, SK, A, MT>(grid, dyn, st, S, R, C, io, backward, stats);
+    else launch_simple<ZDR_COLLOCATED, SK, A, MT>(grid, dyn, st, S, R, C, io, backward, stats);
 }
 template <int SK, class A>
 static void launch_integ(int integrator, dim3 grid, size_t dyn, hipStream_t st, const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int backward, int stats) {
     if (integrator == ZDR_UVGRAD) hipLaunchKernelGGL((k_uvgrad<SK, A>), grid, dim3(WAVE), dyn, st, S, R, C, io);
-    else if (integrator == ZDR_PATH) launch_path<SK, A>(R.ntiles * R.nchunks, dyn, st, S, R, C, io, backward, stats);
-    else if (integrator == ZDR_DIRECT) launch_simple<ZDR_DIRECT, SK, A>(grid, dyn, st, S, R, C, io, backward, stats);
-    else launch_simple<ZDR_COLLOCATED, SK, A>(grid, dyn, st, S, R, C, io, backward, stats);
+    else if (io.mt.nmat > 0) launch_integ_mt<SK, A, true>(integrator, grid, dyn, st, S, R, C, io, backward, stats);
+    else launch_integ_mt<SK, A, false>(integrator, grid, dyn, st, S, R, C, io, backward, stats);
 }
 
 int zdr_launch_render(const DScene &S_in, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io,
@@ -823,7 +874,12 @@ int zdr_launch_render(const DScene &S_in, const RenderCfg &R, const SamplerCfg &
         if (accel_is_bvh) launch_integ<1, BvhAccel>(integrator, grid, dyn, st, S, R, C, io, backward, stats);
         else launch_integ<1, BruteAccel>(integrator, grid, dyn, st, S, R, C, io, backward, stats);
     }
-    if (backward) {   // fold the staging cells into d_material (+=)
+    if (backward && io.mt.nmat > 0) {   // every material's cells into its range of d_material (+=)
+        int mh = 1, mw = 1;
+        for (int k = 0; k < io.mt.nmat; k++) { mh = std::max(mh, (int)io.mt.m[k].h); mw = std::max(mw, (int)io.mt.m[k].w); }
+        dim3 g((mw + 63) / 64, mh, io.mt.nmat);
+        hipLaunchKernelGGL(k_material_cells_to_grad, g, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)io.d_material, io.mt, R.cell_copies);
+    } else if (backward) {   // fold the staging cells into d_material (+=)
         dim3 g((R.tex_w + 63) / 64, R.tex_h);
         hipLaunchKernelGGL(k_cells_to_grad, g, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)io.d_material, R.tex_h, R.tex_w, R.cell_copies);
     }

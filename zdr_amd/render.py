@@ -6,6 +6,9 @@
     image = scene.render(material, res=(W, H), spp=256, seed=0)      # (H, W, 4) float32, differentiable
     image.sum().backward()                                            # material.grad: (Ht, Wt, 4)
 
+    scene.material_slots = [0, 1, None]                               # one material per model (None: light or blocker)
+    image = scene.render([floor, box], res=(W, H), spp=256)           # floor.grad and box.grad after backward()
+
 Images and materials are PyTorch tensors on the GPU; the renderer borrows their device pointers
 for the duration of a call and enqueues its kernels on torch's current HIP stream.
 """
@@ -25,20 +28,73 @@ MAX_DEPTH = 16      # prb.py:15
 RR_DEPTH = 2        # prb.py:16
 
 
+def check_material_slots(slots, ninst: int) -> tuple:
+    """A material slot table as ``Scene.material_slots`` takes it: one entry per model, an int in [0, MAX_MATERIALS) or None.
+    Returns it as a tuple; raises ValueError otherwise."""
+    if isinstance(slots, (str, bytes)) or not hasattr(slots, "__len__"):
+        raise ValueError(f"material_slots must be a list with one entry per model, not {type(slots).__name__}")
+    if len(slots) != ninst:
+        raise ValueError(f"material_slots has {len(slots)} entries, the scene {ninst} models")
+    out = []
+    for i, k in enumerate(slots):
+        if k is None:
+            out.append(None)
+            continue
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"material_slots[{i}] = {k!r}: a slot is an int or None")
+        if not 0 <= int(k) < N.MAX_MATERIALS:
+            raise ValueError(f"material_slots[{i}] = {k}: slots lie in [0, {N.MAX_MATERIALS})")
+        out.append(int(k))
+    return tuple(out)
+
+
+def default_material_slots(emissions) -> tuple:
+    """The slot table of a material list given without ``material_slots``: the k-th non-emitting model gets material k."""
+    slots, k = [], 0
+    for e in emissions:
+        if (normalize_emission(e) > 0).any():
+            slots.append(None)
+        else:
+            slots.append(k)
+            k += 1
+    return tuple(slots)
+
+
+def resolve_material_slots(slots, emissions, nmat: int) -> tuple:
+    """The slot table a call with ``nmat`` materials uses: ``slots`` (already checked), or the default one when it is None."""
+    if not 1 <= nmat <= N.MAX_MATERIALS:
+        raise ValueError(f"{nmat} materials given: between 1 and {N.MAX_MATERIALS} are supported")
+    if slots is None:
+        slots = default_material_slots(emissions)
+        n = sum(k is not None for k in slots)
+        if n != nmat:
+            raise ValueError(f"{nmat} materials given for {n} non-emitting models: set material_slots, or pass one material per non-emitting model")
+        return slots
+    for i, k in enumerate(slots):
+        if k is not None and k >= nmat:
+            raise ValueError(f"material_slots[{i}] = {k}, but only {nmat} materials were given")
+    return tuple(slots)
+
+
 def _camera_pod(cam: Camera) -> N.CameraPOD:
     return N.CameraPOD(float(cam.fov), (C.c_float * 3)(*cam.origin), (C.c_float * 3)(*cam.target), (C.c_float * 3)(*cam.up))
 
 
 class Scene:
-    """A 3D scene for differentiable rendering w.r.t. one (H, W, 4) material texture
-    (diffuse rgb + roughness; specular fixed at 0.04).  Only the first model is textured; any
-    other model is a light (emission > 0) or a blocker (render.py:31-71, prb.py:45).
+    """A 3D scene for differentiable rendering w.r.t. (H, W, 4) material textures
+    (diffuse rgb + roughness; specular fixed at 0.04).  With one material tensor only the first model is
+    textured; any other model is a light (emission > 0) or a blocker (render.py:31-71, prb.py:45).  With a
+    list of materials each model is shaded by the material ``material_slots`` gives it (see ``render``).
 
     Attributes:
         camera (Camera): fov (full horizontal angle, radians), origin, target, up.
         use_tent_filter (bool): tent reconstruction filter if True (default), box filter if False.
         sampler (str): "cmj" (correlated multi-jitter, corrmj.py — default here) or "pmj02bn"
             (needs tables, see ``set_pmj02bn_tables``; the reference's tables are not shipped).
+        material_slots (list | None): one entry per model, the index of its material in the list given to
+            ``render`` or None (path / direct: a light or a blocker as without materials; collocated: black).
+            None (default): a single material tensor shades model 0 as the reference does, and a list shades
+            the k-th non-emitting model with its k-th material.
     """
 
     def __init__(self, models, integrator="direct", *, device=None, accel="auto", sampler="cmj"):
@@ -56,6 +112,8 @@ class Scene:
         self.prb_mode = "expectation"      # or "detached": the reference's constant-roulette / constant-MIS adjoint; "literal": with the BSDF-sample seed of prb.py:162 as written (include/zdr.h)
         self.env_count = 0
         self._handle = None
+        self._material_slots = None
+        self._uploaded_slots = None        # the slot table the native scene holds (None: never uploaded)
         self.load_geometry(models, accel=accel)
 
     # ------------------------------------------------------------------ geometry / lights
@@ -70,6 +128,8 @@ class Scene:
         if getattr(self, "_finalizer", None) is not None:   # a second load_geometry: the old handle (and the tables set on it) go
             self._finalizer()
             self._handle, self.env_count, self._pmj_tables_set = None, 0, False
+        self._material_slots = None
+        self._uploaded_slots = None
         N.check(L.zdr_scene_create(arrays.verts.ctypes.data, arrays.verts.shape[0], arrays.tris.ctypes.data, arrays.tris.shape[0],
                                    arrays.inst_tri_begin.ctypes.data, arrays.inst_xform.ctypes.data, arrays.inst_emission.ctypes.data,
                                    arrays.ninst, self.device.index, N.ACCELS[accel], C.byref(h)))
@@ -120,6 +180,85 @@ class Scene:
         assert pmj.ndim == 3 and pmj.shape[2] == 2 and bn.ndim == 3 and bn.shape[1] == bn.shape[2]
         N.check(N.lib().zdr_scene_set_pmj02bn_tables(self._handle, pmj.ctypes.data, pmj.shape[0], pmj.shape[1], bn.ctypes.data, bn.shape[0], bn.shape[1]))
         self._pmj_tables_set = True
+
+    # -------------------------------------------------------------------------- materials
+    @property
+    def material_slots(self):
+        return None if self._material_slots is None else list(self._material_slots)
+
+    @material_slots.setter
+    def material_slots(self, slots):
+        if slots is None:
+            self._material_slots = None
+            return
+        slots = check_material_slots(slots, self.inst_count)
+        self._upload_slots(slots)
+        self._material_slots = slots
+
+    def _upload_slots(self, slots: tuple):
+        if slots == self._uploaded_slots:
+            return
+        table = np.array([-1 if k is None else k for k in slots], np.int32)
+        N.check(N.lib().zdr_scene_set_material_slots(self._handle, table.ctypes.data, self._stream()))
+        self._uploaded_slots = slots
+
+    def _material_call(self, materials, dims, slots=None):
+        """(packed material tensor, int32 dims array, slot table) of a material-table call: ``materials`` is a list / tuple of
+        (H, W, 4) tensors (packed here, a copy when there are several), or one packed tensor with ``dims`` = [(h, w), ...]."""
+        if isinstance(materials, (list, tuple)):
+            mats = list(materials)
+            for m in mats:
+                self._check_material(m)
+            dims = [(int(m.shape[0]), int(m.shape[1])) for m in mats]
+            packed = mats[0].detach().contiguous() if len(mats) == 1 else torch.cat([m.detach().reshape(-1, 4) for m in mats])
+        else:
+            if dims is None:
+                raise ValueError("a packed material tensor needs dims = [(h, w), ...]")
+            packed = materials.detach().contiguous()
+            if packed.device != self.device or packed.dtype != torch.float32:
+                raise ValueError(f"materials must be float32 tensors on {self.device}")
+            dims = [(int(h), int(w)) for h, w in dims]
+            if packed.numel() != 4 * sum(h * w for h, w in dims):
+                raise ValueError(f"the packed materials hold {packed.numel() // 4} texels, dims {sum(h * w for h, w in dims)}")
+        if slots is None:
+            slots = resolve_material_slots(self._material_slots, self.emissions, len(dims))
+        self._upload_slots(tuple(slots))
+        return packed, np.ascontiguousarray(np.array(dims, np.int32).reshape(-1, 2)), tuple(slots)
+
+    def render_forward_materials(self, materials, res, spp, seed, *, dims=None, rect=None, samples=None, out=None, tile_shard=None, slots=None):
+        """``render_forward`` with one material per slot (include/zdr.h, zdr_render_forward_materials).  ``materials``: a list of
+        (H_k, W_k, 4) tensors, or their packed texels with ``dims``.  ``slots``: the slot table to use (default: ``material_slots``,
+        or the default mapping)."""
+        packed, d, _ = self._material_call(materials, dims, slots)
+        if out is None:
+            image = torch.zeros((res[1], res[0], 4), dtype=torch.float32, device=self.device)
+        else:
+            image = out
+            if image.shape != (res[1], res[0], 4) or image.dtype != torch.float32 or image.device != self.device or not image.is_contiguous():
+                raise ValueError(f"out must be a contiguous float32 ({res[1]}, {res[0]}, 4) tensor on {self.device}")
+        p = self._params(res, spp, seed, (1, 1), rect, samples, tile_shard=tile_shard)
+        N.check(N.lib().zdr_render_forward_materials(self._handle, C.byref(p), packed.data_ptr(), d.ctypes.data, d.shape[0], image.data_ptr(), self._stream()))
+        return image
+
+    def render_backward_materials(self, grad_output, d_materials, materials, res, spp, seed, *, dims=None, rect=None, samples=None, camera=None,
+                                  tile_shard=None, slots=None):
+        """``render_backward`` with one material per slot: accumulates into ``d_materials`` (a list shaped like ``materials``, or
+        one packed tensor); uses ``seed + 1`` like render_backward."""
+        packed, d, _ = self._material_call(materials, dims, slots)
+        listed = isinstance(d_materials, (list, tuple))
+        dpacked = (torch.cat([g.reshape(-1, 4) for g in d_materials]) if len(d_materials) > 1 else d_materials[0]) if listed else d_materials
+        if dpacked.numel() != packed.numel() or not dpacked.is_contiguous() or dpacked.device != self.device or dpacked.dtype != torch.float32:
+            raise ValueError(f"d_materials must be contiguous float32 on {self.device}, shaped like the materials")
+        g = grad_output.reshape(res[1], res[0], 4).to(device=self.device, dtype=torch.float32).contiguous()
+        p = self._params(res, spp, seed + 1, (1, 1), rect, samples, camera, tile_shard=tile_shard)
+        N.check(N.lib().zdr_render_backward_materials(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
+                                                      dpacked.data_ptr(), self._stream()))
+        if listed and len(d_materials) > 1:
+            off = 0
+            for t in d_materials:
+                t.copy_(dpacked[off:off + t.numel() // 4].reshape(t.shape))
+                off += t.numel() // 4
+        return d_materials
 
     # ------------------------------------------------------------------------- launching
     def _stream(self):
@@ -209,10 +348,46 @@ class Scene:
             res, spp, seed = ctx.args
             return scene.render_backward(grad_output, mat_grad, material.detach(), res, spp, seed, camera=ctx.camera)
 
+    class MaterialsOperator(torch.autograd.Function):
+        """render() of several materials: takes their packed texels, returns their packed gradient (torch.cat's own backward
+        hands each material its part)."""
+        @staticmethod
+        def forward(ctx, packed, self, dims, slots, res, spp, seed):
+            ctx.save_for_backward(packed)
+            ctx.scene = weakref.ref(self)
+            ctx.args = (dims, slots, res, spp, seed)
+            ctx.camera = self.camera.copy()
+            ctx.emissions = self.emissions
+            return self.render_forward_materials(packed, res, spp, seed, dims=dims, slots=slots)
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            scene = ctx.scene()
+            if scene.emissions is not ctx.emissions:        # as RenderOperator: lights left at the snapshot
+                scene.update_lights(ctx.emissions)
+            packed, = ctx.saved_tensors
+            dims, slots, res, spp, seed = ctx.args
+            d = torch.zeros(packed.size(), dtype=packed.dtype, device=packed.device)
+            # slots = the forward's table: uploaded again if material_slots changed in between
+            scene.render_backward_materials(grad_output, d, packed.detach(), res, spp, seed, dims=dims, camera=ctx.camera, slots=slots)
+            return d, None, None, None, None, None, None
+
     def render(self, material, *, res, spp, seed=0):
         """Renders the scene; differentiable w.r.t. ``material`` ((Ht, Wt, 4) float32 on the GPU).
-        res = (width, height); returns (height, width, 4) (render.py:225-241)."""
-        return Scene.RenderOperator.apply(material, self, res, spp, seed)
+        res = (width, height); returns (height, width, 4) (render.py:225-241).
+
+        ``material`` may also be a list or tuple of such tensors (sizes may differ): model i is then shaded by material
+        ``material_slots[i]``, or — with ``material_slots`` unset — the k-th non-emitting model by the k-th material (the list
+        must then hold one material per non-emitting model).  With ``material_slots`` set a single tensor is a one-element list."""
+        if not isinstance(material, (list, tuple)) and self._material_slots is None:
+            return Scene.RenderOperator.apply(material, self, res, spp, seed)
+        mats = list(material) if isinstance(material, (list, tuple)) else [material]
+        for m in mats:
+            self._check_material(m)
+        slots = resolve_material_slots(self._material_slots, self.emissions, len(mats))
+        dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
+        packed = mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
+        return Scene.MaterialsOperator.apply(packed, self, dims, slots, res, spp, seed)
 
     def render_duvdxy(self, material, *, res, spp, seed=0):
         """Gradient of the texture coordinates w.r.t. screen-space coordinates: a (height, width, 4) tensor
