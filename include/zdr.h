@@ -33,9 +33,9 @@ extern "C" {
 #endif
 
 #define ZDR_VERSION_STRING "zdr-mi355x 0.3 (gfx950)"
-/* Bumped whenever a struct of this header changes size or meaning (2: tile shard + prb_mode fields; 3: struct_size).
- * A binding asserts zdr_abi_version() == ZDR_ABI_VERSION of the header it was written against. */
-#define ZDR_ABI_VERSION 3
+/* Bumped whenever a struct of this header changes size or meaning, or the entry points grow (2: tile shard + prb_mode fields;
+ * 3: struct_size; 4: environment-map gradient).  A binding asserts zdr_abi_version() == ZDR_ABI_VERSION of the header it was written against. */
+#define ZDR_ABI_VERSION 4
 
 enum { ZDR_OK = 0, ZDR_E_INVALID = -1, ZDR_E_HIP = -2, ZDR_E_UNSUPPORTED = -3, ZDR_E_NOMEM = -4 };
 
@@ -130,6 +130,13 @@ int zdr_scene_set_emissions(zdr_scene *scene, const float *inst_emission, void *
 int zdr_scene_set_envmap(zdr_scene *scene, const float *tex, uint32_t tex_h, uint32_t tex_w, const float *alias_prob,
                          const int32_t *alias_idx, const float *pdf, uint32_t map_w, uint32_t map_h);
 
+/* Replaces the environment map's texels in place, keeping its size and its importance-sampling tables (those of the last
+ * zdr_scene_set_envmap): tex is DEVICE float32, env_h x env_w x 4 as given to zdr_scene_set_envmap (already square).  The copy is
+ * stream-ordered and done by a kernel, and the scene's texture buffer is never reallocated: a captured call records the copy, and
+ * graphs that read the map keep reading the same buffer.  tex must be 16-byte aligned (the copy moves one float4 texel per load;
+ * hipMalloc'ed memory is).  ZDR_E_INVALID when no environment map is set or tex is misaligned. */
+int zdr_scene_set_envmap_texture(zdr_scene *scene, const float *tex, void *stream);
+
 /* Tables of the PMJ02bn sampler (pmj02bn.py:9-18; the reference's own are absent,
  * .MISSING_LARGE_BLOBS).  HOST inputs, copied to the device: pmj [nsets][nsamples][2] uint32
  * (value / 2^32), bn [ntex][res][res] uint16 (value / 2^16). */
@@ -171,6 +178,22 @@ int zdr_render_forward_materials(zdr_scene *scene, const zdr_render_params *para
  * material receives the gradient of the vertices shaded with it.  Staging cells are sized for all materials together. */
 int zdr_render_backward_materials(zdr_scene *scene, const zdr_render_params *params, const float *d_image, const float *materials,
                                   const int32_t *dims, uint32_t nmat, float *d_materials, void *stream);
+
+/* zdr_render_backward / zdr_render_backward_materials that also differentiate with respect to the environment map: d_env (DEVICE,
+ * env_h x env_w x 4 float32, the map's size as set) is ACCUMULATED into (+=) like d_material.  The gradient is exact for the forward in
+ * every prb_mode: the importance-sampling tables are held fixed, and neither Russian roulette nor the MIS weights read the map's values,
+ * so each term of the estimator that reads the map (a path or camera ray that escapes, a light sample on the environment) is a weight
+ * times a bilinear lookup, and its gradient is that weight times the pixel's cotangent at the lookup's four texels.  Alpha receives 0.
+ * A term whose gradient is NaN is dropped on its own; a path whose radiance turns NaN later (the forward drops that sample) keeps the
+ * environment terms it met before.  ZDR_E_INVALID when d_env is given and no environment map is set, whatever the integrator.
+ * Otherwise d_env == NULL behaves exactly like the sibling call, and so does ZDR_COLLOCATED, which has no environment term and
+ * leaves d_env untouched.  The map's staging cells have copies of their own (up to 2^22 cells in all), zeroed and gathered per call.  Runs in the
+ * material-table kernels (a single material is a table of one, instance 0 shading with it), so the material gradient equals the
+ * sibling's up to the order of float atomics; the _materials form takes at most ZDR_MAX_MATERIALS - 1 materials. */
+int zdr_render_backward_env(zdr_scene *scene, const zdr_render_params *params, const float *d_image, const float *material,
+                            float *d_material, float *d_env, void *stream);
+int zdr_render_backward_materials_env(zdr_scene *scene, const zdr_render_params *params, const float *d_image, const float *materials,
+                                      const int32_t *dims, uint32_t nmat, float *d_materials, float *d_env, void *stream);
 
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,

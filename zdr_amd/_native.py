@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "libzdr_hip.so")
 COLLOCATED, DIRECT, PATH, UVGRAD = 0, 1, 2, 3
 SAMPLER_CMJ, SAMPLER_PMJ02BN = 0, 1
 ACCEL_AUTO, ACCEL_BRUTE, ACCEL_BVH = 0, 1, 2
-ABI_VERSION = 3                # ZDR_ABI_VERSION of the include/zdr.h this binding mirrors
+ABI_VERSION = 4                # ZDR_ABI_VERSION of the include/zdr.h this binding mirrors
 MAX_MATERIALS = 16             # ZDR_MAX_MATERIALS
 PRB_MODES = {"expectation": 0, "detached": 1, "literal": 2}
 INTEGRATORS = {"collocated": COLLOCATED, "direct": DIRECT, "path": PATH}   # render.py:65-69
@@ -27,7 +27,8 @@ COUNTER_NAMES = ("samples", "closest_rays", "closest_hits", "shadow_rays", "shad
 EXPORTS = ("zdr_version", "zdr_abi_version", "zdr_last_error", "zdr_scene_create", "zdr_scene_destroy", "zdr_scene_info",
            "zdr_scene_set_emissions", "zdr_scene_set_envmap", "zdr_scene_set_pmj02bn_tables", "zdr_render_forward", "zdr_render_backward",
            "zdr_render_stats", "zdr_scene_check", "zdr_trace_closest", "zdr_trace_any", "zdr_sampler_dump", "zdr_vertex_sampler_dump", "zdr_path_dump", "zdr_debug_build_accel", "zdr_debug_never_occluders",
-           "zdr_scene_set_material_slots", "zdr_render_forward_materials", "zdr_render_backward_materials")
+           "zdr_scene_set_material_slots", "zdr_render_forward_materials", "zdr_render_backward_materials",
+           "zdr_scene_set_envmap_texture", "zdr_render_backward_env", "zdr_render_backward_materials_env")
 
 
 class CameraPOD(C.Structure):
@@ -84,6 +85,9 @@ def lib():
     L.zdr_scene_set_material_slots.argtypes = [vp, ip, vp]
     L.zdr_render_forward_materials.argtypes = [vp, C.POINTER(RenderParams), fp, ip, C.c_uint32, fp, vp]
     L.zdr_render_backward_materials.argtypes = [vp, C.POINTER(RenderParams), fp, fp, ip, C.c_uint32, fp, vp]
+    L.zdr_scene_set_envmap_texture.argtypes = [vp, fp, vp]
+    L.zdr_render_backward_env.argtypes = [vp, C.POINTER(RenderParams), fp, fp, fp, fp, vp]
+    L.zdr_render_backward_materials_env.argtypes = [vp, C.POINTER(RenderParams), fp, fp, ip, C.c_uint32, fp, fp, vp]
     L.zdr_render_stats.argtypes = [vp, C.POINTER(RenderParams), fp, C.POINTER(C.c_uint64), vp]
     L.zdr_scene_check.argtypes = [vp, vp]
     L.zdr_trace_closest.argtypes = [vp, fp, C.c_uint32, ip, fp, vp]

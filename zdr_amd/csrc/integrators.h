@@ -4,6 +4,7 @@
 // trip every live lane shades ONE vertex of its path and finished lanes immediately start
 // their next sample, so short paths do not idle behind the longest path of the wave.
 #pragma once
+#include <type_traits>
 #include "accel.h"
 #include "internal.h"
 #include "microfacet.h"
@@ -39,6 +40,12 @@ ZD bool any_nan4(float4 g) { return (g.x != g.x) | (g.y != g.y) | (g.z != g.z) |
 ZD float4 brdf_grad(float cz_over_pi, float dfdr, f3 ct) {     // d(f cos)[ct] w.r.t. (d.rgb, r), App. A.6
     return make_float4(ct.x * cz_over_pi, ct.y * cz_over_pi, ct.z * cz_over_pi, (ct.x + ct.y + ct.z) * dfdr);
 }
+
+// Environment-gradient kernels (EG, zdr_render_backward_env): one term of the estimator that reads the map, radiance += w * env_lookup(uv).
+// The importance-sampling tables, the roulette and the MIS weights do not read the map's values, so d(radiance)/d(map) is w times the
+// bilinear weights of the lookup at uv: the caller scatters (w * cotangent) there.  w = 0: no such term.
+struct EnvTerm { f3 w; f2 uv; };
+ZD void env_term_clear(EnvTerm &e) { e.w = mk3(0.0f); e.uv.x = 0.0f; e.uv.y = 0.0f; }
 
 // ---------------------------------------------------------------------------- collocated
 // collocated.py:11-31 / 35-57: L = brdf(wo, wo) / t^2
@@ -106,11 +113,18 @@ ZD float4 uvgrad_sample(const DScene &S, int *lds, f3 o, f3 d, f3 odx, f3 ddx, f
 // -------------------------------------------------------------------------------- direct
 // direct.py:21-85 (forward) / 89-167 (adjoint; gradient written once at the primary uv, App. B-11)
 // MT: an instance with a material is shaded by it, one without returns its emission (zdr.h, zdr_scene_set_material_slots)
-template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false>
+// EG (implies ENV): the terms that read the environment map go to e_cam (camera miss, weight 1, or the light sample) and e_bsdf (BSDF sample
+// that escapes), the two cannot both be a camera miss.
+template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false, bool EG = false>
 ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int *lds,
-                    Sampler &smp, f3 o, f3 d, unsigned long long cam_mask, f3 le_grad, Counters &cnt, f2 &guv, float4 &grad, int &gmat) {
+                    Sampler &smp, f3 o, f3 d, unsigned long long cam_mask, f3 le_grad, Counters &cnt, f2 &guv, float4 &grad, int &gmat,
+                    EnvTerm *e_cam = nullptr, EnvTerm *e_bsdf = nullptr) {
+    static_assert(!EG || (ENV && BWD), "the environment gradient is a backward mode of the environment kernels");
     COUNT(C_CLOSEST);
     Hit h = A::closest_camera(S, lds, o, d, cam_mask);
+    if constexpr (EG) {
+        if (h.slot < 0 && S.env_count > 0) { e_cam->w = mk3(1.0f); e_cam->uv = direction_to_uv(d); }
+    }
     if (h.slot < 0) return (ENV && S.env_count > 0) ? env_lookup(S, direction_to_uv(d)) : mk3(0.0f);   // direct.py:23-24
     COUNT(C_HITS);
     Interaction it = surface_interact(S, h);
@@ -133,7 +147,9 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
     // or group by group: (light, triangle) in one pass, either 2-D draw as an index pass + one packed pass, six passes instead of nine — costs it more in
     // spills at 128 VGPRs than the passes save: 1.12 -> 1.18 ms in round 3, 0.873 / 1.05 -> 0.883 / 1.10 ms in round 4.)
     float u_pick = sampler_next<SK>(C, smp);
-    LightSample light = sample_light<ENV>(S, it.p, u_pick, [&]() { return sampler_next<SK>(C, smp); }, [&]() { return sampler_next2<SK>(C, smp); });
+    f2 env_uv; env_uv.x = -1.0f; env_uv.y = 0.0f;
+    LightSample light = sample_light<ENV>(S, it.p, u_pick, [&]() { return sampler_next<SK>(C, smp); }, [&]() { return sampler_next2<SK>(C, smp); },
+                                          EG ? &env_uv : nullptr);
     COUNT(C_SHADOW);
     bool occluded = A::any_shadow(S, lds, it.p, light.wi, 1e-4f, light.dist);
     Onb onb = make_onb(it.ns);
@@ -150,6 +166,9 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
             f3 W = (light.eval * mis) * inv_dn;
             float dl_; float4 gr = brdf_grad(wil.z * ZDR_INV_PI, ggx_dfdr_from(g, wo, wil, roughness, dl_), W * le_grad);
             mat_grad.x += gr.x; mat_grad.y += gr.y; mat_grad.z += gr.z; mat_grad.w += gr.w;
+        }
+        if constexpr (EG) {
+            if (env_uv.x >= 0.0f) { e_cam->w = (bsdf * mis) * inv_dn; e_cam->uv = env_uv; }
         }
     }
     // use_MIS = True (direct.py:14): one BSDF sample, emitter lookup only
@@ -188,6 +207,14 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
                 mat_grad.x += gr.x; mat_grad.y += gr.y; mat_grad.z += gr.z; mat_grad.w += gr.w;
             }
         }
+        if constexpr (EG) {   // an escaping BSDF sample has a gradient even where the map is zero now (the test above skips it)
+            if (h2.slot < 0 && S.env_count > 0) {
+                GgxTerms g = ggx_terms(wo, wi_local, roughness);
+                float pdf_bsdf = ggx_pdf_from(g, wo, wi_local);
+                e_bsdf->w = (ggx_brdf_from(g, wi_local, diffuse) * rcp(pdf_bsdf)) * balanced_heuristic(pdf_bsdf, pdf_light);
+                e_bsdf->uv = direction_to_uv(wi);
+            }
+        }
     }
     if (BWD) { grad = mat_grad; guv = it.uv; }
     return radiance;
@@ -224,14 +251,17 @@ struct PathState {
 // (miss, back face, emitter, untextured instance); otherwise `it` is the vertex to shade.  BWD: sets
 // term_Li (and the MIS-weight fraction of the terminal emitter) when the path ended on a light.
 // MT: the instance's material slot decides (inst_slot: MaterialTable::inst_slot) and `it.mat` receives it.
+// env_hit (environment-gradient kernels): receives the miss term (beta * mis at the map coordinates of the ray), left alone otherwise.
 template <bool BWD, bool STATS, bool ENV, bool MT = false>
 ZD bool path_arrive(const DScene &S, PathState &ps, const Hit &h, Interaction &it, f3 &term_Li, Counters &cnt, float *term_plfrac = nullptr,
-                    const int32_t *inst_slot = nullptr) {
+                    const int32_t *inst_slot = nullptr, EnvTerm *env_hit = nullptr) {
     if (h.slot < 0) {                                                             // prb.py:26-32, in the form of direct.py:70-83
         if (ENV && S.env_count > 0) {
-            f3 em = env_lookup(S, direction_to_uv(ps.d));
+            const f2 euv = direction_to_uv(ps.d);
+            f3 em = env_lookup(S, euv);
             float pdf_light = env_sampled_light_pdf(S, ps.d, S.env_count + S.light_count);
             float mis = balanced_heuristic(ps.pdf_bsdf, pdf_light);
+            if (env_hit) { env_hit->w = ps.beta * mis; env_hit->uv = euv; }
             ps.L = ps.L + (ps.beta * mis) * em;
             if (BWD) { term_Li = em * mis;
                        if (term_plfrac) *term_plfrac = (ps.pdf_bsdf + pdf_light > 1e-4f) ? pdf_light * rcp(ps.pdf_bsdf + pdf_light) : 0.0f; }
@@ -276,7 +306,8 @@ struct NeeTerms { f3 dL, bW, fLW, neeM; float cL, dfLdr; };
 
 // material, frame and the light sample of the vertex (prb.py:47-58); BWD: resets pv
 template <int SK, bool BWD, bool STATS, bool ENV, bool MT = false>
-ZD ShadeCtx shade_ctx(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, PathState &ps, const Interaction &it, PathVertex &pv, Counters &cnt) {
+ZD ShadeCtx shade_ctx(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, PathState &ps, const Interaction &it, PathVertex &pv, Counters &cnt,
+                      f2 *env_uv = nullptr) {
     ShadeCtx x;
     float4 m;
     if constexpr (MT) m = read_bsdf_in(io.material, io.mt.m[it.mat], it.uv);
@@ -295,17 +326,18 @@ ZD ShadeCtx shade_ctx(const DScene &S, const RenderCfg &R, const SamplerCfg &C, 
     if (x.pre) {                                                 // all seven numbers of the vertex at once, two permutations per register (sampler.h)
         const VertexSamples v = cmj_vertex_samples(C, ps.smp);
         x.u_lobe = v.u_lobe; x.u_dir = v.u_dir; x.i_rr = v.i_rr;
-        x.light = sample_light<ENV>(S, it.p, v.u_pick, [&]() { return v.u_prim; }, [&]() { return v.u_pt; });
+        x.light = sample_light<ENV>(S, it.p, v.u_pick, [&]() { return v.u_prim; }, [&]() { return v.u_pt; }, env_uv);
     } else {
         float u_pick = sampler_next<SK>(C, ps.smp);
-        x.light = sample_light<ENV>(S, it.p, u_pick, [&]() { return sampler_next<SK>(C, ps.smp); }, [&]() { return sampler_next2<SK>(C, ps.smp); });
+        x.light = sample_light<ENV>(S, it.p, u_pick, [&]() { return sampler_next<SK>(C, ps.smp); }, [&]() { return sampler_next2<SK>(C, ps.smp); }, env_uv);
     }
     x.wil = to_local(x.onb, x.light.wi);
     return x;
 }
 
-template <bool BWD>
-ZD NeeTerms nee_terms(const ShadeCtx &x, f3 beta_in) {                            // beta_in: throughput arriving at the vertex
+// EG (environment-gradient kernels): env_w receives the per-unit weight of the light sample's radiance, beta_in f mis / max(pdf, 1e-4)
+template <bool BWD, bool EG = false>
+ZD NeeTerms nee_terms(const ShadeCtx &x, f3 beta_in, f3 *env_w = nullptr) {       // beta_in: throughput arriving at the vertex
     NeeTerms n; n.dL = n.bW = n.fLW = n.neeM = mk3(0.0f); n.cL = 0.0f; n.dfLdr = 0.0f;
     GgxTerms g = ggx_terms(x.wo, x.wil, x.roughness);
     f3 bsdf = ggx_brdf_from(g, x.wil, x.diffuse);
@@ -313,6 +345,7 @@ ZD NeeTerms nee_terms(const ShadeCtx &x, f3 beta_in) {                          
     float mis = balanced_heuristic(x.light.pdf, pb);
     float inv_dn = rcp(fmaxf(x.light.pdf, 1e-4f));
     n.dL = (((beta_in * bsdf) * mis) * x.light.eval) * inv_dn;
+    if constexpr (EG) *env_w = ((beta_in * bsdf) * mis) * inv_dn;
     if (BWD) {
         f3 W = (x.light.eval * mis) * inv_dn;
         float dlnpL;
@@ -384,19 +417,29 @@ ZD bool sample_bsdf(const RenderCfg &R, const SamplerCfg &C, const ShadeCtx &x, 
 // so the image and the gradients are the reference's bit for bit.  Returns the shadow segment (if any) and whether the
 // path stops at this vertex; the continuation ray is (ps.o, ps.d).
 struct VertexRays { bool shadow, stop; f3 sd; float stmax; };
-template <int SK, bool BWD, bool STATS, bool ENV, bool MT = false>
+// env (environment-gradient kernels): receives the light sample's weight and map coordinates when it sampled the environment (w = 0
+// otherwise); then a sample that carries no radiance now — a texel that is zero but that the tables still sample — still has a
+// gradient, and its shadow ray is traced.
+template <int SK, bool BWD, bool STATS, bool ENV, bool MT = false, bool EG = false>
 ZD VertexRays path_vertex_begin(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io,
-                                PathState &ps, const Interaction &it, PathVertex &pv, NeeTerms &n, Counters &cnt) {
-    const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, cnt);
+                                PathState &ps, const Interaction &it, PathVertex &pv, NeeTerms &n, Counters &cnt, EnvTerm *env = nullptr) {
+    f2 env_uv; env_uv.x = -1.0f; env_uv.y = 0.0f;
+    const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, cnt, EG ? &env_uv : nullptr);
     VertexRays vr; vr.sd = x.light.wi; vr.stmax = x.light.dist;
     n.dL = n.bW = n.fLW = n.neeM = mk3(0.0f); n.cL = 0.0f; n.dfLdr = 0.0f;
+    if constexpr (EG) env_term_clear(*env);
     COUNT(C_SHADOW);
     vr.shadow = x.wil.z >= 1e-4f;
     if (vr.shadow) {
-        n = nee_terms<BWD>(x, ps.beta);
-        const bool nothing = (n.dL.x == 0.0f) & (n.dL.y == 0.0f) & (n.dL.z == 0.0f) &&
-                             (!BWD || ((n.bW.x == 0.0f) & (n.bW.y == 0.0f) & (n.bW.z == 0.0f) & (n.fLW.x == 0.0f) & (n.fLW.y == 0.0f) & (n.fLW.z == 0.0f) &
-                                       (n.neeM.x == 0.0f) & (n.neeM.y == 0.0f) & (n.neeM.z == 0.0f) & (fabsf(n.dfLdr) < 3.0e38f)));
+        if constexpr (EG) {
+            n = nee_terms<BWD, true>(x, ps.beta, &env->w);
+            if (env_uv.x < 0.0f) env->w = mk3(0.0f);
+            env->uv = env_uv;
+        } else n = nee_terms<BWD>(x, ps.beta);
+        bool nothing = (n.dL.x == 0.0f) & (n.dL.y == 0.0f) & (n.dL.z == 0.0f) &&
+                       (!BWD || ((n.bW.x == 0.0f) & (n.bW.y == 0.0f) & (n.bW.z == 0.0f) & (n.fLW.x == 0.0f) & (n.fLW.y == 0.0f) & (n.fLW.z == 0.0f) &
+                                 (n.neeM.x == 0.0f) & (n.neeM.y == 0.0f) & (n.neeM.z == 0.0f) & (fabsf(n.dfLdr) < 3.0e38f)));
+        if constexpr (EG) nothing = nothing && (env->w.x == 0.0f) & (env->w.y == 0.0f) & (env->w.z == 0.0f);
         vr.shadow = !nothing;
     }
     if (vr.shadow) COUNT(C_SHADOW_TRACED);                                          // counter 7: shadow rays actually traced
@@ -405,16 +448,29 @@ ZD VertexRays path_vertex_begin(const DScene &S, const RenderCfg &R, const Sampl
     return vr;
 }
 
-template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false>
+// EG (implies BWD and ENV): env receives the NEE term of the vertex when its light sample went to the environment unoccluded (else w = 0)
+template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false, bool EG = false>
 ZD bool path_shade(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int *lds,
-                   PathState &ps, const Interaction &it, PathVertex &pv, Hit &h, Counters &cnt) {
+                   PathState &ps, const Interaction &it, PathVertex &pv, Hit &h, Counters &cnt, EnvTerm *env = nullptr) {
     if constexpr (A::kFuseRays) {
         NeeTerms n;
-        const VertexRays vr = path_vertex_begin<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, n, cnt);
+        const VertexRays vr = path_vertex_begin<SK, BWD, STATS, ENV, MT, EG>(S, R, C, io, ps, it, pv, n, cnt, env);
         bool occluded;
         A::shadow_and_closest(S, lds, vr.shadow, it.p, vr.sd, 1e-4f, vr.stmax, !vr.stop, ps.o, ps.d, occluded, h);
         if (vr.shadow && !occluded) nee_apply<BWD>(ps, pv, n);
+        else if constexpr (EG) env->w = mk3(0.0f);
         return vr.stop;
+    } else if constexpr (EG) {
+        f2 env_uv; env_uv.x = -1.0f; env_uv.y = 0.0f;
+        const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, cnt, &env_uv);
+        const bool occluded = A::any_shadow(S, lds, it.p, x.light.wi, 1e-4f, x.light.dist);
+        env_term_clear(*env);
+        if (!occluded && x.wil.z >= 1e-4f) {
+            nee_apply<BWD>(ps, pv, nee_terms<BWD, true>(x, ps.beta, &env->w));
+            if (env_uv.x < 0.0f) env->w = mk3(0.0f);
+            env->uv = env_uv;
+        }
+        return sample_bsdf<SK, BWD>(R, C, x, ps, it, pv);
     } else {
         const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, cnt);
         COUNT(C_SHADOW);
@@ -456,13 +512,18 @@ ZD uint32_t lane_rank(unsigned long long mask) {               // number of set 
 // Generates ZDR_RING_BATCH camera samples for every pixel of the tile (lane = pixel here).  Samples that end
 // at the camera ray (miss, emitter, back face) are finished at once: their radiance goes to `sum`,
 // this lane's own pixel.
-template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false>
+// on_miss (environment-gradient kernels): called by the whole wave once per camera sample with the term of a camera ray that
+// missed (EnvTerm, w = 0 for the other lanes).  NoEnvMiss: no such call.
+struct NoEnvMiss { ZD void operator()(const EnvTerm &) const {} };
+template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false, class MISS = NoEnvMiss>
 ZD void primary_refill(const DScene &S, const RenderCfg &R, const SamplerCfg &C, int *lds, int x, int y, bool valid, unsigned long long cam_mask,
                        uint32_t perm_seed, int bank, uint32_t &next_sample, uint32_t s_end, PrimaryQueue &q, f3 &sum, Counters &cnt,
-                       const int32_t *inst_slot = nullptr) {
+                       const int32_t *inst_slot = nullptr, MISS on_miss = MISS()) {
+    constexpr bool EG = !std::is_same<MISS, NoEnvMiss>::value;
     for (int b = 0; b < ZDR_RING_BATCH && next_sample < s_end; b++, next_sample++) {   // wave-uniform
         bool park = false;
         float4 e0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), e1 = e0;
+        EnvTerm miss; env_term_clear(miss);
         if (valid) {
             PathState ps;
             ps.smp = sampler_make<SK>(C, (uint32_t)x, (uint32_t)y, perm_seed, next_sample);
@@ -471,7 +532,7 @@ ZD void primary_refill(const DScene &S, const RenderCfg &R, const SamplerCfg &C,
             COUNT(C_SAMPLES); COUNT(C_CLOSEST);
             Hit h = A::closest_camera(S, lds, ps.o, ps.d, cam_mask);
             Interaction it; f3 tl;
-            if (path_arrive<false, STATS, ENV, MT>(S, ps, h, it, tl, cnt, nullptr, inst_slot)) {
+            if (path_arrive<false, STATS, ENV, MT>(S, ps, h, it, tl, cnt, nullptr, inst_slot, EG ? &miss : nullptr)) {
                 if (!BWD) {                                                     // a path without vertices has no gradient
                     if (!any_nan(ps.L)) sum = sum + clamp_radiance(ps.L);       // integrator.py:27-28
                     else COUNT(C_NAN);
@@ -482,6 +543,7 @@ ZD void primary_refill(const DScene &S, const RenderCfg &R, const SamplerCfg &C,
                 e1 = make_float4(h.v, __int_as_float(h.slot), __uint_as_float(ps.smp.state), __uint_as_float(((uint32_t)threadIdx.x << 26) | ((uint32_t)bank << 25) | next_sample));
             }
         }
+        if constexpr (EG) on_miss(miss);
         const unsigned long long m = __ballot(park);
         if (park) {
             float4 *e = q.base + (size_t)((q.tail + lane_rank(m)) % ZDR_QUEUE_ENTRIES) * 2;

@@ -22,6 +22,8 @@
 // carries its own copy.  Material k is texels [texel, texel + h w) of the packed buffer and staging cells [cell, cell + (h + 1)(w + 1))
 // of one copy of the cell array (copies are ncells apart).  The texture base pointer stays scalar; only the entry is per lane.
 struct MaterialSlot { int32_t texel, h, w, cell; };
+#define ZDR_ENV_CELL_BUDGET (1u << 22)   // environment gradient: most staging cells the map's copies take (256 MiB; zdr_api.cpp, render_common)
+static_assert(ZDR_ENV_ENTRY == ZDR_MAX_MATERIALS - 1, "the environment-gradient calls keep the map in the last entry of the material table");
 struct MaterialTable {
     const int32_t *inst_slot;         // ninst entries: material of each instance, -1 = none (zdr_scene_set_material_slots)
     int32_t nmat, ncells;             // materials in use; cells of all of them (one copy)
@@ -63,9 +65,12 @@ struct KernelIO {
     MaterialTable mt;                 // material-table calls only (zdr_render_*_materials): `material` is then the packed buffer, `cells` all materials' cells
 };
 
+// d_env != nullptr: environment-gradient backward (zdr_render_backward_env): io.mt is a material table whose entry ZDR_ENV_ENTRY holds the
+// map's cells, and they are gathered into d_env (+=)
 int zdr_launch_render(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io,
-                      int integrator, int accel_is_bvh, int backward, int stats, hipStream_t stream);
+                      int integrator, int accel_is_bvh, int backward, int stats, hipStream_t stream, float *d_env = nullptr);
 int zdr_launch_zero(void *p, size_t bytes, hipStream_t stream);   // kernel zero-fill (graph-safe, see zdr_kernels.hip)
+int zdr_launch_copy(void *dst, const void *src, size_t bytes, hipStream_t stream);   // kernel copy of 16-byte words (graph-safe, as the zero-fill)
 int zdr_launch_trace(const DScene &S, int accel_is_bvh, int any, const float *rays, uint32_t n,
                      int32_t *out_i, float *out_f, hipStream_t stream);
 int zdr_launch_sampler_dump(const SamplerCfg &C, const int32_t *queries, uint32_t n, int32_t nvert,

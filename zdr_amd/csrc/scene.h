@@ -231,11 +231,33 @@ ZD int scatter_cell(f2 uv, int tex_h, int tex_w, float &ox, float &oy) {
     return cx + (tex_w + 1) * cy;
 }
 
+// Environment-gradient calls (zdr_render_backward_env): the map is entry ZDR_ENV_ENTRY of the material table, and its footprint is
+// env_lookup's (texel centres at u W - 0.5, v H - 0.5, clamp to edge).  The base texel folds onto (W + 1) x (H + 1) cells exactly like a
+// material's (clamped to -1 .. W - 1, + 1), so k_material_cells_to_grad gathers it unchanged.
+#define ZDR_ENV_ENTRY 15
+ZD int env_cell(f2 uv, int env_h, int env_w, float &ox, float &oy) {
+    const float x = uv.x * (float)env_w - 0.5f, y = uv.y * (float)env_h - 0.5f;
+    const float x0f = floorf(x), y0f = floorf(y);
+    ox = x - x0f; oy = y - y0f;
+    const int cx = clampi((int)x0f, -1, env_w - 1) + 1, cy = clampi((int)y0f, -1, env_h - 1) + 1;
+    return cx + (env_w + 1) * cy;
+}
+// The cell, copy included, of a queue entry of material-table entry `k` in an environment-gradient call.  The map's cells follow every
+// copy of the materials' cells and have copies of their own, so that the map neither takes copies away from the materials nor shares
+// theirs: for entry ZDR_ENV_ENTRY, m.cell is its first cell and m.texel its number of copies (zdr_api.cpp, render_common).  A wave
+// adds into copy blockIdx % copies of each.  (Measured: with one copy of the map's 263,169 cells the sun's dozen texels, where most light
+// samples go, took the Cornell-box backward from 13.5 to 47.6 ms; DESIGN.md.)
+template <class M>
+ZD int table_cell_env(const M &m, int k, int copy_base, f2 uv, float &ox, float &oy) {
+    if (k == ZDR_ENV_ENTRY) return m.cell + (int)(blockIdx.x % (unsigned)m.texel) * ((m.h + 1) * (m.w + 1)) + env_cell(uv, m.h, m.w, ox, oy);
+    return copy_base + m.cell + scatter_cell(uv, m.h, m.w, ox, oy);
+}
+
 // must be called by the whole wave (reconverged control flow).  The queue holds (g, uv) as pushed; the flush first turns the uv of
 // all its entries into (cell, ox, oy) — lane = entry, once per ~57 entries instead of once per push (5.45 pushes per trip of the
 // backward path kernel, each by the whole wave for the few lanes that hold a gradient) — then adds them, 16 lanes per entry.
-// MT: the cell word of an entry holds its material as pushed; mats = the launch's MaterialTable::m.
-template <bool MT = false, class M = int>
+// MT: the cell word of an entry holds its material as pushed; mats = the launch's MaterialTable::m.  EG: entry ZDR_ENV_ENTRY is the environment map.
+template <bool MT = false, bool EG = false, class M = int>
 ZD void scatter_flush(ScatterQueue &q, float *__restrict__ cells, int tex_h, int tex_w, int ablate, const M *mats = nullptr) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -244,9 +266,15 @@ ZD void scatter_flush(ScatterQueue &q, float *__restrict__ cells, int tex_h, int
         f2 uv; uv.x = q.ox[e]; uv.y = q.oy[e];
         float ox, oy;
         int cell;
+        if constexpr (EG) {
+            const int k = q.cell[e];
+            cell = table_cell_env(mats[k], k, q.copy_base, uv, ox, oy);
+            q.cell[e] = (ablate == 2) ? (cell & 1023) : cell;
+        } else {
         if constexpr (MT) { const M m = mats[q.cell[e]]; cell = m.cell + scatter_cell(uv, m.h, m.w, ox, oy); }
         else cell = scatter_cell(uv, tex_h, tex_w, ox, oy);
         q.cell[e] = (ablate == 2) ? (cell & 1023) : (q.copy_base + cell);   // ablation 2: all atomics hit 64 KiB of L2
+        }
         q.ox[e] = ox; q.oy[e] = oy;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -280,9 +308,9 @@ ZD void scatter_flush(ScatterQueue &q, float *__restrict__ cells, int tex_h, int
 }
 
 // end of the kernel: whatever is still queued, and the LDS cell array if the wave kept one
-template <bool MT = false, class M = int>
+template <bool MT = false, bool EG = false, class M = int>
 ZD void scatter_finish(ScatterQueue &q, float *__restrict__ cells, int tex_h, int tex_w, int ablate, const M *mats = nullptr) {
-    scatter_flush<MT>(q, cells, tex_h, tex_w, ablate, mats);
+    scatter_flush<MT, EG>(q, cells, tex_h, tex_w, ablate, mats);
     if (q.lds_cells) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -294,14 +322,14 @@ ZD void scatter_finish(ScatterQueue &q, float *__restrict__ cells, int tex_h, in
 }
 
 // must be called by the whole wave; lanes with active == false push nothing.  MT: `mat` is the material the gradient belongs to.
-template <bool MT = false, class M = int>
+template <bool MT = false, bool EG = false, class M = int>
 ZD void scatter_push(ScatterQueue &q, float *__restrict__ cells, bool active, f2 uv, float4 g, int tex_h, int tex_w, int ablate,
                      int mat = 0, const M *mats = nullptr) {
     if (ablate == 1) { asm volatile("" ::"v"(g.x), "v"(g.y), "v"(g.z), "v"(g.w), "v"(uv.x), "v"(uv.y)); return; }
     unsigned long long mask = __ballot(active);
     int n = __popcll(mask);
     if (n == 0) return;
-    if (q.lds_cells) {                   // few texels: the cell array is in LDS, 16 ds_add_f32 per vertex
+    if (!EG && q.lds_cells) {            // few texels: the cell array is in LDS, 16 ds_add_f32 per vertex (EG: never, the kernels clear lds_cells)
         if (active) {
             float ox, oy;
             int cell;
@@ -317,7 +345,7 @@ ZD void scatter_push(ScatterQueue &q, float *__restrict__ cells, bool active, f2
         }
         return;
     }
-    if (q.count + n > ZDR_SCATTER_CAP) scatter_flush<MT>(q, cells, tex_h, tex_w, ablate, mats);
+    if (q.count + n > ZDR_SCATTER_CAP) scatter_flush<MT, EG>(q, cells, tex_h, tex_w, ablate, mats);
     if (active) {
         int slot = q.count + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
         *(float4 *)(q.g + 4 * slot) = g;
@@ -325,7 +353,7 @@ ZD void scatter_push(ScatterQueue &q, float *__restrict__ cells, bool active, f2
         if constexpr (MT) q.cell[slot] = mat;      // (free until the flush)
     }
     q.count += n;
-    if (q.count >= ZDR_SCATTER_FLUSH_AT) scatter_flush<MT>(q, cells, tex_h, tex_w, ablate, mats);
+    if (q.count >= ZDR_SCATTER_FLUSH_AT) scatter_flush<MT, EG>(q, cells, tex_h, tex_w, ablate, mats);
 }
 
 // ------------------------------------------------------------------------------------ lights
@@ -389,8 +417,9 @@ ZD float env_sampled_light_pdf(const DScene &S, f3 dir, int n) {  // envmap.py:2
 
 // sample_light (light.py:23-81): u_pick = next() was drawn by the caller; the environment branch then
 // draws only next2f(), the mesh branch next() and next2f() (light.py:29-31 vs 50-63).
+// env_uv (environment-gradient kernels): receives the map coordinates of an environment sample; left alone otherwise.
 template <bool ENV, class NEXT1, class NEXT2>
-ZD LightSample sample_light(const DScene &S, f3 origin, float u_pick, NEXT1 next1, NEXT2 next2) {
+ZD LightSample sample_light(const DScene &S, f3 origin, float u_pick, NEXT1 next1, NEXT2 next2, f2 *env_uv = nullptr) {
     LightSample L;
     int n = (ENV ? S.env_count : 0) + S.light_count;
     if (n <= 0) {  // the reference would index out of bounds; consume the mesh branch's dimensions, contribute nothing
@@ -408,6 +437,7 @@ ZD LightSample sample_light(const DScene &S, f3 origin, float u_pick, NEXT1 next
         L.wi = uv_to_direction(uv); L.dist = 1e30f;
         L.pdf = S.env_pdf[iy * S.map_w + ix] * env_pdf_scale(uv.y, n);
         L.eval = env_lookup(S, uv);
+        if (env_uv) *env_uv = uv;
         return L;
     }
     if (ENV) idx -= S.env_count;

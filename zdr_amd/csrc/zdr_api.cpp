@@ -486,6 +486,7 @@ struct zdr_scene {
     unsigned long long *d_counters = nullptr;
     std::vector<int32_t> inst_slot;                         // material slot of each instance (zdr_scene_set_material_slots), -1 = none; empty = never set
     int32_t *d_inst_slot = nullptr;                         // its device copy, allocated by the first call that needs it
+    int32_t *d_inst_slot0 = nullptr;                        // {0, -1, -1, ...}: the slot table of a single-material environment-gradient call (render_common)
     unsigned int *d_error = nullptr;                        // device error word (scene.h, ZDR_DEVERR_*), sticky until read
     uint64_t device_bytes = 0;
     // A render call recorded while its stream was CAPTURING (hipStreamBeginCapture; torch.cuda.graph) bakes this handle's workspace
@@ -783,7 +784,7 @@ extern "C" int zdr_scene_destroy(zdr_scene *s) {
     if (!s) return ZDR_OK;
     (void)hipSetDevice(s->device);
     if (!s->isect_in_nodes) (void)hipFree(s->d_isect); (void)hipFree(s->d_pairs); (void)hipFree(s->d_ppairs); (void)hipFree(s->d_shade); (void)hipFree(s->d_nodes); (void)hipFree(s->d_emission); (void)hipFree(s->d_light_insts); (void)hipFree(s->d_light_tris); (void)hipFree(s->d_light_range); (void)hipFree(s->d_emission4);
-    (void)hipFree(s->d_inst_tri_begin); (void)hipFree(s->d_slot_of_tri); (void)hipFree(s->d_pmj); (void)hipFree(s->d_bn); (void)hipFree(s->d_env_tex); (void)hipFree(s->d_alias_prob); (void)hipFree(s->d_alias_idx); (void)hipFree(s->d_env_pdf); (void)hipFree(s->d_partial); (void)hipFree(s->d_ring); (void)hipFree(s->d_work_counters); (void)hipFree(s->d_tile_masks); (void)hipFree(s->d_cells); (void)hipFree(s->d_counters); (void)hipFree(s->d_error); (void)hipFree(s->d_inst_slot);
+    (void)hipFree(s->d_inst_tri_begin); (void)hipFree(s->d_slot_of_tri); (void)hipFree(s->d_pmj); (void)hipFree(s->d_bn); (void)hipFree(s->d_env_tex); (void)hipFree(s->d_alias_prob); (void)hipFree(s->d_alias_idx); (void)hipFree(s->d_env_pdf); (void)hipFree(s->d_partial); (void)hipFree(s->d_ring); (void)hipFree(s->d_work_counters); (void)hipFree(s->d_tile_masks); (void)hipFree(s->d_cells); (void)hipFree(s->d_counters); (void)hipFree(s->d_error); (void)hipFree(s->d_inst_slot); (void)hipFree(s->d_inst_slot0);
     for (void *p : s->retired) (void)hipFree(p);
     delete s;
     return ZDR_OK;
@@ -852,6 +853,17 @@ extern "C" int zdr_scene_set_envmap(zdr_scene *s, const float *tex, uint32_t tex
     s->ds.env_tex = s->d_env_tex; s->ds.alias_prob = s->d_alias_prob; s->ds.alias_idx = s->d_alias_idx; s->ds.env_pdf = s->d_env_pdf;
     s->ds.env_h = (int32_t)tex_h; s->ds.env_w = (int32_t)tex_w; s->ds.map_w = (int32_t)map_w; s->ds.map_h = (int32_t)map_h;
     s->ds.env_count = 1;
+    return ZDR_OK;
+}
+
+extern "C" int zdr_scene_set_envmap_texture(zdr_scene *s, const float *tex, void *stream) {
+    if (!s || !tex) return fail(ZDR_E_INVALID, "null argument");
+    if (s->ds.env_count == 0 || !s->d_env_tex) return fail(ZDR_E_INVALID, "the scene has no environment map: zdr_scene_set_envmap first");
+    if ((uintptr_t)tex % 16 != 0) return fail(ZDR_E_INVALID, "tex must be 16-byte aligned (one float4 texel per load)");
+    HIPCHK(hipSetDevice(s->device));
+    // in place, stream-ordered, by a kernel (graph-safe like the zero-fills): the pointer the kernels and any captured graph hold stays valid
+    if (zdr_launch_copy(s->d_env_tex, tex, (size_t)s->ds.env_h * (size_t)s->ds.env_w * sizeof(float4), (hipStream_t)stream))
+        return fail(ZDR_E_HIP, "copy launch failed");
     return ZDR_OK;
 }
 
@@ -1003,8 +1015,9 @@ static int ensure_ring(zdr_scene *s, hipStream_t st, bool capturing) {
 }
 
 // ncells: cells of one copy ((tex_h + 1) x (tex_w + 1), or MaterialTable::ncells)
-static int ensure_cells(zdr_scene *s, const RenderCfg &R, size_t ncells, hipStream_t st, bool capturing) {
-    size_t need = (size_t)R.cell_copies * ncells * 16 * sizeof(float);
+// extra_cells: cells behind all copies (the environment map's, zdr_render_backward_env)
+static int ensure_cells(zdr_scene *s, const RenderCfg &R, size_t ncells, hipStream_t st, bool capturing, size_t extra_cells = 0) {
+    size_t need = ((size_t)R.cell_copies * ncells + extra_cells) * 16 * sizeof(float);
     if (need > s->cells_bytes) {
         if (int rc = may_allocate(capturing, "staging-cell")) return rc;
         release_buffer(s, s->d_cells); s->d_cells = nullptr; s->cells_bytes = 0;
@@ -1062,13 +1075,34 @@ static int make_material_table(zdr_scene *s, const int32_t *dims, uint32_t nmat,
     return ZDR_OK;
 }
 
-// mt_dims / nmat: a material-table call (zdr_render_*_materials), else nullptr / 0
+// The slot table of a single-material call that runs in the material-table kernels (an environment gradient): instance 0 has material 0,
+// every other instance none — what zdr_render_backward does with instances > 0 (path: light or blocker; direct: its emission).
+static int single_material_slots(zdr_scene *s, bool capturing, const int32_t *&out) {
+    if (!s->d_inst_slot0) {
+        if (int rc = may_allocate(capturing, "material-slot")) return rc;
+        std::vector<int32_t> t(s->ninst, -1);
+        t[0] = 0;
+        HIPCHK(upload(&s->d_inst_slot0, t.data(), (size_t)s->ninst * sizeof(int32_t), &s->device_bytes));
+    }
+    out = s->d_inst_slot0;
+    return ZDR_OK;
+}
+
+// mt_dims / nmat: a material-table call (zdr_render_*_materials), else nullptr / 0.  d_env (backward, path / direct): also the gradient of
+// the environment map, through the material-table kernels with the map as entry ZDR_ENV_ENTRY (a single material becomes a table of one).
 static int render_common(zdr_scene *s, const zdr_render_params *p, const float *material, float *image, const float *d_image,
-                         float *d_material, int backward, int stats, void *stream, const int32_t *mt_dims = nullptr, uint32_t nmat = 0) {
+                         float *d_material, int backward, int stats, void *stream, const int32_t *mt_dims = nullptr, uint32_t nmat = 0,
+                         float *d_env = nullptr) {
     if (!s || !p || !material) return fail(ZDR_E_INVALID, "null argument");
     int rc = check_params_abi(p); if (rc) return rc;
     HIPCHK(hipSetDevice(s->device));
     const bool use_mt = nmat > 0 || mt_dims;
+    const bool env_grad = backward && d_env;
+    if (env_grad) {
+        if (p->integrator != ZDR_PATH && p->integrator != ZDR_DIRECT) return fail(ZDR_E_UNSUPPORTED, "an environment gradient needs the path or the direct integrator");
+        if (s->ds.env_count == 0) return fail(ZDR_E_INVALID, "d_env given, but the scene has no environment map");
+        if (use_mt && nmat > ZDR_ENV_ENTRY) return fail(ZDR_E_UNSUPPORTED, "an environment gradient takes at most " + std::to_string(ZDR_ENV_ENTRY) + " materials (the map is the last entry of the material table)");
+    }
     zdr_render_params pm = *p;
     if (use_mt) {                                       // the materials' sizes come from the table
         if (p->integrator == ZDR_UVGRAD) return fail(ZDR_E_UNSUPPORTED, "render_duvdxy has no material-table form");
@@ -1081,11 +1115,32 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
     MaterialTable mt; memset(&mt, 0, sizeof mt);
     if (use_mt) {
         rc = make_material_table(s, mt_dims, nmat, capturing, (hipStream_t)stream, mt); if (rc) return rc;
+    } else if (env_grad) {                              // the one material as a table of one
+        mt.m[0].texel = 0; mt.m[0].h = R.tex_h; mt.m[0].w = R.tex_w; mt.m[0].cell = 0;
+        mt.nmat = 1; mt.ncells = (R.tex_h + 1) * (R.tex_w + 1);
+        rc = single_material_slots(s, capturing, mt.inst_slot); if (rc) return rc;
+    }
+    size_t env_cells_total = 0;                         // environment gradient: the map's cells, all their copies
+    if (use_mt || env_grad) {
         R.tex_h = R.tex_w = 0;                          // (unused in material-table mode)
-        R.cell_copies = cell_copies_for((size_t)mt.ncells);
+        R.cell_copies = cell_copies_for((size_t)mt.ncells);   // the materials' copies: as in the call without the map
+    }
+    if (env_grad) {
+        // The map's cells follow every copy of the materials' cells, with copies of their own (scene.h, table_cell_env): most light
+        // samples go to the map's few brightest texels, whatever the map's size, so even a large map gets copies — up to
+        // ZDR_ENV_CELL_BUDGET cells in all (16 MiB per copy for a 512 x 512 map: 15 copies).  Entry ZDR_ENV_ENTRY = {copies, h, w, first cell}.
+        const size_t mat_cells = (size_t)R.cell_copies * (size_t)mt.ncells;
+        const size_t one = (size_t)(s->ds.env_h + 1) * (size_t)(s->ds.env_w + 1);
+        size_t copies = std::min<size_t>(ZDR_MAX_CELL_COPIES, std::max<size_t>(1, ZDR_ENV_CELL_BUDGET / one));
+        if (mat_cells + one >= (1ull << 26)) return fail(ZDR_E_UNSUPPORTED, "materials and environment map too large for one call (2^26 staging cells)");
+        copies = std::min<size_t>(copies, ((1ull << 26) - 1 - mat_cells) / one);
+        mt.m[ZDR_ENV_ENTRY].texel = (int32_t)copies; mt.m[ZDR_ENV_ENTRY].h = s->ds.env_h; mt.m[ZDR_ENV_ENTRY].w = s->ds.env_w;
+        mt.m[ZDR_ENV_ENTRY].cell = (int32_t)mat_cells;
+        env_cells_total = copies * one;
     }
     if (capturing) s->captured = true;                  // sticky: a graph may name this handle's buffers from now on (zdr_scene)
-    if (backward) { rc = ensure_cells(s, R, use_mt ? (size_t)mt.ncells : (size_t)(R.tex_h + 1) * (R.tex_w + 1), (hipStream_t)stream, capturing); if (rc) return rc; }
+    if (backward) { rc = ensure_cells(s, R, (use_mt || env_grad) ? (size_t)mt.ncells : (size_t)(R.tex_h + 1) * (R.tex_w + 1), (hipStream_t)stream, capturing,
+                                      env_cells_total); if (rc) return rc; }
     else if (!stats) { rc = ensure_partial(s, R, capturing); if (rc) return rc; }
     if (p->integrator == ZDR_PATH) {
         if (p->spp > (1u << 25)) return fail(ZDR_E_UNSUPPORTED, "path integrator: spp above 2^25");   // queue entries pack pixel << 26 | bank << 25 | sample
@@ -1130,7 +1185,7 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
     DScene S = s->ds;
     // shadow segments end on a light's surface; an environment light sends them to infinity, where nothing can be ruled out
     S.shadow_pairs = (S.env_count > 0) ? ~0ull : s->shadow_pairs;
-    if (zdr_launch_render(S, R, C, io, p->integrator, s->accel_is_bvh, backward, stats, (hipStream_t)stream))
+    if (zdr_launch_render(S, R, C, io, p->integrator, s->accel_is_bvh, backward, stats, (hipStream_t)stream, env_grad ? d_env : nullptr))
         return fail(ZDR_E_HIP, std::string("kernel launch: ") + hipGetErrorString(hipGetLastError()));
     static const bool check_every_call = getenv("ZDR_CHECK") && atoi(getenv("ZDR_CHECK")) != 0;   // opt-in: costs a synchronise per call
     if (check_every_call && !stats && !capturing) return check_device_error(s, (hipStream_t)stream);   // (a synchronise cannot be captured: zdr_scene_check after the replay instead)
@@ -1172,6 +1227,23 @@ extern "C" int zdr_render_backward_materials(zdr_scene *s, const zdr_render_para
     if (!d_image || !d_materials || !dims) return fail(ZDR_E_INVALID, "null argument");
     if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
     return render_common(s, p, materials, nullptr, d_image, d_materials, 1, 0, stream, dims, nmat);
+}
+
+extern "C" int zdr_render_backward_env(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *material,
+                                       float *d_material, float *d_env, void *stream) {
+    if (d_env && s && s->ds.env_count == 0) return fail(ZDR_E_INVALID, "d_env given, but the scene has no environment map");
+    if (!d_env || (p && p->integrator == ZDR_COLLOCATED)) return zdr_render_backward(s, p, d_image, material, d_material, stream);   // (collocated: no environment term)
+    if (!d_image || !d_material) return fail(ZDR_E_INVALID, "null gradient buffer");
+    return render_common(s, p, material, nullptr, d_image, d_material, 1, 0, stream, nullptr, 0, d_env);
+}
+
+extern "C" int zdr_render_backward_materials_env(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *materials,
+                                                 const int32_t *dims, uint32_t nmat, float *d_materials, float *d_env, void *stream) {
+    if (d_env && s && s->ds.env_count == 0) return fail(ZDR_E_INVALID, "d_env given, but the scene has no environment map");
+    if (!d_env || (p && p->integrator == ZDR_COLLOCATED)) return zdr_render_backward_materials(s, p, d_image, materials, dims, nmat, d_materials, stream);
+    if (!d_image || !d_materials || !dims) return fail(ZDR_E_INVALID, "null argument");
+    if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
+    return render_common(s, p, materials, nullptr, d_image, d_materials, 1, 0, stream, dims, nmat, d_env);
 }
 
 extern "C" int zdr_render_stats(zdr_scene *s, const zdr_render_params *p, const float *material, uint64_t counters[8], void *stream) {

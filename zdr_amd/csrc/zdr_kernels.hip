@@ -314,6 +314,22 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
 #undef io
 }
 
+// Environment-gradient kernels: the cotangent / spp of pixel (px, py), as a popped path of k_path_bwd computes it
+ZD f3 pixel_cotangent(const SamplerCfg &C, const KernelIO &io, int width, uint32_t px, uint32_t py) {
+    const float4 gi = io.d_image[px + py * (uint32_t)width];
+    f3 g;
+    if (C.spp_pow2) g = mk3(gi.x * C.inv_spp, gi.y * C.inv_spp, gi.z * C.inv_spp);
+    else { const float fs = (float)C.spp; g = mk3(__fdiv_rn(gi.x, fs), __fdiv_rn(gi.y, fs), __fdiv_rn(gi.z, fs)); }
+    if (any_nan(g)) g = mk3(0.0f);
+    return g;
+}
+// queues the gradient g of an environment term at map coordinates uv (whole wave; g = 0: nothing).  A NaN gradient is dropped here, per
+// term: a path whose radiance turns NaN later (the forward drops that sample) keeps the terms it queued before.  Alpha receives nothing.
+ZD void env_push(ScatterQueue &q, const KernelIO &io, const RenderCfg &R, f3 g, f2 uv) {
+    const float4 g4 = make_float4(g.x, g.y, g.z, 0.0f);
+    scatter_push<true, true>(q, io.cells, any_nonzero4(g4) && !any_nan4(g4), uv, g4, R.tex_h, R.tex_w, ZDR_ABLATE, ZDR_ENV_ENTRY, io.mt.m);
+}
+
 // PRB backward with ONE traversal.  Each trip a live lane shades one vertex of its path (same trip
 // order, primary queue, pixel-free lanes, persistent waves and item banks as k_path) and appends it to its record list.  The
 // records (5 float4 + a link to the path's previous one) live in a per-wave LDS POOL, see below; the few that find no slot go to
@@ -327,9 +343,14 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
 // this are kept as profiles/r4_pruned_experiment_branches.patch.)
 // MT (zdr_render_backward_materials): a record's material rides in its link word — the pool's links are 16 bits wide (two slots fewer keep the
 // LDS blocks), the scratch links are ints anyway — as `previous location | material << 8`; the 80-byte record itself is unchanged.
+// EG (zdr_render_backward_env; implies ENV and MT, the map being entry ZDR_ENV_ENTRY of the material table): the terms that read the
+// environment map are queued as they happen, each as (weight x the path's cotangent) at its map coordinates — a camera ray that misses
+// (primary_refill), a light sample on the environment once its shadow ray is known to be free, a continuation ray that misses.  They
+// need no sweep: nothing that decides a path reads the map.  They share the scatter queue with the material gradients.
 typedef unsigned int zdr_u4 __attribute__((ext_vector_type(4)));
-template <int SK, class A, bool ENV, bool MT>
+template <int SK, class A, bool ENV, bool MT, bool EG = false>
 __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KERNEL_PARAMS) {
+    static_assert(!EG || (ENV && MT), "the environment gradient runs in the material-table environment kernels");
     ZDR_KARGS_BEGIN
 #define S (ka->S)
 #define R (ka->R)
@@ -369,6 +390,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
     unsigned long long cam_mask = 0ull;
     f3 le_grad = mk3(0.0f);                                 // cotangent of the running path's pixel
     ScatterQueue q = MT ? scatter_queue_init_cells(lds_q, io.mt.ncells, R.cell_copies) : scatter_queue_init(lds_q, R.tex_h, R.tex_w, R.cell_copies);
+    if constexpr (EG) q.lds_cells = nullptr;                // the map's cells are never in LDS (table_cell_env)
     PackedVertex deep[ZDR_MAX_RECORDED_DEPTH];
     int nrec = 0;
     PrimaryQueue pq = queue_init(io);
@@ -388,6 +410,16 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
         if (pq.tail - pq.head < (uint32_t)__popcll(__ballot(!alive))) {
             if (next_sample < s_end) {
                 const uint32_t t0 = pq.tail;
+                if constexpr (EG) {
+                    // lane = pixel here: a camera ray that misses is a term of this lane's own pixel (weight 1 x mis of pdf_bsdf = 1e30)
+                    auto camera_miss = [&](const EnvTerm &e) {
+                        f3 g = mk3(0.0f);
+                        if (w.valid && ((e.w.x != 0.0f) | (e.w.y != 0.0f) | (e.w.z != 0.0f))) g = e.w * pixel_cotangent(C, io, R.width, (uint32_t)w.x, (uint32_t)w.y);
+                        env_push(q, io, R, g, e.uv);
+                    };
+                    primary_refill<SK, A, true, false, ENV, MT>(S, R, C, lds, w.x, w.y, w.valid, cam_mask, perm_seed, bank, next_sample, s_end, pq, unused_sum, cnt,
+                                                                io.mt.inst_slot, camera_miss);
+                } else
                 primary_refill<SK, A, true, false, ENV, MT>(S, R, C, lds, w.x, w.y, w.valid, cam_mask, perm_seed, bank, next_sample, s_end, pq, unused_sum, cnt,
                                                             MT ? io.mt.inst_slot : nullptr);
                 ib.inflight[bank] += pq.tail - t0;
@@ -433,12 +465,19 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
             int sw_k = -1;                                  // next vertex the sweep consumes
             bool want_store = false, mute = false;
             SweepState sw; sw.A = mk3(0.0f); sw.Lv = mk3(0.0f); sw.s = 0.0f; sw.Z = 0.0f; sw.tw = 0.0f;
+            EnvTerm env_nee, env_miss;                      // EG: this trip's light sample on the environment, continuation ray that missed
+            if constexpr (EG) { env_term_clear(env_nee); env_term_clear(env_miss); }
             if (alive) {
                 PathVertex pv; float term_plfrac = 0.0f;
                 Hit h;
                 if (MT) pmat = it.mat;
+                if constexpr (EG) done = path_shade<SK, A, true, false, ENV, MT, true>(S, R, C, io, lds, ps, it, pv, h, cnt, &env_nee);
+                else
                 done = path_shade<SK, A, true, false, ENV, MT>(S, R, C, io, lds, ps, it, pv, h, cnt);
                 plast = pack_vertex(pv, le_grad, R.prb_mode);
+                if constexpr (EG) {
+                    if (!done) { path_continue<A, false>(S, lds, ps, h, cnt); done = path_arrive<true, false, ENV, MT>(S, ps, h, it, term_Li, cnt, &term_plfrac, io.mt.inst_slot, &env_miss); }
+                } else
                 if (!done) { path_continue<A, false>(S, lds, ps, h, cnt); done = path_arrive<true, false, ENV, MT>(S, ps, h, it, term_Li, cnt, &term_plfrac, MT ? io.mt.inst_slot : nullptr); }
                 // Only a vertex whose path goes on is put away: when the path ends here (52 % of the vertices) the sweep below starts
                 // from plast and nothing would read the record.  (5 LDS or scratch stores per vertex: 16.4 -> 15.5 ms for skipping
@@ -456,6 +495,8 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
                     }
                 }
             }
+            // EG, reconverged: both terms are final (a NaN in one is dropped by its push, whatever the rest of the path does: env_push)
+            if constexpr (EG) { env_push(q, io, R, env_nee.w * le_grad, env_nee.uv); env_push(q, io, R, env_miss.w * le_grad, env_miss.uv); }
             // Reconverged: hand out slots, all requests of the trip at once.  Home slot first (slot == lane: conflict-free LDS access);
             // the lanes whose home is taken — a path's second and later records, or a home another lane borrowed — are ranked, the free
             // slots are ranked (a lane speaks for slot `lane`, then for slot 64 + lane), and request r takes free slot r: one
@@ -567,7 +608,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
                 // (and this wave's LDS operations execute in order anyway: a later write cannot overtake the read)
                 if (pooled) __hip_atomic_fetch_or(&lds_free[loc >> 5], 1u << (loc & 31), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 if (fetch) loc = nloc;
-                scatter_push<MT>(q, io.cells, swp && !mute && any_nonzero4(g) && !any_nan4(g), guv, g, R.tex_h, R.tex_w, ZDR_ABLATE, gmat, io.mt.m);   // prb.py:178-187
+                scatter_push<MT, EG>(q, io.cells, swp && !mute && any_nonzero4(g) && !any_nan4(g), guv, g, R.tex_h, R.tex_w, ZDR_ABLATE, gmat, io.mt.m);   // prb.py:178-187
             }
         }
 #pragma unroll
@@ -577,7 +618,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
         stall = progress ? 0 : stall + 1;
         if (stall > 4) { raise_device_error(S, ZDR_DEVERR_STALL); break; }   // cannot happen (every branch above makes progress); never spin on the GPU, never end silently
     }
-    scatter_finish<MT>(q, io.cells, R.tex_h, R.tex_w, ZDR_ABLATE, io.mt.m);
+    scatter_finish<MT, EG>(q, io.cells, R.tex_h, R.tex_w, ZDR_ABLATE, io.mt.m);
     {   // every path has been swept, so every slot must be back: a leaked or doubly allocated slot is a protocol error, said aloud
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -599,7 +640,8 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
 }
 
 // ---------------------------------------------------------------------- direct / collocated
-template <int INTEG, int SK, class A, bool BWD, bool STATS, bool ENV, bool MT>
+// EG (direct backward only; implies ENV and MT): the terms that read the environment map are queued too (direct_sample, EnvTerm)
+template <int INTEG, int SK, class A, bool BWD, bool STATS, bool ENV, bool MT, bool EG = false>
 #ifndef ZDR_MIN_WAVES_DIRECT
 #define ZDR_MIN_WAVES_DIRECT 4   // brute-force direct kernels, cbox 512^2 spp 64: 153 VGPRs (3 waves per SIMD) 1.175 / 1.331 ms, 128 VGPRs (6 spilled) 1.110 / 1.267 ms
 #endif
@@ -620,6 +662,7 @@ __global__ __launch_bounds__(WAVE, (INTEG == ZDR_DIRECT && !A::kNeedsLds) ? (ENV
     f3 le_grad = mk3(0.0f);
     if (BWD) le_grad = load_le_grad(C, io, w);
     ScatterQueue q = MT ? scatter_queue_init_cells(lds_q, io.mt.ncells, R.cell_copies) : scatter_queue_init(lds_q, R.tex_h, R.tex_w, R.cell_copies);
+    if constexpr (EG) q.lds_cells = nullptr;                // the map's cells are never in LDS (table_cell_env)
     const unsigned long long cam_mask = camera_mask(S, io, w);
     f3 sum = mk3(0.0f);
     for (uint32_t it = w.s_begin; it < w.s_end; it++) {     // integrator.py:15 (wave-uniform trip count)
@@ -627,6 +670,8 @@ __global__ __launch_bounds__(WAVE, (INTEG == ZDR_DIRECT && !A::kNeedsLds) ? (ENV
         float4 grad = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         f2 guv; guv.x = 0.0f; guv.y = 0.0f;
         int gmat = 0;
+        EnvTerm e_cam, e_bsdf;
+        env_term_clear(e_cam); env_term_clear(e_bsdf);
         if (w.valid) {
             Sampler smp = sampler_make<SK>(C, (uint32_t)w.x, (uint32_t)w.y, perm_seed, it);
             f3 o, d;
@@ -634,12 +679,14 @@ __global__ __launch_bounds__(WAVE, (INTEG == ZDR_DIRECT && !A::kNeedsLds) ? (ENV
             COUNT(C_SAMPLES);
             f3 rad;
             if (INTEG == ZDR_COLLOCATED) rad = collocated_sample<A, BWD, STATS, MT>(S, R, io, lds, o, d, cam_mask, le_grad, cnt, guv, grad, gmat);
-            else rad = direct_sample<SK, A, BWD, STATS, ENV, MT>(S, R, C, io, lds, smp, o, d, cam_mask, le_grad, cnt, guv, grad, gmat);
+            else rad = direct_sample<SK, A, BWD, STATS, ENV, MT, EG>(S, R, C, io, lds, smp, o, d, cam_mask, le_grad, cnt, guv, grad, gmat,
+                                                                      EG ? &e_cam : nullptr, EG ? &e_bsdf : nullptr);
             if (!any_nan(rad)) sum = sum + clamp_radiance(rad); else COUNT(C_NAN);
         }
-        if (BWD) scatter_push<MT>(q, io.cells, w.valid && any_nonzero4(grad) && !any_nan4(grad), guv, grad, R.tex_h, R.tex_w, ZDR_ABLATE, gmat, io.mt.m);
+        if (BWD) scatter_push<MT, EG>(q, io.cells, w.valid && any_nonzero4(grad) && !any_nan4(grad), guv, grad, R.tex_h, R.tex_w, ZDR_ABLATE, gmat, io.mt.m);
+        if constexpr (EG) { env_push(q, io, R, e_cam.w * le_grad, e_cam.uv); env_push(q, io, R, e_bsdf.w * le_grad, e_bsdf.uv); }
     }
-    if (BWD) scatter_finish<MT>(q, io.cells, R.tex_h, R.tex_w, ZDR_ABLATE, io.mt.m);
+    if (BWD) scatter_finish<MT, EG>(q, io.cells, R.tex_h, R.tex_w, ZDR_ABLATE, io.mt.m);
     if (!BWD && !STATS) store_pixel(R, C, io, w, sum);
     flush_counters<STATS>(io, cnt);
 #undef S
@@ -775,6 +822,18 @@ int zdr_launch_zero(void *p, size_t bytes, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+__global__ void k_copy16(uint4 *__restrict__ dst, const uint4 *__restrict__ src, size_t n16) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) dst[i] = src[i];
+}
+int zdr_launch_copy(void *dst, const void *src, size_t bytes, hipStream_t st) {   // bytes: a multiple of 16 (float4 texels)
+    if (bytes == 0) return 0;
+    const size_t n16 = bytes / 16;
+    const unsigned blocks = (unsigned)std::min<size_t>((n16 + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(k_copy16, dim3(blocks), dim3(256), 0, st, (uint4 *)dst, (const uint4 *)src, n16);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ----------------------------------------------------------------------------------- launch
 // dynamic LDS of a wave that traverses the BVH: the first entries of the per-lane stacks (accel.h).  Sets S.lds_stack.
 // path_kernels: the launch runs BvhAccel::shadow_and_closest (k_path, k_path_bwd, k_path_dump), whose walk_steal keeps 5 x 64 ints behind the stack.
@@ -858,8 +917,17 @@ static void launch_integ(int integrator, dim3 grid, size_t dyn, hipStream_t st, 
     else launch_integ_mt<SK, A, false>(integrator, grid, dyn, st, S, R, C, io, backward, stats);
 }
 
+// environment-gradient backward (path or direct; the caller has checked both): material-table kernels with the map as entry ZDR_ENV_ENTRY
+template <int SK, class A>
+static void launch_env_grad(int integrator, dim3 grid, size_t dyn, hipStream_t st, const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io) {
+    if (integrator == ZDR_PATH) {
+        auto K = k_path_bwd<SK, A, true, true, true>;
+        hipLaunchKernelGGL(K, persistent_grid(K, dyn, R.ntiles * R.nchunks), dim3(WAVE), dyn, st, S, R, C, io);
+    } else hipLaunchKernelGGL((k_simple<ZDR_DIRECT, SK, A, true, false, true, true, true>), grid, dim3(WAVE), dyn, st, S, R, C, io);
+}
+
 int zdr_launch_render(const DScene &S_in, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io,
-                      int integrator, int accel_is_bvh, int backward, int stats, hipStream_t st) {
+                      int integrator, int accel_is_bvh, int backward, int stats, hipStream_t st, float *d_env) {
     DScene S = S_in;
     int nblocks = R.ntiles * R.nchunks;
     if (nblocks <= 0) return 0;
@@ -867,7 +935,15 @@ int zdr_launch_render(const DScene &S_in, const RenderCfg &R, const SamplerCfg &
     const size_t dyn = accel_is_bvh ? bvh_dyn_lds(S, backward != 0, integrator == ZDR_PATH) : 0;
     if (io.tile_masks && !io.tile_masks_valid)
         hipLaunchKernelGGL(k_tile_masks, dim3(R.tiles_x * R.tiles_y), dim3(WAVE), 0, st, S, R, (unsigned long long *)io.tile_masks);
-    if (C.kind == ZDR_SAMPLER_CMJ) {
+    if (d_env) {
+        if (C.kind == ZDR_SAMPLER_CMJ) {
+            if (accel_is_bvh) launch_env_grad<0, BvhAccel>(integrator, grid, dyn, st, S, R, C, io);
+            else launch_env_grad<0, BruteAccel>(integrator, grid, dyn, st, S, R, C, io);
+        } else {
+            if (accel_is_bvh) launch_env_grad<1, BvhAccel>(integrator, grid, dyn, st, S, R, C, io);
+            else launch_env_grad<1, BruteAccel>(integrator, grid, dyn, st, S, R, C, io);
+        }
+    } else if (C.kind == ZDR_SAMPLER_CMJ) {
         if (accel_is_bvh) launch_integ<0, BvhAccel>(integrator, grid, dyn, st, S, R, C, io, backward, stats);
         else launch_integ<0, BruteAccel>(integrator, grid, dyn, st, S, R, C, io, backward, stats);
     } else {
@@ -879,6 +955,14 @@ int zdr_launch_render(const DScene &S_in, const RenderCfg &R, const SamplerCfg &
         for (int k = 0; k < io.mt.nmat; k++) { mh = std::max(mh, (int)io.mt.m[k].h); mw = std::max(mw, (int)io.mt.m[k].w); }
         dim3 g((mw + 63) / 64, mh, io.mt.nmat);
         hipLaunchKernelGGL(k_material_cells_to_grad, g, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)io.d_material, io.mt, R.cell_copies);
+        if (d_env) {   // the map's cells into d_env (+=): the same gather, a table whose only material is the map, with the map's own copies
+            const MaterialSlot e = io.mt.m[ZDR_ENV_ENTRY];    // {copies, h, w, first cell}
+            MaterialTable me = io.mt;
+            me.m[0] = e; me.m[0].texel = 0;
+            me.ncells = (e.h + 1) * (e.w + 1);                // copy stride
+            dim3 ge((e.w + 63) / 64, e.h, 1);
+            hipLaunchKernelGGL(k_material_cells_to_grad, ge, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)d_env, me, (int)e.texel);
+        }
     } else if (backward) {   // fold the staging cells into d_material (+=)
         dim3 g((R.tex_w + 63) / 64, R.tex_h);
         hipLaunchKernelGGL(k_cells_to_grad, g, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)io.d_material, R.tex_h, R.tex_w, R.cell_copies);

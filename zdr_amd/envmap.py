@@ -41,6 +41,23 @@ def prepare_image(img) -> np.ndarray:
     return np.ascontiguousarray(img, np.float32)
 
 
+def prepare_tensor(img):
+    """``prepare_image`` in torch, differentiable: (H, 2H, 3|4) or (H, H, 3|4) -> (H', H', 4) with alpha set to 1 for RGB input (so it
+    receives no gradient) and a 1:2 map made square with ``repeat_interleave(2, dim=0)`` (each square row's gradient goes back to the row
+    it repeats).  Same values as ``prepare_image``; device and dtype are kept."""
+    import torch
+    if img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise ValueError("envmap must be (H, W, 3) or (H, W, 4)")
+    if img.shape[2] == 3:
+        img = torch.cat([img, torch.ones_like(img[..., :1])], dim=-1)
+    if img.shape[0] != img.shape[1]:
+        if img.shape[1] == img.shape[0] * 2:
+            img = img.repeat_interleave(2, dim=0)
+        else:
+            raise RuntimeError("envmap must be strictly 1:2 or 1:1")
+    return img
+
+
 def texture_sample(img: np.ndarray, u: np.ndarray, v: np.ndarray) -> np.ndarray:
     """bilinear, texel centres at (i + 0.5) / N, clamp to edge; u, v broadcastable float32 arrays."""
     H, W = img.shape[:2]

@@ -9,6 +9,11 @@
     scene.material_slots = [0, 1, None]                               # one material per model (None: light or blocker)
     image = scene.render([floor, box], res=(W, H), spp=256)           # floor.grad and box.grad after backward()
 
+    scene.add_envmap(sky)                                             # the map and its importance-sampling tables
+    env = torch.tensor(sky, device="cuda", requires_grad=True)        # (H, 2H, 3|4) or (H, H, 3|4)
+    image = scene.render(material, res=(W, H), spp=256, envmap=env)   # env.grad after backward(); tables stay fixed
+    scene.update_envmap_sampling(env.detach())                        # now and then: tables rebuilt from the current map
+
 Images and materials are PyTorch tensors on the GPU; the renderer borrows their device pointers
 for the duration of a call and enqueues its kernels on torch's current HIP stream.
 """
@@ -173,6 +178,50 @@ class Scene:
         self.env_count = 1
         self._envmap = (img, prob, alias, pdf)        # kept for tests / the oracle
 
+    def update_envmap_sampling(self, image, compensate_mis=True):
+        """Rebuilds the environment map's importance-sampling tables from ``image`` (and uploads it as the map): ``add_envmap`` for
+        a map that is being optimised.  ``render(..., envmap=)`` keeps the tables of the last ``add_envmap`` or of this call, and
+        differentiates with them held fixed.  Like ``add_envmap`` this synchronises the device and replaces the scene's buffers,
+        so graphs captured before no longer see the map."""
+        if image is None:
+            raise ValueError("update_envmap_sampling needs a map (add_envmap(None) removes it)")
+        self.add_envmap(image.detach() if isinstance(image, torch.Tensor) else image, compensate_mis=compensate_mis)
+
+    def _prepare_envmap(self, envmap):
+        """The tensor given as ``render(..., envmap=)``, prepared in torch (envmap.prepare_tensor) so that autograd returns its
+        gradient in the caller's shape; its size must be the one given to add_envmap."""
+        from . import envmap as E
+        if self.env_count == 0:
+            raise ValueError("envmap= needs an environment map: call add_envmap first (it builds the importance-sampling tables)")
+        if not isinstance(envmap, torch.Tensor) or envmap.device != self.device or envmap.dtype != torch.float32:
+            raise ValueError(f"envmap must be a float32 tensor on {self.device}")
+        try:
+            env = E.prepare_tensor(envmap)
+        except RuntimeError as e:
+            raise ValueError(str(e)) from None
+        if tuple(env.shape) != tuple(self._envmap[0].shape):
+            raise ValueError(f"envmap {tuple(envmap.shape)} is {tuple(env.shape)} once prepared, the scene's map {tuple(self._envmap[0].shape)}: "
+                             "the size must stay that of add_envmap")
+        return env
+
+    def set_envmap_texture(self, env):
+        """Replaces the environment map's texels in place (include/zdr.h, zdr_scene_set_envmap_texture): ``env`` is the prepared
+        (H, H, 4) float32 map on the scene's device, of add_envmap's size.  The importance-sampling tables are kept."""
+        if self.env_count == 0:
+            raise ValueError("the scene has no environment map: call add_envmap first")
+        if tuple(env.shape) != tuple(self._envmap[0].shape) or env.device != self.device or env.dtype != torch.float32:
+            raise ValueError(f"env must be a float32 {tuple(self._envmap[0].shape)} tensor on {self.device}")
+        env = env.detach().contiguous()
+        if env.data_ptr() % 16:                             # the copy moves float4 texels: a view at an odd offset is copied first
+            env = env.clone()
+        N.check(N.lib().zdr_scene_set_envmap_texture(self._handle, env.data_ptr(), self._stream()))
+
+    def _check_d_env(self, d_env):
+        if self.env_count == 0:
+            raise ValueError("d_env needs an environment map: call add_envmap first")
+        if tuple(d_env.shape) != tuple(self._envmap[0].shape) or not d_env.is_contiguous() or d_env.device != self.device or d_env.dtype != torch.float32:
+            raise ValueError(f"d_env must be a contiguous float32 {tuple(self._envmap[0].shape)} tensor on {self.device}")
+
     def set_pmj02bn_tables(self, pmj_samples, blue_noise):
         """pmj_samples: uint32 [nsets][nsamples][2]; blue_noise: uint16 [ntex][res][res] (pmj02bn.py:9-18)."""
         pmj = np.ascontiguousarray(pmj_samples, np.uint32)
@@ -241,9 +290,9 @@ class Scene:
         return image
 
     def render_backward_materials(self, grad_output, d_materials, materials, res, spp, seed, *, dims=None, rect=None, samples=None, camera=None,
-                                  tile_shard=None, slots=None):
+                                  tile_shard=None, slots=None, d_env=None):
         """``render_backward`` with one material per slot: accumulates into ``d_materials`` (a list shaped like ``materials``, or
-        one packed tensor); uses ``seed + 1`` like render_backward."""
+        one packed tensor); uses ``seed + 1`` like render_backward.  ``d_env``: as in render_backward."""
         packed, d, _ = self._material_call(materials, dims, slots)
         listed = isinstance(d_materials, (list, tuple))
         dpacked = (torch.cat([g.reshape(-1, 4) for g in d_materials]) if len(d_materials) > 1 else d_materials[0]) if listed else d_materials
@@ -251,8 +300,13 @@ class Scene:
             raise ValueError(f"d_materials must be contiguous float32 on {self.device}, shaped like the materials")
         g = grad_output.reshape(res[1], res[0], 4).to(device=self.device, dtype=torch.float32).contiguous()
         p = self._params(res, spp, seed + 1, (1, 1), rect, samples, camera, tile_shard=tile_shard)
-        N.check(N.lib().zdr_render_backward_materials(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
-                                                      dpacked.data_ptr(), self._stream()))
+        if d_env is None:
+            N.check(N.lib().zdr_render_backward_materials(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
+                                                          dpacked.data_ptr(), self._stream()))
+        else:
+            self._check_d_env(d_env)
+            N.check(N.lib().zdr_render_backward_materials_env(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
+                                                              dpacked.data_ptr(), d_env.data_ptr(), self._stream()))
         if listed and len(d_materials) > 1:
             off = 0
             for t in d_materials:
@@ -305,8 +359,10 @@ class Scene:
         N.check(N.lib().zdr_render_forward(self._handle, C.byref(p), material.data_ptr(), image.data_ptr(), self._stream()))
         return image
 
-    def render_backward(self, grad_output, d_material, material, res, spp, seed, *, rect=None, samples=None, camera=None, tile_shard=None):
-        """render.py:176-199: accumulates into ``d_material``; uses ``seed + 1`` like the reference (:196)."""
+    def render_backward(self, grad_output, d_material, material, res, spp, seed, *, rect=None, samples=None, camera=None, tile_shard=None, d_env=None):
+        """render.py:176-199: accumulates into ``d_material``; uses ``seed + 1`` like the reference (:196).  ``d_env``: a prepared
+        (H, H, 4) float32 tensor of the map's size that also accumulates the gradient of the environment map (zdr_render_backward_env;
+        path and direct — collocated has no environment term and leaves it alone)."""
         self._check_material(material)
         material = material.detach().contiguous()
         g = grad_output.reshape(res[1], res[0], 4).to(device=self.device, dtype=torch.float32).contiguous()
@@ -314,7 +370,12 @@ class Scene:
         if d_material.device != self.device or d_material.dtype != torch.float32:
             raise ValueError(f"d_material must be a float32 tensor on {self.device}")
         p = self._params(res, spp, seed + 1, material.shape[0:2], rect, samples, camera, tile_shard=tile_shard)
-        N.check(N.lib().zdr_render_backward(self._handle, C.byref(p), g.data_ptr(), material.data_ptr(), d_material.data_ptr(), self._stream()))
+        if d_env is None:
+            N.check(N.lib().zdr_render_backward(self._handle, C.byref(p), g.data_ptr(), material.data_ptr(), d_material.data_ptr(), self._stream()))
+        else:
+            self._check_d_env(d_env)
+            N.check(N.lib().zdr_render_backward_env(self._handle, C.byref(p), g.data_ptr(), material.data_ptr(), d_material.data_ptr(),
+                                                    d_env.data_ptr(), self._stream()))
         return d_material, None, None, None, None
 
     def render_stats(self, material, res, spp, seed=0, *, rect=None, samples=None, tile_shard=None) -> dict:
@@ -327,33 +388,50 @@ class Scene:
         return dict(zip(N.COUNTER_NAMES, list(cnt)))
 
     class RenderOperator(torch.autograd.Function):     # render.py:201-223
+        """render() of one material; with a prepared environment map as a sixth input also differentiable w.r.t. the map."""
         @staticmethod
-        def forward(ctx, material, self, *args):
+        def forward(ctx, material, self, res, spp, seed, env=None):
+            if env is not None:                            # the map this forward renders with: uploaded now, saved for the backward
+                env = env.detach().clone()
+                self.set_envmap_texture(env)
             ctx.save_for_backward(material)
+            ctx.env = env                                  # (a detached copy: kept as it is, not as a saved input)
+            ctx.with_env = env is not None
             ctx.scene = weakref.ref(self)
-            ctx.args = args
+            ctx.args = (res, spp, seed)
             ctx.camera = self.camera.copy()
             ctx.emissions = self.emissions
-            return self.render_forward(material.detach(), *args)
+            return self.render_forward(material.detach(), res, spp, seed)
 
         @staticmethod
         def backward(ctx, grad_output):
             scene = ctx.scene()
-            # scene.camera / lights may have changed between forward and backward: replay the
-            # snapshot (camera restored afterwards, lights left at the snapshot — render.py:216-222)
+            # scene.camera / lights / environment map may have changed between forward and backward: replay the
+            # snapshot (camera restored afterwards, lights and map left at the snapshot — render.py:216-222)
             if scene.emissions is not ctx.emissions:
                 scene.update_lights(ctx.emissions)
             material, = ctx.saved_tensors
+            env = ctx.env
             mat_grad = torch.zeros(material.size(), dtype=material.dtype, device=material.device)
             res, spp, seed = ctx.args
-            return scene.render_backward(grad_output, mat_grad, material.detach(), res, spp, seed, camera=ctx.camera)
+            if not ctx.with_env:
+                return scene.render_backward(grad_output, mat_grad, material.detach(), res, spp, seed, camera=ctx.camera)
+            scene.set_envmap_texture(env)                  # the material gradient depends on the map's values too
+            d_env = torch.zeros_like(env)
+            scene.render_backward(grad_output, mat_grad, material.detach(), res, spp, seed, camera=ctx.camera, d_env=d_env)
+            return mat_grad, None, None, None, None, d_env
 
     class MaterialsOperator(torch.autograd.Function):
         """render() of several materials: takes their packed texels, returns their packed gradient (torch.cat's own backward
         hands each material its part)."""
         @staticmethod
-        def forward(ctx, packed, self, dims, slots, res, spp, seed):
+        def forward(ctx, packed, self, dims, slots, res, spp, seed, env=None):
+            if env is not None:                            # as RenderOperator
+                env = env.detach().clone()
+                self.set_envmap_texture(env)
             ctx.save_for_backward(packed)
+            ctx.env = env
+            ctx.with_env = env is not None
             ctx.scene = weakref.ref(self)
             ctx.args = (dims, slots, res, spp, seed)
             ctx.camera = self.camera.copy()
@@ -366,27 +444,45 @@ class Scene:
             if scene.emissions is not ctx.emissions:        # as RenderOperator: lights left at the snapshot
                 scene.update_lights(ctx.emissions)
             packed, = ctx.saved_tensors
+            env = ctx.env
             dims, slots, res, spp, seed = ctx.args
             d = torch.zeros(packed.size(), dtype=packed.dtype, device=packed.device)
+            d_env = None
+            if ctx.with_env:
+                scene.set_envmap_texture(env)
+                d_env = torch.zeros_like(env)
             # slots = the forward's table: uploaded again if material_slots changed in between
-            scene.render_backward_materials(grad_output, d, packed.detach(), res, spp, seed, dims=dims, camera=ctx.camera, slots=slots)
-            return d, None, None, None, None, None, None
+            scene.render_backward_materials(grad_output, d, packed.detach(), res, spp, seed, dims=dims, camera=ctx.camera, slots=slots, d_env=d_env)
+            return (d, None, None, None, None, None, None) + ((d_env,) if ctx.with_env else ())
 
-    def render(self, material, *, res, spp, seed=0):
+    def render(self, material, *, res, spp, seed=0, envmap=None):
         """Renders the scene; differentiable w.r.t. ``material`` ((Ht, Wt, 4) float32 on the GPU).
         res = (width, height); returns (height, width, 4) (render.py:225-241).
 
         ``material`` may also be a list or tuple of such tensors (sizes may differ): model i is then shaded by material
         ``material_slots[i]``, or — with ``material_slots`` unset — the k-th non-emitting model by the k-th material (the list
-        must then hold one material per non-emitting model).  With ``material_slots`` set a single tensor is a one-element list."""
+        must then hold one material per non-emitting model).  With ``material_slots`` set a single tensor is a one-element list.
+
+        ``envmap``: a float32 tensor on the GPU, (H, 2H, 3|4) or (H, H, 3|4), that the render uses as the environment map and
+        differentiates (path and direct; collocated sees no environment).  It is prepared as add_envmap prepares an image (alpha 1
+        for RGB, a 1:2 map made square), must then have the size given to add_envmap, and becomes the scene's map: later renders
+        without ``envmap=`` use it too.  The importance-sampling tables stay those of add_envmap or of the last
+        update_envmap_sampling, and the gradient holds them fixed.  At most 15 materials with ``envmap=``."""
+        env = None if envmap is None else self._prepare_envmap(envmap)
         if not isinstance(material, (list, tuple)) and self._material_slots is None:
+            if env is not None:
+                return Scene.RenderOperator.apply(material, self, res, spp, seed, env)
             return Scene.RenderOperator.apply(material, self, res, spp, seed)
         mats = list(material) if isinstance(material, (list, tuple)) else [material]
+        if env is not None and len(mats) > N.MAX_MATERIALS - 1:
+            raise ValueError(f"{len(mats)} materials given with envmap=: at most {N.MAX_MATERIALS - 1} (the map takes the last entry of the material table)")
         for m in mats:
             self._check_material(m)
         slots = resolve_material_slots(self._material_slots, self.emissions, len(mats))
         dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
         packed = mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
+        if env is not None:
+            return Scene.MaterialsOperator.apply(packed, self, dims, slots, res, spp, seed, env)
         return Scene.MaterialsOperator.apply(packed, self, dims, slots, res, spp, seed)
 
     def render_duvdxy(self, material, *, res, spp, seed=0):
