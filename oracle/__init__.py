@@ -63,6 +63,9 @@ def lib(variant: str = "ieee"):
         L.zdro_scene_set_envmap.argtypes = [C.c_void_p, fp, C.c_int, C.c_int, fp, ip, C.c_int, fp, C.c_int, C.c_int]
         L.zdro_render_forward.argtypes = [C.c_void_p, C.POINTER(Params), fp, fp, C.POINTER(C.c_uint64)]
         L.zdro_render_backward.argtypes = [C.c_void_p, C.POINTER(Params), fp, fp, fp, C.POINTER(C.c_uint64)]
+        L.zdro_scene_set_material_slots.argtypes = [C.c_void_p, ip]
+        L.zdro_render_forward_materials.argtypes = [C.c_void_p, C.POINTER(Params), fp, ip, C.c_int, fp, C.POINTER(C.c_uint64)]
+        L.zdro_render_backward_materials.argtypes = [C.c_void_p, C.POINTER(Params), fp, fp, ip, C.c_int, fp, C.POINTER(C.c_uint64)]
         L.zdro_path_dump.argtypes = [C.c_void_p, C.POINTER(Params), fp, fp, ip, C.c_int, C.c_int, fp]
         L.zdro_trace_closest.argtypes = [C.c_void_p, fp, C.c_int, ip, fp]
         L.zdro_trace_any.argtypes = [C.c_void_p, fp, C.c_int, ip]
@@ -168,6 +171,50 @@ class OracleScene:
         if rc:
             raise RuntimeError(f"oracle backward failed rc={rc}")
         return (dm, dict(zip(COUNTER_NAMES, list(cnt)))) if counters else dm
+
+    def set_material_slots(self, slots):
+        """One entry per instance: its material's index in the lists given to render_*_materials, or None / -1; None = no material
+        anywhere (zdr_amd.Scene.material_slots)."""
+        if slots is None:
+            self._L.zdro_scene_set_material_slots(self.h, None)
+            return
+        t = np.array([-1 if k is None else int(k) for k in slots], np.int32)
+        assert t.shape == (self.ninst,), (t.shape, self.ninst)
+        self._L.zdro_scene_set_material_slots(self.h, _i(t))
+
+    @staticmethod
+    def _pack(materials):
+        mats = [np.ascontiguousarray(m, np.float32) for m in materials]
+        for m in mats:
+            assert m.ndim == 3 and m.shape[2] == 4, m.shape
+        dims = np.array([m.shape[:2] for m in mats], np.int32).reshape(-1, 2)
+        return mats, np.ascontiguousarray(np.concatenate([m.reshape(-1) for m in mats])), dims
+
+    def render_forward_materials(self, params: Params, materials, counters: bool = False):
+        """render_forward with one material per slot (set_material_slots); ``materials``: a list of (h_k, w_k, 4) arrays."""
+        _, packed, dims = self._pack(materials)
+        img = np.zeros((params.height, params.width, 4), np.float32)
+        cnt = (C.c_uint64 * 8)()
+        rc = self._L.zdro_render_forward_materials(self.h, C.byref(params), _f(packed), _i(dims), dims.shape[0], _f(img), cnt)
+        if rc:
+            raise RuntimeError(f"oracle forward (materials) failed rc={rc}")
+        return (img, dict(zip(COUNTER_NAMES, list(cnt)))) if counters else img
+
+    def render_backward_materials(self, params: Params, d_image: np.ndarray, materials, counters: bool = False):
+        """render_backward with one material per slot: returns one gradient per material, shaped like it."""
+        mats, packed, dims = self._pack(materials)
+        d_image = np.ascontiguousarray(d_image, np.float32)
+        assert d_image.shape == (params.height, params.width, 4)
+        dm = np.zeros_like(packed)
+        cnt = (C.c_uint64 * 8)()
+        rc = self._L.zdro_render_backward_materials(self.h, C.byref(params), _f(d_image), _f(packed), _i(dims), dims.shape[0], _f(dm), cnt)
+        if rc:
+            raise RuntimeError(f"oracle backward (materials) failed rc={rc}")
+        out, off = [], 0
+        for m in mats:
+            out.append(dm[off:off + m.size].reshape(m.shape))
+            off += m.size
+        return (out, dict(zip(COUNTER_NAMES, list(cnt)))) if counters else out
 
     def path_dump(self, params: Params, material: np.ndarray, queries: np.ndarray, d_image=None, maxv: int = 16) -> np.ndarray:
         """queries (n, 3) int32 {px, py, sample_index} -> (n, 8 + 24 maxv) float32 per-path trace (layout: zdr_oracle.c)."""

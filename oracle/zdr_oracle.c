@@ -57,6 +57,7 @@ struct zdro_scene {
     float *xform;       /* ninst x 16 row-major */
     float *nmat;        /* ninst x 9: inverse(transpose(M3x3)) (interaction.py:28) */
     float *emission;    /* ninst x 3 (heap slot 23333, render.py:120-123) */
+    int32_t *slot;      /* ninst: material of each instance in a material-table call, -1 = none (zdro_scene_set_material_slots) */
     int32_t *light_insts; /* heap slot 23334 (render.py:121) */
     int light_count;
     int32_t *tri_inst;  /* instance of each triangle */
@@ -130,6 +131,8 @@ zdro_scene *zdro_scene_create(const float *verts, int nverts, const int32_t *tri
     s->nmat = (float *)malloc(sizeof(float) * 9 * ninst);
     s->emission = (float *)malloc(sizeof(float) * 3 * ninst);
     memcpy(s->emission, inst_emission, sizeof(float) * 3 * ninst);
+    s->slot = (int32_t *)malloc(sizeof(int32_t) * ninst);
+    for (int i = 0; i < ninst; i++) s->slot[i] = -1;
     s->light_insts = (int32_t *)malloc(sizeof(int32_t) * ninst);
     s->tri_inst = (int32_t *)malloc(sizeof(int32_t) * (size_t)ntris);
     s->wp = (v3 *)malloc(sizeof(v3) * 3 * (size_t)ntris);
@@ -153,7 +156,7 @@ zdro_scene *zdro_scene_create(const float *verts, int nverts, const int32_t *tri
 void zdro_scene_destroy(zdro_scene *s) {
     if (!s) return;
     free(s->verts); free(s->tris); free(s->tri_begin); free(s->xform); free(s->nmat);
-    free(s->emission); free(s->light_insts); free(s->tri_inst); free(s->wp); free(s->planes);
+    free(s->emission); free(s->slot); free(s->light_insts); free(s->tri_inst); free(s->wp); free(s->planes);
     free(s->env_tex); free(s->alias_prob); free(s->alias_idx); free(s->env_pdf); free(s->bvh); free(s->bvh_tri); free(s);
 }
 
@@ -175,6 +178,10 @@ void zdro_scene_set_envmap(zdro_scene *s, const float *tex, int tex_h, int tex_w
 void zdro_scene_set_emissions(zdro_scene *s, const float *e) {
     memcpy(s->emission, e, sizeof(float) * 3 * s->ninst);
     rebuild_lights(s);
+}
+
+void zdro_scene_set_material_slots(zdro_scene *s, const int32_t *slots) {
+    for (int i = 0; i < s->ninst; i++) s->slot[i] = slots ? (slots[i] < 0 ? -1 : slots[i]) : -1;
 }
 
 /* ------------------------------------------------- ray / triangle (LC Accel) */
@@ -795,6 +802,19 @@ static void write_bsdf_grad(double *dm, int tex_h, int tex_w, v2 uv, v4 g) { /* 
 static int v4_any_nan(v4 g) { return isnan(g.x) || isnan(g.y) || isnan(g.z) || isnan(g.w); }
 static int v4_any_nonzero(v4 g) { return g.x != 0 || g.y != 0 || g.z != 0 || g.w != 0; }
 
+/* Material table, the twin of the kernels' (zdr_scene_set_material_slots, zdr_render_*_materials; integrators.h): instance i is
+ * shaded by material slot[i] (< 0: none), material k is tex[k] (h[k] x w[k] texels) and its gradient accumulates into dm[k]
+ * (float64; NULL when nothing is accumulated).  A single-material call runs as a table of one with the legacy slots (legacy_slots). */
+typedef struct {
+    int n;
+    const float *tex[ZDRO_MAX_MATERIALS];
+    int h[ZDRO_MAX_MATERIALS], w[ZDRO_MAX_MATERIALS];
+    double *dm[ZDRO_MAX_MATERIALS];
+    const int32_t *slot;
+} mtab_t;
+static v4 mtab_read(const mtab_t *M, int k, v2 uv) { return read_bsdf(M->tex[k], M->h[k], M->w[k], uv); }
+static void mtab_write_grad(const mtab_t *M, int k, v2 uv, v4 g) { write_bsdf_grad(M->dm[k], M->h[k], M->w[k], uv, g); }
+
 /* ------------------------------------------------------------------ lights */
 typedef struct { v3 wi; float dist, pdf; v3 eval; } light_sample_t; /* light.py:11 */
 
@@ -915,14 +935,17 @@ typedef struct { uint64_t c[8]; } counters_t;
 enum { C_SAMPLES, C_CLOSEST, C_HITS, C_SHADOW, C_SHADED, C_EMIT_BSDF, C_NAN, C_SCATTER };
 
 /* ------------------------------------------------------------- collocated */
-static v3 collocated_estimator(const zdro_scene *s, const zdro_params *P, const float *mat, ray_t ray, counters_t *C) { /* collocated.py:11-31 */
+/* an instance without a material is black (legacy table: every instance has material 0) */
+static v3 collocated_estimator(const zdro_scene *s, const zdro_params *P, const mtab_t *M, ray_t ray, counters_t *C) { /* collocated.py:11-31 */
     C->c[C_CLOSEST]++;
     hit_t hit = trace_closest(s, &ray);
     if (hit.inst < 0) return V3(0, 0, 0);
     C->c[C_HITS]++;
     interaction_t it = surface_interact(s, &hit);
     if (vdot(vneg(ray.d), it.ng) < 1e-4f || vdot(vneg(ray.d), it.ns) < 1e-4f) return V3(0, 0, 0);
-    v4 m = read_bsdf(mat, P->tex_h, P->tex_w, it.uv);
+    const int k = M->slot[hit.inst];
+    if (k < 0) return V3(0, 0, 0);
+    v4 m = mtab_read(M, k, it.uv);
     C->c[C_SHADED]++;
     onb_t onb = make_onb(it.ns);
     v3 wo = to_local(&onb, vneg(ray.d));
@@ -931,17 +954,19 @@ static v3 collocated_estimator(const zdro_scene *s, const zdro_params *P, const 
     return vscale(beta, li);
 }
 
-static void collocated_backward(const zdro_scene *s, const zdro_params *P, const float *mat, double *dmat, ray_t ray, v3 le_grad, counters_t *C) { /* collocated.py:35-57 */
+static void collocated_backward(const zdro_scene *s, const zdro_params *P, const mtab_t *M, ray_t ray, v3 le_grad, counters_t *C) { /* collocated.py:35-57 */
     hit_t hit = trace_closest(s, &ray);
     if (hit.inst < 0) return;
     interaction_t it = surface_interact(s, &hit);
     if (vdot(vneg(ray.d), it.ng) < 1e-4f || vdot(vneg(ray.d), it.ns) < 1e-4f) return;
-    v4 m = read_bsdf(mat, P->tex_h, P->tex_w, it.uv);
+    const int k = M->slot[hit.inst];
+    if (k < 0) return;
+    v4 m = mtab_read(M, k, it.uv);
     onb_t onb = make_onb(it.ns);
     v3 wo = to_local(&onb, vneg(ray.d));
     float inv = 1.0f / hit.t, li = inv * inv;
     v4 g = ggx_brdf_grad(wo, wo, V3(m.x, m.y, m.z), 0.04f, m.w, vscale(le_grad, li));
-    if (!v4_any_nan(g)) { write_bsdf_grad(dmat, P->tex_h, P->tex_w, it.uv, g); C->c[C_SCATTER]++; }
+    if (!v4_any_nan(g)) { mtab_write_grad(M, k, it.uv, g); C->c[C_SCATTER]++; }
 }
 
 /* ------------------------------------------------------------------ uvgrad */
@@ -981,18 +1006,20 @@ static v4 uvgrad_estimator(const zdro_scene *s, ray_t ray, ray_t rdx, ray_t rdy)
 }
 
 /* ------------------------------------------------------------------ direct */
-/* Walks direct.py:21-85; when dmat != NULL also accumulates the adjoint of
- * direct.py:89-167 (gradient written at the PRIMARY uv, App. B-11). */
-static v3 direct_walk(const zdro_scene *s, const zdro_params *P, const float *mat, ray_t ray, sampler_t *smp,
-                      double *dmat, v3 le_grad, counters_t *C) {
+/* Walks direct.py:21-85; when dmat != 0 also accumulates the adjoint of
+ * direct.py:89-167 (gradient written at the PRIMARY uv, App. B-11).  An instance without a material returns its emission, one with a
+ * material is shaded by it, even an emitter (legacy table: instance 0 only, direct.py:30-32). */
+static v3 direct_walk(const zdro_scene *s, const zdro_params *P, const mtab_t *M, ray_t ray, sampler_t *smp,
+                      int dmat, v3 le_grad, counters_t *C) {
     C->c[C_CLOSEST]++;
     hit_t hit = trace_closest(s, &ray);
     if (hit.inst < 0) return s->env_count > 0 ? env_lookup(s, direction_to_uv(ray.d)) : V3(0, 0, 0); /* direct.py:23-24 */
     C->c[C_HITS]++;
     interaction_t it = surface_interact(s, &hit);
     if (vdot(vneg(ray.d), it.ng) < 1e-4f || vdot(vneg(ray.d), it.ns) < 1e-4f) return V3(0, 0, 0);
-    if (hit.inst > 0) { const float *e = s->emission + 3 * hit.inst; return V3(e[0], e[1], e[2]); } /* direct.py:30-32 */
-    v4 m = read_bsdf(mat, P->tex_h, P->tex_w, it.uv);
+    const int k = M->slot[hit.inst];
+    if (k < 0) { const float *e = s->emission + 3 * hit.inst; return V3(e[0], e[1], e[2]); } /* direct.py:30-32 */
+    v4 m = mtab_read(M, k, it.uv);
     v3 diffuse = V3(m.x, m.y, m.z); float roughness = m.w; const float specular = 0.04f;
     C->c[C_SHADED]++;
     v2 uv0 = it.uv;
@@ -1050,7 +1077,7 @@ static v3 direct_walk(const zdro_scene *s, const zdro_params *P, const float *ma
         }
     } while (0);
     if (dmat && v4_any_nonzero(mat_grad) && !v4_any_nan(mat_grad)) {
-        write_bsdf_grad(dmat, P->tex_h, P->tex_w, uv0, mat_grad); C->c[C_SCATTER]++;
+        mtab_write_grad(M, k, uv0, mat_grad); C->c[C_SCATTER]++;
     }
     return radiance;
 }
@@ -1068,11 +1095,12 @@ typedef struct {
     float nee_pb_frac;             /* pdf_bsdf / (pdf_light + pdf_bsdf) of the accepted light sample */
     v3 beta_out;                   /* throughput leaving the vertex (unit luminance when rr_scaled) */
     int inst, prim; v3 wi_world, L_nee;   /* zdro_path_dump only: the hit, the sampled direction in world space, the NEE radiance added here */
+    int mk;                        /* material (entry of the material table) */
 } path_vertex_t;
 
 /* prb.py:19-88 with the current helper signatures (App. B-1). Optionally records
  * the shaded vertices (for the adjoint sweep) and the terminal emitter term. */
-static v3 path_walk(const zdro_scene *s, const zdro_params *P, const float *mat, ray_t ray, sampler_t *smp,
+static v3 path_walk(const zdro_scene *s, const zdro_params *P, const mtab_t *M, ray_t ray, sampler_t *smp,
                     path_vertex_t *rec, int *nrec, v3 *terminal_Li, counters_t *C, float *terminal_pl_frac) {
     if (terminal_pl_frac) *terminal_pl_frac = 0.0f;
     v3 radiance = V3(0, 0, 0), beta = V3(1, 1, 1);
@@ -1108,12 +1136,13 @@ static v3 path_walk(const zdro_scene *s, const zdro_params *P, const float *mat,
             if (depth > 0) C->c[C_EMIT_BSDF]++;
             break;
         }
-        if (hit.inst > 0) break; /* prb.py:45-46 */
-        v4 m = read_bsdf(mat, P->tex_h, P->tex_w, it.uv);
+        const int mk = M->slot[hit.inst];
+        if (mk < 0) break; /* prb.py:45-46 (legacy table: instance 0 only) */
+        v4 m = mtab_read(M, mk, it.uv);
         v3 diffuse = V3(m.x, m.y, m.z); float roughness = m.w; const float specular = 0.04f;
         C->c[C_SHADED]++;
         path_vertex_t *pv = rec ? &rec[nr] : 0;
-        if (pv) { memset(pv, 0, sizeof *pv); pv->uv = it.uv; pv->mat = m; pv->beta = beta; pv->q = 1.0f; pv->inst = hit.inst; pv->prim = hit.prim; }
+        if (pv) { memset(pv, 0, sizeof *pv); pv->uv = it.uv; pv->mat = m; pv->beta = beta; pv->q = 1.0f; pv->inst = hit.inst; pv->prim = hit.prim; pv->mk = mk; }
         nr++;
         onb_t onb = make_onb(it.ns);
         v3 wo = to_local(&onb, vneg(ray.d));
@@ -1160,12 +1189,12 @@ static v3 path_walk(const zdro_scene *s, const zdro_params *P, const float *mat,
  * sweep runs last-to-first carrying Li. ZDRO_PRB_LITERAL
  * reproduces the weight of prb.py:162 (beta/pdf * Le_remaining) for comparison. */
 typedef struct { path_vertex_t rec[ZDRO_MAX_DEPTH]; v4 grad[ZDRO_MAX_DEPTH]; int n; v3 L, term_Li; } path_trace_t;   /* zdro_path_dump */
-static void path_backward(const zdro_scene *s, const zdro_params *P, const float *mat, double *dmat, ray_t ray,
+static void path_backward(const zdro_scene *s, const zdro_params *P, const mtab_t *M, ray_t ray,
                           sampler_t *smp, v3 le_grad, counters_t *C, path_trace_t *trace) {
     path_vertex_t rec_local[ZDRO_MAX_DEPTH];
     path_vertex_t *rec = trace ? trace->rec : rec_local;
     int n = 0; v3 Li; float term_pl_frac = 0.0f;
-    v3 Le = path_walk(s, P, mat, ray, smp, rec, &n, &Li, C, &term_pl_frac);
+    v3 Le = path_walk(s, P, M, ray, smp, rec, &n, &Li, C, &term_pl_frac);
     if (trace) { trace->n = n; trace->L = Le; trace->term_Li = Li; memset(trace->grad, 0, sizeof trace->grad); }
     if (vany_nan(Le)) return; /* prb.py:100 */
     const float specular = 0.04f;
@@ -1245,8 +1274,8 @@ static void path_backward(const zdro_scene *s, const zdro_params *P, const float
         Lg = vadd(vmul(vmul(fL, v->W), le_grad), vmul(T, Y));
         Li = vadd(vmul(fL, v->W), vmul(T, Li));
         if (trace) trace->grad[k] = grad;
-        if (dmat && v4_any_nonzero(grad) && !v4_any_nan(grad)) { /* prb.py:178-187 */
-            write_bsdf_grad(dmat, P->tex_h, P->tex_w, v->uv, grad); C->c[C_SCATTER]++;
+        if (M->dm[v->mk] && v4_any_nonzero(grad) && !v4_any_nan(grad)) { /* prb.py:178-187 */
+            mtab_write_grad(M, v->mk, v->uv, grad); C->c[C_SCATTER]++;
         }
     }
 }
@@ -1277,8 +1306,35 @@ static int check_params(const zdro_params *P) {
     return 0;
 }
 
-int zdro_render_forward(const zdro_scene *s, const zdro_params *P, const float *material, float *image, uint64_t *counters) {
-    int rc = check_params(P); if (rc) return rc;
+/* The slot table of a single-material call: path / direct shade instance 0 only (prb.py:45-46, direct.py:30-32), collocated every
+ * instance (collocated.py:11-31).  Caller frees. */
+static int32_t *legacy_slots(const zdro_scene *s, int integrator) {
+    int32_t *t = (int32_t *)malloc(sizeof(int32_t) * (size_t)s->ninst);
+    for (int i = 0; i < s->ninst; i++) t[i] = (i == 0 || integrator == ZDRO_COLLOCATED) ? 0 : -1;
+    return t;
+}
+static void legacy_table(const zdro_params *P, const float *material, const int32_t *slot, mtab_t *M) {
+    memset(M, 0, sizeof *M);
+    M->n = 1; M->tex[0] = material; M->h[0] = P->tex_h; M->w[0] = P->tex_w; M->slot = slot;
+}
+/* a material-table call's table over the packed materials; *ntexel = texels of all materials */
+static int material_table(const zdro_scene *s, const zdro_params *P, const float *materials, const int32_t *dims, int nmat, mtab_t *M, size_t *ntexel) {
+    if (nmat < 1 || nmat > ZDRO_MAX_MATERIALS || !materials || !dims) return -5;
+    if (P->integrator == ZDRO_UVGRAD) return -3;
+    memset(M, 0, sizeof *M);
+    size_t off = 0;
+    for (int k = 0; k < nmat; k++) {
+        if (dims[2 * k] < 1 || dims[2 * k + 1] < 1) return -5;
+        M->tex[k] = materials + 4 * off; M->h[k] = dims[2 * k]; M->w[k] = dims[2 * k + 1];
+        off += (size_t)M->h[k] * (size_t)M->w[k];
+    }
+    for (int i = 0; i < s->ninst; i++) if (s->slot[i] >= nmat) return -5;
+    M->n = nmat; M->slot = s->slot;
+    *ntexel = off;
+    return 0;
+}
+
+static int render_forward_tab(const zdro_scene *s, const zdro_params *P, const mtab_t *M, float *image, uint64_t *counters) {
     counters_t total; memset(&total, 0, sizeof total);
     int nth = P->nthreads;
 #ifdef _OPENMP
@@ -1312,9 +1368,9 @@ int zdro_render_forward(const zdro_scene *s, const zdro_params *P, const float *
                     ray_t ray = pixel_ray(P, x, y, &smp);
                     v3 rad;
                     C.c[C_SAMPLES]++;
-                    if (P->integrator == ZDRO_COLLOCATED) rad = collocated_estimator(s, P, material, ray, &C);
-                    else if (P->integrator == ZDRO_DIRECT) rad = direct_walk(s, P, material, ray, &smp, 0, V3(0, 0, 0), &C);
-                    else rad = path_walk(s, P, material, ray, &smp, 0, 0, 0, &C, 0);
+                    if (P->integrator == ZDRO_COLLOCATED) rad = collocated_estimator(s, P, M, ray, &C);
+                    else if (P->integrator == ZDRO_DIRECT) rad = direct_walk(s, P, M, ray, &smp, 0, V3(0, 0, 0), &C);
+                    else rad = path_walk(s, P, M, ray, &smp, 0, 0, 0, &C, 0);
                     if (!vany_nan(rad)) { /* integrator.py:27-28 */
                         sum.x += clampf(rad.x, 0.0f, 100000.0f); sum.y += clampf(rad.y, 0.0f, 100000.0f); sum.z += clampf(rad.z, 0.0f, 100000.0f);
                     } else C.c[C_NAN]++;
@@ -1330,11 +1386,10 @@ int zdro_render_forward(const zdro_scene *s, const zdro_params *P, const float *
     return 0;
 }
 
-int zdro_render_backward(const zdro_scene *s, const zdro_params *P, const float *d_image, const float *material,
-                         float *d_material, uint64_t *counters) {
-    int rc = check_params(P); if (rc) return rc;
+/* d_out: the gradients of all materials of M, packed in table order (ntex floats), accumulated into (+=) */
+static int render_backward_tab(const zdro_scene *s, const zdro_params *P, const float *d_image, mtab_t *M, size_t ntex,
+                               float *d_out, uint64_t *counters) {
     counters_t total; memset(&total, 0, sizeof total);
-    size_t ntex = (size_t)P->tex_h * P->tex_w * 4;
     int nth = P->nthreads;
 #ifdef _OPENMP
     if (nth <= 0) nth = omp_get_max_threads();
@@ -1345,6 +1400,7 @@ int zdro_render_backward(const zdro_scene *s, const zdro_params *P, const float 
      * atomic_fetch_add (interaction.py:67-70).  float64 sums make the arrival order irrelevant at
      * float32 output precision. */
     double *dm = (double *)calloc(ntex, sizeof(double));
+    for (size_t k = 0, off = 0; k < (size_t)M->n; off += 4 * (size_t)M->h[k] * (size_t)M->w[k], k++) M->dm[k] = dm + off;
     g_atomic_scatter = nth > 1;
 #pragma omp parallel num_threads(nth)
     {
@@ -1359,19 +1415,55 @@ int zdro_render_backward(const zdro_scene *s, const zdro_params *P, const float 
                     sampler_t smp = make_sampler(P->sampler, x, y, P->seed, P->spp, it);
                     ray_t ray = pixel_ray(P, x, y, &smp);
                     C.c[C_SAMPLES]++;
-                    if (P->integrator == ZDRO_COLLOCATED) collocated_backward(s, P, material, dm, ray, le_grad, &C);
-                    else if (P->integrator == ZDRO_DIRECT) (void)direct_walk(s, P, material, ray, &smp, dm, le_grad, &C);
-                    else path_backward(s, P, material, dm, ray, &smp, le_grad, &C, 0);
+                    if (P->integrator == ZDRO_COLLOCATED) collocated_backward(s, P, M, ray, le_grad, &C);
+                    else if (P->integrator == ZDRO_DIRECT) (void)direct_walk(s, P, M, ray, &smp, 1, le_grad, &C);
+                    else path_backward(s, P, M, ray, &smp, le_grad, &C, 0);
                 }
             }
 #pragma omp critical
         for (int i = 0; i < 8; i++) total.c[i] += C.c[i];
     }
 #pragma omp parallel for schedule(static)
-    for (size_t i = 0; i < ntex; i++) d_material[i] = (float)((double)d_material[i] + dm[i]);
+    for (size_t i = 0; i < ntex; i++) d_out[i] = (float)((double)d_out[i] + dm[i]);
     free(dm);
+    for (int k = 0; k < M->n; k++) M->dm[k] = 0;
     if (counters) memcpy(counters, total.c, sizeof total.c);
     return 0;
+}
+
+int zdro_render_forward(const zdro_scene *s, const zdro_params *P, const float *material, float *image, uint64_t *counters) {
+    int rc = check_params(P); if (rc) return rc;
+    int32_t *slot = legacy_slots(s, P->integrator);
+    mtab_t M; legacy_table(P, material, slot, &M);
+    rc = render_forward_tab(s, P, &M, image, counters);
+    free(slot);
+    return rc;
+}
+
+int zdro_render_backward(const zdro_scene *s, const zdro_params *P, const float *d_image, const float *material,
+                         float *d_material, uint64_t *counters) {
+    int rc = check_params(P); if (rc) return rc;
+    int32_t *slot = legacy_slots(s, P->integrator);
+    mtab_t M; legacy_table(P, material, slot, &M);
+    rc = render_backward_tab(s, P, d_image, &M, (size_t)P->tex_h * P->tex_w * 4, d_material, counters);
+    free(slot);
+    return rc;
+}
+
+int zdro_render_forward_materials(const zdro_scene *s, const zdro_params *P, const float *materials, const int32_t *dims, int nmat,
+                                  float *image, uint64_t *counters) {
+    int rc = check_params(P); if (rc) return rc;
+    mtab_t M; size_t ntexel;
+    rc = material_table(s, P, materials, dims, nmat, &M, &ntexel); if (rc) return rc;
+    return render_forward_tab(s, P, &M, image, counters);
+}
+
+int zdro_render_backward_materials(const zdro_scene *s, const zdro_params *P, const float *d_image, const float *materials,
+                                   const int32_t *dims, int nmat, float *d_materials, uint64_t *counters) {
+    int rc = check_params(P); if (rc) return rc;
+    mtab_t M; size_t ntexel;
+    rc = material_table(s, P, materials, dims, nmat, &M, &ntexel); if (rc) return rc;
+    return render_backward_tab(s, P, d_image, &M, 4 * ntexel, d_materials, counters);
 }
 
 /* Per-path trace of the path integrator (test hook; twin of zdr_path_dump in include/zdr.h, same layout):
@@ -1386,6 +1478,8 @@ int zdro_path_dump(const zdro_scene *s, const zdro_params *P, const float *mater
     int rc = check_params(P); if (rc) return rc;
     if (maxv < 1 || maxv > ZDRO_MAX_DEPTH) return -4;
     const int stride = 8 + 24 * maxv;
+    int32_t *slot = legacy_slots(s, P->integrator);
+    mtab_t M; legacy_table(P, material, slot, &M);
 #pragma omp parallel for schedule(dynamic, 64)
     for (int i = 0; i < n; i++) {
         const int x = queries[3 * i], y = queries[3 * i + 1]; const uint32_t it = (uint32_t)queries[3 * i + 2];
@@ -1402,7 +1496,7 @@ int zdro_path_dump(const zdro_scene *s, const zdro_params *P, const float *mater
         ray_t ray = pixel_ray(P, x, y, &smp);
         counters_t C; memset(&C, 0, sizeof C);
         path_trace_t T; memset(&T, 0, sizeof T);
-        path_backward(s, P, material, 0, ray, &smp, le_grad, &C, &T);
+        path_backward(s, P, &M, ray, &smp, le_grad, &C, &T);
         int32_t nv = T.n; memcpy(&o[0], &nv, 4);
         o[1] = T.L.x; o[2] = T.L.y; o[3] = T.L.z; o[5] = T.term_Li.x; o[6] = T.term_Li.y; o[7] = T.term_Li.z;
         for (int k = 0; k < T.n && k < maxv; k++) {
@@ -1416,6 +1510,7 @@ int zdro_path_dump(const zdro_scene *s, const zdro_params *P, const float *mater
             q[16] = v->L_nee.x; q[17] = v->L_nee.y; q[18] = v->L_nee.z;
         }
     }
+    free(slot);
     return 0;
 }
 

@@ -74,6 +74,21 @@ int zdro_render_forward(const zdro_scene *, const zdro_params *, const float *ma
 int zdro_render_backward(const zdro_scene *, const zdro_params *, const float *d_image,
                          const float *material, float *d_material, uint64_t *counters);
 
+/* One material per instance (twins of zdr_scene_set_material_slots and zdr_render_*_materials, include/zdr.h).
+ * slots: ninst entries, the material of each instance, < 0 = none; NULL = none anywhere (the initial state).
+ * materials: the nmat textures packed in order, dims[2k], dims[2k+1] = (h, w) of material k; params' tex_h / tex_w are ignored.
+ * What a slot means is the kernels' (integrators.h): path — an emitter returns its emission first, otherwise no material ends the
+ * path; direct — no material returns the instance's emission, a material shades, even an emitter; collocated — no material is black.
+ * zdro_render_forward / _backward are these calls with the legacy table: path / direct {0, -1, -1, ...}, collocated {0, 0, ...}.
+ * d_materials (packed like materials) is ACCUMULATED into (+=), float64 internally, per material.
+ * Returns -5 for nmat outside [1, ZDRO_MAX_MATERIALS], a dimension < 1 or a slot >= nmat; -3 for the uvgrad integrator. */
+#define ZDRO_MAX_MATERIALS 16
+void zdro_scene_set_material_slots(zdro_scene *, const int32_t *slots);
+int zdro_render_forward_materials(const zdro_scene *, const zdro_params *, const float *materials, const int32_t *dims, int nmat,
+                                  float *image, uint64_t *counters);
+int zdro_render_backward_materials(const zdro_scene *, const zdro_params *, const float *d_image, const float *materials,
+                                   const int32_t *dims, int nmat, float *d_materials, uint64_t *counters);
+
 /* Per-path trace of the path integrator (twin of zdr_path_dump, include/zdr.h; layout in zdr_oracle.c). */
 int zdro_path_dump(const zdro_scene *, const zdro_params *, const float *material, const float *d_image /* or NULL */,
                    const int32_t *queries /* n x 3 */, int n, int maxv, float *out /* n x (8 + 24 maxv) */);

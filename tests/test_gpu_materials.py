@@ -1,5 +1,5 @@
-"""-m gpu: one material per model (Scene.material_slots, render(list); include/zdr.h zdr_render_*_materials).  The CPU oracle
-knows instance 0 only, so correctness rests on identities with the oracle-checked single-texture path — the legacy slot table
+"""-m gpu: one material per model (Scene.material_slots, render(list); include/zdr.h zdr_render_*_materials).  Parity with the
+oracle's material table is tests/test_gpu_materials_oracle.py; these are identities with the single-texture path — the legacy slot table
 renders what render(tensor) renders, a mesh split in two instances renders what it rendered whole, constant textures of any
 size render alike — and on finite differences of the forward render for the second material."""
 import numpy as np

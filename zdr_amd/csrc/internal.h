@@ -19,14 +19,15 @@
 #define ZDR_MAX_PERSISTENT_BLOCKS 8192   // 256 CUs x 4 SIMDs x 8 waves: upper bound of the path kernels' persistent grid
 
 // Material table of the zdr_render_*_materials calls (zdr.h), a kernel argument like the rest of KernelIO so that a captured graph
-// carries its own copy.  Material k is texels [texel, texel + h w) of the packed buffer and staging cells [cell, cell + (h + 1)(w + 1))
-// of one copy of the cell array (copies are ncells apart).  The texture base pointer stays scalar; only the entry is per lane.
-struct MaterialSlot { int32_t texel, h, w, cell; };
+// carries its own copy.  Material k is texels [texel, texel + h w) of the packed buffer; its staging cells have `copies` copies of
+// (h + 1)(w + 1) cells, copy j at [cell + j stride, ...), and a wave adds into copy blockIdx % copies (zdr_api.cpp, material_cell_layout).
+// The texture base pointer stays scalar; only the entry is per lane.
+struct MaterialSlot { int32_t texel, h, w, cell, copies, stride; };
 #define ZDR_ENV_CELL_BUDGET (1u << 22)   // environment gradient: most staging cells the map's copies take (256 MiB; zdr_api.cpp, render_common)
 static_assert(ZDR_ENV_ENTRY == ZDR_MAX_MATERIALS - 1, "the environment-gradient calls keep the map in the last entry of the material table");
 struct MaterialTable {
     const int32_t *inst_slot;         // ninst entries: material of each instance, -1 = none (zdr_scene_set_material_slots)
-    int32_t nmat, ncells;             // materials in use; cells of all of them (one copy)
+    int32_t nmat, ncells;             // materials in use; staging cells of all of them (of one copy when RenderCfg::cell_copies > 1)
     MaterialSlot m[ZDR_MAX_MATERIALS];
 };
 

@@ -180,9 +180,11 @@ static_assert(ZDR_SCATTER_CAP >= 64, "one push can add an entry per lane");
 //        wave adds into copy blockIdx % copies; k_cells_to_grad sums the copies (in float64);
 //      - at most ZDR_LDS_CELLS cells (textures up to 4x4): the wave keeps the WHOLE cell array in LDS (the queue's
 //        block), adds with ds_add_f32 and writes it out once, when the kernel ends.
-//  * Several materials (template MT, zdr_render_*_materials): the cell array is the concatenation of every material's cells
-//    (MaterialSlot::cell is the first), both rules above apply to the TOTAL, a push stores the entry's material in its cell word
-//    and the flush turns (uv, material) into that material's cell.
+//  * Several materials (template MT, zdr_render_*_materials): the cell array is the concatenation of every material's cells.  At
+//    most ZDR_LDS_CELLS cells in all: the LDS rule above for the whole array, with copies of all of it.  Otherwise each material has
+//    copies of its own (MaterialSlot::copies, sized by its own cells, zdr_api.cpp), so that a constant material beside a large
+//    texture is not left with one copy.  A push stores the entry's material in its cell word and the flush turns (uv, material)
+//    into that material's cell in the wave's copy of it.
 #define ZDR_LDS_CELLS 28             // 28 cells x 16 floats = the 448 floats of the queue's LDS block
 #define ZDR_MAX_CELL_COPIES 1024
 struct ScatterQueue {                // pointers into this wave's LDS block
@@ -250,7 +252,7 @@ ZD int env_cell(f2 uv, int env_h, int env_w, float &ox, float &oy) {
 template <class M>
 ZD int table_cell_env(const M &m, int k, int copy_base, f2 uv, float &ox, float &oy) {
     if (k == ZDR_ENV_ENTRY) return m.cell + (int)(blockIdx.x % (unsigned)m.texel) * ((m.h + 1) * (m.w + 1)) + env_cell(uv, m.h, m.w, ox, oy);
-    return copy_base + m.cell + scatter_cell(uv, m.h, m.w, ox, oy);
+    return m.cell + (int)(blockIdx.x % (unsigned)m.copies) * m.stride + scatter_cell(uv, m.h, m.w, ox, oy);
 }
 
 // must be called by the whole wave (reconverged control flow).  The queue holds (g, uv) as pushed; the flush first turns the uv of
@@ -271,9 +273,14 @@ ZD void scatter_flush(ScatterQueue &q, float *__restrict__ cells, int tex_h, int
             cell = table_cell_env(mats[k], k, q.copy_base, uv, ox, oy);
             q.cell[e] = (ablate == 2) ? (cell & 1023) : cell;
         } else {
-        if constexpr (MT) { const M m = mats[q.cell[e]]; cell = m.cell + scatter_cell(uv, m.h, m.w, ox, oy); }
-        else cell = scatter_cell(uv, tex_h, tex_w, ox, oy);
+        if constexpr (MT) {              // the entry's own copy (MaterialSlot): copy_base is not added
+            const M m = mats[q.cell[e]];
+            cell = m.cell + (int)(blockIdx.x % (unsigned)m.copies) * m.stride + scatter_cell(uv, m.h, m.w, ox, oy);
+            q.cell[e] = (ablate == 2) ? (cell & 1023) : cell;
+        } else {
+        cell = scatter_cell(uv, tex_h, tex_w, ox, oy);
         q.cell[e] = (ablate == 2) ? (cell & 1023) : (q.copy_base + cell);   // ablation 2: all atomics hit 64 KiB of L2
+        }
         }
         q.ox[e] = ox; q.oy[e] = oy;
     }

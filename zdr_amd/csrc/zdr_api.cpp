@@ -1088,6 +1088,31 @@ static int single_material_slots(zdr_scene *s, bool capturing, const int32_t *&o
     return ZDR_OK;
 }
 
+// Staging cells of a material table (scene.h, few texels).  At most ZDR_LDS_CELLS cells in all: the kernels keep the whole array in LDS and
+// add it into copy blockIdx % R.cell_copies of it, every material copied alike.  Otherwise each material has copies of its own, sized by
+// its own cells (a share of the budget of cell_copies_for), laid out one after the other; R.cell_copies = 1 and mt.ncells = all cells.
+// (Copies sized by the total left a 1 x 1 material beside a 1024 x 1024 texture with one copy of its 4 cells: 3.4 % off at 512^2 spp 256.)
+static void material_cell_layout(MaterialTable &mt, RenderCfg &R) {
+    if (mt.ncells <= ZDR_LDS_CELLS) {
+        R.cell_copies = cell_copies_for((size_t)mt.ncells);
+        for (int k = 0; k < mt.nmat; k++) { mt.m[k].copies = R.cell_copies; mt.m[k].stride = mt.ncells; }
+        return;
+    }
+    size_t cell = 0;
+    for (int pass = 0; pass < 2; pass++) {                  // pass 1: one copy each, if the copies would pass 2^26 cells
+        cell = 0;
+        for (int k = 0; k < mt.nmat; k++) {
+            const size_t one = (size_t)(mt.m[k].h + 1) * (size_t)(mt.m[k].w + 1);
+            const size_t copies = (pass == 0 && one < (1u << 16)) ? std::min<size_t>(ZDR_MAX_CELL_COPIES, std::max<size_t>(1, ((1u << 20) / (size_t)mt.nmat) / one)) : 1;
+            mt.m[k].cell = (int32_t)cell; mt.m[k].copies = (int32_t)copies; mt.m[k].stride = (int32_t)one;
+            cell += copies * one;
+        }
+        if (cell < (1ull << 26)) break;
+    }
+    R.cell_copies = 1;
+    mt.ncells = (int32_t)cell;
+}
+
 // mt_dims / nmat: a material-table call (zdr_render_*_materials), else nullptr / 0.  d_env (backward, path / direct): also the gradient of
 // the environment map, through the material-table kernels with the map as entry ZDR_ENV_ENTRY (a single material becomes a table of one).
 static int render_common(zdr_scene *s, const zdr_render_params *p, const float *material, float *image, const float *d_image,
@@ -1123,7 +1148,7 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
     size_t env_cells_total = 0;                         // environment gradient: the map's cells, all their copies
     if (use_mt || env_grad) {
         R.tex_h = R.tex_w = 0;                          // (unused in material-table mode)
-        R.cell_copies = cell_copies_for((size_t)mt.ncells);   // the materials' copies: as in the call without the map
+        material_cell_layout(mt, R);                    // the materials' copies: as in the call without the map
     }
     if (env_grad) {
         // The map's cells follow every copy of the materials' cells, with copies of their own (scene.h, table_cell_env): most light

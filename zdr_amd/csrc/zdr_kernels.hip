@@ -732,9 +732,10 @@ __global__ void k_cells_to_grad(const float4 *__restrict__ cells, float4 *__rest
     dmat[(size_t)x + (size_t)tex_w * y] = make_float4(d.x + acc.x, d.y + acc.y, d.z + acc.z, d.w + acc.w);
 }
 // The same for every material of a material-table call in one launch (blockIdx.z = material): material k's range of the packed
-// gradient receives what its range of the cells holds (+=).
-__global__ void k_material_cells_to_grad(const float4 *__restrict__ cells, float4 *__restrict__ dmat, MaterialTable mt, int copies) {
+// gradient receives what its copies of the cells hold (+=).
+__global__ void k_material_cells_to_grad(const float4 *__restrict__ cells, float4 *__restrict__ dmat, MaterialTable mt) {
     const MaterialSlot m = mt.m[blockIdx.z];
+    const int copies = m.copies;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= m.w || y >= m.h) return;
     const int tex_h = m.h, tex_w = m.w;
@@ -750,7 +751,7 @@ __global__ void k_material_cells_to_grad(const float4 *__restrict__ cells, float
     for (int k = 0; k < copies; k++)
         for (int b = 0; b < ny; b++)
             for (int a = 0; a < nx; a++) {
-                const size_t cell = (size_t)k * mt.ncells + (size_t)m.cell + (size_t)(ixs[a] + 1) + (size_t)(tex_w + 1) * (iys[b] + 1);
+                const size_t cell = (size_t)k * m.stride + (size_t)m.cell + (size_t)(ixs[a] + 1) + (size_t)(tex_w + 1) * (iys[b] + 1);
                 const float4 c = cells[4 * cell + 2 * dxs[a] + dys[b]];
                 if (copies == 1) { acc.x += c.x; acc.y += c.y; acc.z += c.z; acc.w += c.w; }
                 else { sx += c.x; sy += c.y; sz += c.z; sw += c.w; }
@@ -954,14 +955,14 @@ int zdr_launch_render(const DScene &S_in, const RenderCfg &R, const SamplerCfg &
         int mh = 1, mw = 1;
         for (int k = 0; k < io.mt.nmat; k++) { mh = std::max(mh, (int)io.mt.m[k].h); mw = std::max(mw, (int)io.mt.m[k].w); }
         dim3 g((mw + 63) / 64, mh, io.mt.nmat);
-        hipLaunchKernelGGL(k_material_cells_to_grad, g, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)io.d_material, io.mt, R.cell_copies);
+        hipLaunchKernelGGL(k_material_cells_to_grad, g, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)io.d_material, io.mt);
         if (d_env) {   // the map's cells into d_env (+=): the same gather, a table whose only material is the map, with the map's own copies
             const MaterialSlot e = io.mt.m[ZDR_ENV_ENTRY];    // {copies, h, w, first cell}
             MaterialTable me = io.mt;
             me.m[0] = e; me.m[0].texel = 0;
-            me.ncells = (e.h + 1) * (e.w + 1);                // copy stride
+            me.m[0].copies = e.texel; me.m[0].stride = (e.h + 1) * (e.w + 1);
             dim3 ge((e.w + 63) / 64, e.h, 1);
-            hipLaunchKernelGGL(k_material_cells_to_grad, ge, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)d_env, me, (int)e.texel);
+            hipLaunchKernelGGL(k_material_cells_to_grad, ge, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)d_env, me);
         }
     } else if (backward) {   // fold the staging cells into d_material (+=)
         dim3 g((R.tex_w + 63) / 64, R.tex_h);
