@@ -33,8 +33,10 @@ extern "C" {
 #endif
 
 #define ZDR_VERSION_STRING "zdr-mi355x 0.3 (gfx950)"
-/* Bumped whenever a struct of this header changes size or meaning, or the entry points grow (2: tile shard + prb_mode fields;
- * 3: struct_size; 4: environment-map gradient).  A binding asserts zdr_abi_version() == ZDR_ABI_VERSION of the header it was written against. */
+/* Bumped whenever a struct of this header changes size or meaning, or an existing entry point changes (2: tile shard + prb_mode fields;
+ * 3: struct_size; 4: environment-map gradient).  A binding asserts zdr_abi_version() == ZDR_ABI_VERSION of the header it was written against.
+ * Entry points that are purely added keep the version: a binding finds them by symbol (the emission gradient, zdr_scene_set_emission_values
+ * and zdr_render_backward*_emission, came to version 4 that way). */
 #define ZDR_ABI_VERSION 4
 
 enum { ZDR_OK = 0, ZDR_E_INVALID = -1, ZDR_E_HIP = -2, ZDR_E_UNSUPPORTED = -3, ZDR_E_NOMEM = -4 };
@@ -122,6 +124,15 @@ int zdr_scene_info(const zdr_scene *scene, zdr_scene_info_t *info);
 /* Replaces Scene.update_lights (render.py:130-148). HOST input ninst x 3; rebuilds the light list. */
 int zdr_scene_set_emissions(zdr_scene *scene, const float *inst_emission, void *stream);
 
+/* Rewrites the emission VALUES of the current light list in place: emission is DEVICE float32, ninst x 3, and the rows of the instances
+ * that are lights now (the list of zdr_scene_create or of the last zdr_scene_set_emissions) replace those lights' emissions everywhere the
+ * kernels read them.  Rows of other instances are ignored, and those instances are left alone: the light list, light_count and every buffer
+ * stay as they are.  Done by a kernel: stream-ordered, no synchronise, no reallocation, so the call can be captured and graphs keep their
+ * pointers.  A component may be zero or negative; a light whose components are ALL <= 0 stays in the list (it is still picked by the light
+ * sampling) but the kernels stop treating its surface as an emitter, as they do for any instance without a positive component.
+ * zdr_scene_set_emissions replaces all of it, list included. */
+int zdr_scene_set_emission_values(zdr_scene *scene, const float *emission, void *stream);
+
 /* Replaces Scene.add_envmap / load_envmap (render.py:150-156, envmap.py:116-203): a lat-long environment
  * light.  HOST inputs, copied to the device: tex (tex_h x tex_w x 4 float32, already made square as
  * envmap.py:123-128 does) and the importance-sampling tables the host builds from it (zdr_amd/envmap.py:
@@ -194,6 +205,25 @@ int zdr_render_backward_env(zdr_scene *scene, const zdr_render_params *params, c
                             float *d_material, float *d_env, void *stream);
 int zdr_render_backward_materials_env(zdr_scene *scene, const zdr_render_params *params, const float *d_image, const float *materials,
                                       const int32_t *dims, uint32_t nmat, float *d_materials, float *d_env, void *stream);
+
+/* zdr_render_backward / zdr_render_backward_materials that also differentiate with respect to the lights' emissions: d_emission (DEVICE,
+ * ninst x 3 float32) is ACCUMULATED into (+=); the rows of instances outside the current light list receive nothing.  With the light list
+ * fixed nothing a path decides reads an emission value (the light pick is uniform over light_count, the MIS weights read pdfs, Russian
+ * roulette reads the throughput), so the forward of one seed is linear in the emissions and each term that reads one — a camera, BSDF-sample
+ * or continuation ray that ends on a light, a light sample on a mesh light that is seen from its front and unoccluded — adds its weight
+ * times the pixel's cotangent.  The gradient is therefore exact for the forward of the same seed in every prb_mode AS LONG AS EVERY LIGHT
+ * KEEPS AT LEAST ONE POSITIVE COMPONENT (not checked: that would take a synchronise).  A light that is zero or negative in every component is
+ * outside that guarantee: the forward stops treating its surface as an emitter, and the BVH kernels skip the shadow ray of a light sample
+ * that carries no radiance.  The clamp of a sample's radiance to [0, 1e5] is not differentiated, as for the other gradients; a term whose
+ * gradient is NaN is dropped on its own.  d_emission == NULL behaves exactly like the sibling call, and so does ZDR_COLLOCATED, which reads
+ * no emission and leaves d_emission untouched; so does a scene without lights.  Not together with an environment-map gradient (there is no
+ * call for both).  A wave sums its terms in LDS, per light, for the first 10 lights of the list; terms of further lights go to memory one by
+ * one (correct, slower).  Runs in the material-table kernels (a single material is a table of one, instance 0 shading with it), so the
+ * material gradient equals the sibling's up to the order of float atomics. */
+int zdr_render_backward_emission(zdr_scene *scene, const zdr_render_params *params, const float *d_image, const float *material,
+                                 float *d_material, float *d_emission, void *stream);
+int zdr_render_backward_materials_emission(zdr_scene *scene, const zdr_render_params *params, const float *d_image, const float *materials,
+                                           const int32_t *dims, uint32_t nmat, float *d_materials, float *d_emission, void *stream);
 
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,

@@ -47,6 +47,14 @@ ZD float4 brdf_grad(float cz_over_pi, float dfdr, f3 ct) {     // d(f cos)[ct] w
 struct EnvTerm { f3 w; f2 uv; };
 ZD void env_term_clear(EnvTerm &e) { e.w = mk3(0.0f); e.uv.x = 0.0f; e.uv.y = 0.0f; }
 
+// Emission-gradient kernels (LG, zdr_render_backward_emission): one term of the estimator that reads a light's emission,
+// radiance += w * emission[light].  With the light list fixed nothing a path decides reads an emission VALUE (the light pick is uniform over
+// light_count, the MIS weights read pdfs, the roulette reads beta), so d(radiance)/d(emission) is w: the caller adds w * cotangent to
+// the light's row (emit_add, zdr_kernels.hip).  light = index in the light list, -1: no such term.
+struct EmitTerm { f3 w; int light; };
+ZD void emit_term_clear(EmitTerm &e) { e.w = mk3(0.0f); e.light = -1; }
+ZD int emit_light_of(const DScene &S, int inst) { return __float_as_int(S.emission4[inst].w); }   // emission4[inst].w: bits of the instance's light index, -1 = not in the list (zdr_api.cpp)
+
 // ---------------------------------------------------------------------------- collocated
 // collocated.py:11-31 / 35-57: L = brdf(wo, wo) / t^2
 // BWD: the vertex gradient is returned through (guv, grad) — grad stays 0 when there is nothing to add —
@@ -115,11 +123,14 @@ ZD float4 uvgrad_sample(const DScene &S, int *lds, f3 o, f3 d, f3 odx, f3 ddx, f
 // MT: an instance with a material is shaded by it, one without returns its emission (zdr.h, zdr_scene_set_material_slots)
 // EG (implies ENV): the terms that read the environment map go to e_cam (camera miss, weight 1, or the light sample) and e_bsdf (BSDF sample
 // that escapes), the two cannot both be a camera miss.
-template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false, bool EG = false>
+// LG (implies BWD and MT): the terms that read an emission go to l_cam (the camera ray that sees a light, weight 1, or the light sample on a
+// mesh light) and l_bsdf (the BSDF sample that lands on a light).
+template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false, bool EG = false, bool LG = false>
 ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int *lds,
                     Sampler &smp, f3 o, f3 d, unsigned long long cam_mask, f3 le_grad, Counters &cnt, f2 &guv, float4 &grad, int &gmat,
-                    EnvTerm *e_cam = nullptr, EnvTerm *e_bsdf = nullptr) {
+                    EnvTerm *e_cam = nullptr, EnvTerm *e_bsdf = nullptr, EmitTerm *l_cam = nullptr, EmitTerm *l_bsdf = nullptr) {
     static_assert(!EG || (ENV && BWD), "the environment gradient is a backward mode of the environment kernels");
+    static_assert(!LG || (BWD && MT && !EG), "the emission gradient is a backward mode of the material-table kernels");
     COUNT(C_CLOSEST);
     Hit h = A::closest_camera(S, lds, o, d, cam_mask);
     if constexpr (EG) {
@@ -132,6 +143,9 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
     float4 m;
     if constexpr (MT) {
         const int slot = io.mt.inst_slot[it.inst];
+        if constexpr (LG) {
+            if (slot < 0) { l_cam->w = mk3(1.0f); l_cam->light = emit_light_of(S, it.inst); }
+        }
         if (slot < 0) return xyz(S.emission4[it.inst]);
         m = read_bsdf_in(io.material, io.mt.m[slot], it.uv);
         gmat = slot;
@@ -148,8 +162,9 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
     // spills at 128 VGPRs than the passes save: 1.12 -> 1.18 ms in round 3, 0.873 / 1.05 -> 0.883 / 1.10 ms in round 4.)
     float u_pick = sampler_next<SK>(C, smp);
     f2 env_uv; env_uv.x = -1.0f; env_uv.y = 0.0f;
-    LightSample light = sample_light<ENV>(S, it.p, u_pick, [&]() { return sampler_next<SK>(C, smp); }, [&]() { return sampler_next2<SK>(C, smp); },
-                                          EG ? &env_uv : nullptr);
+    int mesh_light = -1;
+    LightSample light = sample_light<ENV, LG>(S, it.p, u_pick, [&]() { return sampler_next<SK>(C, smp); }, [&]() { return sampler_next2<SK>(C, smp); },
+                                              EG ? &env_uv : nullptr, LG ? &mesh_light : nullptr);
     COUNT(C_SHADOW);
     bool occluded = A::any_shadow(S, lds, it.p, light.wi, 1e-4f, light.dist);
     Onb onb = make_onb(it.ns);
@@ -170,6 +185,9 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
         if constexpr (EG) {
             if (env_uv.x >= 0.0f) { e_cam->w = (bsdf * mis) * inv_dn; e_cam->uv = env_uv; }
         }
+        if constexpr (LG) {
+            if (mesh_light >= 0) { l_cam->w = (bsdf * mis) * inv_dn; l_cam->light = mesh_light; }
+        }
     }
     // use_MIS = True (direct.py:14): one BSDF sample, emitter lookup only
     float u_lobe = sampler_next<SK>(C, smp);
@@ -181,11 +199,13 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
         COUNT(C_CLOSEST);
         Hit h2 = A::closest(S, lds, o2, wi, 0.0f, 1e30f);
         f3 em = mk3(0.0f); float pdf_light = 0.0f; bool lit = false;
+        int hit_inst = 0;
         if (h2.slot >= 0) {
             COUNT(C_HITS);
             Interaction it2 = surface_interact(S, h2);
             if (!(dot(-wi, it2.ng) < 1e-4f || dot(-wi, it2.ns) < 1e-4f)) {
                 em = xyz(S.emission4[it2.inst]);
+                if (LG) hit_inst = it2.inst;
                 pdf_light = sample_light_pdf<ENV>(S, it.p, it2.inst, h2.slot, it2.p);   // origin = it.p (direct.py:66)
                 lit = true;
             }
@@ -202,6 +222,9 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
             f3 beta = ggx_brdf_from(g, wi_local, diffuse) * inv_p;
             COUNT(C_EMIT_BSDF);
             radiance = radiance + (beta * mis) * em;
+            if constexpr (LG) {
+                if (h2.slot >= 0) { l_bsdf->w = beta * mis; l_bsdf->light = emit_light_of(S, hit_inst); }
+            }
             if (BWD) {
                 float dl_; float4 gr = brdf_grad(wi_local.z * ZDR_INV_PI, ggx_dfdr_from(g, wo, wi_local, roughness, dl_), (em * (mis * inv_p)) * le_grad);
                 mat_grad.x += gr.x; mat_grad.y += gr.y; mat_grad.z += gr.z; mat_grad.w += gr.w;
@@ -252,9 +275,10 @@ struct PathState {
 // term_Li (and the MIS-weight fraction of the terminal emitter) when the path ended on a light.
 // MT: the instance's material slot decides (inst_slot: MaterialTable::inst_slot) and `it.mat` receives it.
 // env_hit (environment-gradient kernels): receives the miss term (beta * mis at the map coordinates of the ray), left alone otherwise.
+// emit_hit (emission-gradient kernels): receives the term of a ray that ends on an emitting instance (beta * mis), left alone otherwise.
 template <bool BWD, bool STATS, bool ENV, bool MT = false>
 ZD bool path_arrive(const DScene &S, PathState &ps, const Hit &h, Interaction &it, f3 &term_Li, Counters &cnt, float *term_plfrac = nullptr,
-                    const int32_t *inst_slot = nullptr, EnvTerm *env_hit = nullptr) {
+                    const int32_t *inst_slot = nullptr, EnvTerm *env_hit = nullptr, EmitTerm *emit_hit = nullptr) {
     if (h.slot < 0) {                                                             // prb.py:26-32, in the form of direct.py:70-83
         if (ENV && S.env_count > 0) {
             const f2 euv = direction_to_uv(ps.d);
@@ -275,6 +299,7 @@ ZD bool path_arrive(const DScene &S, PathState &ps, const Hit &h, Interaction &i
     if (em.x > 0.0f || em.y > 0.0f || em.z > 0.0f) {                              // prb.py:39-44
         float pdf_light = sample_light_pdf<ENV>(S, ps.o, it.inst, h.slot, it.p);
         float mis = balanced_heuristic(ps.pdf_bsdf, pdf_light);
+        if (emit_hit) { emit_hit->w = ps.beta * mis; emit_hit->light = emit_light_of(S, it.inst); }
         ps.L = ps.L + (ps.beta * mis) * em;
         if (BWD) { term_Li = em * mis;
                    if (term_plfrac) *term_plfrac = (ps.pdf_bsdf + pdf_light > 1e-4f) ? pdf_light * rcp(ps.pdf_bsdf + pdf_light) : 0.0f; }
@@ -305,9 +330,9 @@ struct ShadeCtx { f3 diffuse; float roughness; Onb onb; f3 wo, wil; LightSample 
 struct NeeTerms { f3 dL, bW, fLW, neeM; float cL, dfLdr; };
 
 // material, frame and the light sample of the vertex (prb.py:47-58); BWD: resets pv
-template <int SK, bool BWD, bool STATS, bool ENV, bool MT = false>
+template <int SK, bool BWD, bool STATS, bool ENV, bool MT = false, bool LG = false>
 ZD ShadeCtx shade_ctx(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, PathState &ps, const Interaction &it, PathVertex &pv, Counters &cnt,
-                      f2 *env_uv = nullptr) {
+                      f2 *env_uv = nullptr, int *mesh_light = nullptr) {
     ShadeCtx x;
     float4 m;
     if constexpr (MT) m = read_bsdf_in(io.material, io.mt.m[it.mat], it.uv);
@@ -326,10 +351,10 @@ ZD ShadeCtx shade_ctx(const DScene &S, const RenderCfg &R, const SamplerCfg &C, 
     if (x.pre) {                                                 // all seven numbers of the vertex at once, two permutations per register (sampler.h)
         const VertexSamples v = cmj_vertex_samples(C, ps.smp);
         x.u_lobe = v.u_lobe; x.u_dir = v.u_dir; x.i_rr = v.i_rr;
-        x.light = sample_light<ENV>(S, it.p, v.u_pick, [&]() { return v.u_prim; }, [&]() { return v.u_pt; }, env_uv);
+        x.light = sample_light<ENV, LG>(S, it.p, v.u_pick, [&]() { return v.u_prim; }, [&]() { return v.u_pt; }, env_uv, mesh_light);
     } else {
         float u_pick = sampler_next<SK>(C, ps.smp);
-        x.light = sample_light<ENV>(S, it.p, u_pick, [&]() { return sampler_next<SK>(C, ps.smp); }, [&]() { return sampler_next2<SK>(C, ps.smp); }, env_uv);
+        x.light = sample_light<ENV, LG>(S, it.p, u_pick, [&]() { return sampler_next<SK>(C, ps.smp); }, [&]() { return sampler_next2<SK>(C, ps.smp); }, env_uv, mesh_light);
     }
     x.wil = to_local(x.onb, x.light.wi);
     return x;
@@ -420,17 +445,26 @@ struct VertexRays { bool shadow, stop; f3 sd; float stmax; };
 // env (environment-gradient kernels): receives the light sample's weight and map coordinates when it sampled the environment (w = 0
 // otherwise); then a sample that carries no radiance now — a texel that is zero but that the tables still sample — still has a
 // gradient, and its shadow ray is traced.
-template <int SK, bool BWD, bool STATS, bool ENV, bool MT = false, bool EG = false>
+// emit (emission-gradient kernels): receives the light sample's weight and light when it sampled a mesh light from its front (light = -1
+// otherwise).  The shadow ray of a sample that carries no radiance is still skipped: with every light positive in some component that
+// happens only where the weight vanishes too (include/zdr.h).
+template <int SK, bool BWD, bool STATS, bool ENV, bool MT = false, bool EG = false, bool LG = false>
 ZD VertexRays path_vertex_begin(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io,
-                                PathState &ps, const Interaction &it, PathVertex &pv, NeeTerms &n, Counters &cnt, EnvTerm *env = nullptr) {
+                                PathState &ps, const Interaction &it, PathVertex &pv, NeeTerms &n, Counters &cnt, EnvTerm *env = nullptr, EmitTerm *emit = nullptr) {
     f2 env_uv; env_uv.x = -1.0f; env_uv.y = 0.0f;
-    const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, cnt, EG ? &env_uv : nullptr);
+    int mesh_light = -1;
+    const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT, LG>(S, R, C, io, ps, it, pv, cnt, EG ? &env_uv : nullptr, LG ? &mesh_light : nullptr);
     VertexRays vr; vr.sd = x.light.wi; vr.stmax = x.light.dist;
     n.dL = n.bW = n.fLW = n.neeM = mk3(0.0f); n.cL = 0.0f; n.dfLdr = 0.0f;
     if constexpr (EG) env_term_clear(*env);
+    if constexpr (LG) emit_term_clear(*emit);
     COUNT(C_SHADOW);
     vr.shadow = x.wil.z >= 1e-4f;
     if (vr.shadow) {
+        if constexpr (LG) {
+            n = nee_terms<BWD, true>(x, ps.beta, &emit->w);
+            emit->light = mesh_light;
+        } else
         if constexpr (EG) {
             n = nee_terms<BWD, true>(x, ps.beta, &env->w);
             if (env_uv.x < 0.0f) env->w = mk3(0.0f);
@@ -449,17 +483,30 @@ ZD VertexRays path_vertex_begin(const DScene &S, const RenderCfg &R, const Sampl
 }
 
 // EG (implies BWD and ENV): env receives the NEE term of the vertex when its light sample went to the environment unoccluded (else w = 0)
-template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false, bool EG = false>
+// LG (implies BWD): emit receives the NEE term of the vertex when its light sample went to a mesh light unoccluded (else light = -1)
+template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false, bool EG = false, bool LG = false>
 ZD bool path_shade(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int *lds,
-                   PathState &ps, const Interaction &it, PathVertex &pv, Hit &h, Counters &cnt, EnvTerm *env = nullptr) {
+                   PathState &ps, const Interaction &it, PathVertex &pv, Hit &h, Counters &cnt, EnvTerm *env = nullptr, EmitTerm *emit = nullptr) {
+    static_assert(!LG || (BWD && !EG), "the emission gradient is a backward mode of its own");
     if constexpr (A::kFuseRays) {
         NeeTerms n;
-        const VertexRays vr = path_vertex_begin<SK, BWD, STATS, ENV, MT, EG>(S, R, C, io, ps, it, pv, n, cnt, env);
+        const VertexRays vr = path_vertex_begin<SK, BWD, STATS, ENV, MT, EG, LG>(S, R, C, io, ps, it, pv, n, cnt, env, emit);
         bool occluded;
         A::shadow_and_closest(S, lds, vr.shadow, it.p, vr.sd, 1e-4f, vr.stmax, !vr.stop, ps.o, ps.d, occluded, h);
         if (vr.shadow && !occluded) nee_apply<BWD>(ps, pv, n);
         else if constexpr (EG) env->w = mk3(0.0f);
+        else if constexpr (LG) emit->light = -1;
         return vr.stop;
+    } else if constexpr (LG) {
+        int mesh_light = -1;
+        const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT, true>(S, R, C, io, ps, it, pv, cnt, nullptr, &mesh_light);
+        const bool occluded = A::any_shadow(S, lds, it.p, x.light.wi, 1e-4f, x.light.dist);
+        emit_term_clear(*emit);
+        if (!occluded && x.wil.z >= 1e-4f) {
+            nee_apply<BWD>(ps, pv, nee_terms<BWD, true>(x, ps.beta, &emit->w));
+            emit->light = mesh_light;
+        }
+        return sample_bsdf<SK, BWD>(R, C, x, ps, it, pv);
     } else if constexpr (EG) {
         f2 env_uv; env_uv.x = -1.0f; env_uv.y = 0.0f;
         const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, cnt, &env_uv);
@@ -514,12 +561,15 @@ ZD uint32_t lane_rank(unsigned long long mask) {               // number of set 
 // this lane's own pixel.
 // on_miss (environment-gradient kernels): called by the whole wave once per camera sample with the term of a camera ray that
 // missed (EnvTerm, w = 0 for the other lanes).  NoEnvMiss: no such call.
+// on_emit (emission-gradient kernels): called by each lane whose camera ray ended on a light, with that term.  NoEmitHit: no such call.
 struct NoEnvMiss { ZD void operator()(const EnvTerm &) const {} };
-template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false, class MISS = NoEnvMiss>
+struct NoEmitHit { ZD void operator()(const EmitTerm &) const {} };
+template <int SK, class A, bool BWD, bool STATS, bool ENV, bool MT = false, class MISS = NoEnvMiss, class EMIT = NoEmitHit>
 ZD void primary_refill(const DScene &S, const RenderCfg &R, const SamplerCfg &C, int *lds, int x, int y, bool valid, unsigned long long cam_mask,
                        uint32_t perm_seed, int bank, uint32_t &next_sample, uint32_t s_end, PrimaryQueue &q, f3 &sum, Counters &cnt,
-                       const int32_t *inst_slot = nullptr, MISS on_miss = MISS()) {
+                       const int32_t *inst_slot = nullptr, MISS on_miss = MISS(), EMIT on_emit = EMIT()) {
     constexpr bool EG = !std::is_same<MISS, NoEnvMiss>::value;
+    constexpr bool LG = !std::is_same<EMIT, NoEmitHit>::value;
     for (int b = 0; b < ZDR_RING_BATCH && next_sample < s_end; b++, next_sample++) {   // wave-uniform
         bool park = false;
         float4 e0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), e1 = e0;
@@ -532,7 +582,10 @@ ZD void primary_refill(const DScene &S, const RenderCfg &R, const SamplerCfg &C,
             COUNT(C_SAMPLES); COUNT(C_CLOSEST);
             Hit h = A::closest_camera(S, lds, ps.o, ps.d, cam_mask);
             Interaction it; f3 tl;
-            if (path_arrive<false, STATS, ENV, MT>(S, ps, h, it, tl, cnt, nullptr, inst_slot, EG ? &miss : nullptr)) {
+            EmitTerm seen; emit_term_clear(seen);
+            const bool ended = path_arrive<false, STATS, ENV, MT>(S, ps, h, it, tl, cnt, nullptr, inst_slot, EG ? &miss : nullptr, LG ? &seen : nullptr);
+            if constexpr (LG) on_emit(seen);
+            if (ended) {
                 if (!BWD) {                                                     // a path without vertices has no gradient
                     if (!any_nan(ps.L)) sum = sum + clamp_radiance(ps.L);       // integrator.py:27-28
                     else COUNT(C_NAN);

@@ -54,7 +54,10 @@ struct RenderCfg {
 struct KernelIO {
     const float4 *material;           // (tex_h, tex_w) float4
     float4 *image;                    // (H, W) float4
-    float4 *partial;                  // scratch when nchunks > 1: [chunk][tile of the shard][lane] float4 (one 1 KiB line per wave)
+    union {                           // (one pointer: the struct keeps its size and layout, and with them the kernarg offsets of every kernel)
+        float4 *partial;              // forward: scratch when nchunks > 1: [chunk][tile of the shard][lane] float4 (one 1 KiB line per wave)
+        float *emit_acc;              // emission-gradient backward (zdr_render_backward_emission): ZDR_EMISSION_COPIES rows of light_count x 3 floats, zeroed per call; a wave adds into row blockIdx % ZDR_EMISSION_COPIES
+    };
     const float4 *d_image;            // backward: cotangent
     float *d_material;                // backward: += gathered from the staging cells by k_cells_to_grad
     float *cells;                     // backward: (tex_h + 1) x (tex_w + 1) staging cells of 16 floats, zeroed per call
@@ -69,7 +72,11 @@ struct KernelIO {
 // d_env != nullptr: environment-gradient backward (zdr_render_backward_env): io.mt is a material table whose entry ZDR_ENV_ENTRY holds the
 // map's cells, and they are gathered into d_env (+=)
 int zdr_launch_render(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io,
-                      int integrator, int accel_is_bvh, int backward, int stats, hipStream_t stream, float *d_env = nullptr);
+                      int integrator, int accel_is_bvh, int backward, int stats, hipStream_t stream, float *d_env = nullptr, float *d_emission = nullptr);
+// d_emission != nullptr (never together with d_env; the scene has at least one light): emission-gradient backward (zdr_render_backward_emission):
+// io.mt is a material table, io.emit_acc the zeroed accumulator, and its rows are gathered into d_emission (ninst x 3, +=)
+#define ZDR_EMISSION_COPIES 256       // rows of the emission accumulator
+int zdr_launch_set_emission_values(const DScene &S, const float *src, float *emission, float4 *emission4, float4 *light_tris, hipStream_t stream);
 int zdr_launch_zero(void *p, size_t bytes, hipStream_t stream);   // kernel zero-fill (graph-safe, see zdr_kernels.hip)
 int zdr_launch_copy(void *dst, const void *src, size_t bytes, hipStream_t stream);   // kernel copy of 16-byte words (graph-safe, as the zero-fill)
 int zdr_launch_trace(const DScene &S, int accel_is_bvh, int any, const float *rays, uint32_t n,

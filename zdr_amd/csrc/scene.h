@@ -49,7 +49,7 @@ struct DScene {
     const int32_t *slot_of_tri;     // input triangle index -> slot
     // flat light table: light l covers entries [light_range[2l], + light_range[2l+1]); entry = five float4
     //   {p0} {p1} {p2} {ng, area} {emission, 0}   (the floats of the shade records and of `emission`)
-    const float4 *light_tris; const int32_t *light_range; const float4 *emission4;   // emission4: ninst x {e.rgb, 0}
+    const float4 *light_tris; const int32_t *light_range; const float4 *emission4;   // emission4: ninst x {e.rgb, bits(index in the light list, -1 = not a light)}; .w is read as an int, by the emission-gradient kernels only
     int32_t light0_T;               // triangle count of light 0 (the whole table when light_count == 1)
     int32_t ntris, ninst, light_count, nnodes;
     int32_t nquads, nquads2;        // brute-force accel: primitives of the pair walk (quads first, then single triangles) and the number of quads
@@ -425,8 +425,9 @@ ZD float env_sampled_light_pdf(const DScene &S, f3 dir, int n) {  // envmap.py:2
 // sample_light (light.py:23-81): u_pick = next() was drawn by the caller; the environment branch then
 // draws only next2f(), the mesh branch next() and next2f() (light.py:29-31 vs 50-63).
 // env_uv (environment-gradient kernels): receives the map coordinates of an environment sample; left alone otherwise.
-template <bool ENV, class NEXT1, class NEXT2>
-ZD LightSample sample_light(const DScene &S, f3 origin, float u_pick, NEXT1 next1, NEXT2 next2, f2 *env_uv = nullptr) {
+// LG (emission-gradient kernels): mesh_light receives the index of a mesh light sampled from its front (eval = its emission); left alone otherwise.
+template <bool ENV, bool LG = false, class NEXT1, class NEXT2>
+ZD LightSample sample_light(const DScene &S, f3 origin, float u_pick, NEXT1 next1, NEXT2 next2, f2 *env_uv = nullptr, int *mesh_light = nullptr) {
     LightSample L;
     int n = (ENV ? S.env_count : 0) + S.light_count;
     if (n <= 0) {  // the reference would index out of bounds; consume the mesh branch's dimensions, contribute nothing
@@ -463,6 +464,7 @@ ZD LightSample sample_light(const DScene &S, f3 origin, float u_pick, NEXT1 next
     L.pdf = light_pdf(origin, p, xyz(r6), r6.w, n * T, L.wi, cos_light, sqr_dist);
     L.dist = 0.9999f * fsqrt(sqr_dist);
     L.eval = (cos_light > 1e-4f) ? xyz(r4) : mk3(0.0f);
+    if constexpr (LG) { if (cos_light > 1e-4f) *mesh_light = idx; }
     return L;
 }
 

@@ -473,7 +473,7 @@ struct zdr_scene {
     std::vector<float4> tri_geo;            // host copy, 4 float4 per INPUT triangle: p0, p1, p2, {ng, area} (lights may change)
     float4 *d_light_tris = nullptr; size_t light_tris_cap = 0;
     int32_t *d_light_range = nullptr;       // 2 ints per instance slot
-    float4 *d_emission4 = nullptr;          // ninst x {e.rgb, 0}
+    float4 *d_emission4 = nullptr;          // ninst x {e.rgb, bits(light index | -1)}
     int32_t *d_light_insts = nullptr, *d_inst_tri_begin = nullptr, *d_slot_of_tri = nullptr;
     uint32_t *d_pmj = nullptr; uint16_t *d_bn = nullptr; SamplerTables tab{};
     float4 *d_env_tex = nullptr; float *d_alias_prob = nullptr, *d_env_pdf = nullptr; int32_t *d_alias_idx = nullptr;
@@ -487,6 +487,7 @@ struct zdr_scene {
     std::vector<int32_t> inst_slot;                         // material slot of each instance (zdr_scene_set_material_slots), -1 = none; empty = never set
     int32_t *d_inst_slot = nullptr;                         // its device copy, allocated by the first call that needs it
     int32_t *d_inst_slot0 = nullptr;                        // {0, -1, -1, ...}: the slot table of a single-material environment-gradient call (render_common)
+    float *d_emit_acc = nullptr; size_t emit_acc_bytes = 0; // emission-gradient accumulator: ZDR_EMISSION_COPIES rows of light_count x 3 floats (render_common)
     unsigned int *d_error = nullptr;                        // device error word (scene.h, ZDR_DEVERR_*), sticky until read
     uint64_t device_bytes = 0;
     // A render call recorded while its stream was CAPTURING (hipStreamBeginCapture; torch.cuda.graph) bakes this handle's workspace
@@ -567,7 +568,13 @@ static int upload_light_table(zdr_scene *s, const std::vector<int32_t> &lights, 
     if (!s->d_light_range) HIPCHK(hipMalloc((void **)&s->d_light_range, range.size() * sizeof(int32_t)));
     if (!s->d_emission4) HIPCHK(hipMalloc((void **)&s->d_emission4, (size_t)s->ninst * sizeof(float4)));
     std::vector<float4> e4(s->ninst);
-    for (uint32_t i = 0; i < s->ninst; i++) e4[i] = make_float4(s->emission[3 * (size_t)i], s->emission[3 * (size_t)i + 1], s->emission[3 * (size_t)i + 2], 0.0f);
+    // .w: bits of the instance's index in the light list, -1 = not a light (read by the emission-gradient kernels only, as an int)
+    std::vector<int32_t> light_of(s->ninst, -1);
+    for (int l = 0; l < count; l++) light_of[lights[l]] = l;
+    for (uint32_t i = 0; i < s->ninst; i++) {
+        e4[i] = make_float4(s->emission[3 * (size_t)i], s->emission[3 * (size_t)i + 1], s->emission[3 * (size_t)i + 2], 0.0f);
+        memcpy(&e4[i].w, &light_of[i], sizeof(int32_t));
+    }
     HIPCHK(hipMemcpyAsync(s->d_light_tris, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(s->d_light_range, range.data(), range.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(s->d_emission4, e4.data(), e4.size() * sizeof(float4), hipMemcpyHostToDevice, st));
@@ -784,7 +791,7 @@ extern "C" int zdr_scene_destroy(zdr_scene *s) {
     if (!s) return ZDR_OK;
     (void)hipSetDevice(s->device);
     if (!s->isect_in_nodes) (void)hipFree(s->d_isect); (void)hipFree(s->d_pairs); (void)hipFree(s->d_ppairs); (void)hipFree(s->d_shade); (void)hipFree(s->d_nodes); (void)hipFree(s->d_emission); (void)hipFree(s->d_light_insts); (void)hipFree(s->d_light_tris); (void)hipFree(s->d_light_range); (void)hipFree(s->d_emission4);
-    (void)hipFree(s->d_inst_tri_begin); (void)hipFree(s->d_slot_of_tri); (void)hipFree(s->d_pmj); (void)hipFree(s->d_bn); (void)hipFree(s->d_env_tex); (void)hipFree(s->d_alias_prob); (void)hipFree(s->d_alias_idx); (void)hipFree(s->d_env_pdf); (void)hipFree(s->d_partial); (void)hipFree(s->d_ring); (void)hipFree(s->d_work_counters); (void)hipFree(s->d_tile_masks); (void)hipFree(s->d_cells); (void)hipFree(s->d_counters); (void)hipFree(s->d_error); (void)hipFree(s->d_inst_slot); (void)hipFree(s->d_inst_slot0);
+    (void)hipFree(s->d_inst_tri_begin); (void)hipFree(s->d_slot_of_tri); (void)hipFree(s->d_pmj); (void)hipFree(s->d_bn); (void)hipFree(s->d_env_tex); (void)hipFree(s->d_alias_prob); (void)hipFree(s->d_alias_idx); (void)hipFree(s->d_env_pdf); (void)hipFree(s->d_partial); (void)hipFree(s->d_ring); (void)hipFree(s->d_work_counters); (void)hipFree(s->d_tile_masks); (void)hipFree(s->d_cells); (void)hipFree(s->d_counters); (void)hipFree(s->d_error); (void)hipFree(s->d_inst_slot); (void)hipFree(s->d_inst_slot0); (void)hipFree(s->d_emit_acc);
     for (void *p : s->retired) (void)hipFree(p);
     delete s;
     return ZDR_OK;
@@ -811,6 +818,16 @@ extern "C" int zdr_scene_set_emissions(zdr_scene *s, const float *inst_emission,
     HIPCHK(hipStreamSynchronize(st));
     s->ds.light_count = count;
     return upload_light_table(s, lights, count, st);
+}
+
+extern "C" int zdr_scene_set_emission_values(zdr_scene *s, const float *emission, void *stream) {
+    if (!s || !emission) return fail(ZDR_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(s->device));
+    // in place, stream-ordered, by a kernel: the light list, the table's layout and every pointer stay as they are (the host copy of the
+    // emissions, which only zdr_scene_set_emissions reads back, is not touched: that call replaces all of it)
+    if (zdr_launch_set_emission_values(s->ds, emission, s->d_emission, s->d_emission4, s->d_light_tris, (hipStream_t)stream))
+        return fail(ZDR_E_HIP, "emission kernel launch failed");
+    return ZDR_OK;
 }
 
 extern "C" int zdr_scene_set_material_slots(zdr_scene *s, const int32_t *inst_slot, void *stream) {
@@ -1117,12 +1134,17 @@ static void material_cell_layout(MaterialTable &mt, RenderCfg &R) {
 // the environment map, through the material-table kernels with the map as entry ZDR_ENV_ENTRY (a single material becomes a table of one).
 static int render_common(zdr_scene *s, const zdr_render_params *p, const float *material, float *image, const float *d_image,
                          float *d_material, int backward, int stats, void *stream, const int32_t *mt_dims = nullptr, uint32_t nmat = 0,
-                         float *d_env = nullptr) {
+                         float *d_env = nullptr, float *d_emission = nullptr) {
     if (!s || !p || !material) return fail(ZDR_E_INVALID, "null argument");
+    if (d_env && d_emission) return fail(ZDR_E_UNSUPPORTED, "the environment gradient and the emission gradient cannot be taken in one call");
     int rc = check_params_abi(p); if (rc) return rc;
     HIPCHK(hipSetDevice(s->device));
     const bool use_mt = nmat > 0 || mt_dims;
     const bool env_grad = backward && d_env;
+    // d_emission (backward, path / direct): also the gradient of the lights' emissions, through the material-table kernels' emission forms (a
+    // single material becomes a table of one).  A scene without lights has no such term: the plain call.
+    const bool emit_grad = backward && d_emission && s->ds.light_count > 0;
+    if (emit_grad && p->integrator != ZDR_PATH && p->integrator != ZDR_DIRECT) return fail(ZDR_E_UNSUPPORTED, "an emission gradient needs the path or the direct integrator");
     if (env_grad) {
         if (p->integrator != ZDR_PATH && p->integrator != ZDR_DIRECT) return fail(ZDR_E_UNSUPPORTED, "an environment gradient needs the path or the direct integrator");
         if (s->ds.env_count == 0) return fail(ZDR_E_INVALID, "d_env given, but the scene has no environment map");
@@ -1140,13 +1162,13 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
     MaterialTable mt; memset(&mt, 0, sizeof mt);
     if (use_mt) {
         rc = make_material_table(s, mt_dims, nmat, capturing, (hipStream_t)stream, mt); if (rc) return rc;
-    } else if (env_grad) {                              // the one material as a table of one
+    } else if (env_grad || emit_grad) {                 // the one material as a table of one
         mt.m[0].texel = 0; mt.m[0].h = R.tex_h; mt.m[0].w = R.tex_w; mt.m[0].cell = 0;
         mt.nmat = 1; mt.ncells = (R.tex_h + 1) * (R.tex_w + 1);
         rc = single_material_slots(s, capturing, mt.inst_slot); if (rc) return rc;
     }
     size_t env_cells_total = 0;                         // environment gradient: the map's cells, all their copies
-    if (use_mt || env_grad) {
+    if (use_mt || env_grad || emit_grad) {
         R.tex_h = R.tex_w = 0;                          // (unused in material-table mode)
         material_cell_layout(mt, R);                    // the materials' copies: as in the call without the map
     }
@@ -1164,7 +1186,7 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
         env_cells_total = copies * one;
     }
     if (capturing) s->captured = true;                  // sticky: a graph may name this handle's buffers from now on (zdr_scene)
-    if (backward) { rc = ensure_cells(s, R, (use_mt || env_grad) ? (size_t)mt.ncells : (size_t)(R.tex_h + 1) * (R.tex_w + 1), (hipStream_t)stream, capturing,
+    if (backward) { rc = ensure_cells(s, R, (use_mt || env_grad || emit_grad) ? (size_t)mt.ncells : (size_t)(R.tex_h + 1) * (R.tex_w + 1), (hipStream_t)stream, capturing,
                                       env_cells_total); if (rc) return rc; }
     else if (!stats) { rc = ensure_partial(s, R, capturing); if (rc) return rc; }
     if (p->integrator == ZDR_PATH) {
@@ -1172,6 +1194,16 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
         rc = ensure_ring(s, (hipStream_t)stream, capturing); if (rc) return rc;
     }
     KernelIO io; memset(&io, 0, sizeof io);
+    if (emit_grad) {                                    // the accumulator: sized once for every light list the scene can have, zeroed per call
+        const size_t need = (size_t)ZDR_EMISSION_COPIES * 3 * (size_t)s->ninst * sizeof(float);
+        if (need > s->emit_acc_bytes) {
+            if (int rc2 = may_allocate(capturing, "emission-accumulator")) return rc2;
+            release_buffer(s, s->d_emit_acc); s->d_emit_acc = nullptr; s->emit_acc_bytes = 0;
+            HIPCHK(hipMalloc((void **)&s->d_emit_acc, need));
+            s->emit_acc_bytes = need;
+        }
+        if (zdr_launch_zero(s->d_emit_acc, (size_t)ZDR_EMISSION_COPIES * 3 * (size_t)s->ds.light_count * sizeof(float), (hipStream_t)stream)) return fail(ZDR_E_HIP, "zero-fill launch failed");
+    }
     io.ring = s->d_ring; io.work_counters = s->d_work_counters;
     // brute-force scenes of at most 64 triangle pairs: camera rays test only the pairs their tile can see
     const bool masks = !s->accel_is_bvh && s->ds.ntris <= 128 && p->integrator != ZDR_UVGRAD && !getenv("ZDR_NO_TILE_MASKS");
@@ -1198,6 +1230,7 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
         if ((long)R.ntiles * R.nchunks > 0) { memcpy(s->tile_mask_key, key, sizeof key); s->tile_mask_key_set = true; }
     }
     io.material = (const float4 *)material; io.image = (float4 *)image; io.partial = s->d_partial;
+    if (emit_grad) io.emit_acc = s->d_emit_acc;         // (shares the forward's `partial` pointer: KernelIO keeps its size)
     io.d_image = (const float4 *)d_image; io.d_material = d_material; io.cells = s->d_cells; io.counters = s->d_counters;
     io.mt = mt;
     // every pointer a kernel variant dereferences must be live before anything is launched
@@ -1210,7 +1243,7 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
     DScene S = s->ds;
     // shadow segments end on a light's surface; an environment light sends them to infinity, where nothing can be ruled out
     S.shadow_pairs = (S.env_count > 0) ? ~0ull : s->shadow_pairs;
-    if (zdr_launch_render(S, R, C, io, p->integrator, s->accel_is_bvh, backward, stats, (hipStream_t)stream, env_grad ? d_env : nullptr))
+    if (zdr_launch_render(S, R, C, io, p->integrator, s->accel_is_bvh, backward, stats, (hipStream_t)stream, env_grad ? d_env : nullptr, emit_grad ? d_emission : nullptr))
         return fail(ZDR_E_HIP, std::string("kernel launch: ") + hipGetErrorString(hipGetLastError()));
     static const bool check_every_call = getenv("ZDR_CHECK") && atoi(getenv("ZDR_CHECK")) != 0;   // opt-in: costs a synchronise per call
     if (check_every_call && !stats && !capturing) return check_device_error(s, (hipStream_t)stream);   // (a synchronise cannot be captured: zdr_scene_check after the replay instead)
@@ -1269,6 +1302,21 @@ extern "C" int zdr_render_backward_materials_env(zdr_scene *s, const zdr_render_
     if (!d_image || !d_materials || !dims) return fail(ZDR_E_INVALID, "null argument");
     if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
     return render_common(s, p, materials, nullptr, d_image, d_materials, 1, 0, stream, dims, nmat, d_env);
+}
+
+extern "C" int zdr_render_backward_emission(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *material,
+                                            float *d_material, float *d_emission, void *stream) {
+    if (!d_emission || (p && p->integrator == ZDR_COLLOCATED)) return zdr_render_backward(s, p, d_image, material, d_material, stream);   // (collocated reads no emission)
+    if (!d_image || !d_material) return fail(ZDR_E_INVALID, "null gradient buffer");
+    return render_common(s, p, material, nullptr, d_image, d_material, 1, 0, stream, nullptr, 0, nullptr, d_emission);
+}
+
+extern "C" int zdr_render_backward_materials_emission(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *materials,
+                                                      const int32_t *dims, uint32_t nmat, float *d_materials, float *d_emission, void *stream) {
+    if (!d_emission || (p && p->integrator == ZDR_COLLOCATED)) return zdr_render_backward_materials(s, p, d_image, materials, dims, nmat, d_materials, stream);
+    if (!d_image || !d_materials || !dims) return fail(ZDR_E_INVALID, "null argument");
+    if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
+    return render_common(s, p, materials, nullptr, d_image, d_materials, 1, 0, stream, dims, nmat, nullptr, d_emission);
 }
 
 extern "C" int zdr_render_stats(zdr_scene *s, const zdr_render_params *p, const float *material, uint64_t counters[8], void *stream) {

@@ -14,6 +14,9 @@
     image = scene.render(material, res=(W, H), spp=256, envmap=env)   # env.grad after backward(); tables stay fixed
     scene.update_envmap_sampling(env.detach())                        # now and then: tables rebuilt from the current map
 
+    E = torch.tensor([[0, 0, 0], [20, 20, 20]], dtype=torch.float32, device="cuda", requires_grad=True)   # one row per model
+    image = scene.render(material, res=(W, H), spp=256, emissions=E)  # E.grad after backward(); the set of lights stays fixed
+
 Images and materials are PyTorch tensors on the GPU; the renderer borrows their device pointers
 for the duration of a call and enqueues its kernels on torch's current HIP stream.
 """
@@ -79,6 +82,26 @@ def resolve_material_slots(slots, emissions, nmat: int) -> tuple:
         if k is not None and k >= nmat:
             raise ValueError(f"material_slots[{i}] = {k}, but only {nmat} materials were given")
     return tuple(slots)
+
+
+def check_emissions(emissions, ninst: int, device, envmap=None):
+    """The tensor given as ``render(..., emissions=)`` / ``Scene.set_emission_values``: float32, (ninst, 3), on ``device``; not together
+    with ``envmap=``.  Returns it; raises ValueError otherwise."""
+    if envmap is not None:
+        raise ValueError("emissions= and envmap= cannot be given in one call: differentiate the lights and the environment map in separate renders")
+    if not isinstance(emissions, torch.Tensor) or emissions.dtype != torch.float32 or emissions.device != torch.device(device):
+        raise ValueError(f"emissions must be a float32 tensor on {device}")
+    if tuple(emissions.shape) != (ninst, 3):
+        raise ValueError(f"emissions is {tuple(emissions.shape)}, the scene has {ninst} models: one (r, g, b) row per model, ({ninst}, 3)")
+    return emissions
+
+
+class EmissionValues(list):
+    """``scene.emissions`` after ``set_emission_values``: the list that defines which models are lights (as given to ``Scene`` or
+    ``update_lights``) with ``values``, the (ninst, 3) device tensor whose rows those lights now emit.  ``update_lights`` takes it back."""
+    def __init__(self, base, values):
+        super().__init__(base)
+        self.values = values
 
 
 def _camera_pod(cam: Camera) -> N.CameraPOD:
@@ -156,6 +179,27 @@ class Scene:
         e = np.ascontiguousarray(np.stack([normalize_emission(x) for x in emissions]), np.float32)
         self.light_count = int((e > 0).any(axis=1).sum())
         N.check(N.lib().zdr_scene_set_emissions(self._handle, e.ctypes.data, self._stream()))
+        if isinstance(emissions, EmissionValues):         # a snapshot of set_emission_values: the light list, then its values
+            self._apply_emission_values(emissions.values)
+
+    def set_emission_values(self, emissions):
+        """Rewrites, in place and without a synchronise, the emission of the models that are lights now (include/zdr.h,
+        zdr_scene_set_emission_values): ``emissions`` is a float32 (ninst, 3) tensor on the scene's device; rows of models outside the
+        light list of ``Scene(...)`` or of the last ``update_lights`` are ignored.  The values stay the scene's emissions until the next
+        call or ``update_lights``."""
+        values = check_emissions(emissions, self.inst_count, self.device).detach().contiguous()
+        self._apply_emission_values(values)
+        self.emissions = EmissionValues(self.emissions, values)   # a new object: the autograd nodes compare identities
+
+    def _apply_emission_values(self, values):
+        N.check(N.lib().zdr_scene_set_emission_values(self._handle, values.data_ptr(), self._stream()))
+
+    def _check_d_emission(self, d_emission, d_env):
+        if d_env is not None:
+            raise ValueError("d_emission and d_env cannot be given in one call")
+        if (tuple(d_emission.shape) != (self.inst_count, 3) or not d_emission.is_contiguous() or d_emission.device != self.device
+                or d_emission.dtype != torch.float32):
+            raise ValueError(f"d_emission must be a contiguous float32 ({self.inst_count}, 3) tensor on {self.device}")
 
     def add_envmap(self, image, compensate_mis=True):
         """Adds a lat-long environment light (render.py:150-156, envmap.py:116-203).  ``image`` is an
@@ -290,9 +334,9 @@ class Scene:
         return image
 
     def render_backward_materials(self, grad_output, d_materials, materials, res, spp, seed, *, dims=None, rect=None, samples=None, camera=None,
-                                  tile_shard=None, slots=None, d_env=None):
+                                  tile_shard=None, slots=None, d_env=None, d_emission=None):
         """``render_backward`` with one material per slot: accumulates into ``d_materials`` (a list shaped like ``materials``, or
-        one packed tensor); uses ``seed + 1`` like render_backward.  ``d_env``: as in render_backward."""
+        one packed tensor); uses ``seed + 1`` like render_backward.  ``d_env``, ``d_emission``: as in render_backward."""
         packed, d, _ = self._material_call(materials, dims, slots)
         listed = isinstance(d_materials, (list, tuple))
         dpacked = (torch.cat([g.reshape(-1, 4) for g in d_materials]) if len(d_materials) > 1 else d_materials[0]) if listed else d_materials
@@ -300,7 +344,11 @@ class Scene:
             raise ValueError(f"d_materials must be contiguous float32 on {self.device}, shaped like the materials")
         g = grad_output.reshape(res[1], res[0], 4).to(device=self.device, dtype=torch.float32).contiguous()
         p = self._params(res, spp, seed + 1, (1, 1), rect, samples, camera, tile_shard=tile_shard)
-        if d_env is None:
+        if d_emission is not None:
+            self._check_d_emission(d_emission, d_env)
+            N.check(N.lib().zdr_render_backward_materials_emission(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
+                                                                   dpacked.data_ptr(), d_emission.data_ptr(), self._stream()))
+        elif d_env is None:
             N.check(N.lib().zdr_render_backward_materials(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
                                                           dpacked.data_ptr(), self._stream()))
         else:
@@ -359,10 +407,12 @@ class Scene:
         N.check(N.lib().zdr_render_forward(self._handle, C.byref(p), material.data_ptr(), image.data_ptr(), self._stream()))
         return image
 
-    def render_backward(self, grad_output, d_material, material, res, spp, seed, *, rect=None, samples=None, camera=None, tile_shard=None, d_env=None):
+    def render_backward(self, grad_output, d_material, material, res, spp, seed, *, rect=None, samples=None, camera=None, tile_shard=None, d_env=None, d_emission=None):
         """render.py:176-199: accumulates into ``d_material``; uses ``seed + 1`` like the reference (:196).  ``d_env``: a prepared
         (H, H, 4) float32 tensor of the map's size that also accumulates the gradient of the environment map (zdr_render_backward_env;
-        path and direct — collocated has no environment term and leaves it alone)."""
+        path and direct — collocated has no environment term and leaves it alone).  ``d_emission``: a float32 (ninst, 3) tensor that also
+        accumulates the gradient of the lights' emissions (zdr_render_backward_emission; rows of models that are not lights receive
+        nothing, collocated leaves it alone); not together with ``d_env``."""
         self._check_material(material)
         material = material.detach().contiguous()
         g = grad_output.reshape(res[1], res[0], 4).to(device=self.device, dtype=torch.float32).contiguous()
@@ -370,7 +420,11 @@ class Scene:
         if d_material.device != self.device or d_material.dtype != torch.float32:
             raise ValueError(f"d_material must be a float32 tensor on {self.device}")
         p = self._params(res, spp, seed + 1, material.shape[0:2], rect, samples, camera, tile_shard=tile_shard)
-        if d_env is None:
+        if d_emission is not None:
+            self._check_d_emission(d_emission, d_env)
+            N.check(N.lib().zdr_render_backward_emission(self._handle, C.byref(p), g.data_ptr(), material.data_ptr(), d_material.data_ptr(),
+                                                         d_emission.data_ptr(), self._stream()))
+        elif d_env is None:
             N.check(N.lib().zdr_render_backward(self._handle, C.byref(p), g.data_ptr(), material.data_ptr(), d_material.data_ptr(), self._stream()))
         else:
             self._check_d_env(d_env)
@@ -388,15 +442,19 @@ class Scene:
         return dict(zip(N.COUNTER_NAMES, list(cnt)))
 
     class RenderOperator(torch.autograd.Function):     # render.py:201-223
-        """render() of one material; with a prepared environment map as a sixth input also differentiable w.r.t. the map."""
+        """render() of one material; with a prepared environment map as a sixth input also differentiable w.r.t. the map, with an
+        (ninst, 3) emission tensor as a seventh w.r.t. the lights' emissions (one of the two at most)."""
         @staticmethod
-        def forward(ctx, material, self, res, spp, seed, env=None):
+        def forward(ctx, material, self, res, spp, seed, env=None, emissions=None):
             if env is not None:                            # the map this forward renders with: uploaded now, saved for the backward
                 env = env.detach().clone()
                 self.set_envmap_texture(env)
+            if emissions is not None:                      # likewise the emissions: a detached copy becomes the scene's values
+                self.set_emission_values(emissions.detach().clone())
             ctx.save_for_backward(material)
             ctx.env = env                                  # (a detached copy: kept as it is, not as a saved input)
             ctx.with_env = env is not None
+            ctx.with_emissions = emissions is not None
             ctx.scene = weakref.ref(self)
             ctx.args = (res, spp, seed)
             ctx.camera = self.camera.copy()
@@ -414,6 +472,11 @@ class Scene:
             env = ctx.env
             mat_grad = torch.zeros(material.size(), dtype=material.dtype, device=material.device)
             res, spp, seed = ctx.args
+            if ctx.with_emissions:                         # ctx.emissions holds the forward's copy: applied again, whatever happened in between
+                scene._apply_emission_values(ctx.emissions.values)
+                d_emission = torch.zeros_like(ctx.emissions.values)
+                scene.render_backward(grad_output, mat_grad, material.detach(), res, spp, seed, camera=ctx.camera, d_emission=d_emission)
+                return mat_grad, None, None, None, None, None, d_emission
             if not ctx.with_env:
                 return scene.render_backward(grad_output, mat_grad, material.detach(), res, spp, seed, camera=ctx.camera)
             scene.set_envmap_texture(env)                  # the material gradient depends on the map's values too
@@ -425,10 +488,13 @@ class Scene:
         """render() of several materials: takes their packed texels, returns their packed gradient (torch.cat's own backward
         hands each material its part)."""
         @staticmethod
-        def forward(ctx, packed, self, dims, slots, res, spp, seed, env=None):
+        def forward(ctx, packed, self, dims, slots, res, spp, seed, env=None, emissions=None):
             if env is not None:                            # as RenderOperator
                 env = env.detach().clone()
                 self.set_envmap_texture(env)
+            if emissions is not None:
+                self.set_emission_values(emissions.detach().clone())
+            ctx.with_emissions = emissions is not None
             ctx.save_for_backward(packed)
             ctx.env = env
             ctx.with_env = env is not None
@@ -448,6 +514,11 @@ class Scene:
             dims, slots, res, spp, seed = ctx.args
             d = torch.zeros(packed.size(), dtype=packed.dtype, device=packed.device)
             d_env = None
+            if ctx.with_emissions:                          # as RenderOperator
+                scene._apply_emission_values(ctx.emissions.values)
+                d_emission = torch.zeros_like(ctx.emissions.values)
+                scene.render_backward_materials(grad_output, d, packed.detach(), res, spp, seed, dims=dims, camera=ctx.camera, slots=slots, d_emission=d_emission)
+                return d, None, None, None, None, None, None, None, d_emission
             if ctx.with_env:
                 scene.set_envmap_texture(env)
                 d_env = torch.zeros_like(env)
@@ -455,7 +526,7 @@ class Scene:
             scene.render_backward_materials(grad_output, d, packed.detach(), res, spp, seed, dims=dims, camera=ctx.camera, slots=slots, d_env=d_env)
             return (d, None, None, None, None, None, None) + ((d_env,) if ctx.with_env else ())
 
-    def render(self, material, *, res, spp, seed=0, envmap=None):
+    def render(self, material, *, res, spp, seed=0, envmap=None, emissions=None):
         """Renders the scene; differentiable w.r.t. ``material`` ((Ht, Wt, 4) float32 on the GPU).
         res = (width, height); returns (height, width, 4) (render.py:225-241).
 
@@ -467,9 +538,21 @@ class Scene:
         differentiates (path and direct; collocated sees no environment).  It is prepared as add_envmap prepares an image (alpha 1
         for RGB, a 1:2 map made square), must then have the size given to add_envmap, and becomes the scene's map: later renders
         without ``envmap=`` use it too.  The importance-sampling tables stay those of add_envmap or of the last
-        update_envmap_sampling, and the gradient holds them fixed.  At most 15 materials with ``envmap=``."""
+        update_envmap_sampling, and the gradient holds them fixed.  At most 15 materials with ``envmap=``.
+
+        ``emissions``: a float32 (ninst, 3) tensor on the GPU whose rows the render uses as the emission of the models that are lights
+        now (the light list of ``Scene(...)`` or of the last ``update_lights``) and differentiates (path and direct; collocated reads
+        no emission and returns a zero gradient).  Rows of other models are ignored and receive gradient 0: which models emit is not
+        differentiable, and ``update_lights`` stays the way to change it.  The values become the scene's emissions, for later renders
+        without ``emissions=`` too.  For one seed the render is linear in the emissions and the gradient is exact as long as every
+        light keeps at least one positive component (zero or negative components are fine; this is not checked).  Not together
+        with ``envmap=``."""
+        if emissions is not None:
+            check_emissions(emissions, self.inst_count, self.device, envmap)
         env = None if envmap is None else self._prepare_envmap(envmap)
         if not isinstance(material, (list, tuple)) and self._material_slots is None:
+            if emissions is not None:
+                return Scene.RenderOperator.apply(material, self, res, spp, seed, None, emissions)
             if env is not None:
                 return Scene.RenderOperator.apply(material, self, res, spp, seed, env)
             return Scene.RenderOperator.apply(material, self, res, spp, seed)
@@ -481,6 +564,8 @@ class Scene:
         slots = resolve_material_slots(self._material_slots, self.emissions, len(mats))
         dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
         packed = mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
+        if emissions is not None:
+            return Scene.MaterialsOperator.apply(packed, self, dims, slots, res, spp, seed, None, emissions)
         if env is not None:
             return Scene.MaterialsOperator.apply(packed, self, dims, slots, res, spp, seed, env)
         return Scene.MaterialsOperator.apply(packed, self, dims, slots, res, spp, seed)
