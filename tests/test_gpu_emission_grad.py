@@ -72,11 +72,11 @@ class Case:
     """One scene and its materials: forward(e) renders with emission values e (seed + 1, the backward's samples), backward(g, e)
     returns (d_materials, d_emission) of the same samples."""
 
-    def __init__(self, scene, mats=None, slots=None, w=W, spp=SPP, seed=SEED):
+    def __init__(self, scene, mats=None, slots=None, w=W, spp=SPP, seed=SEED, h=None):
         self.s = scene
         self.mats = mats if mats is not None else [cuda(fd_material_np(64, 0))]
         self.slots = slots
-        self.res, self.spp, self.seed = (w, w), spp, seed
+        self.res, self.spp, self.seed = (w, w if h is None else h), spp, seed
         if slots is not None:
             scene.material_slots = slots
 

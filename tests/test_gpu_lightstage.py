@@ -3,7 +3,7 @@ small quad lights, each placed by the script's own `rotate_mat` (yaw @ pitch @ t
 float4x4(*m.transpose().flatten())), camera sphere_camera1, integrator 'direct' — with sphere.obj (reference-pinned geometry,
 tests/golden/obj_fixtures.npz; the script's bunnyuv.obj is not among the reference's files) as the object.  HIP against the oracle,
 forward and backward, for the script's integrator and for `path`, and light switching through update_lights."""
-from math import acos, cos, pi, sin
+from math import acos, pi
 
 import numpy as np
 import pytest
@@ -12,20 +12,12 @@ import torch
 import oracle
 from conftest import ASSETS, fd_material_np
 from gpu_util import Flips, assert_grad_parity, assert_image_parity, oracle_params
-from zdr_amd import Camera, Scene, float3, float4x4, geometry
+from many_lights import CAMERA, NLIGHT, rotate_mat            # (shared with the 30-light stage of many_lights.py)
+from zdr_amd import Scene, geometry
 
 pytestmark = pytest.mark.gpu
 
 
-def rotate_mat(theta, phi, offset):                              # test_lightstage.py:24-45, verbatim in structure
-    pitch = np.array([[cos(theta), -sin(theta), 0, 0], [sin(theta), cos(theta), 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]])
-    yaw = np.array([[cos(phi), 0, -sin(phi), 0], [0, 1, 0, 0], [sin(phi), 0, cos(phi), 0], [0, 0, 0, 1]])
-    translate = np.array([[1, 0, 0, offset[0]], [0, 1, 0, offset[1]], [0, 0, 1, offset[2]], [0, 0, 0, 1]])
-    m = yaw @ pitch @ translate
-    return float4x4(*m.transpose().flatten())
-
-
-NLIGHT = 30
 LIGHTS = (29, 22, 16, 9)                                         # the script keeps i == 29; three more of its 30 positions
 
 
@@ -34,9 +26,6 @@ def models():
     for i in LIGHTS:
         out.append((f"{ASSETS}/quad.obj", rotate_mat(acos((i + 0.5) / NLIGHT * 2 - 1), pi * 2 * 0.618 * (i + 1), (0, 0, 0)), 50))
     return out
-
-
-CAMERA = Camera(fov=50 / 180 * 3.1415926, origin=float3(0, 0.5, 2), target=float3(0, 0, 0), up=float3(0.0, 1.0, 0.0))   # sphere_camera1
 
 
 @pytest.fixture(scope="module")
