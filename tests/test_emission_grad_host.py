@@ -33,9 +33,9 @@ def test_the_emission_gradient_entry_points_are_declared_bound_and_exported():
     assert declared <= set(_native.EXPORTS)
 
 
-# k_path_bwd_emission<SK, A, ENV> and k_direct_bwd_emission<SK, A, ENV>
-PATH_LG = r"k_path_bwd_emissionILi([01])E(10BruteAccel|8BvhAccel)Lb([01])EE"
-DIRECT_LG = r"k_direct_bwd_emissionILi([01])E(10BruteAccel|8BvhAccel)Lb([01])EE"
+# k_path_bwd<SK, A, ENV, MT = true, EG = false, LG = true> and k_simple<ZDR_DIRECT, SK, A, BWD = true, STATS = false, ENV, MT = true, EG = false, LG = true>
+PATH_LG = r"k_path_bwdILi([01])E(10BruteAccel|8BvhAccel)Lb([01])ELb1ELb0ELb1EE"
+DIRECT_LG = r"k_simpleILi1ELi([01])E(10BruteAccel|8BvhAccel)Lb1ELb0ELb([01])ELb1ELb0ELb1EE"
 
 
 def test_emission_gradient_kernels_are_built_for_both_samplers_both_accels_with_and_without_environment():

@@ -34,9 +34,9 @@ def test_the_environment_gradient_entry_points_are_declared_bound_and_exported()
     assert declared <= set(_native.EXPORTS)
 
 
-# k_path_bwd<SK, A, ENV = true, MT = true, EG = true> and k_simple<ZDR_DIRECT, SK, A, BWD = true, STATS = false, ENV, MT, EG = true>
-PATH_EG = r"k_path_bwdILi([01])E(10BruteAccel|8BvhAccel)Lb1ELb1ELb1EE"
-DIRECT_EG = r"k_simpleILi1ELi([01])E(10BruteAccel|8BvhAccel)Lb1ELb0ELb1ELb1ELb1EE"
+# k_path_bwd<SK, A, ENV = true, MT = true, EG = true, LG = false> and k_simple<ZDR_DIRECT, SK, A, BWD = true, STATS = false, ENV, MT, EG = true, LG = false>
+PATH_EG = r"k_path_bwdILi([01])E(10BruteAccel|8BvhAccel)Lb1ELb1ELb1ELb0EE"
+DIRECT_EG = r"k_simpleILi1ELi([01])E(10BruteAccel|8BvhAccel)Lb1ELb0ELb1ELb1ELb1ELb0EE"
 
 
 def test_environment_gradient_kernels_are_built_for_both_samplers_and_both_accels():

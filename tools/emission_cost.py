@@ -4,6 +4,7 @@
     c3        the Cornell box, path 512^2 spp 256, brute force: ONE light, every term lands on three floats
     lights3   zdr_amd.scenes.multi_light_arrays(): three lights of different triangle counts and a blocker, path 512^2 spp 256
     c5        1 M triangles (BVH), path 1024^2 spp 256
+    d3, d3_bvh, dlights3   the direct integrator at 512^2 spp 256: the Cornell box by brute force and with accel="bvh", and lights3's scene
 The plain backward runs the kernels the parent commit runs (tools/isa_diff.py: instruction for instruction), so it is the baseline.
 The two calls alternate, round by round, so that whatever else the box is doing lands on both; the medians, the spread of each and
 the ratio are printed.
@@ -26,6 +27,9 @@ CONFIGS = {   # name: (scene factory, resolution, spp)
     "c3": (lambda: make_scene("path", accel="brute"), 512, 256),
     "lights3": (lambda: make_scene("path", arrays=multi_light_arrays()), 512, 256),
     "c5": (lambda: make_scene("path", arrays=tess1m_arrays()), 1024, 256),
+    "d3": (lambda: make_scene("direct", accel="brute"), 512, 256),
+    "d3_bvh": (lambda: make_scene("direct", accel="bvh"), 512, 256),
+    "dlights3": (lambda: make_scene("direct", arrays=multi_light_arrays()), 512, 256),
 }
 
 

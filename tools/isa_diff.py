@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Which kernels does a source change actually touch?  Compiles csrc/zdr_kernels.hip of a git revision and of the working tree to gfx950
+r"""Which kernels does a source change actually touch?  Compiles csrc/zdr_kernels.hip of a git revision and of the working tree to gfx950
 assembly (hipcc -S, CPU only) and compares every kernel's instruction stream, labels normalised.  A kernel reported `identical` runs the
 very same machine code: no timing is needed for it — and one that is NOT expected to change and does is the thing to time first.
 (Round 4: a sampler change meant for the direct kernels shifted the register allocation of the BVH forward kernel and moved five spill
@@ -8,7 +8,11 @@ operations into its walk loop, +8 %; it had been A/B-timed on the Cornell box on
     python tools/isa_diff.py --pair-appended-false [rev]
         for a change that appends a bool template parameter to kernel templates (the material-table mode of k_path, k_path_bwd and k_simple):
         a kernel of rev that is gone from the tree is compared with the instantiation whose template arguments end in one more `false`
-        (mangled Lb0E inserted before the end of the template argument list) — the kernel the old launch now runs."""
+        (mangled Lb0E inserted before the end of the template argument list) — the kernel the old launch now runs.
+    python tools/isa_diff.py --pair-renamed='REGEX=>REPLACEMENT' [rev]        (may be given several times)
+        for a kernel that was renamed or folded into another template: a mangled name of rev that is gone from the tree is rewritten with
+        re.sub(REGEX, REPLACEMENT) and compared with the kernel of that name, e.g.
+        '_Z19k_path_bwd_emissionI(\w+?Accel)(Lb\dE)E=>_Z10k_path_bwdI\1\2Lb1ELb0ELb1EE'."""
 import os
 import re
 import subprocess
@@ -41,6 +45,7 @@ def stats(body):
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 pair_appended_false = "--pair-appended-false" in sys.argv[1:]
+pair_renamed = [a.split("=", 1)[1].split("=>", 1) for a in sys.argv[1:] if a.startswith("--pair-renamed=")]
 rev = args[0] if args else "HEAD"
 with tempfile.TemporaryDirectory() as tmp:
     old_tree = os.path.join(tmp, "old"); os.makedirs(old_tree)
@@ -63,6 +68,11 @@ if pair_appended_false:   # rename each old kernel the tree no longer has to its
     for name in [n for n in old if n not in new]:
         twin = appended_false(name)
         if twin in new and twin not in old:
+            old[twin] = old.pop(name)
+for pattern, replacement in pair_renamed:
+    for name in [n for n in old if n not in new]:
+        twin = re.sub(pattern, replacement, name)
+        if twin != name and twin in new and twin not in old:
             old[twin] = old.pop(name)
 changed = 0
 for name in sorted(set(old) | set(new)):

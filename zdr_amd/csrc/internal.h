@@ -69,12 +69,15 @@ struct KernelIO {
     MaterialTable mt;                 // material-table calls only (zdr_render_*_materials): `material` is then the packed buffer, `cells` all materials' cells
 };
 
-// d_env != nullptr: environment-gradient backward (zdr_render_backward_env): io.mt is a material table whose entry ZDR_ENV_ENTRY holds the
-// map's cells, and they are gathered into d_env (+=)
-int zdr_launch_render(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io,
-                      int integrator, int accel_is_bvh, int backward, int stats, hipStream_t stream, float *d_env = nullptr, float *d_emission = nullptr);
-// d_emission != nullptr (never together with d_env; the scene has at least one light): emission-gradient backward (zdr_render_backward_emission):
-// io.mt is a material table, io.emit_acc the zeroed accumulator, and its rows are gathered into d_emission (ninst x 3, +=)
+// What zdr_launch_render runs.  The two gradient targets beside d_material are optional and never given together:
+struct RenderLaunch {
+    int integrator, accel_is_bvh, backward, stats;
+    float *d_env;         // environment-gradient backward (zdr_render_backward_env): io.mt is a material table whose entry ZDR_ENV_ENTRY holds
+                          // the map's cells, and they are gathered into d_env (+=)
+    float *d_emission;    // emission-gradient backward (zdr_render_backward_emission; the scene has at least one light): io.mt is a material
+                          // table, io.emit_acc the zeroed accumulator, and its rows are gathered into d_emission (ninst x 3, +=)
+};
+int zdr_launch_render(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, const RenderLaunch &L, hipStream_t stream);
 #define ZDR_EMISSION_COPIES 256       // rows of the emission accumulator
 int zdr_launch_set_emission_values(const DScene &S, const float *src, float *emission, float4 *emission4, float4 *light_tris, hipStream_t stream);
 int zdr_launch_zero(void *p, size_t bytes, hipStream_t stream);   // kernel zero-fill (graph-safe, see zdr_kernels.hip)

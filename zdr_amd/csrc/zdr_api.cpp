@@ -1045,6 +1045,19 @@ static int ensure_cells(zdr_scene *s, const RenderCfg &R, size_t ncells, hipStre
     return ZDR_OK;
 }
 
+// The emission-gradient accumulator (internal.h, KernelIO::emit_acc): sized once for every light list the scene can have, zeroed per call
+static int ensure_emit_acc(zdr_scene *s, hipStream_t st, bool capturing) {
+    const size_t need = (size_t)ZDR_EMISSION_COPIES * 3 * (size_t)s->ninst * sizeof(float);
+    if (need > s->emit_acc_bytes) {
+        if (int rc = may_allocate(capturing, "emission-accumulator")) return rc;
+        release_buffer(s, s->d_emit_acc); s->d_emit_acc = nullptr; s->emit_acc_bytes = 0;
+        HIPCHK(hipMalloc((void **)&s->d_emit_acc, need));
+        s->emit_acc_bytes = need;
+    }
+    if (zdr_launch_zero(s->d_emit_acc, (size_t)ZDR_EMISSION_COPIES * 3 * (size_t)s->ds.light_count * sizeof(float), st)) return fail(ZDR_E_HIP, "zero-fill launch failed");
+    return ZDR_OK;
+}
+
 // Reads (and clears) the device error word; the stream is synchronised first.  A set bit means a watchdog ended
 // work early (zdr_kernels.hip: stall; accel.h: BVH budget): the image / gradient of the calls since the last
 // check is incomplete.
@@ -1067,10 +1080,16 @@ extern "C" int zdr_scene_check(zdr_scene *s, void *stream) {
     return check_device_error(s, (hipStream_t)stream);
 }
 
-// The material table of a zdr_render_*_materials call (internal.h): materials packed in order, their cells likewise.
-static int make_material_table(zdr_scene *s, const int32_t *dims, uint32_t nmat, bool capturing, hipStream_t st, MaterialTable &mt) {
-    if (!dims) return fail(ZDR_E_INVALID, "null material dimensions");
+// What every zdr_render_*_materials entry point checks first: its buffers and `dims` are there, nmat is in range
+static int check_table_args(bool buffers, const int32_t *dims, uint32_t nmat) {
+    if (!buffers || !dims) return fail(ZDR_E_INVALID, "null argument");
     if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
+    return ZDR_OK;
+}
+
+// The material table of a zdr_render_*_materials call (internal.h): materials packed in order, their cells likewise.
+// (dims and nmat have passed check_table_args.)
+static int make_material_table(zdr_scene *s, const int32_t *dims, uint32_t nmat, bool capturing, hipStream_t st, MaterialTable &mt) {
     memset(&mt, 0, sizeof mt);
     size_t texel = 0, cells = 0;
     for (uint32_t k = 0; k < nmat; k++) {
@@ -1130,25 +1149,35 @@ static void material_cell_layout(MaterialTable &mt, RenderCfg &R) {
     mt.ncells = (int32_t)cell;
 }
 
-// mt_dims / nmat: a material-table call (zdr_render_*_materials), else nullptr / 0.  d_env (backward, path / direct): also the gradient of
-// the environment map, through the material-table kernels with the map as entry ZDR_ENV_ENTRY (a single material becomes a table of one).
-static int render_common(zdr_scene *s, const zdr_render_params *p, const float *material, float *image, const float *d_image,
-                         float *d_material, int backward, int stats, void *stream, const int32_t *mt_dims = nullptr, uint32_t nmat = 0,
-                         float *d_env = nullptr, float *d_emission = nullptr) {
-    if (!s || !p || !material) return fail(ZDR_E_INVALID, "null argument");
-    if (d_env && d_emission) return fail(ZDR_E_UNSUPPORTED, "the environment gradient and the emission gradient cannot be taken in one call");
+// One render call as the entry points describe it to render_common.
+struct RenderCall {
+    const float *material = nullptr;                    // the material, or the packed materials of a material-table call
+    const int32_t *dims = nullptr; uint32_t nmat = 0;   // material-table call (zdr_render_*_materials; both have passed check_table_args), else nullptr / 0
+    float *image = nullptr;                             // forward
+    bool backward = false, stats = false;
+    const float *d_image = nullptr; float *d_material = nullptr;   // backward
+    // backward, path / direct, optional and never both: also the gradient of the environment map, through the material-table kernels with the
+    // map as entry ZDR_ENV_ENTRY / of the lights' emissions, through the material-table kernels' emission forms.  A single material becomes
+    // a table of one.
+    float *d_env = nullptr, *d_emission = nullptr;
+    void *stream = nullptr;
+};
+
+static int render_common(zdr_scene *s, const zdr_render_params *p, const RenderCall &call) {
+    const bool backward = call.backward, stats = call.stats;
+    const hipStream_t st = (hipStream_t)call.stream;
+    if (!s || !p || !call.material) return fail(ZDR_E_INVALID, "null argument");
+    if (call.d_env && call.d_emission) return fail(ZDR_E_UNSUPPORTED, "the environment gradient and the emission gradient cannot be taken in one call");
     int rc = check_params_abi(p); if (rc) return rc;
     HIPCHK(hipSetDevice(s->device));
-    const bool use_mt = nmat > 0 || mt_dims;
-    const bool env_grad = backward && d_env;
-    // d_emission (backward, path / direct): also the gradient of the lights' emissions, through the material-table kernels' emission forms (a
-    // single material becomes a table of one).  A scene without lights has no such term: the plain call.
-    const bool emit_grad = backward && d_emission && s->ds.light_count > 0;
+    const bool use_mt = call.dims != nullptr;
+    const bool env_grad = backward && call.d_env;            // (the scene has a map: render_backward_call)
+    const bool emit_grad = backward && call.d_emission && s->ds.light_count > 0;   // a scene without lights has no such term: the plain call
+    const bool table_form = use_mt || env_grad || emit_grad;   // the call runs in the material-table kernels
     if (emit_grad && p->integrator != ZDR_PATH && p->integrator != ZDR_DIRECT) return fail(ZDR_E_UNSUPPORTED, "an emission gradient needs the path or the direct integrator");
     if (env_grad) {
         if (p->integrator != ZDR_PATH && p->integrator != ZDR_DIRECT) return fail(ZDR_E_UNSUPPORTED, "an environment gradient needs the path or the direct integrator");
-        if (s->ds.env_count == 0) return fail(ZDR_E_INVALID, "d_env given, but the scene has no environment map");
-        if (use_mt && nmat > ZDR_ENV_ENTRY) return fail(ZDR_E_UNSUPPORTED, "an environment gradient takes at most " + std::to_string(ZDR_ENV_ENTRY) + " materials (the map is the last entry of the material table)");
+        if (use_mt && call.nmat > ZDR_ENV_ENTRY) return fail(ZDR_E_UNSUPPORTED, "an environment gradient takes at most " + std::to_string(ZDR_ENV_ENTRY) + " materials (the map is the last entry of the material table)");
     }
     zdr_render_params pm = *p;
     if (use_mt) {                                       // the materials' sizes come from the table
@@ -1158,17 +1187,17 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
     RenderCfg R; SamplerCfg C;
     rc = make_render_cfg(&pm, backward != 0, R); if (rc) return rc;
     rc = make_sampler_cfg(s, p->sampler, p->seed, p->spp, C); if (rc) return rc;
-    const bool capturing = stream_is_capturing((hipStream_t)stream);
+    const bool capturing = stream_is_capturing(st);
     MaterialTable mt; memset(&mt, 0, sizeof mt);
     if (use_mt) {
-        rc = make_material_table(s, mt_dims, nmat, capturing, (hipStream_t)stream, mt); if (rc) return rc;
-    } else if (env_grad || emit_grad) {                 // the one material as a table of one
+        rc = make_material_table(s, call.dims, call.nmat, capturing, st, mt); if (rc) return rc;
+    } else if (table_form) {                            // the one material as a table of one
         mt.m[0].texel = 0; mt.m[0].h = R.tex_h; mt.m[0].w = R.tex_w; mt.m[0].cell = 0;
         mt.nmat = 1; mt.ncells = (R.tex_h + 1) * (R.tex_w + 1);
         rc = single_material_slots(s, capturing, mt.inst_slot); if (rc) return rc;
     }
     size_t env_cells_total = 0;                         // environment gradient: the map's cells, all their copies
-    if (use_mt || env_grad || emit_grad) {
+    if (table_form) {
         R.tex_h = R.tex_w = 0;                          // (unused in material-table mode)
         material_cell_layout(mt, R);                    // the materials' copies: as in the call without the map
     }
@@ -1186,24 +1215,15 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
         env_cells_total = copies * one;
     }
     if (capturing) s->captured = true;                  // sticky: a graph may name this handle's buffers from now on (zdr_scene)
-    if (backward) { rc = ensure_cells(s, R, (use_mt || env_grad || emit_grad) ? (size_t)mt.ncells : (size_t)(R.tex_h + 1) * (R.tex_w + 1), (hipStream_t)stream, capturing,
+    if (backward) { rc = ensure_cells(s, R, table_form ? (size_t)mt.ncells : (size_t)(R.tex_h + 1) * (R.tex_w + 1), st, capturing,
                                       env_cells_total); if (rc) return rc; }
     else if (!stats) { rc = ensure_partial(s, R, capturing); if (rc) return rc; }
     if (p->integrator == ZDR_PATH) {
         if (p->spp > (1u << 25)) return fail(ZDR_E_UNSUPPORTED, "path integrator: spp above 2^25");   // queue entries pack pixel << 26 | bank << 25 | sample
-        rc = ensure_ring(s, (hipStream_t)stream, capturing); if (rc) return rc;
+        rc = ensure_ring(s, st, capturing); if (rc) return rc;
     }
     KernelIO io; memset(&io, 0, sizeof io);
-    if (emit_grad) {                                    // the accumulator: sized once for every light list the scene can have, zeroed per call
-        const size_t need = (size_t)ZDR_EMISSION_COPIES * 3 * (size_t)s->ninst * sizeof(float);
-        if (need > s->emit_acc_bytes) {
-            if (int rc2 = may_allocate(capturing, "emission-accumulator")) return rc2;
-            release_buffer(s, s->d_emit_acc); s->d_emit_acc = nullptr; s->emit_acc_bytes = 0;
-            HIPCHK(hipMalloc((void **)&s->d_emit_acc, need));
-            s->emit_acc_bytes = need;
-        }
-        if (zdr_launch_zero(s->d_emit_acc, (size_t)ZDR_EMISSION_COPIES * 3 * (size_t)s->ds.light_count * sizeof(float), (hipStream_t)stream)) return fail(ZDR_E_HIP, "zero-fill launch failed");
-    }
+    if (emit_grad) { rc = ensure_emit_acc(s, st, capturing); if (rc) return rc; }
     io.ring = s->d_ring; io.work_counters = s->d_work_counters;
     // brute-force scenes of at most 64 triangle pairs: camera rays test only the pairs their tile can see
     const bool masks = !s->accel_is_bvh && s->ds.ntris <= 128 && p->integrator != ZDR_UVGRAD && !getenv("ZDR_NO_TILE_MASKS");
@@ -1229,9 +1249,9 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
         // tiles) launches nothing, and must not leave the key of masks nobody built behind for the next call
         if ((long)R.ntiles * R.nchunks > 0) { memcpy(s->tile_mask_key, key, sizeof key); s->tile_mask_key_set = true; }
     }
-    io.material = (const float4 *)material; io.image = (float4 *)image; io.partial = s->d_partial;
+    io.material = (const float4 *)call.material; io.image = (float4 *)call.image; io.partial = s->d_partial;
     if (emit_grad) io.emit_acc = s->d_emit_acc;         // (shares the forward's `partial` pointer: KernelIO keeps its size)
-    io.d_image = (const float4 *)d_image; io.d_material = d_material; io.cells = s->d_cells; io.counters = s->d_counters;
+    io.d_image = (const float4 *)call.d_image; io.d_material = call.d_material; io.cells = s->d_cells; io.counters = s->d_counters;
     io.mt = mt;
     // every pointer a kernel variant dereferences must be live before anything is launched
     if (backward && (!io.d_image || !io.d_material || !io.cells)) return fail(ZDR_E_INVALID, "backward needs d_image, d_material and the staging cells");
@@ -1243,80 +1263,82 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const float *
     DScene S = s->ds;
     // shadow segments end on a light's surface; an environment light sends them to infinity, where nothing can be ruled out
     S.shadow_pairs = (S.env_count > 0) ? ~0ull : s->shadow_pairs;
-    if (zdr_launch_render(S, R, C, io, p->integrator, s->accel_is_bvh, backward, stats, (hipStream_t)stream, env_grad ? d_env : nullptr, emit_grad ? d_emission : nullptr))
+    const RenderLaunch L = {p->integrator, s->accel_is_bvh, backward, stats, env_grad ? call.d_env : nullptr, emit_grad ? call.d_emission : nullptr};
+    if (zdr_launch_render(S, R, C, io, L, st))
         return fail(ZDR_E_HIP, std::string("kernel launch: ") + hipGetErrorString(hipGetLastError()));
     static const bool check_every_call = getenv("ZDR_CHECK") && atoi(getenv("ZDR_CHECK")) != 0;   // opt-in: costs a synchronise per call
-    if (check_every_call && !stats && !capturing) return check_device_error(s, (hipStream_t)stream);   // (a synchronise cannot be captured: zdr_scene_check after the replay instead)
+    if (check_every_call && !stats && !capturing) return check_device_error(s, st);   // (a synchronise cannot be captured: zdr_scene_check after the replay instead)
     return ZDR_OK;
 }
 
 extern "C" int zdr_render_forward(zdr_scene *s, const zdr_render_params *p, const float *material, float *image, void *stream) {
     if (!image) return fail(ZDR_E_INVALID, "null image");
-    return render_common(s, p, material, image, nullptr, nullptr, 0, 0, stream);
-}
-
-extern "C" int zdr_render_backward(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *material,
-                                   float *d_material, void *stream) {
-    if (!d_image || !d_material) return fail(ZDR_E_INVALID, "null gradient buffer");
-#ifdef ZDR_MEASURE_STATS   // measurement build (tools/bwd_stats.sh): the path backward kernel counts its trips, sweep iterations and flushes
-    if (s) { (void)hipSetDevice(s->device); (void)hipMemsetAsync(s->d_counters, 0, 8 * sizeof(unsigned long long), (hipStream_t)stream); }
-    int rc = render_common(s, p, material, nullptr, d_image, d_material, 1, 0, stream);
-    if (!rc) {
-        unsigned long long h[8];
-        (void)hipMemcpyAsync(h, s->d_counters, sizeof h, hipMemcpyDeviceToHost, (hipStream_t)stream); (void)hipStreamSynchronize((hipStream_t)stream);
-        fprintf(stderr, "[bwd stats] trips %llu shaded %llu finished %llu sweep_iterations %llu sweep_steps %llu flushes %llu entries %llu duplicate_cells %llu\n",
-                h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
-    }
-    return rc;
-#else
-    return render_common(s, p, material, nullptr, d_image, d_material, 1, 0, stream);
-#endif
+    RenderCall c; c.material = material; c.image = image; c.stream = stream;
+    return render_common(s, p, c);
 }
 
 extern "C" int zdr_render_forward_materials(zdr_scene *s, const zdr_render_params *p, const float *materials, const int32_t *dims, uint32_t nmat,
                                             float *image, void *stream) {
-    if (!image || !dims) return fail(ZDR_E_INVALID, "null argument");
-    if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
-    return render_common(s, p, materials, image, nullptr, nullptr, 0, 0, stream, dims, nmat);
+    if (int rc = check_table_args(image != nullptr, dims, nmat)) return rc;
+    RenderCall c; c.material = materials; c.dims = dims; c.nmat = nmat; c.image = image; c.stream = stream;
+    return render_common(s, p, c);
+}
+
+// Every zdr_render_backward* entry point.  table: a zdr_render_backward_materials* call (dims, nmat), else one material.  d_env, d_emission:
+// the optional target of the *_env / *_emission calls; NULL, or the collocated integrator (which has no environment term and reads no
+// emission), makes the call its plain sibling.
+static int render_backward_call(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *materials, bool table, const int32_t *dims,
+                                uint32_t nmat, float *d_materials, float *d_env, float *d_emission, void *stream) {
+    if (d_env && s && s->ds.env_count == 0) return fail(ZDR_E_INVALID, "d_env given, but the scene has no environment map");
+    if (p && p->integrator == ZDR_COLLOCATED) d_env = d_emission = nullptr;
+    if (table) { if (int rc = check_table_args(d_image && d_materials, dims, nmat)) return rc; }
+    else if (!d_image || !d_materials) return fail(ZDR_E_INVALID, "null gradient buffer");
+    RenderCall c; c.material = materials; c.backward = true; c.d_image = d_image; c.d_material = d_materials; c.d_env = d_env; c.d_emission = d_emission; c.stream = stream;
+    if (table) { c.dims = dims; c.nmat = nmat; }
+#ifdef ZDR_MEASURE_STATS   // measurement build (tools/bwd_stats.sh): the path backward kernel counts its trips, sweep iterations and flushes
+    if (!table && !d_env && !d_emission) {   // zdr_render_backward, and the *_env / *_emission calls that behave exactly like it
+        if (s) { (void)hipSetDevice(s->device); (void)hipMemsetAsync(s->d_counters, 0, 8 * sizeof(unsigned long long), (hipStream_t)stream); }
+        int rc = render_common(s, p, c);
+        if (!rc) {
+            unsigned long long h[8];
+            (void)hipMemcpyAsync(h, s->d_counters, sizeof h, hipMemcpyDeviceToHost, (hipStream_t)stream); (void)hipStreamSynchronize((hipStream_t)stream);
+            fprintf(stderr, "[bwd stats] trips %llu shaded %llu finished %llu sweep_iterations %llu sweep_steps %llu flushes %llu entries %llu duplicate_cells %llu\n",
+                    h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
+        }
+        return rc;
+    }
+#endif
+    return render_common(s, p, c);
+}
+
+extern "C" int zdr_render_backward(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *material,
+                                   float *d_material, void *stream) {
+    return render_backward_call(s, p, d_image, material, false, nullptr, 0, d_material, nullptr, nullptr, stream);
 }
 
 extern "C" int zdr_render_backward_materials(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *materials,
                                              const int32_t *dims, uint32_t nmat, float *d_materials, void *stream) {
-    if (!d_image || !d_materials || !dims) return fail(ZDR_E_INVALID, "null argument");
-    if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
-    return render_common(s, p, materials, nullptr, d_image, d_materials, 1, 0, stream, dims, nmat);
+    return render_backward_call(s, p, d_image, materials, true, dims, nmat, d_materials, nullptr, nullptr, stream);
 }
 
 extern "C" int zdr_render_backward_env(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *material,
                                        float *d_material, float *d_env, void *stream) {
-    if (d_env && s && s->ds.env_count == 0) return fail(ZDR_E_INVALID, "d_env given, but the scene has no environment map");
-    if (!d_env || (p && p->integrator == ZDR_COLLOCATED)) return zdr_render_backward(s, p, d_image, material, d_material, stream);   // (collocated: no environment term)
-    if (!d_image || !d_material) return fail(ZDR_E_INVALID, "null gradient buffer");
-    return render_common(s, p, material, nullptr, d_image, d_material, 1, 0, stream, nullptr, 0, d_env);
+    return render_backward_call(s, p, d_image, material, false, nullptr, 0, d_material, d_env, nullptr, stream);
 }
 
 extern "C" int zdr_render_backward_materials_env(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *materials,
                                                  const int32_t *dims, uint32_t nmat, float *d_materials, float *d_env, void *stream) {
-    if (d_env && s && s->ds.env_count == 0) return fail(ZDR_E_INVALID, "d_env given, but the scene has no environment map");
-    if (!d_env || (p && p->integrator == ZDR_COLLOCATED)) return zdr_render_backward_materials(s, p, d_image, materials, dims, nmat, d_materials, stream);
-    if (!d_image || !d_materials || !dims) return fail(ZDR_E_INVALID, "null argument");
-    if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
-    return render_common(s, p, materials, nullptr, d_image, d_materials, 1, 0, stream, dims, nmat, d_env);
+    return render_backward_call(s, p, d_image, materials, true, dims, nmat, d_materials, d_env, nullptr, stream);
 }
 
 extern "C" int zdr_render_backward_emission(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *material,
                                             float *d_material, float *d_emission, void *stream) {
-    if (!d_emission || (p && p->integrator == ZDR_COLLOCATED)) return zdr_render_backward(s, p, d_image, material, d_material, stream);   // (collocated reads no emission)
-    if (!d_image || !d_material) return fail(ZDR_E_INVALID, "null gradient buffer");
-    return render_common(s, p, material, nullptr, d_image, d_material, 1, 0, stream, nullptr, 0, nullptr, d_emission);
+    return render_backward_call(s, p, d_image, material, false, nullptr, 0, d_material, nullptr, d_emission, stream);
 }
 
 extern "C" int zdr_render_backward_materials_emission(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *materials,
                                                       const int32_t *dims, uint32_t nmat, float *d_materials, float *d_emission, void *stream) {
-    if (!d_emission || (p && p->integrator == ZDR_COLLOCATED)) return zdr_render_backward_materials(s, p, d_image, materials, dims, nmat, d_materials, stream);
-    if (!d_image || !d_materials || !dims) return fail(ZDR_E_INVALID, "null argument");
-    if (nmat < 1 || nmat > ZDR_MAX_MATERIALS) return fail(ZDR_E_INVALID, "nmat is " + std::to_string(nmat) + ", must lie in [1, " + std::to_string(ZDR_MAX_MATERIALS) + "]");
-    return render_common(s, p, materials, nullptr, d_image, d_materials, 1, 0, stream, dims, nmat, nullptr, d_emission);
+    return render_backward_call(s, p, d_image, materials, true, dims, nmat, d_materials, nullptr, d_emission, stream);
 }
 
 extern "C" int zdr_render_stats(zdr_scene *s, const zdr_render_params *p, const float *material, uint64_t counters[8], void *stream) {
@@ -1324,7 +1346,8 @@ extern "C" int zdr_render_stats(zdr_scene *s, const zdr_render_params *p, const 
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(s->d_counters, 0, 8 * sizeof(unsigned long long), st));
-    int rc = render_common(s, p, material, nullptr, nullptr, nullptr, 0, 1, stream); if (rc) return rc;
+    RenderCall c; c.material = material; c.stats = true; c.stream = stream;
+    int rc = render_common(s, p, c); if (rc) return rc;
     unsigned long long h[8];
     HIPCHK(hipMemcpyAsync(h, s->d_counters, sizeof h, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

@@ -323,12 +323,7 @@ class Scene:
         (H_k, W_k, 4) tensors, or their packed texels with ``dims``.  ``slots``: the slot table to use (default: ``material_slots``,
         or the default mapping)."""
         packed, d, _ = self._material_call(materials, dims, slots)
-        if out is None:
-            image = torch.zeros((res[1], res[0], 4), dtype=torch.float32, device=self.device)
-        else:
-            image = out
-            if image.shape != (res[1], res[0], 4) or image.dtype != torch.float32 or image.device != self.device or not image.is_contiguous():
-                raise ValueError(f"out must be a contiguous float32 ({res[1]}, {res[0]}, 4) tensor on {self.device}")
+        image = self._image_out(out, res)
         p = self._params(res, spp, seed, (1, 1), rect, samples, tile_shard=tile_shard)
         N.check(N.lib().zdr_render_forward_materials(self._handle, C.byref(p), packed.data_ptr(), d.ctypes.data, d.shape[0], image.data_ptr(), self._stream()))
         return image
@@ -344,17 +339,7 @@ class Scene:
             raise ValueError(f"d_materials must be contiguous float32 on {self.device}, shaped like the materials")
         g = grad_output.reshape(res[1], res[0], 4).to(device=self.device, dtype=torch.float32).contiguous()
         p = self._params(res, spp, seed + 1, (1, 1), rect, samples, camera, tile_shard=tile_shard)
-        if d_emission is not None:
-            self._check_d_emission(d_emission, d_env)
-            N.check(N.lib().zdr_render_backward_materials_emission(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
-                                                                   dpacked.data_ptr(), d_emission.data_ptr(), self._stream()))
-        elif d_env is None:
-            N.check(N.lib().zdr_render_backward_materials(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
-                                                          dpacked.data_ptr(), self._stream()))
-        else:
-            self._check_d_env(d_env)
-            N.check(N.lib().zdr_render_backward_materials_env(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
-                                                              dpacked.data_ptr(), d_env.data_ptr(), self._stream()))
+        self._native_backward(p, g, packed, d, dpacked, d_env, d_emission)
         if listed and len(d_materials) > 1:
             off = 0
             for t in d_materials:
@@ -386,6 +371,40 @@ class Scene:
         p.prb_mode = N.PRB_MODES[self.prb_mode]
         return p
 
+    def _image_out(self, out, res):
+        """The image a forward call writes: ``out`` once checked, or a fresh one — zero-filled even when the call covers every pixel: a
+        dropped work item must never surface as uninitialised memory."""
+        if out is None:
+            return torch.zeros((res[1], res[0], 4), dtype=torch.float32, device=self.device)
+        if out.shape != (res[1], res[0], 4) or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 ({res[1]}, {res[0]}, 4) tensor on {self.device}")
+        return out
+
+    def _native_backward(self, p, g, material, dims, d_material, d_env, d_emission):
+        """The native backward call of render_backward (``dims`` None) and render_backward_materials (``dims``: the int32 array of
+        _material_call), with the one further target that is given."""
+        lib = N.lib()
+        target, d_target = None, None
+        if d_emission is not None:
+            self._check_d_emission(d_emission, d_env)
+            target, d_target = "emission", d_emission
+        elif d_env is not None:
+            self._check_d_env(d_env)
+            target, d_target = "env", d_env
+        fn = {(False, None): lib.zdr_render_backward,
+              (False, "env"): lib.zdr_render_backward_env,
+              (False, "emission"): lib.zdr_render_backward_emission,
+              (True, None): lib.zdr_render_backward_materials,
+              (True, "env"): lib.zdr_render_backward_materials_env,
+              (True, "emission"): lib.zdr_render_backward_materials_emission}[dims is not None, target]
+        args = [self._handle, C.byref(p), g.data_ptr(), material.data_ptr()]
+        if dims is not None:
+            args += [dims.ctypes.data, dims.shape[0]]
+        args.append(d_material.data_ptr())
+        if d_target is not None:
+            args.append(d_target.data_ptr())
+        N.check(fn(*args, self._stream()))
+
     def _check_material(self, material):
         assert material.ndim == 3 and material.shape[2] == 4           # render.py:160,177
         if material.device != self.device or material.dtype != torch.float32:
@@ -397,12 +416,7 @@ class Scene:
         (index, count): the 8x8 tiles of the rectangle numbered index, index + count, ... (include/zdr.h)."""
         self._check_material(material)
         material = material.detach().contiguous()
-        if out is None:   # zero-filled even when the call covers every pixel: a dropped work item must never surface as uninitialised memory
-            image = torch.zeros((res[1], res[0], 4), dtype=torch.float32, device=self.device)
-        else:
-            image = out
-            if image.shape != (res[1], res[0], 4) or image.dtype != torch.float32 or image.device != self.device or not image.is_contiguous():
-                raise ValueError(f"out must be a contiguous float32 ({res[1]}, {res[0]}, 4) tensor on {self.device}")
+        image = self._image_out(out, res)
         p = self._params(res, spp, seed, material.shape[0:2], rect, samples, integrator=kernel, tile_shard=tile_shard)
         N.check(N.lib().zdr_render_forward(self._handle, C.byref(p), material.data_ptr(), image.data_ptr(), self._stream()))
         return image
@@ -420,16 +434,7 @@ class Scene:
         if d_material.device != self.device or d_material.dtype != torch.float32:
             raise ValueError(f"d_material must be a float32 tensor on {self.device}")
         p = self._params(res, spp, seed + 1, material.shape[0:2], rect, samples, camera, tile_shard=tile_shard)
-        if d_emission is not None:
-            self._check_d_emission(d_emission, d_env)
-            N.check(N.lib().zdr_render_backward_emission(self._handle, C.byref(p), g.data_ptr(), material.data_ptr(), d_material.data_ptr(),
-                                                         d_emission.data_ptr(), self._stream()))
-        elif d_env is None:
-            N.check(N.lib().zdr_render_backward(self._handle, C.byref(p), g.data_ptr(), material.data_ptr(), d_material.data_ptr(), self._stream()))
-        else:
-            self._check_d_env(d_env)
-            N.check(N.lib().zdr_render_backward_env(self._handle, C.byref(p), g.data_ptr(), material.data_ptr(), d_material.data_ptr(),
-                                                    d_env.data_ptr(), self._stream()))
+        self._native_backward(p, g, material, None, d_material, d_env, d_emission)
         return d_material, None, None, None, None
 
     def render_stats(self, material, res, spp, seed=0, *, rect=None, samples=None, tile_shard=None) -> dict:
@@ -442,10 +447,11 @@ class Scene:
         return dict(zip(N.COUNTER_NAMES, list(cnt)))
 
     class RenderOperator(torch.autograd.Function):     # render.py:201-223
-        """render() of one material; with a prepared environment map as a sixth input also differentiable w.r.t. the map, with an
-        (ninst, 3) emission tensor as a seventh w.r.t. the lights' emissions (one of the two at most)."""
+        """render() of one material (``dims`` None), or of the packed texels of several (``dims``, ``slots``; it returns their packed
+        gradient, and torch.cat's own backward hands each material its part).  With a prepared environment map ``env`` also
+        differentiable w.r.t. the map, with an (ninst, 3) tensor ``emissions`` w.r.t. the lights' emissions (one of the two at most)."""
         @staticmethod
-        def forward(ctx, material, self, res, spp, seed, env=None, emissions=None):
+        def forward(ctx, material, self, res, spp, seed, env, emissions, dims, slots):
             if env is not None:                            # the map this forward renders with: uploaded now, saved for the backward
                 env = env.detach().clone()
                 self.set_envmap_texture(env)
@@ -453,13 +459,14 @@ class Scene:
                 self.set_emission_values(emissions.detach().clone())
             ctx.save_for_backward(material)
             ctx.env = env                                  # (a detached copy: kept as it is, not as a saved input)
-            ctx.with_env = env is not None
             ctx.with_emissions = emissions is not None
             ctx.scene = weakref.ref(self)
-            ctx.args = (res, spp, seed)
+            ctx.args = (res, spp, seed, dims, slots)
             ctx.camera = self.camera.copy()
             ctx.emissions = self.emissions
-            return self.render_forward(material.detach(), res, spp, seed)
+            if dims is None:
+                return self.render_forward(material.detach(), res, spp, seed)
+            return self.render_forward_materials(material, res, spp, seed, dims=dims, slots=slots)
 
         @staticmethod
         def backward(ctx, grad_output):
@@ -469,62 +476,21 @@ class Scene:
             if scene.emissions is not ctx.emissions:
                 scene.update_lights(ctx.emissions)
             material, = ctx.saved_tensors
-            env = ctx.env
             mat_grad = torch.zeros(material.size(), dtype=material.dtype, device=material.device)
-            res, spp, seed = ctx.args
+            res, spp, seed, dims, slots = ctx.args
+            d_env = d_emission = None
             if ctx.with_emissions:                         # ctx.emissions holds the forward's copy: applied again, whatever happened in between
                 scene._apply_emission_values(ctx.emissions.values)
                 d_emission = torch.zeros_like(ctx.emissions.values)
-                scene.render_backward(grad_output, mat_grad, material.detach(), res, spp, seed, camera=ctx.camera, d_emission=d_emission)
-                return mat_grad, None, None, None, None, None, d_emission
-            if not ctx.with_env:
-                return scene.render_backward(grad_output, mat_grad, material.detach(), res, spp, seed, camera=ctx.camera)
-            scene.set_envmap_texture(env)                  # the material gradient depends on the map's values too
-            d_env = torch.zeros_like(env)
-            scene.render_backward(grad_output, mat_grad, material.detach(), res, spp, seed, camera=ctx.camera, d_env=d_env)
-            return mat_grad, None, None, None, None, d_env
-
-    class MaterialsOperator(torch.autograd.Function):
-        """render() of several materials: takes their packed texels, returns their packed gradient (torch.cat's own backward
-        hands each material its part)."""
-        @staticmethod
-        def forward(ctx, packed, self, dims, slots, res, spp, seed, env=None, emissions=None):
-            if env is not None:                            # as RenderOperator
-                env = env.detach().clone()
-                self.set_envmap_texture(env)
-            if emissions is not None:
-                self.set_emission_values(emissions.detach().clone())
-            ctx.with_emissions = emissions is not None
-            ctx.save_for_backward(packed)
-            ctx.env = env
-            ctx.with_env = env is not None
-            ctx.scene = weakref.ref(self)
-            ctx.args = (dims, slots, res, spp, seed)
-            ctx.camera = self.camera.copy()
-            ctx.emissions = self.emissions
-            return self.render_forward_materials(packed, res, spp, seed, dims=dims, slots=slots)
-
-        @staticmethod
-        def backward(ctx, grad_output):
-            scene = ctx.scene()
-            if scene.emissions is not ctx.emissions:        # as RenderOperator: lights left at the snapshot
-                scene.update_lights(ctx.emissions)
-            packed, = ctx.saved_tensors
-            env = ctx.env
-            dims, slots, res, spp, seed = ctx.args
-            d = torch.zeros(packed.size(), dtype=packed.dtype, device=packed.device)
-            d_env = None
-            if ctx.with_emissions:                          # as RenderOperator
-                scene._apply_emission_values(ctx.emissions.values)
-                d_emission = torch.zeros_like(ctx.emissions.values)
-                scene.render_backward_materials(grad_output, d, packed.detach(), res, spp, seed, dims=dims, camera=ctx.camera, slots=slots, d_emission=d_emission)
-                return d, None, None, None, None, None, None, None, d_emission
-            if ctx.with_env:
-                scene.set_envmap_texture(env)
-                d_env = torch.zeros_like(env)
-            # slots = the forward's table: uploaded again if material_slots changed in between
-            scene.render_backward_materials(grad_output, d, packed.detach(), res, spp, seed, dims=dims, camera=ctx.camera, slots=slots, d_env=d_env)
-            return (d, None, None, None, None, None, None) + ((d_env,) if ctx.with_env else ())
+            elif ctx.env is not None:
+                scene.set_envmap_texture(ctx.env)          # the material gradient depends on the map's values too
+                d_env = torch.zeros_like(ctx.env)
+            if dims is None:
+                scene.render_backward(grad_output, mat_grad, material.detach(), res, spp, seed, camera=ctx.camera, d_env=d_env, d_emission=d_emission)
+            else:                                          # slots = the forward's table: uploaded again if material_slots changed in between
+                scene.render_backward_materials(grad_output, mat_grad, material.detach(), res, spp, seed, dims=dims, camera=ctx.camera, slots=slots,
+                                                d_env=d_env, d_emission=d_emission)
+            return mat_grad, None, None, None, None, d_env, d_emission, None, None
 
     def render(self, material, *, res, spp, seed=0, envmap=None, emissions=None):
         """Renders the scene; differentiable w.r.t. ``material`` ((Ht, Wt, 4) float32 on the GPU).
@@ -551,11 +517,7 @@ class Scene:
             check_emissions(emissions, self.inst_count, self.device, envmap)
         env = None if envmap is None else self._prepare_envmap(envmap)
         if not isinstance(material, (list, tuple)) and self._material_slots is None:
-            if emissions is not None:
-                return Scene.RenderOperator.apply(material, self, res, spp, seed, None, emissions)
-            if env is not None:
-                return Scene.RenderOperator.apply(material, self, res, spp, seed, env)
-            return Scene.RenderOperator.apply(material, self, res, spp, seed)
+            return Scene.RenderOperator.apply(material, self, res, spp, seed, env, emissions, None, None)
         mats = list(material) if isinstance(material, (list, tuple)) else [material]
         if env is not None and len(mats) > N.MAX_MATERIALS - 1:
             raise ValueError(f"{len(mats)} materials given with envmap=: at most {N.MAX_MATERIALS - 1} (the map takes the last entry of the material table)")
@@ -564,11 +526,7 @@ class Scene:
         slots = resolve_material_slots(self._material_slots, self.emissions, len(mats))
         dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
         packed = mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
-        if emissions is not None:
-            return Scene.MaterialsOperator.apply(packed, self, dims, slots, res, spp, seed, None, emissions)
-        if env is not None:
-            return Scene.MaterialsOperator.apply(packed, self, dims, slots, res, spp, seed, env)
-        return Scene.MaterialsOperator.apply(packed, self, dims, slots, res, spp, seed)
+        return Scene.RenderOperator.apply(packed, self, res, spp, seed, env, emissions, dims, slots)
 
     def render_duvdxy(self, material, *, res, spp, seed=0):
         """Gradient of the texture coordinates w.r.t. screen-space coordinates: a (height, width, 4) tensor
