@@ -67,7 +67,8 @@ ZD bool tri_test(float4 N, float4 U, float4 V, f3 o, f3 d, float tmin, float tma
 
 ZD void hit_barycentrics(const DScene &S, Hit &h, f3 o, f3 d) {
     if (h.slot < 0) return;
-    float4 U = S.isect[3 * (size_t)h.slot + 1], V = S.isect[3 * (size_t)h.slot + 2];
+    const uint32_t r = 48u * (uint32_t)h.slot;
+    float4 U = load_at<float4>(S.isect, r, 16), V = load_at<float4>(S.isect, r, 32);
     f3 p = o + d * h.t;
     h.u = U.x * p.x + U.y * p.y + U.z * p.z + U.w;
     h.v = V.x * p.x + V.y * p.y + V.z * p.z + V.w;
@@ -148,11 +149,12 @@ ZD void brute_resolve(const DScene &S, Hit &h, int prim, f3 o, f3 d) {
     const bool quad = prim < S.nquads2;
     int slot = quad ? 2 * prim : prim + S.nquads2;
     const f3 p = o + d * h.t;
-    float4 U = S.isect[3 * (size_t)slot + 1], V = S.isect[3 * (size_t)slot + 2];
+    const uint32_t r = 48u * (uint32_t)slot;                   // (load_at, scene.h)
+    float4 U = load_at<float4>(S.isect, r, 16), V = load_at<float4>(S.isect, r, 32);
     float u = U.x * p.x + U.y * p.y + U.z * p.z + U.w, v = V.x * p.x + V.y * p.y + V.z * p.z + V.w;
     if (quad && 1.0f - (u + v) < 0.0f) {                       // beyond the diagonal: the quad's second triangle
         slot += 1;
-        U = S.isect[3 * (size_t)slot + 1]; V = S.isect[3 * (size_t)slot + 2];
+        U = load_at<float4>(S.isect, r + 48u, 16); V = load_at<float4>(S.isect, r + 48u, 32);   // (an offset of its own: an address shared with the first triangle's block would be carried over as a 64-bit pair)
         u = U.x * p.x + U.y * p.y + U.z * p.z + U.w; v = V.x * p.x + V.y * p.y + V.z * p.z + V.w;
     }
     h.slot = slot; h.u = u; h.v = v;

@@ -53,7 +53,7 @@ ZD void env_term_clear(EnvTerm &e) { e.w = mk3(0.0f); e.uv.x = 0.0f; e.uv.y = 0.
 // the light's row (emit_add, zdr_kernels.hip).  light = index in the light list, -1: no such term.
 struct EmitTerm { f3 w; int light; };
 ZD void emit_term_clear(EmitTerm &e) { e.w = mk3(0.0f); e.light = -1; }
-ZD int emit_light_of(const DScene &S, int inst) { return __float_as_int(S.emission4[inst].w); }   // emission4[inst].w: bits of the instance's light index, -1 = not in the list (zdr_api.cpp)
+ZD int emit_light_of(const DScene &S, int inst) { return load_at<int32_t>(S.emission4, 16u * (uint32_t)inst, 12); }   // emission4[inst].w: bits of the instance's light index, -1 = not in the list (zdr_api.cpp)
 
 // ---------------------------------------------------------------------------- collocated
 // collocated.py:11-31 / 35-57: L = brdf(wo, wo) / t^2
@@ -71,11 +71,11 @@ ZD f3 collocated_sample(const DScene &S, const RenderCfg &R, const KernelIO &io,
     if (dot(-d, it.ng) < 1e-4f || dot(-d, it.ns) < 1e-4f) return mk3(0.0f);
     float4 m;
     if constexpr (MT) {
-        const int slot = io.mt.inst_slot[it.inst];
+        const int slot = load_at<int32_t>(io.mt.inst_slot, 4u * (uint32_t)it.inst);
         if (slot < 0) return mk3(0.0f);
-        m = read_bsdf_in(io.material, io.mt.m[slot], it.uv);
+        m = read_bsdf_in(io.material, io.mt.m[slot], it.uv, io.wide_offsets != 0);
         gmat = slot;
-    } else m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w);
+    } else m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w, io.wide_offsets != 0);
     COUNT(C_SHADED);
     Onb onb = make_onb(it.ns);
     f3 wo = to_local(onb, -d);
@@ -142,16 +142,16 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
     if (dot(-d, it.ng) < 1e-4f || dot(-d, it.ns) < 1e-4f) return mk3(0.0f);
     float4 m;
     if constexpr (MT) {
-        const int slot = io.mt.inst_slot[it.inst];
+        const int slot = load_at<int32_t>(io.mt.inst_slot, 4u * (uint32_t)it.inst);
         if constexpr (LG) {
             if (slot < 0) { l_cam->w = mk3(1.0f); l_cam->light = emit_light_of(S, it.inst); }
         }
-        if (slot < 0) return xyz(S.emission4[it.inst]);
-        m = read_bsdf_in(io.material, io.mt.m[slot], it.uv);
+        if (slot < 0) return xyz(load_at<float4>(S.emission4, 16u * (uint32_t)it.inst));
+        m = read_bsdf_in(io.material, io.mt.m[slot], it.uv, io.wide_offsets != 0);
         gmat = slot;
     } else {
-        if (it.inst > 0) return xyz(S.emission4[it.inst]);                        // direct.py:30-32
-        m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w);
+        if (it.inst > 0) return xyz(load_at<float4>(S.emission4, 16u * (uint32_t)it.inst));                        // direct.py:30-32
+        m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w, io.wide_offsets != 0);
     }
     f3 diffuse = mk3(m.x, m.y, m.z); float roughness = m.w;
     COUNT(C_SHADED);
@@ -204,7 +204,7 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
             COUNT(C_HITS);
             Interaction it2 = surface_interact(S, h2);
             if (!(dot(-wi, it2.ng) < 1e-4f || dot(-wi, it2.ns) < 1e-4f)) {
-                em = xyz(S.emission4[it2.inst]);
+                em = xyz(load_at<float4>(S.emission4, 16u * (uint32_t)it2.inst));
                 if (LG) hit_inst = it2.inst;
                 pdf_light = sample_light_pdf<ENV>(S, it.p, it2.inst, h2.slot, it2.p);   // origin = it.p (direct.py:66)
                 lit = true;
@@ -293,11 +293,11 @@ ZD bool path_arrive(const DScene &S, PathState &ps, const Hit &h, Interaction &i
         return true;
     }
     COUNT(C_HITS);
-    it = surface_interact(S, h);
+    it = surface_interact<!MT>(S, h);
     if (dot(-ps.d, it.ng) < 1e-4f || dot(-ps.d, it.ns) < 1e-4f) return true;      // prb.py:35-36
-    f3 em = xyz(S.emission4[it.inst]);
+    f3 em = xyz(load_at<float4>(S.emission4, 16u * (uint32_t)it.inst));
     if (em.x > 0.0f || em.y > 0.0f || em.z > 0.0f) {                              // prb.py:39-44
-        float pdf_light = sample_light_pdf<ENV>(S, ps.o, it.inst, h.slot, it.p);
+        float pdf_light = sample_light_pdf<ENV, !MT>(S, ps.o, it.inst, h.slot, it.p);
         float mis = balanced_heuristic(ps.pdf_bsdf, pdf_light);
         if (emit_hit) { emit_hit->w = ps.beta * mis; emit_hit->light = emit_light_of(S, it.inst); }
         ps.L = ps.L + (ps.beta * mis) * em;
@@ -307,7 +307,7 @@ ZD bool path_arrive(const DScene &S, PathState &ps, const Hit &h, Interaction &i
         return true;
     }
     if constexpr (MT) {
-        it.mat = inst_slot[it.inst];
+        it.mat = load_at<int32_t>(inst_slot, 4u * (uint32_t)it.inst);
         return it.mat < 0;
     }
     if (it.inst > 0) return true;                                                 // prb.py:45-46
@@ -335,8 +335,8 @@ ZD ShadeCtx shade_ctx(const DScene &S, const RenderCfg &R, const SamplerCfg &C, 
                       f2 *env_uv = nullptr, int *mesh_light = nullptr) {
     ShadeCtx x;
     float4 m;
-    if constexpr (MT) m = read_bsdf_in(io.material, io.mt.m[it.mat], it.uv);
-    else m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w);
+    if constexpr (MT) m = read_bsdf_in(io.material, io.mt.m[it.mat], it.uv, io.wide_offsets != 0);
+    else m = read_bsdf(io.material, it.uv, R.tex_h, R.tex_w, io.wide_offsets != 0);
     x.diffuse = mk3(m.x, m.y, m.z); x.roughness = m.w;
     COUNT(C_SHADED);
     if (BWD) {
@@ -599,8 +599,8 @@ ZD void primary_refill(const DScene &S, const RenderCfg &R, const SamplerCfg &C,
         if constexpr (EG) on_miss(miss);
         const unsigned long long m = __ballot(park);
         if (park) {
-            float4 *e = q.base + (size_t)((q.tail + lane_rank(m)) % ZDR_QUEUE_ENTRIES) * 2;
-            e[0] = e0; e[1] = e1;
+            const uint32_t e = 32u * ((q.tail + lane_rank(m)) % ZDR_QUEUE_ENTRIES);   // (store_at, scene.h: q.base is wave-uniform)
+            store_at(q.base, e, 0, e0); store_at(q.base, e, 16, e1);
         }
         q.tail += (uint32_t)__popcll(m);
     }
@@ -621,11 +621,11 @@ ZD int primary_pop(const DScene &S, const SamplerCfg &C, bool idle, const uint32
     int pix = -1;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (take) {
-        const float4 *e = q.base + (size_t)((q.head + rank) % ZDR_QUEUE_ENTRIES) * 2;
-        float4 a = e[0], b = e[1];
+        const uint32_t e = 32u * ((q.head + rank) % ZDR_QUEUE_ENTRIES);
+        float4 a = load_at<float4>(q.base, e, 0), b = load_at<float4>(q.base, e, 16);
         Hit h; h.slot = __float_as_int(b.y); h.u = a.w; h.v = b.x; h.t = 0.0f;
-        it = surface_interact(S, h);
-        if constexpr (MT) it.mat = inst_slot[it.inst];
+        it = surface_interact<!MT>(S, h);
+        if constexpr (MT) it.mat = load_at<int32_t>(inst_slot, 4u * (uint32_t)it.inst);
         ps.d = mk3(a.x, a.y, a.z); ps.o = mk3(0.0f);
         ps.beta = mk3(1.0f); ps.L = mk3(0.0f); ps.pdf_bsdf = 1e30f; ps.depth = 0;
         const uint32_t key = __float_as_uint(b.w);

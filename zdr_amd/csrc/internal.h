@@ -64,6 +64,7 @@ struct KernelIO {
     unsigned long long *counters;     // stats variant: 8 counters
     const unsigned long long *tile_masks;   // brute-force accel: per 8x8 tile, the triangle pairs its camera rays can hit (k_tile_masks); null = all
     int32_t tile_masks_valid;               // the masks in the buffer already belong to this camera and shard: skip k_tile_masks
+    int32_t wide_offsets;                   // the material (or the packed materials) or the image does not end within 4 GiB, or ZDR_WIDE_OFFSETS=1: read_bsdf, read_bsdf_in and the cotangent load of a popped path use 64-bit addresses instead of 32-bit byte offsets (scene.h, load_at).  (In the padding behind tile_masks_valid: the kernel arguments keep their offsets, and the kernels their register allocation.)
     unsigned int *work_counters;      // path integrator: 8 item counters, one per XCD, zeroed before the launch (fetch_item)
     float4 *ring;                     // path integrator: one FIFO of parked camera-ray vertices per persistent workgroup (integrators.h)
     MaterialTable mt;                 // material-table calls only (zdr_render_*_materials): `material` is then the packed buffer, `cells` all materials' cells

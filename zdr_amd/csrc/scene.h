@@ -83,9 +83,39 @@ struct Interaction {                       // interaction.py:6
 
 ZD f3 xyz(float4 a) { return mk3(a.x, a.y, a.z); }
 
+// Record fetch: the wave-uniform base stays in its SGPR pair, the record's byte offset is ONE 32-bit VGPR and the field within the
+// record rides in the instruction's immediate offset (global_load v, v_off, s[base:base+1] offset:imm).  `base + index` with a
+// 64-bit index costs a four-pass v_mad_u64_u32 (or a sign extension and a 64-bit shift-add) PER LOAD instead: seven of them for the
+// seven float4 of a shade record.  The offset wraps at 4 GiB, so every buffer read this way is bounded by the host: the scene's own
+// records at creation (zdr_api.cpp, ZDR_MAX_TRIS), the caller's buffers per launch (KernelIO::wide_offsets).
+template <class T>
+ZD T load_at(const void *base, uint32_t byte_off, int imm = 0) { return *(const T *)((const char *)base + (size_t)byte_off + imm); }
+template <class T>
+ZD void store_at(void *base, uint32_t byte_off, int imm, T v) { *(T *)((char *)base + (size_t)byte_off + imm) = v; }
+// The 64-bit form of a lookup that has both (the branch is wave-uniform).  The loads are volatile so that they stay in their branch:
+// the optimiser otherwise sinks the loads of both branches into one block behind the branch, and the narrow form then has to widen its
+// offsets to the 64-bit addresses that block takes.
+ZD float4 load_wide(const float4 *base, long long index) {
+    typedef float v4 __attribute__((ext_vector_type(4)));
+    const v4 v = *(const volatile v4 *)(base + index);
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+#define ZDR_MAX_TRIS (1u << 25)      // 128-byte shade records within 4 GiB (the 48-byte isect records and the 80-byte light entries with them)
+
+// NARROW = false keeps the 64-bit form (one address pair for the record, then immediate offsets): the material-table path kernels ask for
+// it.  Their backward kernel sits at its 128 VGPRs, and with the offset form here or in sample_light_pdf the register allocator spills four
+// more dwords in its loop (1,392 instead of 1,376 bytes of scratch; tests/test_kernel_resources.py says what that costs).
+template <bool NARROW = true>
 ZD Interaction surface_interact(const DScene &S, const Hit &h) {   // interaction.py:9-30
-    const float4 *r = S.shade + 8 * (size_t)h.slot;
-    float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4], r5 = r[5], r6 = r[6];   // seven of the record's eight float4
+    float4 r0, r1, r2, r3, r4, r5, r6;                             // seven of the record's eight float4
+    if constexpr (NARROW) {
+        const uint32_t r = 128u * (uint32_t)h.slot;
+        r0 = load_at<float4>(S.shade, r, 0); r1 = load_at<float4>(S.shade, r, 16); r2 = load_at<float4>(S.shade, r, 32); r3 = load_at<float4>(S.shade, r, 48);
+        r4 = load_at<float4>(S.shade, r, 64); r5 = load_at<float4>(S.shade, r, 80); r6 = load_at<float4>(S.shade, r, 96);
+    } else {
+        const float4 *r = S.shade + 8 * (size_t)h.slot;
+        r0 = r[0]; r1 = r[1]; r2 = r[2]; r3 = r[3]; r4 = r[4]; r5 = r[5]; r6 = r[6];
+    }
     float w0 = 1.0f - h.u - h.v, w1 = h.u, w2 = h.v;               // Hit::interpolate
     Interaction it;
     it.p = xyz(r0) * w0 + xyz(r1) * w1 + xyz(r2) * w2;
@@ -111,9 +141,16 @@ ZD TexFoot tex_footprint(f2 uv, int tex_h, int tex_w) {
     return f;
 }
 
-ZD float4 read_bsdf(const float4 *__restrict__ mat, f2 uv, int tex_h, int tex_w) {
+// wide (KernelIO::wide_offsets, wave-uniform): the material does not end within 4 GiB, so the texels are addressed with 64-bit
+// element indices; otherwise with 32-bit byte offsets from the scalar base (load_at).  Same texels, same weights.
+ZD float4 read_bsdf(const float4 *__restrict__ mat, f2 uv, int tex_h, int tex_w, bool wide) {
     TexFoot f = tex_footprint(uv, tex_h, tex_w);
-    float4 c00 = mat[f.i00], c01 = mat[f.i01], c10 = mat[f.i10], c11 = mat[f.i11];
+    float4 c00, c01, c10, c11;
+    if (wide) { c00 = load_wide(mat, f.i00); c01 = load_wide(mat, f.i01); c10 = load_wide(mat, f.i10); c11 = load_wide(mat, f.i11); }
+    else {
+        c00 = load_at<float4>(mat, 16u * (uint32_t)f.i00); c01 = load_at<float4>(mat, 16u * (uint32_t)f.i01);
+        c10 = load_at<float4>(mat, 16u * (uint32_t)f.i10); c11 = load_at<float4>(mat, 16u * (uint32_t)f.i11);
+    }
     float4 r;
     r.x = lerpf(lerpf(c00.x, c01.x, f.oy), lerpf(c10.x, c11.x, f.oy), f.ox);
     r.y = lerpf(lerpf(c00.y, c01.y, f.oy), lerpf(c10.y, c11.y, f.oy), f.ox);
@@ -127,7 +164,7 @@ ZD float4 read_bsdf(const float4 *__restrict__ mat, f2 uv, int tex_h, int tex_w)
 // the backend otherwise contracts px * 1 - ix into one FMA for the offsets (as it does not in read_bsdf of the forward
 // kernels), and the material-table image would differ from render_forward's in the last bit.
 template <class M>
-ZD float4 read_bsdf_in(const float4 *__restrict__ mats, const M &m, f2 uv) {
+ZD float4 read_bsdf_in(const float4 *__restrict__ mats, const M &m, f2 uv, bool wide) {
     float px = uv.x * (float)(m.w - 1), py = (1.0f - uv.y) * (float)(m.h - 1);
     asm volatile("" : "+v"(px), "+v"(py));
     int ix = (int)px, iy = (int)py;
@@ -136,8 +173,14 @@ ZD float4 read_bsdf_in(const float4 *__restrict__ mats, const M &m, f2 uv) {
     int x0 = clampi(ix, 0, m.w - 1), x1 = clampi(ix + 1, 0, m.w - 1);
     int y0 = clampi(iy, 0, m.h - 1), y1 = clampi(iy + 1, 0, m.h - 1);
     f.i00 = x0 + m.w * y0; f.i01 = x0 + m.w * y1; f.i10 = x1 + m.w * y0; f.i11 = x1 + m.w * y1;
-    const float4 *t = mats + m.texel;
-    float4 c00 = t[f.i00], c01 = t[f.i01], c10 = t[f.i10], c11 = t[f.i11];
+    float4 c00, c01, c10, c11;
+    if (wide) {
+        const float4 *t = mats + m.texel;
+        c00 = load_wide(t, f.i00); c01 = load_wide(t, f.i01); c10 = load_wide(t, f.i10); c11 = load_wide(t, f.i11);
+    } else {                             // the whole packed buffer within 4 GiB: byte offsets from its scalar base
+        c00 = load_at<float4>(mats, 16u * (uint32_t)(m.texel + f.i00)); c01 = load_at<float4>(mats, 16u * (uint32_t)(m.texel + f.i01));
+        c10 = load_at<float4>(mats, 16u * (uint32_t)(m.texel + f.i10)); c11 = load_at<float4>(mats, 16u * (uint32_t)(m.texel + f.i11));
+    }
     float4 r;
     r.x = lerpf(lerpf(c00.x, c01.x, f.oy), lerpf(c10.x, c11.x, f.oy), f.ox);
     r.y = lerpf(lerpf(c00.y, c01.y, f.oy), lerpf(c10.y, c11.y, f.oy), f.ox);
@@ -454,10 +497,14 @@ ZD LightSample sample_light(const DScene &S, f3 origin, float u_pick, NEXT1 next
     // light.py:33-48 walks light -> instance -> triangle range -> triangle -> emission; the flat table makes that one
     // lookup (none for a single light) + the entry
     int base = 0, T = S.light0_T;
-    if (S.light_count > 1) { base = S.light_range[2 * idx]; T = S.light_range[2 * idx + 1]; }
+    // (read here, as the scalar load it is: left alone the optimiser turns "T of the table or T of the scene" into a choice between two
+    // ADDRESSES, the kernel argument's among them, and reads the chosen one per lane with a flat load — once per shaded vertex)
+    asm volatile("" : "+s"(T));
+    if (S.light_count > 1) { const int2 bt = load_at<int2>(S.light_range, 8u * (uint32_t)idx); base = bt.x; T = bt.y; }
     int prim = clampi((int)(u_prim * (float)T), 0, T - 1);
-    const float4 *r = S.light_tris + 5 * (size_t)(base + prim);
-    float4 r0 = r[0], r1 = r[1], r2 = r[2], r6 = r[3], r4 = r[4];
+    const uint32_t r = 80u * (uint32_t)(base + prim);
+    float4 r0 = load_at<float4>(S.light_tris, r, 0), r1 = load_at<float4>(S.light_tris, r, 16), r2 = load_at<float4>(S.light_tris, r, 32),
+           r6 = load_at<float4>(S.light_tris, r, 48), r4 = load_at<float4>(S.light_tris, r, 64);
     f3 abc = sample_uniform_triangle(u_pt);
     f3 p = xyz(r0) * abc.x + xyz(r1) * abc.y + xyz(r2) * abc.z;
     float cos_light, sqr_dist;
@@ -469,11 +516,19 @@ ZD LightSample sample_light(const DScene &S, f3 origin, float u_pick, NEXT1 next
 }
 
 // sample_light_pdf (light.py:84-111): pdf of having light-sampled point p on (inst, slot)
-template <bool ENV>
+template <bool ENV, bool NARROW = true>                         // NARROW: as surface_interact
 ZD float sample_light_pdf(const DScene &S, f3 origin, int inst, int slot, f3 p) {
-    float4 r6 = S.shade[8 * (size_t)slot + 6];
-    float area = S.shade[8 * (size_t)slot + 7].x;
-    int T = S.inst_tri_begin[inst + 1] - S.inst_tri_begin[inst];
+    float4 r6; float area; int T;
+    if constexpr (NARROW) {
+        const uint32_t r = 128u * (uint32_t)slot, i = 4u * (uint32_t)inst;
+        r6 = load_at<float4>(S.shade, r, 96);
+        area = load_at<float>(S.shade, r, 112);
+        T = load_at<int32_t>(S.inst_tri_begin, i, 4) - load_at<int32_t>(S.inst_tri_begin, i, 0);
+    } else {
+        r6 = S.shade[8 * (size_t)slot + 6];
+        area = S.shade[8 * (size_t)slot + 7].x;
+        T = S.inst_tri_begin[inst + 1] - S.inst_tri_begin[inst];
+    }
     f3 wi; float c, d2;
     return light_pdf(origin, p, xyz(r6), area, ((ENV ? S.env_count : 0) + S.light_count) * T, wi, c, d2);
 }

@@ -559,6 +559,7 @@ static int upload_light_table(zdr_scene *s, const std::vector<int32_t> &lights, 
         }
     }
     if (tab.empty()) tab.push_back(make_float4(0, 0, 0, 0));
+    if (tab.size() * sizeof(float4) > (1ull << 32)) return fail(ZDR_E_UNSUPPORTED, "light table above 4 GiB: the kernels address its entries with 32-bit byte offsets");
     if (tab.size() > s->light_tris_cap) {
         HIPCHK(hipStreamSynchronize(st));
         release_buffer(s, s->d_light_tris); s->d_light_tris = nullptr; s->light_tris_cap = 0;
@@ -590,7 +591,7 @@ extern "C" int zdr_scene_create(const float *verts8, uint32_t nverts, const int3
     if (!verts8 || !tris || !inst_tri_begin || !inst_emission || !out) return fail(ZDR_E_INVALID, "null argument");
     if (ntris == 0 || nverts == 0 || ninst == 0) return fail(ZDR_E_INVALID, "empty scene");
     if (ninst > 10000) return fail(ZDR_E_INVALID, "exceeding maximum number of mesh instances");   // render.py:114-115
-    if (ntris >= (1u << 28)) return fail(ZDR_E_UNSUPPORTED, "too many triangles");
+    if (ntris >= ZDR_MAX_TRIS) return fail(ZDR_E_UNSUPPORTED, "too many triangles: the kernels address the per-triangle records with 32-bit byte offsets (2^25 triangles)");
     if (inst_tri_begin[0] != 0 || (uint32_t)inst_tri_begin[ninst] != ntris) return fail(ZDR_E_INVALID, "inst_tri_begin must span [0, ntris]");
     for (uint32_t i = 0; i < ninst; i++) if (inst_tri_begin[i + 1] < inst_tri_begin[i]) return fail(ZDR_E_INVALID, "inst_tri_begin must be non-decreasing");
     for (size_t i = 0; i < (size_t)ntris * 3; i++) if (tris[i] < 0 || (uint32_t)tris[i] >= nverts) return fail(ZDR_E_INVALID, "triangle index out of range");
@@ -938,6 +939,15 @@ static int32_t cell_copies_for(size_t ncells) {
     return (ncells < (1u << 16)) ? (int32_t)std::min<size_t>(ZDR_MAX_CELL_COPIES, (1u << 20) / ncells) : 1;
 }
 
+// KernelIO::wide_offsets: 32-bit byte offsets reach every texel of `texels` float4 and every pixel of the image.  ZDR_WIDE_OFFSETS=1
+// (read per launch) forces the 64-bit form, ZDR_LOG_OFFSETS=1 reports the choice on stderr: for the tests of the two forms.
+static int32_t wide_offsets_for(size_t texels, size_t pixels) {
+    const char *force = getenv("ZDR_WIDE_OFFSETS"), *log = getenv("ZDR_LOG_OFFSETS");
+    const int32_t wide = (force && atoi(force) != 0) || texels * sizeof(float4) > (1ull << 32) || pixels * sizeof(float4) > (1ull << 32);
+    if (log && atoi(log) != 0) fprintf(stderr, "[zdr offsets] wide=%d texels=%zu pixels=%zu\n", (int)wide, texels, pixels);
+    return wide;
+}
+
 static int make_render_cfg(const zdr_render_params *p, bool backward, RenderCfg &R) {
     { int rc = check_params_abi(p); if (rc) return rc; }
     if (p->integrator < 0 || p->integrator > ZDR_UVGRAD) return fail(ZDR_E_INVALID, "unknown integrator");
@@ -954,6 +964,7 @@ static int make_render_cfg(const zdr_render_params *p, bool backward, RenderCfg 
     R.sample_begin = p->sample_begin; R.sample_end = p->sample_end;
     R.use_tent = p->use_tent; R.max_depth = p->max_depth; R.rr_depth = p->rr_depth; R.tex_h = p->tex_h; R.tex_w = p->tex_w;
     R.cell_copies = cell_copies_for((size_t)(p->tex_h + 1) * (size_t)(p->tex_w + 1));
+    if ((size_t)p->tex_h * (size_t)p->tex_w >= (1ull << 31)) return fail(ZDR_E_UNSUPPORTED, "material of 2^31 texels or more");   // texel indices are ints (tex_footprint)
     R.two_over_w = 2.0f / (float)p->width; R.two_over_h = 2.0f / (float)p->height;
     R.aspect = (float)p->height / (float)p->width;
     R.inv_spp = 1.0f / (float)p->spp;
@@ -1253,6 +1264,11 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const RenderC
     if (emit_grad) io.emit_acc = s->d_emit_acc;         // (shares the forward's `partial` pointer: KernelIO keeps its size)
     io.d_image = (const float4 *)call.d_image; io.d_material = call.d_material; io.cells = s->d_cells; io.counters = s->d_counters;
     io.mt = mt;
+    {
+        size_t texels = (size_t)p->tex_h * (size_t)p->tex_w;    // the material, or every material of the table
+        if (use_mt) { texels = 0; for (int k = 0; k < mt.nmat; k++) texels += (size_t)mt.m[k].h * (size_t)mt.m[k].w; }
+        io.wide_offsets = wide_offsets_for(texels, (size_t)R.width * (size_t)R.height);
+    }
     // every pointer a kernel variant dereferences must be live before anything is launched
     if (backward && (!io.d_image || !io.d_material || !io.cells)) return fail(ZDR_E_INVALID, "backward needs d_image, d_material and the staging cells");
     if (!backward && !stats && !io.image) return fail(ZDR_E_INVALID, "forward needs an image");
@@ -1381,6 +1397,7 @@ extern "C" int zdr_path_dump(zdr_scene *s, const zdr_render_params *p, const flo
     rc = make_sampler_cfg(s, p->sampler, p->seed, p->spp, C); if (rc) return rc;
     KernelIO io; memset(&io, 0, sizeof io);
     io.material = (const float4 *)material; io.d_image = (const float4 *)d_image;
+    io.wide_offsets = wide_offsets_for((size_t)p->tex_h * (size_t)p->tex_w, (size_t)p->width * (size_t)p->height);
     DScene S = s->ds;
     S.shadow_pairs = (S.env_count > 0) ? ~0ull : s->shadow_pairs;
     if (zdr_launch_path_dump(S, R, C, io, s->accel_is_bvh, queries, n, maxv, out, (hipStream_t)stream)) return fail(ZDR_E_HIP, "path dump launch failed");

@@ -274,8 +274,9 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
         }
         const int took = primary_pop<SK, MT>(S, C, !alive, lds_perm, lds_origin, q, ps, it, MT ? io.mt.inst_slot : nullptr);
         if (took >= 0) { alive = true; pix = took; }
-        if (__ballot(alive) != 0ull) {
-            progress = true;
+        {   // (No wave-uniform `if (__ballot(alive) != 0ull)` around this: with it the compiler kept the path state in two register sets, one
+            // that lives across the trips and one that the shading works on, and copied all 27 registers in before and back after every trip.)
+            if (__ballot(alive) != 0ull) progress = true;
             bool done = false;
             if (alive) {
                 Hit h;
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
 
 // Environment-gradient kernels: the cotangent / spp of pixel (px, py), as a popped path of k_path_bwd computes it
 ZD f3 pixel_cotangent(const SamplerCfg &C, const KernelIO &io, int width, uint32_t px, uint32_t py) {
-    const float4 gi = io.d_image[px + py * (uint32_t)width];
+    const float4 gi = io.d_image[px + py * (uint32_t)width];   // (once per camera sample or term, not per trip: left in the 64-bit form)
     f3 g;
     if (C.spp_pow2) g = mk3(gi.x * C.inv_spp, gi.y * C.inv_spp, gi.z * C.inv_spp);
     else { const float fs = (float)C.spp; g = mk3(__fdiv_rn(gi.x, fs), __fdiv_rn(gi.y, fs), __fdiv_rn(gi.z, fs)); }
@@ -525,7 +526,8 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
         const int took = primary_pop<SK, MT>(S, C, !alive, nullptr, lds_origin, pq, ps, it, MT ? io.mt.inst_slot : nullptr);
         if (took >= 0) {
             {   // the pixel's cotangent / spp, straight from the image (load_le_grad; a popped path is inside the shard)
-                const float4 gi = io.d_image[ps.smp.px + ps.smp.py * (uint32_t)R.width];
+                const uint32_t gp = ps.smp.px + ps.smp.py * (uint32_t)R.width;
+                const float4 gi = io.wide_offsets ? io.d_image[gp] : load_at<float4>(io.d_image, 16u * gp);   // (an image within 4 GiB: load_at, scene.h)
                 if (C.spp_pow2) le_grad = mk3(gi.x * C.inv_spp, gi.y * C.inv_spp, gi.z * C.inv_spp);   // x / 2^k == x * 2^-k exactly: three IEEE divisions (~30 VALU per trip) less
                 else { const float fs = (float)C.spp; le_grad = mk3(__fdiv_rn(gi.x, fs), __fdiv_rn(gi.y, fs), __fdiv_rn(gi.z, fs)); }
                 if (any_nan(le_grad)) le_grad = mk3(0.0f);
