@@ -171,9 +171,30 @@ __global__ __launch_bounds__(WAVE) void k_tile_masks(DScene S, RenderCfg R, unsi
 // its paths finish on.  Those are fixed for the first item a wave draws.  A later item starts among the last paths of the one
 // before, and which item that was depends on the order in which the waves reached the work counters: its sums are the same terms,
 // added in an order that can differ from run to run, i.e. in the last bit (DESIGN.md section 5 has the measurement).
+// Four named scalars, chosen by a wave-uniform bank with a select and never with an index: as two arrays indexed by `bank` the
+// struct was demoted to scratch memory in every k_path_bwd (16 bytes of its private segment), and each trip read and wrote these
+// four loop counters through the vector-memory path, behind the flush's atomics (profiles/item_banks_isa.txt).  Every writer pins
+// its value with readfirstlane, so the members live in SGPRs and the bookkeeping runs on the scalar unit.
 struct ItemBanks {
-    int logical[2];          // item held by each bank, -1 = free (wave-uniform)
-    uint32_t inflight[2];    // parked + running paths of each bank (wave-uniform)
+    int logical0, logical1;          // item held by each bank, -1 = free (wave-uniform)
+    uint32_t inflight0, inflight1;   // parked + running paths of each bank (wave-uniform)
+    ZD void init() { logical0 = logical1 = -1; inflight0 = inflight1 = 0u; }
+    ZD int logical(int bank) const { return bank ? logical1 : logical0; }
+    ZD uint32_t inflight(int bank) const { return bank ? inflight1 : inflight0; }
+    ZD void set_logical(int bank, int item) {
+        item = __builtin_amdgcn_readfirstlane(item);
+        logical0 = bank ? logical0 : item; logical1 = bank ? item : logical1;
+    }
+    ZD void parked(int bank, uint32_t n) {              // n more paths of `bank` are in the FIFO
+        n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n);
+        inflight0 += bank ? 0u : n; inflight1 += bank ? n : 0u;
+    }
+    ZD void finished(bool done, int pix) {              // the paths that ended this trip leave their banks (pix: bank * 64 + pixel)
+        inflight0 -= (uint32_t)__popcll(__ballot(done && (pix >> 6) == 0));
+        inflight1 -= (uint32_t)__popcll(__ballot(done && (pix >> 6) == 1));
+    }
+    // every camera sample generated and no path left (cur: the current item's bank, drained: it has no camera sample left)
+    ZD bool retirable(int b, int cur, bool drained) const { return logical(b) >= 0 && inflight(b) == 0u && (b != cur || drained); }
 };
 
 // The persistent kernels read their launch constants (scene pointers, camera, sampler grid ...) through a pointer to the kernarg
@@ -224,7 +245,7 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
 #pragma unroll
     for (int i = 0; i < 8; i++) cnt.c[i] = 0;
     PathVertex pv; f3 term_Li = mk3(0.0f);
-    ItemBanks ib; ib.logical[0] = ib.logical[1] = -1; ib.inflight[0] = ib.inflight[1] = 0;
+    ItemBanks ib; ib.init();
     int bank = 1;                                           // bank of the current item (the first fetch flips it to 0)
     bool more_items = true;
     WorkItem w = decode_item(R, -1);
@@ -247,9 +268,9 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
                 const uint32_t t0 = q.tail;
                 primary_refill<SK, A, false, STATS, ENV, MT>(S, R, C, lds, w.x, w.y, w.valid, cam_mask, perm_seed, bank, next_sample, s_end, q, sum, cnt,
                                                              MT ? io.mt.inst_slot : nullptr);
-                ib.inflight[bank] += q.tail - t0;
-            } else if (more_items && ib.logical[bank ^ 1] < 0) {                // next item, into the free bank
-                if (ib.logical[bank] >= 0) {                                    // park the register part of the old item's sums
+                ib.parked(bank, q.tail - t0);
+            } else if (more_items && ib.logical(bank ^ 1) < 0) {                // next item, into the free bank
+                if (ib.logical(bank) >= 0) {                                    // park the register part of the old item's sums
                     atomicAdd(&lds_sum[(bank * 3 + 0) * WAVE + lane], sum.x); atomicAdd(&lds_sum[(bank * 3 + 1) * WAVE + lane], sum.y);
                     atomicAdd(&lds_sum[(bank * 3 + 2) * WAVE + lane], sum.z);
                     sum = mk3(0.0f);
@@ -258,7 +279,7 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
                 if (nxt < 0) more_items = false;
                 else {
                     bank ^= 1;
-                    ib.logical[bank] = nxt;
+                    ib.set_logical(bank, nxt);
                     w = decode_item(R, nxt);
                     perm_seed = (SK == 0) ? xxhash32_4((uint32_t)w.x, (uint32_t)w.y, C.seed, 0u) : 0u;
                     cam_mask = camera_mask(S, io, w);
@@ -292,19 +313,18 @@ __global__ __launch_bounds__(WAVE, ENV ? A::kMinWavesFwdEnv : A::kMinWavesFwd) v
                     } else COUNT(C_NAN);
                 }
             }
-            ib.inflight[0] -= (uint32_t)__popcll(__ballot(done && (pix >> 6) == 0));
-            ib.inflight[1] -= (uint32_t)__popcll(__ballot(done && (pix >> 6) == 1));
+            ib.finished(done, pix);
         }
         // retire finished items: every camera sample generated and no path left
 #pragma unroll
         for (int b = 0; b < 2; b++) {
-            if (ib.logical[b] >= 0 && ib.inflight[b] == 0 && (b != bank || next_sample >= s_end)) {
+            if (ib.retirable(b, bank, next_sample >= s_end)) {
                 __syncthreads();
-                const WorkItem wb = decode_item(R, ib.logical[b]);
+                const WorkItem wb = decode_item(R, ib.logical(b));
                 f3 tot = mk3(lds_sum[(b * 3 + 0) * WAVE + lane], lds_sum[(b * 3 + 1) * WAVE + lane], lds_sum[(b * 3 + 2) * WAVE + lane]);
                 if (b == bank) { tot = tot + sum; sum = mk3(0.0f); }
                 if (!STATS) store_pixel(R, C, io, wb, tot);         // the stats variant owns no image
-                ib.logical[b] = -1;
+                ib.set_logical(b, -1);
             }
         }
         if (__ballot(alive) == 0ull && q.tail == q.head && next_sample >= s_end && !more_items) break;   // both banks are retired by now
@@ -456,7 +476,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
     int last = -1;                                          // where the running path's most recent record lives: slot, 255 = scratch, -1 = none yet
     int deep_link[ZDR_MAX_RECORDED_DEPTH];
     Counters cnt;
-    ItemBanks ib; ib.logical[0] = ib.logical[1] = -1; ib.inflight[0] = ib.inflight[1] = 0;
+    ItemBanks ib; ib.init();
     int bank = 1;
     bool more_items = true;
     WorkItem w = decode_item(R, -1);
@@ -504,14 +524,14 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
                 } else
                 primary_refill<SK, A, true, false, ENV, MT>(S, R, C, lds, w.x, w.y, w.valid, cam_mask, perm_seed, bank, next_sample, s_end, pq, unused_sum, cnt,
                                                             MT ? io.mt.inst_slot : nullptr);
-                ib.inflight[bank] += pq.tail - t0;
+                ib.parked(bank, pq.tail - t0);
                 progress = true;
-            } else if (more_items && ib.logical[bank ^ 1] < 0) {
+            } else if (more_items && ib.logical(bank ^ 1) < 0) {
                 const int nxt = fetch_item(R, io.work_counters);
                 if (nxt < 0) more_items = false;
                 else {
                     bank ^= 1;
-                    ib.logical[bank] = nxt;
+                    ib.set_logical(bank, nxt);
                     w = decode_item(R, nxt);
                     perm_seed = (SK == 0) ? xxhash32_4((uint32_t)w.x, (uint32_t)w.y, C.seed, 0u) : 0u;
                     cam_mask = camera_mask(S, io, w);
@@ -653,8 +673,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
                     }
                 }
             }
-            ib.inflight[0] -= (uint32_t)__popcll(__ballot(done && (pix >> 6) == 0));
-            ib.inflight[1] -= (uint32_t)__popcll(__ballot(done && (pix >> 6) == 1));
+            ib.finished(done, pix);
             // wave-uniform: sweep every finished path to its first vertex.  The sweep starts from the vertex packed this
             // trip (still in registers).
             PackedVertex cur = plast;
@@ -708,7 +727,7 @@ __global__ __launch_bounds__(WAVE, A::kMinWavesBwd) void k_path_bwd(ZDR_PATH_KER
         }
 #pragma unroll
         for (int b = 0; b < 2; b++)                         // an item whose samples are all generated and whose paths have ended frees its bank
-            if (ib.logical[b] >= 0 && ib.inflight[b] == 0 && (b != bank || next_sample >= s_end)) ib.logical[b] = -1;
+            if (ib.retirable(b, bank, next_sample >= s_end)) ib.set_logical(b, -1);
         if (__ballot(alive) == 0ull && pq.tail == pq.head && next_sample >= s_end && !more_items) break;
         stall = progress ? 0 : stall + 1;
         if (stall > 4) { raise_device_error(S, ZDR_DEVERR_STALL); break; }   // cannot happen (every branch above makes progress); never spin on the GPU, never end silently
