@@ -4,6 +4,9 @@ descent — the workflow of the reference's example.py (render a ground truth, s
 image loss through scene.render's PRB backward), on the assets this repository ships.
 
     python examples/optimize_texture.py --iters 200 --res 256 --spp 16 --out /tmp/zdr_example
+
+--albedo-smoothness W adds W times a screen-space smoothness prior on the albedo the camera sees (scene.render_aovs: the first-hit
+albedo buffer of the same camera samples, differentiable in the material; neighbours on another model or on the background do not count).
 """
 import argparse
 import os
@@ -32,7 +35,16 @@ def save_png(path, img):
     Image.fromarray((img[..., :3].clamp(0, 1) ** 0.454 * 255).to(torch.uint8).cpu().numpy()).save(path)
 
 
-def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True):
+def albedo_smoothness_loss(f):
+    """Mean absolute difference of the albedo of neighbouring pixels that see the same model (f: zdr_amd.Aovs)."""
+    albedo = f.albedo / f.coverage.clamp_min(1e-6)[..., None]                              # the buffers are premultiplied by coverage
+    inst, seen = f.instance.detach(), f.coverage.detach() > 0
+    dx = (albedo[:, 1:] - albedo[:, :-1]).abs().sum(-1) * (seen[:, 1:] & seen[:, :-1] & (inst[:, 1:] == inst[:, :-1]))
+    dy = (albedo[1:] - albedo[:-1]).abs().sum(-1) * (seen[1:] & seen[:-1] & (inst[1:] == inst[:-1]))
+    return dx.mean() + dy.mean()
+
+
+def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0):
     scene = Scene([(os.path.join(ASSETS, "cboxuv.obj"), None, float3(0.0)),
                    (os.path.join(ASSETS, "cbox-light.obj"), None, float3(17, 12, 4))], integrator=integrator)
     scene.camera = Camera(fov=50 / 180 * 3.1415926, origin=float3(-0.2, 2.6, 6.0), target=float3(-0.2, 2.6, -2.5), up=float3(0.0, 1.0, 0.0))
@@ -45,8 +57,11 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
     losses = []
     for it in range(iters):
         opt.zero_grad()
-        image = scene.render(material, res=(res, res), spp=spp, seed=rng.randint(0, 2147483646))
+        step_seed = rng.randint(0, 2147483646)
+        image = scene.render(material, res=(res, res), spp=spp, seed=step_seed)
         loss = (image[..., :3] - image_gt[..., :3]).abs().mean()
+        if albedo_smoothness > 0.0:
+            loss = loss + albedo_smoothness * albedo_smoothness_loss(scene.render_aovs(material, res=(res, res), spp=spp, seed=step_seed))
         loss.backward()
         opt.step()
         with torch.no_grad():
@@ -73,5 +88,6 @@ if __name__ == "__main__":
     ap.add_argument("--tex", type=int, default=256)
     ap.add_argument("--integrator", default="path")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--albedo-smoothness", type=float, default=0.0)
     a = ap.parse_args()
-    run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator)
+    run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness)

@@ -225,6 +225,34 @@ int zdr_render_backward_emission(zdr_scene *scene, const zdr_render_params *para
 int zdr_render_backward_materials_emission(zdr_scene *scene, const zdr_render_params *params, const float *d_image, const float *materials,
                                            const int32_t *dims, uint32_t nmat, float *d_materials, float *d_emission, void *stream);
 
+/* First-hit feature buffers: what each pixel SEES, rendered with the camera samples of zdr_render_forward of the same seed (not seed + 1:
+ * the buffers line up with the forward image), and their adjoint with respect to the materials.  For pixel (x, y) and sample s in [0, spp):
+ *   camera ray   the one zdr_render_forward draws: sampler of (x, y, s), its first 2-D draw is the jitter, tent-warped when use_tent is on
+ *   first hit    the closest hit in (0, 1e30); no facing test, a surface seen from behind is still a hit
+ *   interaction  p, uv, ns (normalised interpolated normal, not flipped), instance and t of that hit
+ *   slot         the instance's entry in the table of zdr_scene_set_material_slots, -1 = none
+ * With Hs the samples of the pixel that hit, a pixel holds ZDR_AOV_CHANNELS floats (four float4), the tensor is (H, W, 16):
+ *   floats 0..2, 3     albedo, roughness     (1/spp) sum over s in Hs with slot >= 0 of read_bsdf(material[slot], uv_s), all four channels
+ *   floats 4..6, 7     normal, depth         (1/spp) sum over Hs of ns_s;  (1/spp) sum over Hs of t_s
+ *   floats 8..10, 11   position, coverage    (1/spp) sum over Hs of p_s;  |Hs| / spp
+ *   floats 12..13      uv                    (1/spp) sum over Hs of uv_s
+ *   floats 14, 15      instance, slot        of the hit with the lowest sample index, as floats; -1 when Hs is empty
+ * Every averaged channel is premultiplied by coverage (a miss adds 0; divide by coverage for the mean over the hits).  The sums run in
+ * sample order in float32 and are divided by (float)spp with an IEEE division; a sample with a NaN in any summed value is dropped whole.
+ * params->integrator, max_depth, rr_depth, prb_mode and tex_h / tex_w are ignored: a scene of any integrator gives the same buffers.
+ * The pixel rectangle and the tile shard are honoured (pixels outside keep their value); a sample range other than [0, spp) is
+ * ZDR_E_UNSUPPORTED, the instance channel having no partial form.  materials, dims, nmat: as zdr_render_forward_materials.
+ *
+ * zdr_render_aovs_backward: only floats 0..3 depend on the materials, and linearly.  d_materials (DEVICE, packed like materials) is
+ * ACCUMULATED into (+=):  d_materials[slot] += sum over s in Hs with slot >= 0 of bilinear_weights(uv_s) d_aovs[pixel, 0..3] / spp.
+ * Floats 4..15 of d_aovs are not read; a cotangent with a NaN counts as 0.  The SAME seed as the forward: this is the exact transpose
+ * of the forward, there is no seed + 1 here.  Both calls only enqueue and follow the stream-capture rules above. */
+#define ZDR_AOV_CHANNELS 16
+int zdr_render_aovs(zdr_scene *scene, const zdr_render_params *params, const float *materials, const int32_t *dims, uint32_t nmat,
+                    float *aovs /* DEVICE H x W x 16 */, void *stream);
+int zdr_render_aovs_backward(zdr_scene *scene, const zdr_render_params *params, const float *d_aovs /* DEVICE H x W x 16 */,
+                             const float *materials, const int32_t *dims, uint32_t nmat, float *d_materials, void *stream);
+
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,
  * shadow rays (one per shaded vertex, prb.py:59), shaded vertices, emitter hits via BSDF sampling, NaN-dropped samples,

@@ -16,6 +16,7 @@ SAMPLER_CMJ, SAMPLER_PMJ02BN = 0, 1
 ACCEL_AUTO, ACCEL_BRUTE, ACCEL_BVH = 0, 1, 2
 ABI_VERSION = 4                # ZDR_ABI_VERSION of the include/zdr.h this binding mirrors
 MAX_MATERIALS = 16             # ZDR_MAX_MATERIALS
+AOV_CHANNELS = 16              # ZDR_AOV_CHANNELS
 PRB_MODES = {"expectation": 0, "detached": 1, "literal": 2}
 INTEGRATORS = {"collocated": COLLOCATED, "direct": DIRECT, "path": PATH}   # render.py:65-69
 SAMPLERS = {"cmj": SAMPLER_CMJ, "corrmj": SAMPLER_CMJ, "pmj02bn": SAMPLER_PMJ02BN}
@@ -29,7 +30,8 @@ EXPORTS = ("zdr_version", "zdr_abi_version", "zdr_last_error", "zdr_scene_create
            "zdr_render_stats", "zdr_scene_check", "zdr_trace_closest", "zdr_trace_any", "zdr_sampler_dump", "zdr_vertex_sampler_dump", "zdr_path_dump", "zdr_debug_build_accel", "zdr_debug_never_occluders",
            "zdr_scene_set_material_slots", "zdr_render_forward_materials", "zdr_render_backward_materials",
            "zdr_scene_set_envmap_texture", "zdr_render_backward_env", "zdr_render_backward_materials_env",
-           "zdr_scene_set_emission_values", "zdr_render_backward_emission", "zdr_render_backward_materials_emission")
+           "zdr_scene_set_emission_values", "zdr_render_backward_emission", "zdr_render_backward_materials_emission",
+           "zdr_render_aovs", "zdr_render_aovs_backward")
 
 
 class CameraPOD(C.Structure):
@@ -92,6 +94,8 @@ def lib():
     L.zdr_scene_set_emission_values.argtypes = [vp, fp, vp]
     L.zdr_render_backward_emission.argtypes = [vp, C.POINTER(RenderParams), fp, fp, fp, fp, vp]
     L.zdr_render_backward_materials_emission.argtypes = [vp, C.POINTER(RenderParams), fp, fp, ip, C.c_uint32, fp, fp, vp]
+    L.zdr_render_aovs.argtypes = [vp, C.POINTER(RenderParams), fp, ip, C.c_uint32, fp, vp]
+    L.zdr_render_aovs_backward.argtypes = [vp, C.POINTER(RenderParams), fp, fp, ip, C.c_uint32, fp, vp]
     L.zdr_render_stats.argtypes = [vp, C.POINTER(RenderParams), fp, C.POINTER(C.c_uint64), vp]
     L.zdr_scene_check.argtypes = [vp, vp]
     L.zdr_trace_closest.argtypes = [vp, fp, C.c_uint32, ip, fp, vp]

@@ -118,6 +118,30 @@ ZD float4 uvgrad_sample(const DScene &S, int *lds, f3 o, f3 d, f3 odx, f3 ddx, f
     return make_float4(j00 * bx0 + j01 * bx1, j01 * bx0 + j11 * bx1, j00 * by0 + j01 * by1, j01 * by0 + j11 * by1);
 }
 
+// ----------------------------------------------------------------------- feature buffers
+// One camera sample of zdr_render_aovs / zdr_render_aovs_backward (include/zdr.h has the semantics): the camera ray of the direct and
+// collocated kernels (same sampler, same packed pixel draw), its first hit without a facing test, and what surface_interact and the
+// slot table say about it.  hit = false: nothing else is set.
+struct AovSample { bool hit; f3 p, ns; f2 uv; float t; int inst, slot; };
+template <int SK, class A>
+ZD AovSample aov_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int *lds, int x, int y, uint32_t perm_seed,
+                        uint32_t index, unsigned long long cam_mask) {
+    Sampler smp = sampler_make<SK>(C, (uint32_t)x, (uint32_t)y, perm_seed, index);
+    f3 o, d;
+    pixel_ray<SK, true>(R, C, smp, x, y, o, d);
+    const Hit h = A::closest_camera(S, lds, o, d, cam_mask);
+    AovSample a;
+    a.hit = h.slot >= 0;
+    if (a.hit) {
+        const Interaction it = surface_interact(S, h);
+        a.p = it.p; a.ns = it.ns; a.uv = it.uv; a.t = h.t; a.inst = it.inst;
+        a.slot = load_at<int32_t>(io.mt.inst_slot, 4u * (uint32_t)it.inst);
+    }
+    return a;
+}
+// the sample's geometric values hold a NaN (a degenerate normal, say): both kernels drop the sample whole
+ZD bool aov_geometry_nan(const AovSample &a) { return any_nan(a.p) | any_nan(a.ns) | (a.uv.x != a.uv.x) | (a.uv.y != a.uv.y) | (a.t != a.t); }
+
 // -------------------------------------------------------------------------------- direct
 // direct.py:21-85 (forward) / 89-167 (adjoint; gradient written once at the primary uv, App. B-11)
 // MT: an instance with a material is shaded by it, one without returns its emission (zdr.h, zdr_scene_set_material_slots)

@@ -77,6 +77,8 @@ struct RenderLaunch {
                           // the map's cells, and they are gathered into d_env (+=)
     float *d_emission;    // emission-gradient backward (zdr_render_backward_emission; the scene has at least one light): io.mt is a material
                           // table, io.emit_acc the zeroed accumulator, and its rows are gathered into d_emission (ninst x 3, +=)
+    int aov;              // feature buffers (zdr_render_aovs / zdr_render_aovs_backward): k_aov / k_aov_bwd run whatever `integrator` says; io.mt is
+                          // a material table, R has one chunk, io.image / io.d_image are (H, W, 16) and the cells are gathered like any table's
 };
 int zdr_launch_render(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, const RenderLaunch &L, hipStream_t stream);
 #define ZDR_EMISSION_COPIES 256       // rows of the emission accumulator

@@ -1171,6 +1171,9 @@ struct RenderCall {
     // map as entry ZDR_ENV_ENTRY / of the lights' emissions, through the material-table kernels' emission forms.  A single material becomes
     // a table of one.
     float *d_env = nullptr, *d_emission = nullptr;
+    // feature buffers (zdr_render_aovs / zdr_render_aovs_backward): a material-table call whose image / d_image are (H, W, ZDR_AOV_CHANNELS)
+    // and whose kernels are k_aov / k_aov_bwd, whatever integrator the parameters name
+    bool aov = false;
     void *stream = nullptr;
 };
 
@@ -1198,6 +1201,7 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const RenderC
     RenderCfg R; SamplerCfg C;
     rc = make_render_cfg(&pm, backward != 0, R); if (rc) return rc;
     rc = make_sampler_cfg(s, p->sampler, p->seed, p->spp, C); if (rc) return rc;
+    if (call.aov) { R.chunk = p->spp; R.nchunks = 1; }  // a lane owns its pixel's whole sum (and its first hit)
     const bool capturing = stream_is_capturing(st);
     MaterialTable mt; memset(&mt, 0, sizeof mt);
     if (use_mt) {
@@ -1267,7 +1271,7 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const RenderC
     {
         size_t texels = (size_t)p->tex_h * (size_t)p->tex_w;    // the material, or every material of the table
         if (use_mt) { texels = 0; for (int k = 0; k < mt.nmat; k++) texels += (size_t)mt.m[k].h * (size_t)mt.m[k].w; }
-        io.wide_offsets = wide_offsets_for(texels, (size_t)R.width * (size_t)R.height);
+        io.wide_offsets = wide_offsets_for(texels, (size_t)R.width * (size_t)R.height * (call.aov ? ZDR_AOV_CHANNELS / 4 : 1));
     }
     // every pointer a kernel variant dereferences must be live before anything is launched
     if (backward && (!io.d_image || !io.d_material || !io.cells)) return fail(ZDR_E_INVALID, "backward needs d_image, d_material and the staging cells");
@@ -1279,7 +1283,7 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const RenderC
     DScene S = s->ds;
     // shadow segments end on a light's surface; an environment light sends them to infinity, where nothing can be ruled out
     S.shadow_pairs = (S.env_count > 0) ? ~0ull : s->shadow_pairs;
-    const RenderLaunch L = {p->integrator, s->accel_is_bvh, backward, stats, env_grad ? call.d_env : nullptr, emit_grad ? call.d_emission : nullptr};
+    const RenderLaunch L = {p->integrator, s->accel_is_bvh, backward, stats, env_grad ? call.d_env : nullptr, emit_grad ? call.d_emission : nullptr, call.aov ? 1 : 0};
     if (zdr_launch_render(S, R, C, io, L, st))
         return fail(ZDR_E_HIP, std::string("kernel launch: ") + hipGetErrorString(hipGetLastError()));
     static const bool check_every_call = getenv("ZDR_CHECK") && atoi(getenv("ZDR_CHECK")) != 0;   // opt-in: costs a synchronise per call
@@ -1355,6 +1359,36 @@ extern "C" int zdr_render_backward_emission(zdr_scene *s, const zdr_render_param
 extern "C" int zdr_render_backward_materials_emission(zdr_scene *s, const zdr_render_params *p, const float *d_image, const float *materials,
                                                       const int32_t *dims, uint32_t nmat, float *d_materials, float *d_emission, void *stream) {
     return render_backward_call(s, p, d_image, materials, true, dims, nmat, d_materials, nullptr, d_emission, stream);
+}
+
+// The parameters of a feature-buffer call as render_common takes them: the integrator and its settings are ignored (include/zdr.h), so
+// valid ones stand in — the collocated integrator's, which needs no path workspace.  The whole sample range only.
+static int aov_params(const zdr_render_params *p, zdr_render_params &out) {
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (int rc = check_params_abi(p)) return rc;
+    if (p->sample_begin != 0 || p->sample_end != p->spp)
+        return fail(ZDR_E_UNSUPPORTED, "feature buffers take the whole sample range [0, spp): the instance channel has no partial form");
+    out = *p;
+    out.integrator = ZDR_COLLOCATED; out.max_depth = 1; out.rr_depth = 0; out.prb_mode = ZDR_PRB_EXPECTATION;
+    return ZDR_OK;
+}
+
+extern "C" int zdr_render_aovs(zdr_scene *s, const zdr_render_params *p, const float *materials, const int32_t *dims, uint32_t nmat, float *aovs, void *stream) {
+    if (int rc = check_table_args(aovs != nullptr, dims, nmat)) return rc;
+    zdr_render_params pa;
+    if (int rc = aov_params(p, pa)) return rc;
+    RenderCall c; c.material = materials; c.dims = dims; c.nmat = nmat; c.image = aovs; c.aov = true; c.stream = stream;
+    return render_common(s, &pa, c);
+}
+
+extern "C" int zdr_render_aovs_backward(zdr_scene *s, const zdr_render_params *p, const float *d_aovs, const float *materials, const int32_t *dims,
+                                        uint32_t nmat, float *d_materials, void *stream) {
+    if (int rc = check_table_args(d_aovs && d_materials, dims, nmat)) return rc;
+    zdr_render_params pa;
+    if (int rc = aov_params(p, pa)) return rc;
+    RenderCall c; c.material = materials; c.dims = dims; c.nmat = nmat; c.backward = true; c.d_image = d_aovs; c.d_material = d_materials; c.aov = true;
+    c.stream = stream;
+    return render_common(s, &pa, c);
 }
 
 extern "C" int zdr_render_stats(zdr_scene *s, const zdr_render_params *p, const float *material, uint64_t counters[8], void *stream) {

@@ -919,6 +919,97 @@ __global__ __launch_bounds__(WAVE) void k_uvgrad(DScene S, RenderCfg R, SamplerC
     }
 }
 
+// ----------------------------------------------------------------------- feature buffers
+// zdr_render_aovs (include/zdr.h has the channel table): one wave per 8x8 tile, lane = pixel, every sample of the pixel in index order
+// (the launcher gives these kernels one chunk: the instance channel has no partial form).  A lane keeps its pixel's sixteen sums in
+// registers and writes its own 64-byte line once, as four dwordx4 stores.  Material-table form only; the launch constants are read
+// through the laundered kernarg pointer like k_simple's, so that the table and the camera stay in the kernarg segment and in SGPRs.
+template <int SK, class A>
+__global__ __launch_bounds__(WAVE) void k_aov(ZDR_PATH_KERNEL_PARAMS) {
+    ZDR_KARGS_BEGIN
+#define S (ka->S)
+#define R (ka->R)
+#define C (ka->C)
+#define io (ka->io)
+    extern __shared__ int lds[];        // BvhAccel: traversal stacks (sized at launch); unused otherwise
+    const WorkItem w = decode_block(R);
+    const uint32_t perm_seed = (SK == 0) ? xxhash32_4((uint32_t)w.x, (uint32_t)w.y, C.seed, 0u) : 0u;
+    const unsigned long long cam_mask = camera_mask(S, io, w);
+    float4 mat = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nrm = mat, pos = mat;   // {albedo, roughness} {normal, depth} {position, hits}
+    f2 uv; uv.x = 0.0f; uv.y = 0.0f;
+    float first_inst = -1.0f, first_slot = -1.0f;
+    bool seen = false;
+    for (uint32_t it = w.s_begin; it < w.s_end; it++) {     // wave-uniform trip count
+        ZDR_KARGS_REFRESH
+        if (!w.valid) continue;
+        const AovSample a = aov_sample<SK, A>(S, R, C, io, lds, w.x, w.y, perm_seed, it, cam_mask);
+        if (!a.hit) continue;
+        float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (a.slot >= 0) m = read_bsdf_in(io.material, io.mt.m[a.slot], a.uv, io.wide_offsets != 0);
+        if (aov_geometry_nan(a) || any_nan4(m)) continue;
+        mat.x += m.x; mat.y += m.y; mat.z += m.z; mat.w += m.w;
+        nrm.x += a.ns.x; nrm.y += a.ns.y; nrm.z += a.ns.z; nrm.w += a.t;
+        pos.x += a.p.x; pos.y += a.p.y; pos.z += a.p.z; pos.w += 1.0f;
+        uv.x += a.uv.x; uv.y += a.uv.y;
+        if (!seen) { seen = true; first_inst = (float)a.inst; first_slot = (float)a.slot; }
+    }
+    if (w.valid) {
+        const float fs = (float)C.spp;
+        float4 *o = io.image + 4 * (size_t)w.pix;
+        o[0] = make_float4(__fdiv_rn(mat.x, fs), __fdiv_rn(mat.y, fs), __fdiv_rn(mat.z, fs), __fdiv_rn(mat.w, fs));
+        o[1] = make_float4(__fdiv_rn(nrm.x, fs), __fdiv_rn(nrm.y, fs), __fdiv_rn(nrm.z, fs), __fdiv_rn(nrm.w, fs));
+        o[2] = make_float4(__fdiv_rn(pos.x, fs), __fdiv_rn(pos.y, fs), __fdiv_rn(pos.z, fs), __fdiv_rn(pos.w, fs));
+        o[3] = make_float4(__fdiv_rn(uv.x, fs), __fdiv_rn(uv.y, fs), first_inst, first_slot);
+    }
+#undef S
+#undef R
+#undef C
+#undef io
+}
+
+// zdr_render_aovs_backward: the transpose of the albedo / roughness channels.  Same samples, same hits; a sample whose instance has a
+// material queues (uv, cotangent of floats 0..3 / spp, slot) into the scatter queue of the backward kernels (scene.h), once per
+// sample iteration by the whole wave; cells, copies and the few-texel LDS path are those of every material-table backward call, and
+// k_material_cells_to_grad gathers them.  The cotangent is read once per pixel, outside the loop.
+template <int SK, class A>
+__global__ __launch_bounds__(WAVE) void k_aov_bwd(ZDR_PATH_KERNEL_PARAMS) {
+    ZDR_KARGS_BEGIN
+#define S (ka->S)
+#define R (ka->R)
+#define C (ka->C)
+#define io (ka->io)
+    extern __shared__ int lds[];        // BvhAccel: traversal stacks (sized at launch); unused otherwise
+    __shared__ __attribute__((aligned(16))) float lds_q[ZDR_SCATTER_LDS_FLOATS];
+    const WorkItem w = decode_block(R);
+    const uint32_t perm_seed = (SK == 0) ? xxhash32_4((uint32_t)w.x, (uint32_t)w.y, C.seed, 0u) : 0u;
+    const unsigned long long cam_mask = camera_mask(S, io, w);
+    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (w.valid) {
+        const float4 gi = io.d_image[4 * (size_t)w.pix];
+        const float fs = (float)C.spp;
+        g = make_float4(__fdiv_rn(gi.x, fs), __fdiv_rn(gi.y, fs), __fdiv_rn(gi.z, fs), __fdiv_rn(gi.w, fs));
+        if (any_nan4(g)) g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    const bool carries = any_nonzero4(g);
+    ScatterQueue q = scatter_queue_init_cells(lds_q, io.mt.ncells, R.cell_copies);
+    for (uint32_t it = w.s_begin; it < w.s_end; it++) {     // wave-uniform trip count
+        ZDR_KARGS_REFRESH
+        bool push = false;
+        f2 guv; guv.x = 0.0f; guv.y = 0.0f;
+        int gmat = 0;
+        if (w.valid) {
+            const AovSample a = aov_sample<SK, A>(S, R, C, io, lds, w.x, w.y, perm_seed, it, cam_mask);
+            if (a.hit && a.slot >= 0 && !aov_geometry_nan(a)) { push = carries; guv = a.uv; gmat = a.slot; }
+        }
+        scatter_push<true, false>(q, io.cells, push, guv, g, R.tex_h, R.tex_w, 0, gmat, io.mt.m);
+    }
+    scatter_finish<true, false>(q, io.cells, R.tex_h, R.tex_w, 0, io.mt.m);
+#undef S
+#undef R
+#undef C
+#undef io
+}
+
 // sums the per-chunk partial images in chunk order (deterministic), integrator.py:29
 __global__ void k_reduce_chunks(RenderCfg R, uint32_t spp, const float4 *partial, float4 *image) {
     int x = R.x0 + blockIdx.x * blockDim.x + threadIdx.x, y = R.y0 + blockIdx.y;
@@ -1075,7 +1166,7 @@ int zdr_launch_render(const DScene &S_in, const RenderCfg &R, const SamplerCfg &
     int nblocks = R.ntiles * R.nchunks;
     if (nblocks <= 0) return 0;
     dim3 grid(((nblocks + 7) >> 3) << 3);                   // multiple of 8 for the XCD remap
-    const size_t dyn = L.accel_is_bvh ? bvh_dyn_lds(S, backward != 0, integrator == ZDR_PATH) : 0;
+    const size_t dyn = L.accel_is_bvh ? bvh_dyn_lds(S, backward != 0, integrator == ZDR_PATH && !L.aov) : 0;
     if (io.tile_masks && !io.tile_masks_valid)
         hipLaunchKernelGGL(k_tile_masks, dim3(R.tiles_x * R.tiles_y), dim3(WAVE), 0, st, S, R, (unsigned long long *)io.tile_masks);
     const KernelForm k = {backward != 0, stats != 0, S.env_count > 0, io.mt.nmat > 0, d_env != nullptr, d_emission != nullptr};
@@ -1083,7 +1174,9 @@ int zdr_launch_render(const DScene &S_in, const RenderCfg &R, const SamplerCfg &
     with_sampler_accel(C.kind, L.accel_is_bvh, [&](auto sk, auto acc) {
         constexpr int SK = decltype(sk)::value;
         typedef typename decltype(acc)::type A;
-        if (integrator == ZDR_UVGRAD) hipLaunchKernelGGL((k_uvgrad<SK, A>), grid, dim3(WAVE), dyn, st, S, R, C, io);
+        if (L.aov && backward) hipLaunchKernelGGL((k_aov_bwd<SK, A>), grid, dim3(WAVE), dyn, st, S, R, C, io);
+        else if (L.aov) hipLaunchKernelGGL((k_aov<SK, A>), grid, dim3(WAVE), dyn, st, S, R, C, io);
+        else if (integrator == ZDR_UVGRAD) hipLaunchKernelGGL((k_uvgrad<SK, A>), grid, dim3(WAVE), dyn, st, S, R, C, io);
         else if (integrator == ZDR_PATH) launched = launch_path<SK, A>(k, nblocks, dyn, st, S, R, C, io);
         else if (integrator == ZDR_DIRECT) launched = launch_simple<ZDR_DIRECT, SK, A>(k, grid, dyn, st, S, R, C, io);
         else launched = launch_simple<ZDR_COLLOCATED, SK, A>(k, grid, dyn, st, S, R, C, io);

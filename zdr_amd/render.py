@@ -14,6 +14,9 @@
     image = scene.render(material, res=(W, H), spp=256, envmap=env)   # env.grad after backward(); tables stay fixed
     scene.update_envmap_sampling(env.detach())                        # now and then: tables rebuilt from the current map
 
+    f = scene.render_aovs(material, res=(W, H), spp=16, seed=0)       # first-hit feature buffers of render()'s camera samples
+    f.albedo, f.normal, f.depth, f.coverage, f.instance               # views of f.data, (H, W, 16); albedo / roughness carry the graph
+
     E = torch.tensor([[0, 0, 0], [20, 20, 20]], dtype=torch.float32, device="cuda", requires_grad=True)   # one row per model
     image = scene.render(material, res=(W, H), spp=256, emissions=E)  # E.grad after backward(); the set of lights stays fixed
 
@@ -102,6 +105,24 @@ class EmissionValues(list):
     def __init__(self, base, values):
         super().__init__(base)
         self.values = values
+
+
+class Aovs:
+    """First-hit feature buffers of ``Scene.render_aovs`` (include/zdr.h, zdr_render_aovs): ``data`` is the (H, W, 16) tensor, the
+    attributes are views into it.  Every averaged channel is premultiplied by ``coverage`` (divide by it for the mean over the
+    samples that hit); ``instance`` and ``slot`` are those of the pixel's first sample that hit, -1 where none did.  ``albedo`` and
+    ``roughness`` are differentiable with respect to the materials; the views carry the graph."""
+    CHANNELS = {"albedo": (0, 3), "roughness": (3, 4), "normal": (4, 7), "depth": (7, 8), "position": (8, 11), "coverage": (11, 12),
+                "uv": (12, 14), "instance": (14, 15), "slot": (15, 16)}
+
+    def __init__(self, data):
+        self.data = data
+
+    def __getattr__(self, name):                       # (reached for names that are not attributes: the channels)
+        if name not in Aovs.CHANNELS:
+            raise AttributeError(name)
+        a, b = Aovs.CHANNELS[name]
+        return self.data[..., a] if b - a == 1 else self.data[..., a:b]
 
 
 def _camera_pod(cam: Camera) -> N.CameraPOD:
@@ -346,6 +367,90 @@ class Scene:
                 t.copy_(dpacked[off:off + t.numel() // 4].reshape(t.shape))
                 off += t.numel() // 4
         return d_materials
+
+    # --------------------------------------------------------------------- feature buffers
+    def _aov_call(self, materials, dims, slots):
+        """_material_call for the feature buffers: one (H, W, 4) tensor is a list of one, and without ``slots`` and ``material_slots``
+        one material belongs to model 0 alone — what the path and the direct integrator do with a single material."""
+        if isinstance(materials, torch.Tensor) and dims is None:
+            materials = [materials]
+        if slots is None and self._material_slots is None and (len(dims) if dims is not None else len(materials)) == 1:
+            slots = (0,) + (None,) * (self.inst_count - 1)
+        return self._material_call(materials, dims, slots)
+
+    def render_aovs_forward(self, materials, res, spp, seed, *, dims=None, slots=None, rect=None, tile_shard=None, out=None):
+        """The (H, W, 16) feature buffers of include/zdr.h, zdr_render_aovs, rendered with the camera samples of ``render_forward``
+        of the same ``seed``.  ``materials``, ``dims``, ``slots``: as ``render_forward_materials`` (one tensor: a list of one, on model
+        0 unless ``material_slots`` says otherwise).  With ``rect`` / ``tile_shard`` only that shard is written; other pixels of
+        ``out`` keep their value, a fresh buffer is zero-filled."""
+        packed, d, _ = self._aov_call(materials, dims, slots)
+        shape = (int(res[1]), int(res[0]), N.AOV_CHANNELS)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
+        p = self._params(res, spp, seed, (1, 1), rect, None, tile_shard=tile_shard)
+        N.check(N.lib().zdr_render_aovs(self._handle, C.byref(p), packed.data_ptr(), d.ctypes.data, d.shape[0], out.data_ptr(), self._stream()))
+        return out
+
+    def render_aovs_backward(self, grad, d_materials, materials, res, spp, seed, *, dims=None, slots=None, camera=None, rect=None, tile_shard=None):
+        """The adjoint of ``render_aovs_forward`` with respect to the materials: accumulates into ``d_materials`` (a list shaped
+        like ``materials``, one tensor, or the packed texels).  ``grad`` is the (H, W, 16) cotangent, of which floats 0..3 are read.
+        The SAME ``seed`` as the forward: this is its exact transpose."""
+        packed, d, _ = self._aov_call(materials, dims, slots)
+        listed = isinstance(d_materials, (list, tuple))
+        dpacked = (torch.cat([g.reshape(-1, 4) for g in d_materials]) if len(d_materials) > 1 else d_materials[0]) if listed else d_materials
+        if dpacked.numel() != packed.numel() or not dpacked.is_contiguous() or dpacked.device != self.device or dpacked.dtype != torch.float32:
+            raise ValueError(f"d_materials must be contiguous float32 on {self.device}, shaped like the materials")
+        g = grad.reshape(res[1], res[0], N.AOV_CHANNELS).to(device=self.device, dtype=torch.float32).contiguous()
+        p = self._params(res, spp, seed, (1, 1), rect, None, camera, tile_shard=tile_shard)
+        N.check(N.lib().zdr_render_aovs_backward(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
+                                                 dpacked.data_ptr(), self._stream()))
+        if listed and len(d_materials) > 1:
+            off = 0
+            for t in d_materials:
+                t.copy_(dpacked[off:off + t.numel() // 4].reshape(t.shape))
+                off += t.numel() // 4
+        return d_materials
+
+    class AovOperator(torch.autograd.Function):
+        """render_aovs() of the packed texels of its materials: returns the (H, W, 16) buffers and, backward, the packed gradient
+        (torch.cat's own backward hands each material its part).  The camera is snapshotted like RenderOperator's."""
+        @staticmethod
+        def forward(ctx, packed, self, res, spp, seed, dims, slots):
+            ctx.save_for_backward(packed)
+            ctx.scene = weakref.ref(self)
+            ctx.args = (res, spp, seed, dims, slots)
+            ctx.camera = self.camera.copy()
+            return self.render_aovs_forward(packed, res, spp, seed, dims=dims, slots=slots)
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            scene = ctx.scene()
+            packed, = ctx.saved_tensors
+            res, spp, seed, dims, slots = ctx.args
+            grad = torch.zeros(packed.size(), dtype=packed.dtype, device=packed.device)
+            scene.render_aovs_backward(grad_output, grad, packed.detach(), res, spp, seed, dims=dims, slots=slots, camera=ctx.camera)
+            return grad, None, None, None, None, None, None
+
+    def render_aovs(self, material, *, res, spp, seed=0) -> Aovs:
+        """What each pixel sees: an ``Aovs`` whose ``data`` is the (height, width, 16) tensor of include/zdr.h, zdr_render_aovs —
+        albedo, roughness, normal, depth, position, coverage, uv, instance and slot of the first hit, averaged over the camera
+        samples that ``render(material, res=res, spp=spp, seed=seed)`` draws — with a named view for each.  ``material`` is a tensor
+        or a list exactly as ``render`` takes it; albedo and roughness are differentiable with respect to it (to each tensor of a
+        list).  The scene's integrator does not matter.  With one tensor and ``material_slots`` unset only model 0 has a material
+        (slot 0), as in the path and direct integrators; every other model reads albedo 0 and slot -1."""
+        if not isinstance(material, (list, tuple)) and self._material_slots is None:
+            mats = [material]
+            slots = (0,) + (None,) * (self.inst_count - 1)
+        else:
+            mats = list(material) if isinstance(material, (list, tuple)) else [material]
+            slots = resolve_material_slots(self._material_slots, self.emissions, len(mats))
+        for m in mats:
+            self._check_material(m)
+        dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
+        packed = mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
+        return Aovs(Scene.AovOperator.apply(packed, self, res, spp, seed, dims, slots))
 
     # ------------------------------------------------------------------------- launching
     def _stream(self):
