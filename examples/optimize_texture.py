@@ -7,6 +7,8 @@ image loss through scene.render's PRB backward), on the assets this repository s
 
 --albedo-smoothness W adds W times a screen-space smoothness prior on the albedo the camera sees (scene.render_aovs: the first-hit
 albedo buffer of the same camera samples, differentiable in the material; neighbours on another model or on the background do not count).
+--denoise puts the feature-guided denoiser between the step's render and the loss (scene.render_denoised): the L1 loss of a noisy
+render is a biased estimate of the loss of the converged image, the filtered render's less so.
 """
 import argparse
 import os
@@ -44,7 +46,7 @@ def albedo_smoothness_loss(f):
     return dx.mean() + dy.mean()
 
 
-def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0):
+def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0, denoise=False):
     scene = Scene([(os.path.join(ASSETS, "cboxuv.obj"), None, float3(0.0)),
                    (os.path.join(ASSETS, "cbox-light.obj"), None, float3(17, 12, 4))], integrator=integrator)
     scene.camera = Camera(fov=50 / 180 * 3.1415926, origin=float3(-0.2, 2.6, 6.0), target=float3(-0.2, 2.6, -2.5), up=float3(0.0, 1.0, 0.0))
@@ -58,7 +60,7 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
     for it in range(iters):
         opt.zero_grad()
         step_seed = rng.randint(0, 2147483646)
-        image = scene.render(material, res=(res, res), spp=spp, seed=step_seed)
+        image = (scene.render_denoised if denoise else scene.render)(material, res=(res, res), spp=spp, seed=step_seed)
         loss = (image[..., :3] - image_gt[..., :3]).abs().mean()
         if albedo_smoothness > 0.0:
             loss = loss + albedo_smoothness * albedo_smoothness_loss(scene.render_aovs(material, res=(res, res), spp=spp, seed=step_seed))
@@ -89,5 +91,6 @@ if __name__ == "__main__":
     ap.add_argument("--integrator", default="path")
     ap.add_argument("--out", default=None)
     ap.add_argument("--albedo-smoothness", type=float, default=0.0)
+    ap.add_argument("--denoise", action="store_true")
     a = ap.parse_args()
-    run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness)
+    run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness, denoise=a.denoise)

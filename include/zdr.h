@@ -26,6 +26,7 @@
  */
 #ifndef ZDR_H
 #define ZDR_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -252,6 +253,45 @@ int zdr_render_aovs(zdr_scene *scene, const zdr_render_params *params, const flo
                     float *aovs /* DEVICE H x W x 16 */, void *stream);
 int zdr_render_aovs_backward(zdr_scene *scene, const zdr_render_params *params, const float *d_aovs /* DEVICE H x W x 16 */,
                              const float *materials, const int32_t *dims, uint32_t nmat, float *d_materials, void *stream);
+
+/* Feature-guided à-trous denoiser: an edge-stopping wavelet filter of an (H, W, 4) image guided by the (H, W, 16) feature buffers of
+ * zdr_render_aovs rendered with the same camera samples, and its adjoint with respect to the image.  No scene handle.
+ * Guides of pixel p with feature row A:  c = A[11] (coverage);  if c > 0:  n = A[4..6] / c,  z = A[7] / c,  a = A[0..2] / c;  otherwise
+ * n = 0, z = 0, a = 0;  id = A[14] (-1 where nothing was hit).
+ * Weights, with b = (1/16, 1/4, 3/8, 1/4, 1/16), level l = 0 .. levels - 1, s = 2^l and q = p + s (i, j), i, j in {-2 .. 2}:
+ *   w_l(p, q) = b[i + 2] b[j + 2] [id_p == id_q] exp(-(Tn + Tz + Ta))
+ *   Tn = |n_p - n_q|^2 / sigma_normal^2
+ *   Tz = (z_p - z_q)^2 / ((sigma_depth (z_p + z_q) / 2)^2 + 1e-20)            (relative depth)
+ *   Ta = |a_p - a_q|^2 / sigma_albedo^2
+ * A term whose sigma is <= 0 is switched off (contributes 0).  Taps outside the image do not exist.  w is symmetric in (p, q) and
+ * w(p, p) = 9/64, so the normaliser below is never 0.
+ * Forward:  x_0 = image, all four channels alike;  x_{l+1}(p) = sum_q w_l(p, q) x_l(q) / D_l(p),  D_l(p) = sum_q w_l(p, q);  out = x_levels.
+ * The guides always come from the given feature buffers, never from a filtered level: each level is a fixed linear map
+ * K_l = D_l^-1 W_l of the image, and a constant image (alpha = 1) stays constant.
+ * Adjoint:  d_image = K_0^T ... K_{levels-1}^T d_out,  (K_l^T g)(q) = sum_p w_l(p, q) g(p) / D_l(p): by the symmetry of w a gather over
+ * the same 25 taps of g / D_l, without atomics, bit-identical from run to run.  The feature buffers receive NO gradient: the
+ * edge-stopping weights are held fixed.  Inputs are assumed finite; nothing is checked for NaN.
+ *
+ * All pointers are DEVICE pointers, 16-byte aligned; aovs is H x W x 16, image / out / d_out / d_image are H x W x 4.  The caller
+ * provides `workspace`, at least zdr_denoise_workspace_bytes(params) bytes (0 = invalid params; grows with the size, and does not
+ * shrink with the levels).  Both calls only enqueue on `stream`: they never allocate and never synchronise, so they can be captured
+ * in a HIP graph without a call before.  Neither call reads what an earlier call left in the workspace — each packs the guides and
+ * computes the normalisers it needs itself — so zdr_denoise_backward needs no forward call before it, and one workspace may serve
+ * calls of any parameters it is large enough for, one call in flight at a time.  out and d_image are overwritten (not accumulated
+ * into) and must not overlap the inputs or the workspace.
+ * ZDR_E_INVALID: struct_size other than sizeof(zdr_denoise_params), levels outside 1 .. ZDR_DENOISE_MAX_LEVELS, a width or height
+ * <= 0, a null or misaligned pointer, an output that overlaps an input or the workspace, a workspace that overlaps an input (byte
+ * ranges as the parameters size them).  ZDR_E_UNSUPPORTED: more than 2^30 pixels.  Any other width and height >= 1 is taken. */
+#define ZDR_DENOISE_MAX_LEVELS 6
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_denoise_params) */
+    int32_t width, height, levels;
+    float sigma_normal, sigma_depth, sigma_albedo;
+} zdr_denoise_params;
+size_t zdr_denoise_workspace_bytes(const zdr_denoise_params *params);
+int zdr_denoise(const zdr_denoise_params *params, const float *aovs, const float *image, float *out, void *workspace, void *stream);
+int zdr_denoise_backward(const zdr_denoise_params *params, const float *aovs, const float *d_out, float *d_image, void *workspace,
+                         void *stream);
 
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,

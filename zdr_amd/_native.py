@@ -17,6 +17,7 @@ ACCEL_AUTO, ACCEL_BRUTE, ACCEL_BVH = 0, 1, 2
 ABI_VERSION = 4                # ZDR_ABI_VERSION of the include/zdr.h this binding mirrors
 MAX_MATERIALS = 16             # ZDR_MAX_MATERIALS
 AOV_CHANNELS = 16              # ZDR_AOV_CHANNELS
+DENOISE_MAX_LEVELS = 6         # ZDR_DENOISE_MAX_LEVELS
 PRB_MODES = {"expectation": 0, "detached": 1, "literal": 2}
 INTEGRATORS = {"collocated": COLLOCATED, "direct": DIRECT, "path": PATH}   # render.py:65-69
 SAMPLERS = {"cmj": SAMPLER_CMJ, "corrmj": SAMPLER_CMJ, "pmj02bn": SAMPLER_PMJ02BN}
@@ -31,7 +32,8 @@ EXPORTS = ("zdr_version", "zdr_abi_version", "zdr_last_error", "zdr_scene_create
            "zdr_scene_set_material_slots", "zdr_render_forward_materials", "zdr_render_backward_materials",
            "zdr_scene_set_envmap_texture", "zdr_render_backward_env", "zdr_render_backward_materials_env",
            "zdr_scene_set_emission_values", "zdr_render_backward_emission", "zdr_render_backward_materials_emission",
-           "zdr_render_aovs", "zdr_render_aovs_backward")
+           "zdr_render_aovs", "zdr_render_aovs_backward",
+           "zdr_denoise_workspace_bytes", "zdr_denoise", "zdr_denoise_backward")
 
 
 class CameraPOD(C.Structure):
@@ -48,6 +50,11 @@ class RenderParams(C.Structure):
         ("camera", CameraPOD), ("tex_h", C.c_int32), ("tex_w", C.c_int32),
         ("tile_shard_index", C.c_int32), ("tile_shard_count", C.c_int32), ("prb_mode", C.c_int32),
     ]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("levels", C.c_int32),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
 
 
 class SceneInfo(C.Structure):
@@ -96,6 +103,10 @@ def lib():
     L.zdr_render_backward_materials_emission.argtypes = [vp, C.POINTER(RenderParams), fp, fp, ip, C.c_uint32, fp, fp, vp]
     L.zdr_render_aovs.argtypes = [vp, C.POINTER(RenderParams), fp, ip, C.c_uint32, fp, vp]
     L.zdr_render_aovs_backward.argtypes = [vp, C.POINTER(RenderParams), fp, fp, ip, C.c_uint32, fp, vp]
+    L.zdr_denoise_workspace_bytes.argtypes = [C.POINTER(DenoiseParams)]
+    L.zdr_denoise_workspace_bytes.restype = C.c_size_t
+    L.zdr_denoise.argtypes = [C.POINTER(DenoiseParams), fp, fp, fp, vp, vp]
+    L.zdr_denoise_backward.argtypes = [C.POINTER(DenoiseParams), fp, fp, fp, vp, vp]
     L.zdr_render_stats.argtypes = [vp, C.POINTER(RenderParams), fp, C.POINTER(C.c_uint64), vp]
     L.zdr_scene_check.argtypes = [vp, vp]
     L.zdr_trace_closest.argtypes = [vp, fp, C.c_uint32, ip, fp, vp]

@@ -65,6 +65,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # host side: IEEE float32 for the per-triangle constants
         # (-D options of ZDR_KERNEL_FLAGS go to both halves: some macros size shared workspaces)
         ("zdr_api.cpp", ["-O2", "-ffp-contract=off", "-x", "hip", *[f for f in os.environ.get("ZDR_KERNEL_FLAGS", "").split() if f.startswith("-D")]]),
+        # the denoiser's kernels, a translation unit of their own (linked last: the path kernels' code object stays the first in the
+        # library); no fast-math either, and none of the measurement macros reach it
+        ("zdr_denoise.hip", ["-O3", "-fno-slp-vectorize"]),
     ]
     procs = []
     for src, extra in jobs:

@@ -6,10 +6,13 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
 
+#define ZDR_DENOISE_LAUNCHER_REF __attribute__((weak))   // (csrc/denoise.h)
+#include "denoise.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1389,6 +1392,102 @@ extern "C" int zdr_render_aovs_backward(zdr_scene *s, const zdr_render_params *p
     RenderCall c; c.material = materials; c.dims = dims; c.nmat = nmat; c.backward = true; c.d_image = d_aovs; c.d_material = d_materials; c.aov = true;
     c.stream = stream;
     return render_common(s, &pa, c);
+}
+
+// ------------------------------------------------------------------------------- denoiser
+// zdr_denoise / zdr_denoise_backward (include/zdr.h): no scene handle, no allocation, no synchronisation — argument checks, then
+// launches of zdr_denoise.hip on the caller's stream.  Workspace: [guides: 2 float4 per pixel][A: 1 float4 per pixel][B: the same,
+// from two levels on].  Neither call leaves anything in it that the other reads: both pack the guides themselves, and the adjoint
+// recomputes the normalisers D_l.
+static int denoise_check(const zdr_denoise_params *p) {
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (p->struct_size != sizeof(zdr_denoise_params))
+        return fail(ZDR_E_INVALID, "zdr_denoise_params.struct_size is " + std::to_string(p->struct_size) + ", this library expects " +
+                                   std::to_string(sizeof(zdr_denoise_params)) + ": caller and library were built from different include/zdr.h");
+    if (p->width <= 0 || p->height <= 0) return fail(ZDR_E_INVALID, "zdr_denoise_params: width and height must be positive");
+    if (p->levels < 1 || p->levels > ZDR_DENOISE_MAX_LEVELS)
+        return fail(ZDR_E_INVALID, "zdr_denoise_params.levels is " + std::to_string(p->levels) + ": between 1 and " + std::to_string(ZDR_DENOISE_MAX_LEVELS));
+    if ((uint64_t)p->width * (uint64_t)p->height > (1ull << 30)) return fail(ZDR_E_UNSUPPORTED, "zdr_denoise: more than 2^30 pixels");
+    return ZDR_OK;
+}
+
+static int denoise_check_pointers(std::initializer_list<const void *> ptrs) {
+    for (const void *q : ptrs) {
+        if (!q) return fail(ZDR_E_INVALID, "null argument");
+        if ((uintptr_t)q % 16) return fail(ZDR_E_INVALID, "zdr_denoise: every pointer must be 16-byte aligned");
+    }
+    if (!zdr_launch_denoise_guides || !zdr_launch_denoise_level)     // (weak: csrc/denoise.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the denoiser's kernels (zdr_denoise.hip)");
+    return ZDR_OK;
+}
+
+// [a, a + na) meets one of the other byte ranges (the sizes follow from the parameters, so the header's "must not overlap" is checked)
+struct DenoiseRange { const void *p; size_t bytes; };
+static bool denoise_overlap(const void *a, size_t na, std::initializer_list<DenoiseRange> others) {
+    const uintptr_t a0 = (uintptr_t)a;
+    for (const DenoiseRange &r : others) {
+        const uintptr_t b0 = (uintptr_t)r.p;
+        if (a0 < b0 + r.bytes && b0 < a0 + na) return true;
+    }
+    return false;
+}
+
+static DenoiseCfg denoise_cfg(const zdr_denoise_params *p) {
+    DenoiseCfg R;
+    R.width = p->width; R.height = p->height;
+    R.inv_sn2 = p->sigma_normal > 0.f ? 1.f / (p->sigma_normal * p->sigma_normal) : 0.f;
+    R.half_sz = p->sigma_depth > 0.f ? 0.5f * p->sigma_depth : 0.f;
+    R.inv_sa2 = p->sigma_albedo > 0.f ? 1.f / (p->sigma_albedo * p->sigma_albedo) : 0.f;
+    return R;
+}
+
+extern "C" size_t zdr_denoise_workspace_bytes(const zdr_denoise_params *p) {
+    if (denoise_check(p)) return 0;
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    return n * sizeof(float4) * (p->levels > 1 ? 4 : 3);
+}
+
+extern "C" int zdr_denoise(const zdr_denoise_params *p, const float *aovs, const float *image, float *out, void *workspace, void *stream) {
+    if (int rc = denoise_check(p)) return rc;
+    if (int rc = denoise_check_pointers({aovs, image, out, workspace})) return rc;
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    if (denoise_overlap(out, 16 * n, {{image, 16 * n}, {aovs, 64 * n}, {workspace, zdr_denoise_workspace_bytes(p)}}))
+        return fail(ZDR_E_INVALID, "zdr_denoise: out must not alias or overlap an input or the workspace");
+    if (denoise_overlap(workspace, zdr_denoise_workspace_bytes(p), {{image, 16 * n}, {aovs, 64 * n}}))
+        return fail(ZDR_E_INVALID, "zdr_denoise: the workspace must not overlap an input");
+    const DenoiseCfg R = denoise_cfg(p);
+    hipStream_t st = (hipStream_t)stream;
+    float4 *guides = (float4 *)workspace, *buf[2] = {guides + 2 * n, guides + 3 * n};
+    if (zdr_launch_denoise_guides(R, (const float4 *)aovs, guides, st)) return fail(ZDR_E_HIP, "denoise guide launch failed");
+    const float4 *src = (const float4 *)image;
+    for (int l = 0; l < p->levels; l++) {
+        float4 *dst = l == p->levels - 1 ? (float4 *)out : buf[l & 1];
+        if (zdr_launch_denoise_level(R, ZDR_DENOISE_FILTER, 1 << l, guides, src, dst, st)) return fail(ZDR_E_HIP, "denoise level launch failed");
+        src = dst;
+    }
+    return ZDR_OK;
+}
+
+extern "C" int zdr_denoise_backward(const zdr_denoise_params *p, const float *aovs, const float *d_out, float *d_image, void *workspace, void *stream) {
+    if (int rc = denoise_check(p)) return rc;
+    if (int rc = denoise_check_pointers({aovs, d_out, d_image, workspace})) return rc;
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    if (denoise_overlap(d_image, 16 * n, {{d_out, 16 * n}, {aovs, 64 * n}, {workspace, zdr_denoise_workspace_bytes(p)}}))
+        return fail(ZDR_E_INVALID, "zdr_denoise_backward: d_image must not alias or overlap an input or the workspace");
+    if (denoise_overlap(workspace, zdr_denoise_workspace_bytes(p), {{d_out, 16 * n}, {aovs, 64 * n}}))
+        return fail(ZDR_E_INVALID, "zdr_denoise_backward: the workspace must not overlap an input");
+    const DenoiseCfg R = denoise_cfg(p);
+    hipStream_t st = (hipStream_t)stream;
+    float4 *guides = (float4 *)workspace, *A = guides + 2 * n, *B = guides + 3 * n;
+    if (zdr_launch_denoise_guides(R, (const float4 *)aovs, guides, st)) return fail(ZDR_E_HIP, "denoise guide launch failed");
+    const float4 *g = (const float4 *)d_out;
+    for (int l = p->levels - 1; l >= 0; l--) {                       // K_l^T g = gather of g / D_l
+        float4 *dst = l == 0 ? (float4 *)d_image : B;
+        if (zdr_launch_denoise_level(R, ZDR_DENOISE_DIVIDE, 1 << l, guides, g, A, st) ||
+            zdr_launch_denoise_level(R, ZDR_DENOISE_GATHER, 1 << l, guides, A, dst, st)) return fail(ZDR_E_HIP, "denoise level launch failed");
+        g = dst;
+    }
+    return ZDR_OK;
 }
 
 extern "C" int zdr_render_stats(zdr_scene *s, const zdr_render_params *p, const float *material, uint64_t counters[8], void *stream) {

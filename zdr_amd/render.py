@@ -16,6 +16,8 @@
 
     f = scene.render_aovs(material, res=(W, H), spp=16, seed=0)       # first-hit feature buffers of render()'s camera samples
     f.albedo, f.normal, f.depth, f.coverage, f.instance               # views of f.data, (H, W, 16); albedo / roughness carry the graph
+    clean = zdr_amd.denoise(image, f)                                 # edge-stopping filter guided by f, differentiable in the image
+    clean = scene.render_denoised(material, res=(W, H), spp=16)       # the three calls in one
 
     E = torch.tensor([[0, 0, 0], [20, 20, 20]], dtype=torch.float32, device="cuda", requires_grad=True)   # one row per model
     image = scene.render(material, res=(W, H), spp=256, emissions=E)  # E.grad after backward(); the set of lights stays fixed
@@ -451,6 +453,15 @@ class Scene:
         dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
         packed = mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
         return Aovs(Scene.AovOperator.apply(packed, self, res, spp, seed, dims, slots))
+
+    def render_denoised(self, material, *, res, spp, seed=0, **denoise_kwargs):
+        """``render`` followed by the feature-guided denoiser: ``denoise(render(material), render_aovs(material), **denoise_kwargs)``
+        with the same ``res``, ``spp`` and ``seed`` for both, so that the guides line up with the image (zdr_amd/denoiser.py for the
+        keywords).  Differentiable with respect to ``material`` like ``render``, through the filter's adjoint and, with
+        ``demodulate``, through the albedo it divides by.  Any integrator: the feature buffers do not depend on it."""
+        from .denoiser import denoise
+        image = self.render(material, res=res, spp=spp, seed=seed)
+        return denoise(image, self.render_aovs(material, res=res, spp=spp, seed=seed), **denoise_kwargs)
 
     # ------------------------------------------------------------------------- launching
     def _stream(self):
