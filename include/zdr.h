@@ -351,6 +351,21 @@ int zdr_vertex_sampler_dump(zdr_scene *scene, int32_t integrator, int32_t sample
 int zdr_path_dump(zdr_scene *scene, const zdr_render_params *params, const float *material, const float *d_image,
                   const int32_t *queries, uint32_t n, int32_t maxv, float *out, void *stream);
 
+/* The FUSED walk of the BVH path kernels as a batch query (test hook): what a path vertex hands the acceleration structure — a shadow
+ * ray and a continuation ray per lane, walked in one loop in which lanes that are through take subtrees from lanes that are not
+ * (csrc/accel.h, BvhAccel::shadow_and_closest / walk_steal) — where zdr_trace_closest / zdr_trace_any walk one ray per lane without
+ * stealing.  Ray pair i is lane i % 64 of wave i / 64: the caller chooses who shares a wave, hence who can steal from whom; the lanes
+ * of the last wave beyond n take part without a ray.  shadow_rays / next_rays: DEVICE n x 8 {o[3], tmin, d[3], tmax}; tmin / tmax of
+ * next_rays are ignored (0 and 1e30, as the path kernels pass them).  need (DEVICE, n): bit 0 the pair has a shadow ray, bit 1 a
+ * continuation ray.  backward_layout != 0: the LDS layout of the backward path kernel (fewer stack entries in LDS) instead of the
+ * forward one's.  occluded (n): 1 when the shadow ray is blocked, 0 without bit 0; inst_prim / bary_t as zdr_trace_closest, (-1, -1)
+ * and (0, 0, 1e30) on a miss or without bit 1.  The answers are those of zdr_trace_any / zdr_trace_closest for the same rays.
+ * The call compiles the fused walk into a kernel of its own: it checks the routine's logic, not the copy of it inlined into the
+ * path kernels (that is what the path-by-path parity tests run).  BVH scenes only: ZDR_E_UNSUPPORTED on a brute-force scene.
+ * n = 0 does nothing. */
+int zdr_trace_fused(zdr_scene *scene, const float *shadow_rays, const float *next_rays, const int32_t *need, uint32_t n,
+                    int32_t backward_layout, int32_t *occluded, int32_t *inst_prim, float *bary_t, void *stream);
+
 /* Host-only: builds the acceleration structure exactly as zdr_scene_create does and returns it,
  * without touching a GPU, so that the CPU test-suite can run an emulation of the device traversal
  * on the very data the kernels read (tests/test_bvh_emulation.py).  tri_xyz: ntris x 9 world-space

@@ -1,4 +1,4 @@
-"""CPU emulation of the DEVICE traversal (csrc/accel.h, BvhAccel::traverse) on the node / triangle
+"""CPU emulation of the DEVICE traversal (csrc/accel.h: BvhAccel::consume, the visit-and-pop that walk() and walk_steal() repeat per ray) on the node / triangle
 arrays the host builder produces (zdr_debug_build_accel, no GPU involved), checked against the
 oracle's brute force.  This is the executable spec of the traversal: change accel.h and this file
 together.  It exists because a traversal bug on the GPU is a hang, not a failed assert."""
@@ -37,15 +37,23 @@ def build(A, accel):
     return nodes[:nn.value], order, isect
 
 
-def tri_test(q, o, d, tmin, tmax):
+def tri_tuv(q, o, d):
+    """(t, u, v) of the plane-form record q (12 floats) in float32.  Scalars or arrays: q[k], o[k], d[k] may be float32 arrays of
+    shapes that broadcast (tests/ray_cases.py evaluates every ray against every record at once)."""
     f = np.float32
-    nd = f(q[0] * d[0] + q[1] * d[1] + q[2] * d[2])
-    tn = f(q[3] - f(q[0] * o[0] + q[1] * o[1] + q[2] * o[2]))
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        nd = f(q[0] * d[0] + q[1] * d[1] + q[2] * d[2])
+        tn = f(q[3] - f(q[0] * o[0] + q[1] * o[1] + q[2] * o[2]))
         t = f(tn / nd)
-    p = o + d * t
-    u = f(q[4] * p[0] + q[5] * p[1] + q[6] * p[2] + q[7]); v = f(q[8] * p[0] + q[9] * p[1] + q[10] * p[2] + q[11])
-    return bool(t > tmin and t < tmax and u >= 0 and v >= 0 and u + v <= 1), t
+        p = [f(o[k] + f(d[k] * t)) for k in range(3)]
+        u = f(q[4] * p[0] + q[5] * p[1] + q[6] * p[2] + q[7]); v = f(q[8] * p[0] + q[9] * p[1] + q[10] * p[2] + q[11])
+    return t, u, v
+
+
+def tri_test(q, o, d, tmin, tmax):
+    t, u, v = tri_tuv(q, o, d)
+    with np.errstate(invalid="ignore"):
+        return (t > tmin) & (t < tmax) & (u >= 0) & (v >= 0) & (u + v <= 1), t
 
 
 def qbox_entry(k, q, A, B, tmin, tmax, inv):
@@ -74,7 +82,8 @@ def decode_node(n):
 
 
 def traverse(nodes, isect, o, d, tmin, tmax, any_hit):
-    """line-by-line mirror of BvhAccel::traverse<ANY>"""
+    """line-by-line mirror of one ray's walk (BvhAccel::start, then consume() until it returns false) -> (slot, t, trips, the most
+    entries the stack held)"""
     ntris, nnodes = isect.shape[0], nodes.shape[0]
     best_t, slot = np.float32(tmax), -1
     with np.errstate(divide="ignore"):
@@ -84,10 +93,15 @@ def traverse(nodes, isect, o, d, tmin, tmax, any_hit):
     isect_off = 64 * nnodes
     def where(word):
         off, c = word & ~15, word & 7
+        if c == 0:                                     # whatever the walk follows lies inside the one allocation of nodes and records
+            assert off % 64 == 0 and 0 <= off < isect_off, (word, nnodes)
+        elif c != 7:
+            assert (off - isect_off) % 48 == 0 and isect_off <= off and (off - isect_off) // 48 + c <= ntris, (word, nnodes, ntris)
         return (off // 64 if c == 0 else (off - isect_off) // 48), c
     nid, cnt = 0, (ntris if nnodes == 0 else 0)
     budget = 2 * (nnodes + ntris) + 8
     steps = 0
+    pending = 0
     while True:
         budget -= 1
         if budget < 0:
@@ -99,7 +113,7 @@ def traverse(nodes, isect, o, d, tmin, tmax, any_hit):
             with np.errstate(invalid="ignore", over="ignore"):
                 A = (scale * inv).astype(np.float32); B = ((origin - o) * inv).astype(np.float32)
             e = [qbox_entry(c, q, A, B, tmin, best_t, inv) for c in range(4)]      # unused slots carry an inverted box: no test for them
-            if np.isfinite(o).all() and np.isfinite(d).all():              # (a ray of NaNs / infinities decides no comparison: it may "enter" one, and its walk ends there)
+            if np.isfinite(o).all() and np.isfinite(d).all() and (d != 0).any():   # (a ray of NaNs / infinities, or one without a direction — 1 / d infinite on every axis —, decides no comparison: it may "enter" one, and its walk ends there)
                 assert all(e[c] > 2.0e38 for c in range(4) if (p[c] & 7) == 7), (o, d)
             em = min(e)
             if em < 2.0e38:
@@ -111,8 +125,11 @@ def traverse(nodes, isect, o, d, tmin, tmax, any_hit):
                 for c in range(4):
                     if not taken[c] and e[c] < 2.0e38:
                         stack.append(p[c])
+                pending = max(pending, len(stack))
                 if nxt >= 0:
                     nid, cnt = where(nxt)
+                    if cnt == 7:                       # (fetch() marks the lane dead: the ray ends)
+                        break
                     descended = True
         else:
             for s in range(nid, nid + cnt):
@@ -120,7 +137,7 @@ def traverse(nodes, isect, o, d, tmin, tmax, any_hit):
                 if ok:
                     best_t, slot = t, s
             if any_hit and slot >= 0:
-                return slot, best_t, steps
+                return slot, best_t, steps, pending
         if descended:
             continue
         if not stack:
@@ -129,7 +146,7 @@ def traverse(nodes, isect, o, d, tmin, tmax, any_hit):
         nid, cnt = where(e)
         if cnt == 7:                                   # only a ray of NaNs gets into an unused slot: its walk ends, it hits nothing
             break
-    return slot, best_t, steps
+    return slot, best_t, steps, pending
 
 
 def rays_for(lo, hi, n, seed):
@@ -150,7 +167,7 @@ def check_scene(A, lo, hi, nrays, seed):
     tri_inst = np.repeat(np.arange(A.ninst), np.diff(A.inst_tri_begin))
     worst = 0
     for i in range(nrays):
-        slot, t, steps = traverse(nodes, isect, o[i], d[i], np.float32(0), np.float32(1e30), False)
+        slot, t, steps, _ = traverse(nodes, isect, o[i], d[i], np.float32(0), np.float32(1e30), False)
         worst = max(worst, steps)
         if rip[i, 0] < 0:
             assert slot < 0, i
@@ -162,7 +179,7 @@ def check_scene(A, lo, hi, nrays, seed):
             assert abs(t - rbt[i, 2]) <= 1e-5 * abs(rbt[i, 2]) + 5e-6
         # any-hit with a bounded ray agrees with the closest hit
         tm = np.float32(0.7 * rbt[i, 2]) if rip[i, 0] >= 0 else np.float32(5.0)
-        s_any, _, _ = traverse(nodes, isect, o[i], d[i], np.float32(1e-4), tm, True)
+        s_any, _, _, _ = traverse(nodes, isect, o[i], d[i], np.float32(1e-4), tm, True)
         occ = S.trace_any(np.concatenate([o[i], [1e-4], d[i], [tm]]).astype(np.float32)[None])[0]
         assert (s_any >= 0) == bool(occ), i
     return nodes.shape[0], worst
@@ -187,7 +204,7 @@ def test_nan_and_axis_aligned_rays_terminate():
     nodes, order, isect = build(A, _native.ACCEL_BVH)
     for o, d in [((np.nan, 0, 0), (0, -1, 0)), ((0, 2, 0), (0, -1, 0)), ((0, 2, 0), (np.nan, np.nan, np.nan)),
                  ((0.3, 2, 0.1), (1, 0, 0)), ((3, 0.0, 3), (-1, 0, 0)), ((np.inf, 0, 0), (1, 0, 0))]:
-        slot, t, steps = traverse(nodes, isect, np.array(o, np.float32), np.array(d, np.float32), np.float32(0), np.float32(1e30), False)
+        slot, t, steps, _ = traverse(nodes, isect, np.array(o, np.float32), np.array(d, np.float32), np.float32(0), np.float32(1e30), False)
         assert steps <= 2 * (nodes.shape[0] + isect.shape[0]) + 8
 
 
@@ -196,7 +213,7 @@ def test_tiny_scene_is_a_single_leaf():
     A = geometry.from_arrays(v, np.array([[0, 2, 1]], np.int32))
     nodes, order, isect = build(A, _native.ACCEL_BVH)
     assert nodes.shape[0] == 0
-    slot, t, _ = traverse(nodes, isect, np.array([0.2, 1, 0.2], np.float32), np.array([0, -1, 0], np.float32), np.float32(0), np.float32(1e30), False)
+    slot, t, _, _ = traverse(nodes, isect, np.array([0.2, 1, 0.2], np.float32), np.array([0, -1, 0], np.float32), np.float32(0), np.float32(1e30), False)
     assert slot == 0 and abs(t - 1) < 1e-6
 
 

@@ -87,6 +87,8 @@ int zdr_launch_zero(void *p, size_t bytes, hipStream_t stream);   // kernel zero
 int zdr_launch_copy(void *dst, const void *src, size_t bytes, hipStream_t stream);   // kernel copy of 16-byte words (graph-safe, as the zero-fill)
 int zdr_launch_trace(const DScene &S, int accel_is_bvh, int any, const float *rays, uint32_t n,
                      int32_t *out_i, float *out_f, hipStream_t stream);
+int zdr_launch_trace_fused(const DScene &S, const float *shadow, const float *next, const int32_t *need, uint32_t n, int backward_layout,
+                           int32_t *occluded, int32_t *out_i, float *out_f, hipStream_t stream);   // BVH scenes only
 int zdr_launch_sampler_dump(const SamplerCfg &C, const int32_t *queries, uint32_t n, int32_t nvert,
                             int32_t rr_depth, float *out, int as_path_kernels, int *batched, hipStream_t stream);
 int zdr_launch_path_dump(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int accel_is_bvh,

@@ -1518,6 +1518,17 @@ extern "C" int zdr_trace_any(zdr_scene *s, const float *rays, uint32_t n, int32_
     return ZDR_OK;
 }
 
+extern "C" int zdr_trace_fused(zdr_scene *s, const float *shadow_rays, const float *next_rays, const int32_t *need, uint32_t n, int32_t backward_layout,
+                               int32_t *occluded, int32_t *inst_prim, float *bary_t, void *stream) {
+    if (!s) return fail(ZDR_E_INVALID, "null argument");
+    if (!s->accel_is_bvh) return fail(ZDR_E_UNSUPPORTED, "the fused walk exists for BVH scenes only (a brute-force scene walks its two rays one after the other)");
+    if (n == 0) return ZDR_OK;
+    if (!shadow_rays || !next_rays || !need || !occluded || !inst_prim || !bary_t) return fail(ZDR_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(s->device));
+    if (zdr_launch_trace_fused(s->ds, shadow_rays, next_rays, need, n, backward_layout, occluded, inst_prim, bary_t, (hipStream_t)stream)) return fail(ZDR_E_HIP, "fused trace launch failed");
+    return ZDR_OK;
+}
+
 extern "C" int zdr_path_dump(zdr_scene *s, const zdr_render_params *p, const float *material, const float *d_image,
                              const int32_t *queries, uint32_t n, int32_t maxv, float *out, void *stream) {
     if (!s || !p || !material || !queries || !out) return fail(ZDR_E_INVALID, "null argument");

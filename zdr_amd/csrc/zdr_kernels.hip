@@ -1249,6 +1249,48 @@ int zdr_launch_trace(const DScene &S_in, int accel_is_bvh, int any, const float 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ------------------------------------------------------------------------------ fused walk
+// Test hook (zdr_trace_fused, include/zdr.h): lane i of wave i / 64 is ray pair i and hands BvhAccel::shadow_and_closest its two rays
+// exactly as path_shade does, under the LDS layout of the path kernels (bvh_dyn_lds: the stack of either layout + the cells of
+// walk_steal).  Every lane of a wave takes part, the ones beyond n with no ray.  This is walk_steal compiled into a kernel of its
+// own: it runs the routine's logic, not the instance inlined into k_path / k_path_bwd (the path parity tests run those).
+template <class A>
+__global__ __launch_bounds__(WAVE) void k_trace_fused(DScene S, const float4 *shadow, const float4 *next, const int32_t *need, uint32_t n,
+                                                      int32_t *occluded, int32_t *out_i, float *out_f) {
+    extern __shared__ int lds[];
+    const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+    const bool valid = i < n;
+    const int nd = valid ? need[i] : 0;
+    const float4 sa = valid ? shadow[2 * (size_t)i] : make_float4(0, 0, 0, 0), sb = valid ? shadow[2 * (size_t)i + 1] : make_float4(0, 0, 1, 0);
+    const float4 na = valid ? next[2 * (size_t)i] : make_float4(0, 0, 0, 0), nb = valid ? next[2 * (size_t)i + 1] : make_float4(0, 0, 1, 0);
+    bool occ; Hit h;
+    A::shadow_and_closest(S, lds, (nd & 1) != 0, xyz(sa), xyz(sb), sa.w, sb.w, (nd & 2) != 0, xyz(na), xyz(nb), occ, h);
+    if (!valid) return;
+    occluded[i] = ((nd & 1) && occ) ? 1 : 0;
+    const bool hit = (nd & 2) && h.slot >= 0;
+    int inst = -1, prim = -1;
+    float hu = 0.0f, hv = 0.0f;
+    if (hit) {                          // as k_trace reports them: the barycentrics of the INPUT corners 1 and 2
+        inst = __float_as_int(S.shade[8 * (size_t)h.slot + 6].w); prim = __float_as_int(S.shade[8 * (size_t)h.slot + 7].y);
+        const int ro = __float_as_int(S.shade[8 * (size_t)h.slot + 7].z);
+        const float hw = 1.0f - h.u - h.v;
+        hu = h.u; hv = h.v;
+        if (ro == 1) { hu = hw; hv = h.u; } else if (ro == 2) { hu = h.v; hv = hw; }
+    }
+    out_i[2 * (size_t)i] = inst; out_i[2 * (size_t)i + 1] = prim;
+    out_f[3 * (size_t)i] = hu; out_f[3 * (size_t)i + 1] = hv; out_f[3 * (size_t)i + 2] = hit ? h.t : 1e30f;
+}
+
+int zdr_launch_trace_fused(const DScene &S_in, const float *shadow, const float *next, const int32_t *need, uint32_t n, int backward_layout,
+                           int32_t *occluded, int32_t *out_i, float *out_f, hipStream_t st) {
+    DScene S = S_in;
+    if (n == 0) return 0;
+    dim3 grid((n + WAVE - 1) / WAVE);
+    const size_t dyn = bvh_dyn_lds(S, backward_layout != 0, true);
+    hipLaunchKernelGGL((k_trace_fused<BvhAccel>), grid, dim3(WAVE), dyn, st, S, (const float4 *)shadow, (const float4 *)next, need, n, occluded, out_i, out_f);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ------------------------------------------------------------------------------- path dump
 // Test hook (zdr_path_dump, include/zdr.h): lane = one queried camera sample, walked vertex by vertex with the SAME
 // device functions the path kernels run (path_arrive, path_shade, path_continue, pack_vertex, sweep_vertex), records kept

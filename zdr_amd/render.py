@@ -676,6 +676,21 @@ class Scene:
         N.check(N.lib().zdr_trace_any(self._handle, rays.data_ptr(), rays.shape[0], occ.data_ptr(), self._stream()))
         return occ
 
+    def trace_fused(self, shadow, nxt, need, backward_layout=False):
+        """The fused walk of the BVH path kernels (include/zdr.h, zdr_trace_fused): row i of ``shadow`` / ``nxt`` ((n, 8) float32) is the
+        shadow / continuation ray of lane i % 64 of wave i // 64, ``need`` (n,) int32 says which of the two it has (bit 0 / bit 1)
+        -> (occluded (n,) int32, inst_prim (n, 2) int32, bary_t (n, 3) float32)."""
+        shadow, nxt = self._rays(shadow), self._rays(nxt)
+        need = need.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        n = shadow.shape[0]
+        assert nxt.shape[0] == n and need.shape[0] == n
+        occ = torch.empty((n,), dtype=torch.int32, device=self.device)
+        ip = torch.empty((n, 2), dtype=torch.int32, device=self.device)
+        bt = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        N.check(N.lib().zdr_trace_fused(self._handle, shadow.data_ptr(), nxt.data_ptr(), need.data_ptr(), n, 1 if backward_layout else 0,
+                                        occ.data_ptr(), ip.data_ptr(), bt.data_ptr(), self._stream()))
+        return occ, ip, bt
+
     def sampler_dump(self, queries, spp, seed=0, nvert=3, rr_depth=RR_DEPTH):
         """queries: (n, 3) int32 cuda {px, py, sample_index} -> (n, 2 + 8*nvert) float32 sampler draws."""
         q = queries.reshape(-1, 3).to(device=self.device, dtype=torch.int32).contiguous()
