@@ -366,6 +366,25 @@ int zdr_path_dump(zdr_scene *scene, const zdr_render_params *params, const float
 int zdr_trace_fused(zdr_scene *scene, const float *shadow_rays, const float *next_rays, const int32_t *need, uint32_t n,
                     int32_t backward_layout, int32_t *occluded, int32_t *inst_prim, float *bary_t, void *stream);
 
+/* The shading math point by point (test hook): row i (lane i of a kernel of its own) calls the very device functions the path kernels
+ * call at a vertex — csrc/microfacet.h (ggx_terms, ggx_brdf_from, ggx_pdf_from, ggx_dfdr_from, ggx_sample / sample_wm_disk), brdf_grad
+ * and the shading frame (make_onb, to_local, to_world) — on inputs the caller chooses; no geometry is read, `scene` only names the
+ * device.  in / out: DEVICE float32, n rows of 16 floats each; the floats of a row that are not listed are ignored (in) or written
+ * as 0 (out); rows n and beyond are not touched.  Directions are LOCAL (z = shading normal) and taken as they are, not normalised.
+ *   ZDR_SHADING_EVAL    in  {wo[3], wi[3], roughness, diffuse[3], ct[3]}
+ *                       out {f[3] (BRDF times cosine), pdf, dfdr = d f / d roughness, dlnpdf_dr, t, D (of GgxTerms: t = nh^2 (a2 - 1) + 1,
+ *                            D = a2 / (pi t^2)), brdf_grad(wi.z / pi, dfdr, ct)[4]}
+ *   ZDR_SHADING_SAMPLE  in  {wo[3], roughness, diffuse[3], u_lobe, u_dir[2]}
+ *                       out {wi_local[3], pdf, (f * rcp(pdf))[3] — the throughput factor as sample_bsdf forms it —, dfdr, dlnpdf_dr,
+ *                            1.0 if wi_local.z < 1e-4 (the path stops, prb.py:74) else 0.0, t, D}; everything after wi_local is evaluated at it
+ *   ZDR_SHADING_FRAME   in  {n[3] (unit normal), d[3]}
+ *                       out {tangent[3], binormal[3], normal[3] of make_onb(n), to_local(onb, d)[3], to_world(onb, to_local(onb, d))[3]}
+ * The call only enqueues on `stream`.  ZDR_E_INVALID for a null scene, an unknown mode, or null in / out with n > 0; n = 0 does nothing.
+ * It checks the functions' arithmetic as compiled into this kernel, not the instances inlined into the path kernels (the path-by-path
+ * parity tests run those). */
+enum { ZDR_SHADING_EVAL = 0, ZDR_SHADING_SAMPLE = 1, ZDR_SHADING_FRAME = 2 };
+int zdr_shading_dump(zdr_scene *scene, int32_t mode, const float *in, uint32_t n, float *out, void *stream);
+
 /* Host-only: builds the acceleration structure exactly as zdr_scene_create does and returns it,
  * without touching a GPU, so that the CPU test-suite can run an emulation of the device traversal
  * on the very data the kernels read (tests/test_bvh_emulation.py).  tri_xyz: ntris x 9 world-space

@@ -80,6 +80,10 @@ def lib(variant: str = "ieee"):
         L.zdro_ggx_sample_pdf.argtypes = [fp, fp, C.c_float]
         L.zdro_ggx_sample.argtypes = [fp, C.c_float, C.c_float, fp, fp]
         L.zdro_ggx_brdf_grad.argtypes = [fp, fp, fp, C.c_float, fp, fp]
+        L.zdro_ggx_dlnpdf_dr.restype = C.c_float
+        L.zdro_ggx_dlnpdf_dr.argtypes = [fp, fp, C.c_float]
+        L.zdro_ggx_eval_batch.argtypes = [fp, C.c_int, fp]
+        L.zdro_ggx_sample_batch.argtypes = [fp, C.c_int, fp]
         L.zdro_generate_ray.argtypes = [C.POINTER(Params), C.c_float, C.c_float, fp, fp]
         L.zdro_offset_ray_origin.argtypes = [fp, fp, fp]
         L.zdro_read_bsdf.argtypes = [fp, C.c_int, C.c_int, C.c_float, C.c_float, fp]

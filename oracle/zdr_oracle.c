@@ -1517,3 +1517,26 @@ int zdro_path_dump(const zdro_scene *s, const zdro_params *P, const float *mater
 float zdro_ggx_dlnpdf_dr(const float wo[3], const float wi[3], float r) {
     return ggx_dlnpdf_dr(V3(wo[0], wo[1], wo[2]), V3(wi[0], wi[1], wi[2]), r);
 }
+
+/* Batches of the point functions above, for tests/brdf_cases.py: each row goes through the very zdro_ggx_* entry point (no formula
+ * is repeated here).  eval rows: in {wo[3], wi[3], r, diffuse[3], g[3]} (13 floats), out {f[3], pdf, grad[4] for cotangent g,
+ * d f / d r (grad[3] for cotangent (1, 0, 0)), dlnpdf_dr} (10 floats).  sample rows: in {wo[3], r, u_lobe, u2[2]} (7 floats), out wi[3]. */
+void zdro_ggx_eval_batch(const float *in, int n, float *out) {
+    static const float e0[3] = {1.0f, 0.0f, 0.0f};
+    for (int i = 0; i < n; i++) {
+        const float *a = in + 13 * (size_t)i;
+        float *o = out + 10 * (size_t)i, g1[4];
+        zdro_ggx_brdf(a, a + 3, a + 7, a[6], o);
+        o[3] = zdro_ggx_sample_pdf(a, a + 3, a[6]);
+        zdro_ggx_brdf_grad(a, a + 3, a + 7, a[6], a + 10, o + 4);
+        zdro_ggx_brdf_grad(a, a + 3, a + 7, a[6], e0, g1);
+        o[8] = g1[3];
+        o[9] = zdro_ggx_dlnpdf_dr(a, a + 3, a[6]);
+    }
+}
+void zdro_ggx_sample_batch(const float *in, int n, float *out) {
+    for (int i = 0; i < n; i++) {
+        const float *a = in + 7 * (size_t)i;
+        zdro_ggx_sample(a, a[3], a[4], a + 5, out + 3 * (size_t)i);
+    }
+}

@@ -118,6 +118,9 @@ void zdro_ggx_sample(const float wo[3], float roughness, float u_lobe, const flo
 void zdro_ggx_brdf_grad(const float wo[3], const float wi[3], const float diffuse[3], float roughness,
                         const float g[3], float out[4]);
 float zdro_ggx_dlnpdf_dr(const float wo[3], const float wi[3], float r);
+/* batches of the five point functions above, row by row through those very entry points (layouts: zdr_oracle.c) */
+void zdro_ggx_eval_batch(const float *in, int n, float *out);
+void zdro_ggx_sample_batch(const float *in, int n, float *out);
 void zdro_generate_ray(const zdro_params *, float px, float py, float o[3], float d[3]);
 void zdro_offset_ray_origin(const float p[3], const float n[3], float out[3]);
 void zdro_read_bsdf(const float *material, int tex_h, int tex_w, float u, float v, float out[4]);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 r"""Which kernels does a source change actually touch?  Compiles csrc/zdr_kernels.hip of a git revision and of the working tree to gfx950
-assembly (hipcc -S, CPU only) and compares every kernel's instruction stream, labels normalised.  A kernel reported `identical` runs the
+assembly (hipcc -S, CPU only) and compares every kernel's instruction stream, labels normalised, and its kernel descriptor
+(the .amdhsa_ resource directives: VGPRs, SGPRs, LDS, scratch).  A kernel reported `identical` runs the
 very same machine code: no timing is needed for it — and one that is NOT expected to change and does is the thing to time first.
 (Round 4: a sampler change meant for the direct kernels shifted the register allocation of the BVH forward kernel and moved five spill
 operations into its walk loop, +8 %; it had been A/B-timed on the Cornell box only.)
@@ -27,8 +28,15 @@ FLAGS = ["-O3", "-munsafe-fp-atomics", "-fno-slp-vectorize", "--offload-arch=gfx
 def assemble(tree, out):
     subprocess.run([HIPCC, *FLAGS, "-I" + os.path.join(tree, "include"), "-I" + os.path.join(tree, "zdr_amd", "csrc"),
                     os.path.join(tree, "zdr_amd", "csrc", "zdr_kernels.hip"), "-o", out], check=True, capture_output=True)
-    kernels, name = {}, None
+    kernels, name, res, rname = {}, None, {}, None
     for line in open(out):
+        r = re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", line)      # the kernel descriptor: registers, LDS, scratch, the enabled SGPR inputs
+        if r:
+            rname = r.group(1); res[rname] = []
+        elif line.strip() == ".end_amdhsa_kernel":
+            rname = None
+        elif rname:
+            res[rname].append(line.strip())
         m = re.match(r"^(_Z\w+):\s", line)
         if m and ".type" not in line:
             name = m.group(1); kernels[name] = []
@@ -36,10 +44,13 @@ def assemble(tree, out):
             name = None
         elif name and line.startswith("\t") and not line.strip().startswith((";", ".")):
             kernels[name].append(re.sub(r"\.?L?BB\d+_\d+", "L", line.strip()))
+    for k in kernels:                                           # resources ride along as the tail of the instruction stream: `identical` covers both
+        kernels[k] += ["; " + l for l in res.get(k, [])]
     return kernels
 
 
 def stats(body):
+    body = [l for l in body if not l.startswith("; ")]
     return len(body), sum(l.startswith("v_") for l in body), sum(l.startswith("scratch_") for l in body)
 
 

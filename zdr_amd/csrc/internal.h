@@ -89,6 +89,7 @@ int zdr_launch_trace(const DScene &S, int accel_is_bvh, int any, const float *ra
                      int32_t *out_i, float *out_f, hipStream_t stream);
 int zdr_launch_trace_fused(const DScene &S, const float *shadow, const float *next, const int32_t *need, uint32_t n, int backward_layout,
                            int32_t *occluded, int32_t *out_i, float *out_f, hipStream_t stream);   // BVH scenes only
+int zdr_launch_shading_dump(int mode, const float *in, uint32_t n, float *out, hipStream_t stream);   // rows of 16 floats, include/zdr.h
 int zdr_launch_sampler_dump(const SamplerCfg &C, const int32_t *queries, uint32_t n, int32_t nvert,
                             int32_t rr_depth, float *out, int as_path_kernels, int *batched, hipStream_t stream);
 int zdr_launch_path_dump(const DScene &S, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, int accel_is_bvh,

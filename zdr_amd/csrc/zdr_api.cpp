@@ -1548,6 +1548,16 @@ extern "C" int zdr_path_dump(zdr_scene *s, const zdr_render_params *p, const flo
     return ZDR_OK;
 }
 
+extern "C" int zdr_shading_dump(zdr_scene *s, int32_t mode, const float *in, uint32_t n, float *out, void *stream) {
+    if (!s) return fail(ZDR_E_INVALID, "null argument");
+    if (mode != ZDR_SHADING_EVAL && mode != ZDR_SHADING_SAMPLE && mode != ZDR_SHADING_FRAME) return fail(ZDR_E_INVALID, "unknown shading dump mode");
+    if (n == 0) return ZDR_OK;
+    if (!in || !out) return fail(ZDR_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(s->device));
+    if (zdr_launch_shading_dump(mode, in, n, out, (hipStream_t)stream)) return fail(ZDR_E_HIP, "shading dump launch failed");
+    return ZDR_OK;
+}
+
 extern "C" int zdr_sampler_dump(zdr_scene *s, int32_t sampler, uint32_t seed, uint32_t spp, const int32_t *queries, uint32_t n,
                                 int32_t nvert, int32_t rr_depth, float *out, void *stream) {
     if (!s || !queries || !out || nvert < 0) return fail(ZDR_E_INVALID, "bad argument");

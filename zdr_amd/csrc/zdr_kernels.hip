@@ -1368,6 +1368,58 @@ int zdr_launch_path_dump(const DScene &S_in, const RenderCfg &R, const SamplerCf
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ---------------------------------------------------------------------------- shading dump
+// Test hook (zdr_shading_dump, include/zdr.h): lane i is row i and calls the device functions of microfacet.h, brdf_grad and the
+// shading frame (scene.h) as sample_bsdf / nee_terms / the collocated integrator call them — no formula is written a second time.
+// This compiles those functions into a kernel of its own: it runs their arithmetic, not the instances inlined into k_path /
+// k_path_bwd, whose registers and contraction the compiler chooses afresh (the path parity tests run those).  16 floats in, 16 out.
+__global__ void k_shading_dump(int mode, const float *in, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *a = in + 16 * (size_t)i;
+    float *o = out + 16 * (size_t)i;
+    float r[16];
+    for (int k = 0; k < 16; k++) r[k] = 0.0f;
+    if (mode == ZDR_SHADING_EVAL) {
+        const f3 wo = ld3(a), wi = ld3(a + 3), diffuse = ld3(a + 7), ct = ld3(a + 10);
+        const float roughness = a[6];
+        const GgxTerms g = ggx_terms(wo, wi, roughness);
+        const f3 f = ggx_brdf_from(g, wi, diffuse);
+        float dlnp;
+        const float dfdr = ggx_dfdr_from(g, wo, wi, roughness, dlnp);
+        const float4 gr = brdf_grad(wi.z * ZDR_INV_PI, dfdr, ct);
+        r[0] = f.x; r[1] = f.y; r[2] = f.z; r[3] = ggx_pdf_from(g, wo, wi); r[4] = dfdr; r[5] = dlnp; r[6] = g.t; r[7] = g.D;
+        r[8] = gr.x; r[9] = gr.y; r[10] = gr.z; r[11] = gr.w;
+    } else if (mode == ZDR_SHADING_SAMPLE) {                   // the first lines of sample_bsdf (integrators.h)
+        const f3 wo = ld3(a), diffuse = ld3(a + 4);
+        const float roughness = a[3], u_lobe = a[7];
+        f2 u_dir; u_dir.x = a[8]; u_dir.y = a[9];
+        const f3 wi_local = ggx_sample(wo, roughness, u_lobe, u_dir);
+        const GgxTerms g = ggx_terms(wo, wi_local, roughness);
+        const float pdf = ggx_pdf_from(g, wo, wi_local);
+        const f3 f = ggx_brdf_from(g, wi_local, diffuse);
+        const float inv_p = rcp(pdf);
+        const f3 w = f * inv_p;
+        float dlnp;
+        const float dfdr = ggx_dfdr_from(g, wo, wi_local, roughness, dlnp);
+        r[0] = wi_local.x; r[1] = wi_local.y; r[2] = wi_local.z; r[3] = pdf; r[4] = w.x; r[5] = w.y; r[6] = w.z;
+        r[7] = dfdr; r[8] = dlnp; r[9] = (wi_local.z < 1e-4f) ? 1.0f : 0.0f; r[10] = g.t; r[11] = g.D;
+    } else {                                                   // ZDR_SHADING_FRAME
+        const f3 nrm = ld3(a), d = ld3(a + 3);
+        const Onb onb = make_onb(nrm);
+        const f3 l = to_local(onb, d), w = to_world(onb, l);
+        r[0] = onb.tangent.x; r[1] = onb.tangent.y; r[2] = onb.tangent.z; r[3] = onb.binormal.x; r[4] = onb.binormal.y; r[5] = onb.binormal.z;
+        r[6] = onb.normal.x; r[7] = onb.normal.y; r[8] = onb.normal.z; r[9] = l.x; r[10] = l.y; r[11] = l.z; r[12] = w.x; r[13] = w.y; r[14] = w.z;
+    }
+    for (int k = 0; k < 16; k++) o[k] = r[k];
+}
+
+int zdr_launch_shading_dump(int mode, const float *in, uint32_t n, float *out, hipStream_t st) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_shading_dump, dim3((n + 63) / 64), dim3(64), 0, st, mode, in, n, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ---------------------------------------------------------------------------- sampler dump
 template <int SK>
 __global__ void k_sampler_dump(SamplerCfg C, const int32_t *q, uint32_t n, int nvert, int rr_depth, float *out) {

@@ -691,6 +691,17 @@ class Scene:
                                         occ.data_ptr(), ip.data_ptr(), bt.data_ptr(), self._stream()))
         return occ, ip, bt
 
+    SHADING_MODES = {"eval": 0, "sample": 1, "frame": 2}
+
+    def shading_dump(self, mode, rows):
+        """The shading math point by point (include/zdr.h, zdr_shading_dump): ``mode`` "eval" | "sample" | "frame", ``rows`` (n, 16)
+        float32 laid out as the header says -> (n, 16) float32.  No geometry is read; the scene only names the device."""
+        rows = rows.to(device=self.device, dtype=torch.float32).contiguous()
+        assert rows.ndim == 2 and rows.shape[1] == 16, rows.shape
+        out = torch.empty_like(rows)
+        N.check(N.lib().zdr_shading_dump(self._handle, self.SHADING_MODES[mode], rows.data_ptr(), rows.shape[0], out.data_ptr(), self._stream()))
+        return out
+
     def sampler_dump(self, queries, spp, seed=0, nvert=3, rr_depth=RR_DEPTH):
         """queries: (n, 3) int32 cuda {px, py, sample_index} -> (n, 2 + 8*nvert) float32 sampler draws."""
         q = queries.reshape(-1, 3).to(device=self.device, dtype=torch.int32).contiguous()
