@@ -149,6 +149,22 @@ int zdr_scene_set_envmap(zdr_scene *scene, const float *tex, uint32_t tex_h, uin
  * hipMalloc'ed memory is).  ZDR_E_INVALID when no environment map is set or tex is misaligned. */
 int zdr_scene_set_envmap_texture(zdr_scene *scene, const float *tex, void *stream);
 
+/* Rebuilds the importance-sampling tables (alias_prob, alias_idx, pdf) on the device from the environment texture as it is on `stream`,
+ * after an earlier zdr_scene_set_envmap_texture on that stream for instance: the device form of what the host does before
+ * zdr_scene_set_envmap (zdr_amd/envmap.py, build_tables; compensate_mis != 0 subtracts the map's mean, row by row, and clamps at 0).
+ * In place and stream-ordered: no host copy, no synchronisation, and pointers and sizes stay as they are, so the call can be captured and
+ * graphs captured earlier read the new tables.  Two calls on the same texture give the same bytes.  An entry whose weight is 0 in a table
+ * with a positive total gets probability 0 and is nobody's alias: a texel whose pdf is 0 is never drawn.  The sample map must be the
+ * 512 x 256 one (ZDR_E_UNSUPPORTED otherwise).  The first call on a handle allocates about 0.5 MiB of workspace, kept until
+ * zdr_scene_destroy: made while the stream is capturing it is refused (ZDR_E_INVALID: call once before capturing).
+ * ZDR_E_INVALID when no environment map is set. */
+int zdr_scene_update_envmap_sampling(zdr_scene *scene, int compensate_mis, void *stream);
+
+/* Copies the importance-sampling tables to HOST arrays in the layout of zdr_scene_set_envmap (alias_prob / alias_idx: map_h + map_h x map_w
+ * entries, the marginal table first, then the rows; pdf: map_h x map_w) and synchronises `stream`.  For tests, and for handing the tables
+ * to another renderer.  ZDR_E_INVALID when no environment map is set. */
+int zdr_scene_get_envmap_sampling(zdr_scene *scene, float *alias_prob, int32_t *alias_idx, float *pdf, void *stream);
+
 /* Tables of the PMJ02bn sampler (pmj02bn.py:9-18; the reference's own are absent,
  * .MISSING_LARGE_BLOBS).  HOST inputs, copied to the device: pmj [nsets][nsamples][2] uint32
  * (value / 2^32), bn [ntex][res][res] uint16 (value / 2^16). */

@@ -30,7 +30,7 @@ EXPORTS = ("zdr_version", "zdr_abi_version", "zdr_last_error", "zdr_scene_create
            "zdr_scene_set_emissions", "zdr_scene_set_envmap", "zdr_scene_set_pmj02bn_tables", "zdr_render_forward", "zdr_render_backward",
            "zdr_render_stats", "zdr_scene_check", "zdr_trace_closest", "zdr_trace_any", "zdr_sampler_dump", "zdr_vertex_sampler_dump", "zdr_path_dump", "zdr_trace_fused", "zdr_shading_dump", "zdr_debug_build_accel", "zdr_debug_never_occluders",
            "zdr_scene_set_material_slots", "zdr_render_forward_materials", "zdr_render_backward_materials",
-           "zdr_scene_set_envmap_texture", "zdr_render_backward_env", "zdr_render_backward_materials_env",
+           "zdr_scene_set_envmap_texture", "zdr_scene_update_envmap_sampling", "zdr_scene_get_envmap_sampling", "zdr_render_backward_env", "zdr_render_backward_materials_env",
            "zdr_scene_set_emission_values", "zdr_render_backward_emission", "zdr_render_backward_materials_emission",
            "zdr_render_aovs", "zdr_render_aovs_backward",
            "zdr_denoise_workspace_bytes", "zdr_denoise", "zdr_denoise_backward")
@@ -96,6 +96,8 @@ def lib():
     L.zdr_render_forward_materials.argtypes = [vp, C.POINTER(RenderParams), fp, ip, C.c_uint32, fp, vp]
     L.zdr_render_backward_materials.argtypes = [vp, C.POINTER(RenderParams), fp, fp, ip, C.c_uint32, fp, vp]
     L.zdr_scene_set_envmap_texture.argtypes = [vp, fp, vp]
+    L.zdr_scene_update_envmap_sampling.argtypes = [vp, C.c_int, vp]
+    L.zdr_scene_get_envmap_sampling.argtypes = [vp, fp, ip, fp, vp]
     L.zdr_render_backward_env.argtypes = [vp, C.POINTER(RenderParams), fp, fp, fp, fp, vp]
     L.zdr_render_backward_materials_env.argtypes = [vp, C.POINTER(RenderParams), fp, fp, ip, C.c_uint32, fp, fp, vp]
     L.zdr_scene_set_emission_values.argtypes = [vp, fp, vp]

@@ -68,6 +68,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # the denoiser's kernels, a translation unit of their own (linked last: the path kernels' code object stays the first in the
         # library); no fast-math either, and none of the measurement macros reach it
         ("zdr_denoise.hip", ["-O3", "-fno-slp-vectorize"]),
+        # the environment-table kernels, likewise on their own and behind the denoiser's; no contraction: the weight map follows the
+        # host's float32 operations one by one (zdr_amd/envmap.py)
+        ("zdr_envmap.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
     ]
     procs = []
     for src, extra in jobs:

@@ -13,6 +13,8 @@
 
 #define ZDR_DENOISE_LAUNCHER_REF __attribute__((weak))   // (csrc/denoise.h)
 #include "denoise.h"
+#define ZDR_ENVMAP_LAUNCHER_REF __attribute__((weak))    // (csrc/envsample.h)
+#include "envsample.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -480,6 +482,7 @@ struct zdr_scene {
     int32_t *d_light_insts = nullptr, *d_inst_tri_begin = nullptr, *d_slot_of_tri = nullptr;
     uint32_t *d_pmj = nullptr; uint16_t *d_bn = nullptr; SamplerTables tab{};
     float4 *d_env_tex = nullptr; float *d_alias_prob = nullptr, *d_env_pdf = nullptr; int32_t *d_alias_idx = nullptr;
+    EnvSamplingScratch *d_env_scratch = nullptr;            // workspace of zdr_scene_update_envmap_sampling: allocated by its first call, kept until zdr_scene_destroy
     float4 *d_partial = nullptr; size_t partial_bytes = 0;
     unsigned long long *d_tile_masks = nullptr; size_t tile_mask_bytes = 0;   // camera-ray candidate pairs per tile (k_tile_masks)
     float tile_mask_key[24]; bool tile_mask_key_set = false;                  // camera + tile grid the masks in the buffer were built for (all tiles of the rectangle, whatever the shard)
@@ -795,7 +798,7 @@ extern "C" int zdr_scene_destroy(zdr_scene *s) {
     if (!s) return ZDR_OK;
     (void)hipSetDevice(s->device);
     if (!s->isect_in_nodes) (void)hipFree(s->d_isect); (void)hipFree(s->d_pairs); (void)hipFree(s->d_ppairs); (void)hipFree(s->d_shade); (void)hipFree(s->d_nodes); (void)hipFree(s->d_emission); (void)hipFree(s->d_light_insts); (void)hipFree(s->d_light_tris); (void)hipFree(s->d_light_range); (void)hipFree(s->d_emission4);
-    (void)hipFree(s->d_inst_tri_begin); (void)hipFree(s->d_slot_of_tri); (void)hipFree(s->d_pmj); (void)hipFree(s->d_bn); (void)hipFree(s->d_env_tex); (void)hipFree(s->d_alias_prob); (void)hipFree(s->d_alias_idx); (void)hipFree(s->d_env_pdf); (void)hipFree(s->d_partial); (void)hipFree(s->d_ring); (void)hipFree(s->d_work_counters); (void)hipFree(s->d_tile_masks); (void)hipFree(s->d_cells); (void)hipFree(s->d_counters); (void)hipFree(s->d_error); (void)hipFree(s->d_inst_slot); (void)hipFree(s->d_inst_slot0); (void)hipFree(s->d_emit_acc);
+    (void)hipFree(s->d_inst_tri_begin); (void)hipFree(s->d_slot_of_tri); (void)hipFree(s->d_pmj); (void)hipFree(s->d_bn); (void)hipFree(s->d_env_tex); (void)hipFree(s->d_alias_prob); (void)hipFree(s->d_alias_idx); (void)hipFree(s->d_env_pdf); (void)hipFree(s->d_env_scratch); (void)hipFree(s->d_partial); (void)hipFree(s->d_ring); (void)hipFree(s->d_work_counters); (void)hipFree(s->d_tile_masks); (void)hipFree(s->d_cells); (void)hipFree(s->d_counters); (void)hipFree(s->d_error); (void)hipFree(s->d_inst_slot); (void)hipFree(s->d_inst_slot0); (void)hipFree(s->d_emit_acc);
     for (void *p : s->retired) (void)hipFree(p);
     delete s;
     return ZDR_OK;
@@ -885,6 +888,72 @@ extern "C" int zdr_scene_set_envmap_texture(zdr_scene *s, const float *tex, void
     // in place, stream-ordered, by a kernel (graph-safe like the zero-fills): the pointer the kernels and any captured graph hold stays valid
     if (zdr_launch_copy(s->d_env_tex, tex, (size_t)s->ds.env_h * (size_t)s->ds.env_w * sizeof(float4), (hipStream_t)stream))
         return fail(ZDR_E_HIP, "copy launch failed");
+    return ZDR_OK;
+}
+
+// The constants of the table kernels (csrc/envsample.h), in double: the 289 tap weights of the weight map's filter and their sum
+// (zdr_amd/envmap.py, weight_map) and the row factors of the MIS compensation (build_tables).
+static void envmap_sampling_constants(std::vector<double> &row_factor, std::vector<float> &taps) {
+    const int n = ZDR_ENVS_TAPS / 2;
+    taps.assign(sizeof(EnvSamplingScratch::taps) / sizeof(float), 0.0f);
+    double sum = 0.0;
+    for (int dy = -n; dy <= n; dy++)
+        for (int dx = -n; dx <= n; dx++) {
+            const double ox = dx * 0.125, oy = dy * 0.125;
+            const float w = (float)exp(-4.0 * (ox * ox + oy * oy));
+            taps[(size_t)(dy + n) * ZDR_ENVS_TAPS + (size_t)(dx + n)] = w;
+            sum += (double)w;
+        }
+    taps[ZDR_ENVS_TAPS * ZDR_ENVS_TAPS] = (float)sum;
+    const double pi = 3.14159265358979323846;
+    row_factor.assign(ZDR_ENVS_H, 0.0);
+    double mean = 0.0;
+    for (int y = 0; y < ZDR_ENVS_H; y++) { row_factor[y] = sin((y + 0.5) / ZDR_ENVS_H * pi); mean += row_factor[y]; }
+    mean /= ZDR_ENVS_H;
+    for (int y = 0; y < ZDR_ENVS_H; y++) row_factor[y] /= mean;
+}
+
+extern "C" int zdr_scene_update_envmap_sampling(zdr_scene *s, int compensate_mis, void *stream) {
+    if (!s) return fail(ZDR_E_INVALID, "null scene");
+    if (s->ds.env_count == 0 || !s->d_env_tex) return fail(ZDR_E_INVALID, "the scene has no environment map: zdr_scene_set_envmap first");
+    if (s->ds.map_w != ZDR_ENVS_W || s->ds.map_h != ZDR_ENVS_H)
+        return fail(ZDR_E_UNSUPPORTED, "the sampling tables are rebuilt on the device for a " + std::to_string(ZDR_ENVS_W) + " x " + std::to_string(ZDR_ENVS_H) + " sample map only");
+    if (!zdr_launch_envmap_sampling)                                 // (weak: csrc/envsample.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the environment-table kernels (zdr_envmap.hip)");
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool capturing = stream_is_capturing(st);
+    if (!s->d_env_scratch) {
+        if (capturing) return fail(ZDR_E_INVALID, "the workspace of zdr_scene_update_envmap_sampling would have to be allocated while the stream is capturing: call it once on the handle before capturing");
+        std::vector<double> row_factor; std::vector<float> taps;
+        envmap_sampling_constants(row_factor, taps);
+        EnvSamplingScratch *d = nullptr;
+        HIPCHK(hipMalloc((void **)&d, sizeof(EnvSamplingScratch)));
+        hipError_t e = hipMemcpy(d->row_factor, row_factor.data(), sizeof d->row_factor, hipMemcpyHostToDevice);   // (device addresses only: d is not read here)
+        if (e == hipSuccess) e = hipMemcpy(d->taps, taps.data(), sizeof d->taps, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d); return fail(ZDR_E_HIP, std::string("envmap sampling constants: ") + hipGetErrorString(e)); }
+        s->d_env_scratch = d;
+        s->device_bytes += sizeof(EnvSamplingScratch);
+    }
+    if (capturing) s->captured = true;                              // a graph names the tables and the workspace from now on (zdr_scene)
+    EnvSamplingArgs A;
+    A.tex = s->d_env_tex; A.env_h = s->ds.env_h; A.env_w = s->ds.env_w;
+    A.alias_prob = s->d_alias_prob; A.alias_idx = s->d_alias_idx; A.pdf = s->d_env_pdf;
+    A.scratch = s->d_env_scratch; A.compensate_mis = compensate_mis ? 1 : 0;
+    if (zdr_launch_envmap_sampling(A, st)) return fail(ZDR_E_HIP, "environment-table kernel launch failed");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_scene_get_envmap_sampling(zdr_scene *s, float *alias_prob, int32_t *alias_idx, float *pdf, void *stream) {
+    if (!s || !alias_prob || !alias_idx || !pdf) return fail(ZDR_E_INVALID, "null argument");
+    if (s->ds.env_count == 0 || !s->d_alias_prob) return fail(ZDR_E_INVALID, "the scene has no environment map: zdr_scene_set_envmap first");
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n_alias = (size_t)s->ds.map_h + (size_t)s->ds.map_h * (size_t)s->ds.map_w;
+    HIPCHK(hipMemcpyAsync(alias_prob, s->d_alias_prob, n_alias * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(alias_idx, s->d_alias_idx, n_alias * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pdf, s->d_env_pdf, (size_t)s->ds.map_h * (size_t)s->ds.map_w * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return ZDR_OK;
 }
 

@@ -12,7 +12,7 @@
     scene.add_envmap(sky)                                             # the map and its importance-sampling tables
     env = torch.tensor(sky, device="cuda", requires_grad=True)        # (H, 2H, 3|4) or (H, H, 3|4)
     image = scene.render(material, res=(W, H), spp=256, envmap=env)   # env.grad after backward(); tables stay fixed
-    scene.update_envmap_sampling(env.detach())                        # now and then: tables rebuilt from the current map
+    scene.update_envmap_sampling(None, on_device=True)                # tables rebuilt from the current map, on the GPU and in place
 
     f = scene.render_aovs(material, res=(W, H), spp=16, seed=0)       # first-hit feature buffers of render()'s camera samples
     f.albedo, f.normal, f.depth, f.coverage, f.instance               # views of f.data, (H, W, 16); albedo / roughness carry the graph
@@ -162,6 +162,7 @@ class Scene:
         self.rr_depth = RR_DEPTH
         self.prb_mode = "expectation"      # or "detached": the reference's constant-roulette / constant-MIS adjoint; "literal": with the BSDF-sample seed of prb.py:162 as written (include/zdr.h)
         self.env_count = 0
+        self._env_compensate_mis = True    # what the environment map's tables were last built with (add_envmap, update_envmap_sampling)
         self._handle = None
         self._material_slots = None
         self._uploaded_slots = None        # the slot table the native scene holds (None: never uploaded)
@@ -244,15 +245,44 @@ class Scene:
                                              pdf.ctypes.data, E.SAMPLE_MAP_W, E.SAMPLE_MAP_H))
         self.env_count = 1
         self._envmap = (img, prob, alias, pdf)        # kept for tests / the oracle
+        self._env_compensate_mis = bool(compensate_mis)
 
-    def update_envmap_sampling(self, image, compensate_mis=True):
+    def update_envmap_sampling(self, image, compensate_mis=True, on_device=False):
         """Rebuilds the environment map's importance-sampling tables from ``image`` (and uploads it as the map): ``add_envmap`` for
         a map that is being optimised.  ``render(..., envmap=)`` keeps the tables of the last ``add_envmap`` or of this call, and
         differentiates with them held fixed.  Like ``add_envmap`` this synchronises the device and replaces the scene's buffers,
-        so graphs captured before no longer see the map."""
+        so graphs captured before no longer see the map.
+
+        ``on_device=True`` rebuilds them on the GPU instead (include/zdr.h, zdr_scene_update_envmap_sampling): ``image`` is a float32
+        tensor on the scene's device, of add_envmap's size as ``render(..., envmap=)`` takes it, or None for the map the scene holds.
+        It is uploaded in place (set_envmap_texture) and the tables are rebuilt in the scene's buffers, on torch's current stream:
+        no copy to the host, no synchronisation, no new buffers, so the call can be captured in a graph once it has been made once,
+        and graphs captured earlier read the new tables.  The host copies of the tables in ``_envmap[1:]`` are then stale until
+        ``envmap_sampling_tables()`` refreshes them."""
+        if on_device:
+            if self.env_count == 0:
+                raise ValueError("the scene has no environment map: call add_envmap first")
+            if image is not None:
+                self.set_envmap_texture(self._prepare_envmap(image))
+            N.check(N.lib().zdr_scene_update_envmap_sampling(self._handle, 1 if compensate_mis else 0, self._stream()))
+            self._env_compensate_mis = bool(compensate_mis)
+            return
         if image is None:
             raise ValueError("update_envmap_sampling needs a map (add_envmap(None) removes it)")
         self.add_envmap(image.detach() if isinstance(image, torch.Tensor) else image, compensate_mis=compensate_mis)
+
+    def envmap_sampling_tables(self):
+        """(alias_prob, alias_idx, pdf) as the device holds them now, as NumPy arrays in add_envmap's layout (the marginal table first,
+        then the rows); synchronises torch's current stream.  Also refreshes the host copies in ``_envmap[1:]``, which an on-device
+        rebuild leaves behind."""
+        from . import envmap as E
+        if self.env_count == 0:
+            raise ValueError("the scene has no environment map: call add_envmap first")
+        n = E.SAMPLE_MAP_H + E.SAMPLE_MAP_H * E.SAMPLE_MAP_W
+        prob, alias, pdf = np.empty(n, np.float32), np.empty(n, np.int32), np.empty(E.SAMPLE_MAP_H * E.SAMPLE_MAP_W, np.float32)
+        N.check(N.lib().zdr_scene_get_envmap_sampling(self._handle, prob.ctypes.data, alias.ctypes.data, pdf.ctypes.data, self._stream()))
+        self._envmap = (self._envmap[0], prob, alias, pdf)
+        return prob, alias, pdf
 
     def _prepare_envmap(self, envmap):
         """The tensor given as ``render(..., envmap=)``, prepared in torch (envmap.prepare_tensor) so that autograd returns its
@@ -567,10 +597,12 @@ class Scene:
         gradient, and torch.cat's own backward hands each material its part).  With a prepared environment map ``env`` also
         differentiable w.r.t. the map, with an (ninst, 3) tensor ``emissions`` w.r.t. the lights' emissions (one of the two at most)."""
         @staticmethod
-        def forward(ctx, material, self, res, spp, seed, env, emissions, dims, slots):
+        def forward(ctx, material, self, res, spp, seed, env, emissions, dims, slots, update_sampling=False):
             if env is not None:                            # the map this forward renders with: uploaded now, saved for the backward
                 env = env.detach().clone()
                 self.set_envmap_texture(env)
+                if update_sampling:                        # tables of THIS map, built on the device; the backward holds them fixed
+                    self.update_envmap_sampling(None, compensate_mis=self._env_compensate_mis, on_device=True)
             if emissions is not None:                      # likewise the emissions: a detached copy becomes the scene's values
                 self.set_emission_values(emissions.detach().clone())
             ctx.save_for_backward(material)
@@ -606,9 +638,9 @@ class Scene:
             else:                                          # slots = the forward's table: uploaded again if material_slots changed in between
                 scene.render_backward_materials(grad_output, mat_grad, material.detach(), res, spp, seed, dims=dims, camera=ctx.camera, slots=slots,
                                                 d_env=d_env, d_emission=d_emission)
-            return mat_grad, None, None, None, None, d_env, d_emission, None, None
+            return mat_grad, None, None, None, None, d_env, d_emission, None, None, None
 
-    def render(self, material, *, res, spp, seed=0, envmap=None, emissions=None):
+    def render(self, material, *, res, spp, seed=0, envmap=None, emissions=None, update_sampling=False):
         """Renders the scene; differentiable w.r.t. ``material`` ((Ht, Wt, 4) float32 on the GPU).
         res = (width, height); returns (height, width, 4) (render.py:225-241).
 
@@ -621,6 +653,9 @@ class Scene:
         for RGB, a 1:2 map made square), must then have the size given to add_envmap, and becomes the scene's map: later renders
         without ``envmap=`` use it too.  The importance-sampling tables stay those of add_envmap or of the last
         update_envmap_sampling, and the gradient holds them fixed.  At most 15 materials with ``envmap=``.
+        ``update_sampling=True`` rebuilds the tables from this map on the GPU (update_envmap_sampling, on_device, with the
+        ``compensate_mis`` the tables were last built with) right after the forward uploads it; the gradient still holds them fixed,
+        which is exact for the rendered seed and unbiased overall: the estimator's expectation does not depend on the sampling density.
 
         ``emissions``: a float32 (ninst, 3) tensor on the GPU whose rows the render uses as the emission of the models that are lights
         now (the light list of ``Scene(...)`` or of the last ``update_lights``) and differentiates (path and direct; collocated reads
@@ -631,9 +666,11 @@ class Scene:
         with ``envmap=``."""
         if emissions is not None:
             check_emissions(emissions, self.inst_count, self.device, envmap)
+        if update_sampling and envmap is None:
+            raise ValueError("update_sampling=True needs envmap=: it rebuilds the tables of the map this call uploads")
         env = None if envmap is None else self._prepare_envmap(envmap)
         if not isinstance(material, (list, tuple)) and self._material_slots is None:
-            return Scene.RenderOperator.apply(material, self, res, spp, seed, env, emissions, None, None)
+            return Scene.RenderOperator.apply(material, self, res, spp, seed, env, emissions, None, None, bool(update_sampling))
         mats = list(material) if isinstance(material, (list, tuple)) else [material]
         if env is not None and len(mats) > N.MAX_MATERIALS - 1:
             raise ValueError(f"{len(mats)} materials given with envmap=: at most {N.MAX_MATERIALS - 1} (the map takes the last entry of the material table)")
@@ -642,7 +679,7 @@ class Scene:
         slots = resolve_material_slots(self._material_slots, self.emissions, len(mats))
         dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
         packed = mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
-        return Scene.RenderOperator.apply(packed, self, res, spp, seed, env, emissions, dims, slots)
+        return Scene.RenderOperator.apply(packed, self, res, spp, seed, env, emissions, dims, slots, bool(update_sampling))
 
     def render_duvdxy(self, material, *, res, spp, seed=0):
         """Gradient of the texture coordinates w.r.t. screen-space coordinates: a (height, width, 4) tensor
