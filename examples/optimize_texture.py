@@ -9,6 +9,11 @@ image loss through scene.render's PRB backward), on the assets this repository s
 albedo buffer of the same camera samples, differentiable in the material; neighbours on another model or on the background do not count).
 --denoise puts the feature-guided denoiser between the step's render and the loss (scene.render_denoised): the L1 loss of a noisy
 render is a biased estimate of the loss of the converged image, the filtered render's less so.
+--texel-prior W adds W times a smoothness prior in TEXTURE space that stops at chart borders: the mean over the covered texels of
+|material - denoise(material, guides)|, the guides being scene.texel_aovs(material).as_guides() — the per-texel normal and instance
+of the surface the texel lies on (seam padding included: texels that a lookup reaches take part).
+--mask-unreached writes texture_diffuse.png with the texels that no lookup can ever read (reach 0: they never receive gradient and
+stay random noise) black.
 """
 import argparse
 import os
@@ -22,7 +27,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from zdr_amd import Camera, Scene, float3
+from zdr_amd import Camera, Scene, denoise as zdr_denoise, float3
 
 ASSETS = os.path.join(ROOT, "tests", "golden", "assets")
 
@@ -46,7 +51,15 @@ def albedo_smoothness_loss(f):
     return dx.mean() + dy.mean()
 
 
-def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0, denoise=False):
+def texel_prior_loss(material, f, guides):
+    """Mean over the covered texels of |material - its chart-aware filter| (f: zdr_amd.TexelAovs, guides: f.as_guides())."""
+    smooth = zdr_denoise(material, guides, demodulate=False, sigma_depth=0, sigma_albedo=0)
+    covered = f.coverage > 0
+    return ((material - smooth).abs().sum(-1) * covered).sum() / covered.sum().clamp_min(1)
+
+
+def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0, denoise=False,
+        texel_prior=0.0, mask_unreached=False):
     scene = Scene([(os.path.join(ASSETS, "cboxuv.obj"), None, float3(0.0)),
                    (os.path.join(ASSETS, "cbox-light.obj"), None, float3(17, 12, 4))], integrator=integrator)
     scene.camera = Camera(fov=50 / 180 * 3.1415926, origin=float3(-0.2, 2.6, 6.0), target=float3(-0.2, 2.6, -2.5), up=float3(0.0, 1.0, 0.0))
@@ -57,6 +70,8 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
     material = torch.rand((tex, tex, 4), device="cuda", generator=g).requires_grad_()
     opt = torch.optim.Adam([material], lr=0.02)
     losses = []
+    texels = scene.texel_aovs(material.detach()) if (texel_prior > 0.0 or mask_unreached) else None   # geometry only: once
+    guides = texels.as_guides() if texel_prior > 0.0 else None
     for it in range(iters):
         opt.zero_grad()
         step_seed = rng.randint(0, 2147483646)
@@ -64,6 +79,8 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
         loss = (image[..., :3] - image_gt[..., :3]).abs().mean()
         if albedo_smoothness > 0.0:
             loss = loss + albedo_smoothness * albedo_smoothness_loss(scene.render_aovs(material, res=(res, res), spp=spp, seed=step_seed))
+        if texel_prior > 0.0:
+            loss = loss + texel_prior * texel_prior_loss(material, texels, guides)
         loss.backward()
         opt.step()
         with torch.no_grad():
@@ -75,7 +92,7 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
         os.makedirs(out, exist_ok=True)
         save_png(os.path.join(out, "target.png"), image_gt)
         save_png(os.path.join(out, "result.png"), scene.render(material.detach(), res=(res, res), spp=max(256, 4 * spp)))
-        save_png(os.path.join(out, "texture_diffuse.png"), material.detach())
+        save_png(os.path.join(out, "texture_diffuse.png"), material.detach() * (texels.reach[..., None] if mask_unreached else 1.0))
         duvdxy = scene.render_duvdxy(material.detach(), res=(res, res), spp=16)            # screen -> texture Jacobian (example.py)
         footprint = torch.det(duvdxy.reshape(res, res, 2, 2)).abs() * tex * tex
         Image.fromarray((footprint.clamp(0, 1) ** 0.454 * 255).to(torch.uint8).cpu().numpy()).save(os.path.join(out, "footprints.png"))
@@ -92,5 +109,8 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=None)
     ap.add_argument("--albedo-smoothness", type=float, default=0.0)
     ap.add_argument("--denoise", action="store_true")
+    ap.add_argument("--texel-prior", type=float, default=0.0)
+    ap.add_argument("--mask-unreached", action="store_true")
     a = ap.parse_args()
-    run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness, denoise=a.denoise)
+    run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness, denoise=a.denoise,
+        texel_prior=a.texel_prior, mask_unreached=a.mask_unreached)

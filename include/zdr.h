@@ -309,6 +309,54 @@ int zdr_denoise(const zdr_denoise_params *params, const float *aovs, const float
 int zdr_denoise_backward(const zdr_denoise_params *params, const float *aovs, const float *d_out, float *d_image, void *workspace,
                          void *stream);
 
+/* Texture-space feature buffers: what each TEXEL of a material is, where the screen-side buffers of zdr_render_aovs say what each pixel
+ * sees.  The models are rasterised into the texture: which texels lie on a model, which a lookup can ever read (and so can ever receive
+ * gradient), where a texel sits in the world, what its normal is and how much surface it stands for.  The layout is that of
+ * zdr_render_aovs, so zdr_denoise takes the buffers as guides: a chart-aware filter of a material or of its gradient.
+ *
+ * Material, size, pixel space.  The call takes a material index m and a texture size tex_h x tex_w.  Pixel space is that of read_bsdf /
+ * tex_footprint (csrc/scene.h): X = u (tex_w - 1), Y = (1 - v) (tex_h - 1), computed in float32 as those products.  Texel (x, y) is the
+ * lattice point (x, y).
+ * Triangles.  The triangles of m are those of every instance whose entry in the table of zdr_scene_set_material_slots is m (never set:
+ * every entry is -1 and the buffers are empty).  Each has a global input index g = inst_tri_begin[inst] + prim.
+ * coverage(x, y) = 1 iff the lattice point lies in the closed pixel-space triangle of some triangle of m, of either winding.  The test is
+ * watertight: the edge function of an edge is evaluated with its two endpoints in canonical order (lexicographic on (X, Y)) and the caller
+ * flips the sign, without contraction, so that two triangles that share an edge compute the same float and disagree in sign only; a lattice
+ * point on a shared edge is claimed by at least one of them.  The winner is the covering triangle with the lowest g.
+ * reach(x, y) = 1 iff the closed box [x - 1, x + 1] x [y - 1, y + 1] meets the closed triangle of some triangle of m (a separating-axis
+ * test with the two box axes and the three edge normals), or the texel is covered: the texels a bilinear lookup somewhere on the triangle
+ * can read, conservative only on a rim of measure zero where the weight is exactly 0.  The reach winner is the lowest g among the reaching
+ * triangles.  coverage is a subset of reach.
+ * Degenerate triangles.  A triangle with a NaN pixel-space coordinate is skipped.  One whose pixel-space area (the edge function of the side
+ * opposite corner 0, at corner 0) is 0 or NaN gives no coverage, and reach by the bounding-box part of the test alone (conservative).  A
+ * 1 x 1 texture makes every triangle degenerate: reach 1, coverage 0.
+ * UVs outside [0, 1] are NOT clamped: the bounding box is clipped to the texture and what falls outside is ignored.  Limitation: the CLAMP
+ * addressing of lookups out there, which folds them onto the border texels, is not modelled.
+ * Sample point.  A covered texel: the lattice point, with barycentrics = the three edge functions over their sum, in the coverage winner.
+ * A texel that is only reached: the closest point, Euclidean in pixel space, of the reach winner's closed triangle (the nearest of the
+ * closest points of its three sides; barycentrics (1 - t, t) along that side).  A degenerate winner: its corner 0.  Attributes are
+ * interpolated as surface_interact does: (a0 w0 + a1 w1) + a2 w2, the normal normalised afterwards.
+ * A texel holds ZDR_AOV_CHANNELS floats, the tensor is (tex_h, tex_w, 16):
+ *   floats 0..3        0 (no material is read: the buffers depend on the geometry and the slot table only)
+ *   floats 4..6, 7     normal, texel_size    normalised interpolated normal at the sample point;  world length of one texel,
+ *                                            sqrt(world area / pixel-space area) of the winner, 0 for a degenerate winner
+ *   floats 8..10, 11   position, coverage    world position at the sample point;  0 or 1
+ *   floats 12, 13      reach, -              0 or 1;  0
+ *   floats 14, 15      instance, slot        the winner's instance and m, as floats;  -1 and -1 where reach = 0 (every other float is 0 there)
+ * Float 7 sits where the screen buffers hold depth: zdr_denoise's relative-depth term then keeps texels of very different density apart
+ * (sigma_depth = 0 switches it off).  zdr_denoise reads float 11 as coverage: copy float 12 there to let reached-only texels take part.
+ * The result is bit-identical from run to run and between ZDR_ACCEL_BRUTE and ZDR_ACCEL_BVH (the key is g, not the slot).
+ *
+ * aovs (DEVICE, tex_h x tex_w x 16) is overwritten.  The caller provides `workspace`, zdr_texel_aovs_workspace_bytes(tex_h, tex_w) bytes
+ * (0 = invalid size).  Three launches on `stream` — clear the keys, rasterise with atomicMin of g, resolve — that never allocate and never
+ * synchronise, so the call can be captured in a HIP graph without a call before.  The scene is only read.
+ * ZDR_E_INVALID: a null or misaligned (16 bytes) pointer, a size <= 0, material outside 0 .. ZDR_MAX_MATERIALS - 1, an output that overlaps
+ * the workspace.  ZDR_E_UNSUPPORTED: more than 2^26 texels, or a dimension above 2^24.  A material that no instance has gives all-empty
+ * buffers; it is not an error. */
+size_t zdr_texel_aovs_workspace_bytes(int32_t tex_h, int32_t tex_w);   /* 0 = invalid size */
+int zdr_scene_texel_aovs(zdr_scene *scene, int32_t material, int32_t tex_h, int32_t tex_w,
+                         float *aovs /* DEVICE tex_h x tex_w x 16 */, void *workspace, void *stream);
+
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,
  * shadow rays (one per shaded vertex, prb.py:59), shaded vertices, emitter hits via BSDF sampling, NaN-dropped samples,

@@ -10,6 +10,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libzdr_hip.so")
+TEXEL_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_texel.so")   # the texture-space kernels: a dependency of libzdr_hip.so, found beside it
 
 COLLOCATED, DIRECT, PATH, UVGRAD = 0, 1, 2, 3
 SAMPLER_CMJ, SAMPLER_PMJ02BN = 0, 1
@@ -33,7 +34,8 @@ EXPORTS = ("zdr_version", "zdr_abi_version", "zdr_last_error", "zdr_scene_create
            "zdr_scene_set_envmap_texture", "zdr_scene_update_envmap_sampling", "zdr_scene_get_envmap_sampling", "zdr_render_backward_env", "zdr_render_backward_materials_env",
            "zdr_scene_set_emission_values", "zdr_render_backward_emission", "zdr_render_backward_materials_emission",
            "zdr_render_aovs", "zdr_render_aovs_backward",
-           "zdr_denoise_workspace_bytes", "zdr_denoise", "zdr_denoise_backward")
+           "zdr_denoise_workspace_bytes", "zdr_denoise", "zdr_denoise_backward",
+           "zdr_texel_aovs_workspace_bytes", "zdr_scene_texel_aovs")
 
 
 class CameraPOD(C.Structure):
@@ -78,8 +80,9 @@ def lib():
     from . import build as _build
     if _build.stale():
         _build.build()
-    if not os.path.exists(LIB_PATH):
-        raise ZdrError(f"{LIB_PATH} is missing: the zdr HIP back end was not built (python -m zdr_amd.build)")
+    for path in (LIB_PATH, TEXEL_LIB_PATH):
+        if not os.path.exists(path):
+            raise ZdrError(f"{path} is missing: the zdr HIP back end was not built (python -m zdr_amd.build)")
     L = C.CDLL(LIB_PATH)
     vp, fp, ip = C.c_void_p, C.c_void_p, C.c_void_p   # raw addresses (host numpy or device data_ptr)
     L.zdr_version.restype = C.c_char_p
@@ -109,6 +112,9 @@ def lib():
     L.zdr_denoise_workspace_bytes.restype = C.c_size_t
     L.zdr_denoise.argtypes = [C.POINTER(DenoiseParams), fp, fp, fp, vp, vp]
     L.zdr_denoise_backward.argtypes = [C.POINTER(DenoiseParams), fp, fp, fp, vp, vp]
+    L.zdr_texel_aovs_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.zdr_texel_aovs_workspace_bytes.restype = C.c_size_t
+    L.zdr_scene_texel_aovs.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp, vp, vp]
     L.zdr_render_stats.argtypes = [vp, C.POINTER(RenderParams), fp, C.POINTER(C.c_uint64), vp]
     L.zdr_scene_check.argtypes = [vp, vp]
     L.zdr_trace_closest.argtypes = [vp, fp, C.c_uint32, ip, fp, vp]

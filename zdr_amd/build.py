@@ -15,6 +15,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(CSRC, "libzdr_hip.so")
+# The texture-space kernels (zdr_texel.hip) are a library of their own that libzdr_hip.so names as a dependency and finds beside itself
+# ($ORIGIN): libzdr_hip.so keeps exactly the code objects it had, path kernels first (tests/test_envmap_sampling_resources.py counts them).
+TEXEL_LIB = os.path.join(CSRC, "libzdr_texel.so")
 ARCH = "gfx950"
 
 
@@ -44,7 +47,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not os.path.exists(LIB):
+    if not os.path.exists(LIB) or not os.path.exists(TEXEL_LIB):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -71,6 +74,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # the environment-table kernels, likewise on their own and behind the denoiser's; no contraction: the weight map follows the
         # host's float32 operations one by one (zdr_amd/envmap.py)
         ("zdr_envmap.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
+        # the texture-space rasteriser, last and linked into libzdr_texel.so; no contraction: two triangles that share an edge must
+        # compute the same edge function, whatever it is inlined into (include/zdr.h, zdr_scene_texel_aovs)
+        ("zdr_texel.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -84,10 +90,13 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    texel_obj = objs.pop()                                  # (zdr_texel.o: the last job)
+    links = [[hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", TEXEL_LIB, texel_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-Wl,-rpath,$ORIGIN"]]
+    for cmd in links:
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
     return LIB
 
 

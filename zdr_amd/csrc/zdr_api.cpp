@@ -15,6 +15,8 @@
 #include "denoise.h"
 #define ZDR_ENVMAP_LAUNCHER_REF __attribute__((weak))    // (csrc/envsample.h)
 #include "envsample.h"
+#define ZDR_TEXEL_LAUNCHER_REF __attribute__((weak))     // (csrc/texel.h)
+#include "texel.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1556,6 +1558,41 @@ extern "C" int zdr_denoise_backward(const zdr_denoise_params *p, const float *ao
             zdr_launch_denoise_level(R, ZDR_DENOISE_GATHER, 1 << l, guides, A, dst, st)) return fail(ZDR_E_HIP, "denoise level launch failed");
         g = dst;
     }
+    return ZDR_OK;
+}
+
+// ------------------------------------------------------------------- texture-space buffers
+// zdr_scene_texel_aovs (include/zdr.h): argument checks, then the three launches of zdr_texel.hip on the caller's stream.  The handle is
+// only read — the shade records, slot_of_tri, inst_tri_begin and the material-slot table as they are — so nothing is allocated and the
+// call can be captured without a call before.  A table that was never set (every slot -1) travels as a null pointer.
+static int texel_check_size(int32_t tex_h, int32_t tex_w) {
+    if (tex_h <= 0 || tex_w <= 0) return fail(ZDR_E_INVALID, "zdr_scene_texel_aovs: the texture size must be positive");
+    if ((uint64_t)tex_h * (uint64_t)tex_w > ZDR_TEXEL_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, "zdr_scene_texel_aovs: more than 2^26 texels");
+    if (tex_h > ZDR_TEXEL_MAX_DIM || tex_w > ZDR_TEXEL_MAX_DIM) return fail(ZDR_E_UNSUPPORTED, "zdr_scene_texel_aovs: a dimension above 2^24 (lattice points must be exact in float32)");
+    return ZDR_OK;
+}
+
+extern "C" size_t zdr_texel_aovs_workspace_bytes(int32_t tex_h, int32_t tex_w) {
+    if (texel_check_size(tex_h, tex_w)) return 0;
+    return (size_t)tex_h * (size_t)tex_w * sizeof(uint2);
+}
+
+extern "C" int zdr_scene_texel_aovs(zdr_scene *s, int32_t material, int32_t tex_h, int32_t tex_w, float *aovs, void *workspace, void *stream) {
+    if (!s || !aovs || !workspace) return fail(ZDR_E_INVALID, "null argument");
+    if ((uintptr_t)aovs % 16 || (uintptr_t)workspace % 16) return fail(ZDR_E_INVALID, "zdr_scene_texel_aovs: aovs and workspace must be 16-byte aligned");
+    if (material < 0 || material >= ZDR_MAX_MATERIALS)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_aovs: material " + std::to_string(material) + " outside [0, " + std::to_string(ZDR_MAX_MATERIALS) + ")");
+    if (int rc = texel_check_size(tex_h, tex_w)) return rc;
+    const size_t n = (size_t)tex_h * (size_t)tex_w;
+    if (denoise_overlap(aovs, 64 * n, {{workspace, 8 * n}})) return fail(ZDR_E_INVALID, "zdr_scene_texel_aovs: aovs must not overlap the workspace");
+    if (!zdr_launch_texel_aovs)                                      // (weak: csrc/texel.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the texture-space kernels (zdr_texel.hip)");
+    HIPCHK(hipSetDevice(s->device));
+    TexelArgs A;
+    A.shade = s->ds.shade; A.slot_of_tri = s->ds.slot_of_tri; A.inst_tri_begin = s->ds.inst_tri_begin; A.inst_slot = s->d_inst_slot;
+    A.ntris = (int32_t)s->ntris; A.material = material; A.tex_h = tex_h; A.tex_w = tex_w;
+    A.keys = (uint2 *)workspace; A.aovs = (float4 *)aovs;
+    if (zdr_launch_texel_aovs(A, (hipStream_t)stream)) return fail(ZDR_E_HIP, "texel feature-buffer launch failed");
     return ZDR_OK;
 }
 

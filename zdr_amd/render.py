@@ -127,6 +127,34 @@ class Aovs:
         return self.data[..., a] if b - a == 1 else self.data[..., a:b]
 
 
+class TexelAovs:
+    """Texture-space feature buffers of ``Scene.texel_aovs`` (include/zdr.h, zdr_scene_texel_aovs): ``data`` is the (H, W, 16) tensor of
+    one material's texels, the attributes are views into it.  ``coverage``: the texel's lattice point lies on a model; ``reach``: a
+    bilinear lookup somewhere on a model can read the texel (so it can receive gradient); ``position``, ``normal``: of the surface at
+    the texel, or at the closest point of the nearest triangle for a texel that is only reached; ``texel_size``: world length of one
+    texel there; ``instance``, ``slot``: the model the texel belongs to and the material index, -1 where ``reach`` is 0.  The buffers
+    depend on the geometry and the slot table only and carry no gradient.  The layout is ``Aovs``'s, so ``denoise`` takes them as guides."""
+    CHANNELS = {"normal": (4, 7), "texel_size": (7, 8), "position": (8, 11), "coverage": (11, 12), "reach": (12, 13),
+                "instance": (14, 15), "slot": (15, 16)}
+
+    def __init__(self, data):
+        self.data = data
+
+    def __getattr__(self, name):
+        if name not in TexelAovs.CHANNELS:
+            raise AttributeError(name)
+        a, b = TexelAovs.CHANNELS[name]
+        return self.data[..., a] if b - a == 1 else self.data[..., a:b]
+
+    def as_guides(self, reached=True):
+        """A copy of ``data`` for ``denoise``, which reads channel 11 as its coverage: with ``reached`` that channel holds ``reach``, so
+        that texels that are only reached take part in the normal and depth terms too — the form for seam padding."""
+        g = self.data.clone()
+        if reached:
+            g[..., 11] = self.data[..., 12]
+        return g
+
+
 def _camera_pod(cam: Camera) -> N.CameraPOD:
     return N.CameraPOD(float(cam.fov), (C.c_float * 3)(*cam.origin), (C.c_float * 3)(*cam.target), (C.c_float * 3)(*cam.up))
 
@@ -483,6 +511,47 @@ class Scene:
         dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
         packed = mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
         return Aovs(Scene.AovOperator.apply(packed, self, res, spp, seed, dims, slots))
+
+    # ------------------------------------------------------------- texture-space buffers
+    def texel_aovs_forward(self, index, tex_hw, *, slots=None, out=None, workspace=None):
+        """The (H, W, 16) texture-space buffers of include/zdr.h, zdr_scene_texel_aovs, for material ``index`` at ``tex_hw`` = (H, W).
+        ``slots``: the slot table to use (default: the one the scene holds).  ``out`` and ``workspace`` (any tensor of at least
+        ``zdr_texel_aovs_workspace_bytes`` bytes) are allocated when not given.  Only enqueues, on torch's current stream."""
+        H, W = int(tex_hw[0]), int(tex_hw[1])
+        if slots is not None:
+            self._upload_slots(check_material_slots(slots, self.inst_count))
+        need = int(N.lib().zdr_texel_aovs_workspace_bytes(H, W))
+        if need == 0:
+            raise N.ZdrError(f"libzdr_hip error: {N.lib().zdr_last_error().decode()}")
+        shape = (H, W, N.AOV_CHANNELS)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        elif workspace.device != self.device or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {self.device}")
+        N.check(N.lib().zdr_scene_texel_aovs(self._handle, int(index), H, W, out.data_ptr(), workspace.data_ptr(), self._stream()))
+        return out
+
+    def texel_aovs(self, material, index=0) -> TexelAovs:
+        """What each texel of ``material[index]`` is: a ``TexelAovs`` whose ``data`` is the (H, W, 16) tensor of include/zdr.h,
+        zdr_scene_texel_aovs, at that material's size — coverage, reach, world position, normal, texel size, instance and slot, with a
+        named view for each.  ``material`` is a tensor or a list exactly as ``render_aovs`` takes it; it is used for its sizes and to
+        resolve the slots only (with one tensor and ``material_slots`` unset only model 0 has material 0).  No gradient."""
+        if not isinstance(material, (list, tuple)) and self._material_slots is None:
+            mats = [material]
+            slots = (0,) + (None,) * (self.inst_count - 1)
+        else:
+            mats = list(material) if isinstance(material, (list, tuple)) else [material]
+            slots = resolve_material_slots(self._material_slots, self.emissions, len(mats))
+        for m in mats:
+            self._check_material(m)
+        if not 0 <= int(index) < len(mats):
+            raise ValueError(f"index {index}: {len(mats)} materials were given")
+        m = mats[int(index)]
+        return TexelAovs(self.texel_aovs_forward(int(index), (int(m.shape[0]), int(m.shape[1])), slots=slots))
 
     def render_denoised(self, material, *, res, spp, seed=0, **denoise_kwargs):
         """``render`` followed by the feature-guided denoiser: ``denoise(render(material), render_aovs(material), **denoise_kwargs)``
