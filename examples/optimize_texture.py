@@ -14,6 +14,9 @@ render is a biased estimate of the loss of the converged image, the filtered ren
 of the surface the texel lies on (seam padding included: texels that a lookup reaches take part).
 --mask-unreached writes texture_diffuse.png with the texels that no lookup can ever read (reach 0: they never receive gradient and
 stay random noise) black.
+--save-lighting writes irradiance.png and openness.png, the texture-space lighting of the material (scene.texel_lighting: direct
+irradiance and the open fraction of the hemisphere per texel), and prints the share of the reached texels that no light sample reached:
+a texel in shadow gets only noise for a gradient, whatever its reach.
 """
 import argparse
 import os
@@ -59,7 +62,7 @@ def texel_prior_loss(material, f, guides):
 
 
 def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0, denoise=False,
-        texel_prior=0.0, mask_unreached=False):
+        texel_prior=0.0, mask_unreached=False, save_lighting=False):
     scene = Scene([(os.path.join(ASSETS, "cboxuv.obj"), None, float3(0.0)),
                    (os.path.join(ASSETS, "cbox-light.obj"), None, float3(17, 12, 4))], integrator=integrator)
     scene.camera = Camera(fov=50 / 180 * 3.1415926, origin=float3(-0.2, 2.6, 6.0), target=float3(-0.2, 2.6, -2.5), up=float3(0.0, 1.0, 0.0))
@@ -70,7 +73,7 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
     material = torch.rand((tex, tex, 4), device="cuda", generator=g).requires_grad_()
     opt = torch.optim.Adam([material], lr=0.02)
     losses = []
-    texels = scene.texel_aovs(material.detach()) if (texel_prior > 0.0 or mask_unreached) else None   # geometry only: once
+    texels = scene.texel_aovs(material.detach()) if (texel_prior > 0.0 or mask_unreached or save_lighting) else None   # geometry only: once
     guides = texels.as_guides() if texel_prior > 0.0 else None
     for it in range(iters):
         opt.zero_grad()
@@ -88,11 +91,21 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
         losses.append(float(loss))
         if verbose and (it % 20 == 0 or it == iters - 1):
             print(f"iteration {it:4d}  L1 image loss {losses[-1]:.5f}", flush=True)
+    if save_lighting:                                              # printed with or without --out; the images need it
+        light = scene.texel_lighting(material.detach(), spp=max(64, spp), texels=texels)
+        reached = texels.reach == 1
+        unlit = reached & (light.irradiance.sum(-1) == 0)
+        if verbose:
+            print(f"texture-space lighting: {int(unlit.sum())} of {int(reached.sum())} reached texels ({float(unlit.sum()) / max(int(reached.sum()), 1):.1%}) "
+                  "were reached by no light sample")
     if out:
         os.makedirs(out, exist_ok=True)
         save_png(os.path.join(out, "target.png"), image_gt)
         save_png(os.path.join(out, "result.png"), scene.render(material.detach(), res=(res, res), spp=max(256, 4 * spp)))
         save_png(os.path.join(out, "texture_diffuse.png"), material.detach() * (texels.reach[..., None] if mask_unreached else 1.0))
+        if save_lighting:
+            save_png(os.path.join(out, "irradiance.png"), light.irradiance / light.irradiance.max().clamp_min(1e-8))
+            save_png(os.path.join(out, "openness.png"), light.openness[..., None].expand(-1, -1, 3))
         duvdxy = scene.render_duvdxy(material.detach(), res=(res, res), spp=16)            # screen -> texture Jacobian (example.py)
         footprint = torch.det(duvdxy.reshape(res, res, 2, 2)).abs() * tex * tex
         Image.fromarray((footprint.clamp(0, 1) ** 0.454 * 255).to(torch.uint8).cpu().numpy()).save(os.path.join(out, "footprints.png"))
@@ -111,6 +124,7 @@ if __name__ == "__main__":
     ap.add_argument("--denoise", action="store_true")
     ap.add_argument("--texel-prior", type=float, default=0.0)
     ap.add_argument("--mask-unreached", action="store_true")
+    ap.add_argument("--save-lighting", action="store_true")
     a = ap.parse_args()
     run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness, denoise=a.denoise,
-        texel_prior=a.texel_prior, mask_unreached=a.mask_unreached)
+        texel_prior=a.texel_prior, mask_unreached=a.mask_unreached, save_lighting=a.save_lighting)

@@ -357,6 +357,55 @@ size_t zdr_texel_aovs_workspace_bytes(int32_t tex_h, int32_t tex_w);   /* 0 = in
 int zdr_scene_texel_aovs(zdr_scene *scene, int32_t material, int32_t tex_h, int32_t tex_w,
                          float *aovs /* DEVICE tex_h x tex_w x 16 */, void *workspace, void *stream);
 
+/* Texture-space lighting: whether any light reaches a texel, where zdr_scene_texel_aovs says where the texel is.  Per texel, the direct
+ * irradiance on the normal's side and the open fraction of the hemisphere (sky visibility; with a finite max_distance, ambient
+ * occlusion) — a baker's lightmap, and for texture recovery the mask "lit by nothing".
+ *
+ * Input.  texel_aovs (DEVICE, tex_h x tex_w x 16) has the layout of zdr_scene_texel_aovs.  Only floats 4..6 (normal n), 8..10 (position p)
+ * and 12 (reach) are read: any buffer with those channels is a valid set of surface points.  n is used as it is (not normalised again).
+ * Output.  out (DEVICE, tex_h x tex_w x 4, the shape of a material, so zdr_denoise filters it with the same guides):
+ *   floats 0..2        irradiance         direct irradiance arriving on the side n points to, per colour channel
+ *   float 3            openness           fraction of the cosine-weighted hemisphere about n that is free up to max_distance, in [0, 1]
+ * A texel whose reach is not 1, or whose p or n holds a NaN, is four zeros.
+ * Draws.  For texel (x, y) and sample s the sampler is the render kernels': sampler_make(cfg, x, y, perm_seed, s) with perm_seed =
+ * xxhash32_4(x, y, seed, 0) for CMJ and 0 for pmj02bn.  Four draws, always all four, always in this order: u_ao = next2, u_pick = next,
+ * u_prim = next, u_pt = next2 — floats 0..5 of zdr_sampler_dump with nvert = 1.  The light sampler gets u_prim and u_pt handed over, so
+ * its environment branch uses u_pt and ignores u_prim: the sequence does not depend on the branch.
+ * Irradiance of one sample.  L = sample_light(p, u_pick, u_prim, u_pt) over the scene's current lights (zdr_scene_update_lights,
+ * zdr_scene_set_emission_values) and, if one is set, the environment map, which counts as a light exactly as in the render kernels;
+ * c = dot(n, L.wi).  If c > 0, L.eval has a positive component and the segment from p towards L.wi over (1e-4, L.dist) is free (the shadow
+ * ray of the direct integrator), the sample adds L.eval * (c / max(L.pdf, 1e-4)).  A contribution that holds a NaN or an infinity is dropped.
+ * Every primitive can occlude the segment: the brute-force accelerator's mask of primitives that no shadow segment FROM THE SCENE'S OWN
+ * SURFACES can meet is not applied, since p is the caller's and may lie anywhere.
+ * Openness of one sample.  The direction is to_world(make_onb(n), (r cos phi, r sin phi, sqrt(1 - u_ao.x))), r = sqrt(u_ao.x),
+ * phi = 2 pi u_ao.y — the cosine lobe of the BSDF sampler.  The sample adds 1 unless ANY primitive of the scene meets the ray over
+ * (1e-4, max_distance): every primitive counts, also those a shadow segment can never meet.  A direction of NaNs hits nothing.
+ * Sample range.  irradiance = (1 / spp) x the sum over s in [sample_begin, sample_end), a subrange of [0, spp); openness = the count of
+ * open samples of that range / spp, correctly rounded.  The outputs of disjoint ranges add up to the whole: progressive accumulation.
+ * Determinism.  The same bits from run to run: no float atomic; the any-hit walks are per lane; where several lanes share a texel's
+ * samples (lane j of 2^k takes s = begin + j, begin + j + 2^k, ...; k depends on tex_h x tex_w and the length of the range only) each
+ * adds its samples in order and the lanes' sums are added in lane order.  Nothing depends on the launch grid.
+ * No gradient is defined.
+ *
+ * The caller provides `workspace`, zdr_texel_lighting_workspace_bytes(tex_h, tex_w) bytes (0 = invalid size): a counter and the list of
+ * texels to shade.  Three launches on `stream` — clear the counter, compact, shade — that never allocate and never synchronise, with a
+ * grid that does not depend on the list's length, so the call can be captured in a HIP graph without a call before.  The scene is only read.
+ * ZDR_E_INVALID: a null or misaligned (16 bytes) pointer, struct_size other than sizeof(zdr_texel_lighting_params), a size <= 0, spp = 0,
+ * a sample range that is empty or not within [0, spp), max_distance that is not positive, an unknown sampler, spp beyond the pmj02bn
+ * tables, an output that overlaps the workspace or the input, a workspace that overlaps the input.  ZDR_E_UNSUPPORTED: more than 2^26
+ * texels; pmj02bn without tables; a library linked without these kernels. */
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_texel_lighting_params) */
+    int32_t tex_h, tex_w;
+    uint32_t spp, sample_begin, sample_end;
+    uint32_t seed;
+    int32_t sampler;                   /* ZDR_SAMPLER_* */
+    float max_distance;                /* > 0; 1e30 = unbounded (sky visibility) */
+} zdr_texel_lighting_params;
+size_t zdr_texel_lighting_workspace_bytes(int32_t tex_h, int32_t tex_w);   /* 0 = invalid size */
+int zdr_scene_texel_lighting(zdr_scene *scene, const zdr_texel_lighting_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
+                             float *out /* DEVICE tex_h x tex_w x 4 */, void *workspace, void *stream);
+
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,
  * shadow rays (one per shaded vertex, prb.py:59), shaded vertices, emitter hits via BSDF sampling, NaN-dropped samples,

@@ -2,6 +2,6 @@
 (``from zdr import Scene, Camera, float3``; /root/reference/__init__.py:1)."""
 from .denoiser import denoise
 from .mathtypes import Camera, float3, float4x4
-from .render import Aovs, Scene, TexelAovs
+from .render import Aovs, Scene, TexelAovs, TexelLighting
 
-__all__ = ["Scene", "Aovs", "TexelAovs", "Camera", "float3", "float4x4", "denoise"]
+__all__ = ["Scene", "Aovs", "TexelAovs", "TexelLighting", "Camera", "float3", "float4x4", "denoise"]

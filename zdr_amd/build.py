@@ -18,6 +18,8 @@ LIB = os.path.join(CSRC, "libzdr_hip.so")
 # The texture-space kernels (zdr_texel.hip) are a library of their own that libzdr_hip.so names as a dependency and finds beside itself
 # ($ORIGIN): libzdr_hip.so keeps exactly the code objects it had, path kernels first (tests/test_envmap_sampling_resources.py counts them).
 TEXEL_LIB = os.path.join(CSRC, "libzdr_texel.so")
+# The texture-space light baker (zdr_bake.hip) likewise: a third library, so that libzdr_texel.so keeps exactly its three kernels too.
+BAKE_LIB = os.path.join(CSRC, "libzdr_bake.so")
 ARCH = "gfx950"
 
 
@@ -47,7 +49,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not os.path.exists(LIB) or not os.path.exists(TEXEL_LIB):
+    if not os.path.exists(LIB) or not os.path.exists(TEXEL_LIB) or not os.path.exists(BAKE_LIB):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -77,6 +79,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # the texture-space rasteriser, last and linked into libzdr_texel.so; no contraction: two triangles that share an edge must
         # compute the same edge function, whatever it is inlined into (include/zdr.h, zdr_scene_texel_aovs)
         ("zdr_texel.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
+        # the texture-space light baker, linked into libzdr_bake.so: the path kernels' device code (sample_light, the any-hit walks)
+        # under the path kernels' flags, without the atomics option (it has no float atomic)
+        ("zdr_bake.hip", ["-O3", "-fno-slp-vectorize"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -90,9 +95,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    texel_obj = objs.pop()                                  # (zdr_texel.o: the last job)
+    bake_obj = objs.pop()                                   # (zdr_bake.o: the last job)
+    texel_obj = objs.pop()                                  # (zdr_texel.o: the one before)
     links = [[hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", TEXEL_LIB, texel_obj],
-             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-Wl,-rpath,$ORIGIN"]]
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BAKE_LIB, bake_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake",
+              "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:

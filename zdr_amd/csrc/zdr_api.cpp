@@ -17,6 +17,8 @@
 #include "envsample.h"
 #define ZDR_TEXEL_LAUNCHER_REF __attribute__((weak))     // (csrc/texel.h)
 #include "texel.h"
+#define ZDR_BAKE_LAUNCHER_REF __attribute__((weak))      // (csrc/bake.h)
+#include "bake.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1593,6 +1595,51 @@ extern "C" int zdr_scene_texel_aovs(zdr_scene *s, int32_t material, int32_t tex_
     A.ntris = (int32_t)s->ntris; A.material = material; A.tex_h = tex_h; A.tex_w = tex_w;
     A.keys = (uint2 *)workspace; A.aovs = (float4 *)aovs;
     if (zdr_launch_texel_aovs(A, (hipStream_t)stream)) return fail(ZDR_E_HIP, "texel feature-buffer launch failed");
+    return ZDR_OK;
+}
+
+// ------------------------------------------------------------------- texture-space lighting
+// zdr_scene_texel_lighting (include/zdr.h): argument checks, then the three launches of zdr_bake.hip on the caller's stream.  The handle
+// is only read — the records, the acceleration structure, the light table and the environment tables as they are — so nothing is
+// allocated and the call can be captured without a call before.
+static int bake_check_size(int32_t tex_h, int32_t tex_w) {
+    if (tex_h <= 0 || tex_w <= 0) return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting: the texture size must be positive");
+    if ((uint64_t)tex_h * (uint64_t)tex_w > ZDR_BAKE_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, "zdr_scene_texel_lighting: more than 2^26 texels");
+    return ZDR_OK;
+}
+
+extern "C" size_t zdr_texel_lighting_workspace_bytes(int32_t tex_h, int32_t tex_w) {
+    if (bake_check_size(tex_h, tex_w)) return 0;
+    return ZDR_BAKE_HEADER_BYTES + (((size_t)tex_h * (size_t)tex_w * sizeof(uint32_t) + 15) & ~(size_t)15);
+}
+
+extern "C" int zdr_scene_texel_lighting(zdr_scene *s, const zdr_texel_lighting_params *p, const float *texel_aovs, float *out, void *workspace, void *stream) {
+    if (!s || !p || !texel_aovs || !out || !workspace) return fail(ZDR_E_INVALID, "null argument");
+    if (p->struct_size != sizeof(zdr_texel_lighting_params))
+        return fail(ZDR_E_INVALID, "zdr_texel_lighting_params.struct_size is " + std::to_string(p->struct_size) + ", this library expects " + std::to_string(sizeof(zdr_texel_lighting_params)));
+    if ((uintptr_t)texel_aovs % 16 || (uintptr_t)out % 16 || (uintptr_t)workspace % 16)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting: texel_aovs, out and workspace must be 16-byte aligned");
+    if (int rc = bake_check_size(p->tex_h, p->tex_w)) return rc;
+    if (p->spp == 0) return fail(ZDR_E_INVALID, "spp must be positive");
+    if (p->sample_begin >= p->sample_end || p->sample_end > p->spp)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting: the sample range [" + std::to_string(p->sample_begin) + ", " + std::to_string(p->sample_end) + ") is empty or not within [0, spp)");
+    if (!(p->max_distance > 0.0f)) return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting: max_distance must be positive");
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, wbytes = zdr_texel_lighting_workspace_bytes(p->tex_h, p->tex_w);
+    if (denoise_overlap(out, 16 * n, {{workspace, wbytes}, {texel_aovs, 64 * n}})) return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting: out must not overlap the workspace or texel_aovs");
+    if (denoise_overlap(workspace, wbytes, {{texel_aovs, 64 * n}})) return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting: the workspace must not overlap texel_aovs");
+    SamplerCfg C;
+    if (int rc = make_sampler_cfg(s, p->sampler, p->seed, p->spp, C)) return rc;
+    if (!zdr_launch_texel_lighting)                                  // (weak: csrc/bake.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the texture-space lighting kernels (zdr_bake.hip)");
+    HIPCHK(hipSetDevice(s->device));
+    DScene S = s->ds;
+    S.shadow_pairs = ~0ull;      // every pair: the host proves its mask of never-occluders for origins on the scene's own surfaces only, and these points are the caller's
+    BakeArgs B;
+    B.texels = (const float4 *)texel_aovs; B.out = (float4 *)out;
+    B.count = (uint32_t *)workspace; B.list = (uint32_t *)((char *)workspace + ZDR_BAKE_HEADER_BYTES);
+    B.ntexels = (uint32_t)n; B.tex_w = p->tex_w; B.sample_begin = p->sample_begin; B.sample_end = p->sample_end;
+    B.inv_spp = 1.0f / (float)p->spp; B.spp_f = (float)p->spp; B.max_distance = p->max_distance;
+    if (zdr_launch_texel_lighting(S, s->accel_is_bvh, C, B, (hipStream_t)stream)) return fail(ZDR_E_HIP, "texel lighting launch failed");
     return ZDR_OK;
 }
 

@@ -155,6 +155,24 @@ class TexelAovs:
         return g
 
 
+class TexelLighting:
+    """Texture-space lighting of ``Scene.texel_lighting`` (include/zdr.h, zdr_scene_texel_lighting): ``data`` is the (H, W, 4) tensor of
+    one material's texels, the shape of a material, so ``denoise`` filters it with ``TexelAovs.as_guides()``.  ``irradiance`` (H, W, 3):
+    direct irradiance on the side the texel's normal points to; ``openness`` (H, W): the open fraction of the cosine-weighted hemisphere,
+    up to ``max_distance``.  Four zeros where ``reach`` is 0.  No gradient."""
+
+    def __init__(self, data):
+        self.data = data
+
+    @property
+    def irradiance(self):
+        return self.data[..., 0:3]
+
+    @property
+    def openness(self):
+        return self.data[..., 3]
+
+
 def _camera_pod(cam: Camera) -> N.CameraPOD:
     return N.CameraPOD(float(cam.fov), (C.c_float * 3)(*cam.origin), (C.c_float * 3)(*cam.target), (C.c_float * 3)(*cam.up))
 
@@ -552,6 +570,57 @@ class Scene:
             raise ValueError(f"index {index}: {len(mats)} materials were given")
         m = mats[int(index)]
         return TexelAovs(self.texel_aovs_forward(int(index), (int(m.shape[0]), int(m.shape[1])), slots=slots))
+
+    # ------------------------------------------------------------- texture-space lighting
+    def texel_lighting_forward(self, texel_data, *, spp, seed=0, samples=None, max_distance=None, sampler=None, out=None, workspace=None):
+        """The (H, W, 4) lighting buffer of include/zdr.h, zdr_scene_texel_lighting — direct irradiance (floats 0..2) and openness
+        (float 3) — for the surface points of ``texel_data``, an (H, W, 16) tensor in the layout of ``texel_aovs_forward`` of which the
+        normal, the position and ``reach`` are read.  ``samples`` = (begin, end): a subrange of [0, spp) (default: all; the outputs of
+        disjoint ranges add up).  ``max_distance``: how far an openness ray looks (default 1e30: sky visibility; finite: ambient
+        occlusion).  ``sampler``: "cmj" or "pmj02bn" (default: the scene's).  ``out`` and ``workspace`` (any tensor of at least
+        ``zdr_texel_lighting_workspace_bytes`` bytes) are allocated when not given.  Only enqueues, on torch's current stream."""
+        if texel_data.ndim != 3 or texel_data.shape[2] != N.AOV_CHANNELS or texel_data.dtype != torch.float32 or texel_data.device != self.device:
+            raise ValueError(f"texel_data must be a float32 (H, W, {N.AOV_CHANNELS}) tensor on {self.device}")
+        texel_data = texel_data.detach().contiguous()
+        H, W = int(texel_data.shape[0]), int(texel_data.shape[1])
+        sampler = self.sampler if sampler is None else sampler
+        if sampler not in N.SAMPLERS:
+            raise ValueError(f"unknown sampler {sampler!r}")
+        if sampler == "pmj02bn" and not getattr(self, "_pmj_tables_set", False):
+            from . import pmj02bn_tables                                # (as _params: generated tables when none were set)
+            self.set_pmj02bn_tables(*pmj02bn_tables.default_tables(verbose=True))
+        need = int(N.lib().zdr_texel_lighting_workspace_bytes(H, W))
+        if need == 0:
+            raise N.ZdrError(f"libzdr_hip error: {N.lib().zdr_last_error().decode()}")
+        shape = (H, W, 4)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        elif workspace.device != self.device or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {self.device}")
+        p = N.TexelLightingParams()
+        p.struct_size = C.sizeof(N.TexelLightingParams)
+        p.tex_h, p.tex_w, p.spp, p.seed, p.sampler = H, W, int(spp), int(seed) & 0xFFFFFFFF, N.SAMPLERS[sampler]
+        begin, end = (0, int(spp)) if samples is None else (int(samples[0]), int(samples[1]))
+        if not 0 <= begin < end <= int(spp):
+            raise ValueError(f"samples {(begin, end)} must be a non-empty subrange of [0, {int(spp)})")
+        p.sample_begin, p.sample_end = begin, end
+        p.max_distance = 1e30 if max_distance is None else float(max_distance)
+        N.check(N.lib().zdr_scene_texel_lighting(self._handle, C.byref(p), texel_data.data_ptr(), out.data_ptr(), workspace.data_ptr(), self._stream()))
+        return out
+
+    def texel_lighting(self, material, index=0, *, spp=16, seed=0, samples=None, max_distance=None, texels=None) -> TexelLighting:
+        """Whether any light reaches each texel of ``material[index]``: a ``TexelLighting`` whose ``data`` is the (H, W, 4) tensor of
+        include/zdr.h, zdr_scene_texel_lighting, at that material's size — ``irradiance`` and ``openness``.  ``material`` and ``index``
+        are taken as ``texel_aovs`` takes them; ``texels``: a ``TexelAovs`` already computed for them (without it one is computed
+        here).  The lights are the scene's current ones (``update_lights``, ``set_emission_values``), the environment map included.
+        No gradient."""
+        if texels is None:
+            texels = self.texel_aovs(material, index)
+        return TexelLighting(self.texel_lighting_forward(texels.data, spp=spp, seed=seed, samples=samples, max_distance=max_distance))
 
     def render_denoised(self, material, *, res, spp, seed=0, **denoise_kwargs):
         """``render`` followed by the feature-guided denoiser: ``denoise(render(material), render_aovs(material), **denoise_kwargs)``
