@@ -498,6 +498,46 @@ int zdr_trace_fused(zdr_scene *scene, const float *shadow_rays, const float *nex
 enum { ZDR_SHADING_EVAL = 0, ZDR_SHADING_SAMPLE = 1, ZDR_SHADING_FRAME = 2 };
 int zdr_shading_dump(zdr_scene *scene, int32_t mode, const float *in, uint32_t n, float *out, void *stream);
 
+/* The bilinear texture lookup row by row (test hook): row i (lane i of a kernel of its own) calls the device functions the kernels shade
+ * with — read_bsdf and read_bsdf_in, each with 32-bit byte offsets ("narrow") and with 64-bit addresses ("wide"), and env_lookup of the
+ * scene's environment map — at a uv the caller chooses, outside [0, 1] included.  materials / dims / nmat: as zdr_render_*_materials takes
+ * them (DEVICE packed float4 texels; HOST nmat x {h, w}; 1 <= nmat <= ZDR_MAX_MATERIALS).  The scene's material slots are not consulted.
+ * rows (DEVICE float32, n x 4): {u, v, bits(material index), ignored}.
+ * out  (DEVICE float32, n x 20): {read_bsdf narrow[4], read_bsdf wide[4], read_bsdf_in narrow[4], read_bsdf_in wide[4],
+ *                                 env_lookup(u, v)[3] (zeros when the scene has no map), 0}.
+ * ZDR_E_INVALID, before anything is launched or written, for a null scene or dims, nmat outside [1, 16], a size < 1, a material index
+ * outside [0, nmat), or null materials / rows / out with n > 0; n = 0 does nothing.  The rows are read back and checked on the host, so the
+ * call synchronises `stream` and cannot be captured into a graph (ZDR_E_UNSUPPORTED on a capturing stream).
+ * It checks the functions as compiled into this kernel, not the instances inlined into the render kernels (the parity tests run those). */
+int zdr_texture_lookup(zdr_scene *scene, const float *materials, const int32_t *dims, uint32_t nmat, const float *rows, uint32_t n,
+                       float *out, void *stream);
+
+/* The lookup's adjoint row by row (test hook): the staging-cell scatter of the backward kernels and the fold into the gradient texture,
+ * on gradients, uvs and ballots the caller chooses.  The call does what a backward call does around its kernel: it lays the staging
+ * cells out and zeroes them with the code the render calls use, launches a kernel of its own that runs scatter_queue_init[_cells], the
+ * pushes and scatter_finish (csrc/scene.h), and then the fold of the backward calls (k_cells_to_grad / k_material_cells_to_grad), which
+ * ADDS to what the gradient buffers hold.
+ * rows (DEVICE float32, n x 8): {u, v, g[4], bits(material index), ignored}; a negative material index is an inactive row.
+ * One wave per block; wave b makes `rounds` pushes, and in round r its lane l holds row 64 (b rounds + r) + l and calls scatter_push
+ * with active = the row exists (< n) and is active: the caller decides every ballot and with it every flush of the queue.
+ * form: the template instance of the render kernels that runs —
+ *   ZDR_SCATTER_SINGLE     one material (nmat = 1), as zdr_render_backward: copies from the size of its cell grid;
+ *   ZDR_SCATTER_TABLE      a material table, as zdr_render_backward_materials: the per-material cell layout;
+ *   ZDR_SCATTER_TABLE_ENV  a material table (nmat <= 15) and the scene's environment map as entry 15, as zdr_render_backward_materials_env:
+ *                          a row whose material index is 15 is a gradient of the map at (u, v), in env_lookup's footprint, and lands in d_env.
+ * dims / nmat: as above.  d_materials: DEVICE, the packed gradient, every material's texels x 4.  d_env: DEVICE (env_h, env_w, 4), the third
+ * form only (ignored otherwise).  copies (HOST, ZDR_MAX_MATERIALS int32, or NULL): receives how many copies of its staging cells each
+ * material was given (entry 15: the map's, third form; unused entries 0) — which of the storage regimes of csrc/scene.h the call ran in.
+ * ZDR_E_INVALID, before anything is launched or written, for a null scene or dims, an unknown form, nmat outside [1, 16] (or != 1, or > 15,
+ * as the form demands), a size < 1, rounds outside [1, 65536], the third form on a scene without a map, a material index >= nmat (other
+ * than 15 in the third form), or null rows / d_materials / d_env (third form) with n > 0.  n = 0 reports the copies and does nothing else.
+ * The rows are read back and checked on the host, so the call synchronises `stream` and cannot be captured (ZDR_E_UNSUPPORTED).
+ * It checks the functions as compiled into this kernel, not the instances inlined into k_path_bwd, k_simple and k_aov_bwd (the rendered
+ * gradient parity tests run those); the fold kernels are the very kernels the backward calls launch. */
+enum { ZDR_SCATTER_SINGLE = 0, ZDR_SCATTER_TABLE = 1, ZDR_SCATTER_TABLE_ENV = 2 };
+int zdr_texture_scatter(zdr_scene *scene, int32_t form, const int32_t *dims, uint32_t nmat, const float *rows, uint32_t n, uint32_t rounds,
+                        float *d_materials, float *d_env, int32_t *copies, void *stream);
+
 /* Host-only: builds the acceleration structure exactly as zdr_scene_create does and returns it,
  * without touching a GPU, so that the CPU test-suite can run an emulation of the device traversal
  * on the very data the kernels read (tests/test_bvh_emulation.py).  tri_xyz: ntris x 9 world-space

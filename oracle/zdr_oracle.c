@@ -799,6 +799,14 @@ static void write_bsdf_grad(double *dm, int tex_h, int tex_w, v2 uv, v4 g) { /* 
     write_single_bsdf_grad(dm, tex_h, tex_w, ix + 1, iy, ox * (1 - oy), g);
     write_single_bsdf_grad(dm, tex_h, tex_w, ix + 1, iy + 1, ox * oy, g);
 }
+/* rows: n x {u, v, g[4]}; dm: tex_h x tex_w x 4 float64, accumulated into (+=) */
+void zdro_write_bsdf_grad(double *dm, int tex_h, int tex_w, const float *rows, int n) {
+    for (int i = 0; i < n; i++) {
+        const float *r = rows + 6 * (size_t)i;
+        v2 uv = {r[0], r[1]}; v4 g = {r[2], r[3], r[4], r[5]};
+        write_bsdf_grad(dm, tex_h, tex_w, uv, g);
+    }
+}
 static int v4_any_nan(v4 g) { return isnan(g.x) || isnan(g.y) || isnan(g.z) || isnan(g.w); }
 static int v4_any_nonzero(v4 g) { return g.x != 0 || g.y != 0 || g.z != 0 || g.w != 0; }
 

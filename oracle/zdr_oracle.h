@@ -124,6 +124,9 @@ void zdro_ggx_sample_batch(const float *in, int n, float *out);
 void zdro_generate_ray(const zdro_params *, float px, float py, float o[3], float d[3]);
 void zdro_offset_ray_origin(const float p[3], const float n[3], float out[3]);
 void zdro_read_bsdf(const float *material, int tex_h, int tex_w, float u, float v, float out[4]);
+/* its adjoint, write_bsdf_grad (interaction.py:73-89), row by row: rows = n x {u, v, g[4]}; the float32 terms are added into dm
+ * (tex_h x tex_w x 4 float64, +=) */
+void zdro_write_bsdf_grad(double *dm, int tex_h, int tex_w, const float *rows, int n);
 
 #ifdef __cplusplus
 }

@@ -1176,7 +1176,7 @@ static int check_table_args(bool buffers, const int32_t *dims, uint32_t nmat) {
 
 // The material table of a zdr_render_*_materials call (internal.h): materials packed in order, their cells likewise.
 // (dims and nmat have passed check_table_args.)
-static int make_material_table(zdr_scene *s, const int32_t *dims, uint32_t nmat, bool capturing, hipStream_t st, MaterialTable &mt) {
+static int pack_material_table(const int32_t *dims, uint32_t nmat, MaterialTable &mt) {
     memset(&mt, 0, sizeof mt);
     size_t texel = 0, cells = 0;
     for (uint32_t k = 0; k < nmat; k++) {
@@ -1186,6 +1186,12 @@ static int make_material_table(zdr_scene *s, const int32_t *dims, uint32_t nmat,
         texel += (size_t)h * (size_t)w; cells += (size_t)(h + 1) * (size_t)(w + 1);
         if (texel >= (1ull << 31) || cells >= (1ull << 26)) return fail(ZDR_E_UNSUPPORTED, "materials too large for one material-table call (2^31 texels, 2^26 staging cells)");
     }
+    mt.nmat = (int32_t)nmat; mt.ncells = (int32_t)cells;
+    return ZDR_OK;
+}
+// ... and the scene's slot table with it: what a render call hands its kernels.
+static int make_material_table(zdr_scene *s, const int32_t *dims, uint32_t nmat, bool capturing, hipStream_t st, MaterialTable &mt) {
+    if (int rc = pack_material_table(dims, nmat, mt)) return rc;
     for (size_t i = 0; i < s->inst_slot.size(); i++)
         if (s->inst_slot[i] >= (int32_t)nmat)
             return fail(ZDR_E_INVALID, "instance " + std::to_string(i) + " has material slot " + std::to_string(s->inst_slot[i]) + ", but only " + std::to_string(nmat) + " materials were passed");
@@ -1194,7 +1200,7 @@ static int make_material_table(zdr_scene *s, const int32_t *dims, uint32_t nmat,
         std::vector<int32_t> none(s->ninst, -1);
         if (int rc = zdr_scene_set_material_slots(s, none.data(), st)) return rc;
     }
-    mt.inst_slot = s->d_inst_slot; mt.nmat = (int32_t)nmat; mt.ncells = (int32_t)cells;
+    mt.inst_slot = s->d_inst_slot;
     return ZDR_OK;
 }
 
@@ -1234,6 +1240,23 @@ static void material_cell_layout(MaterialTable &mt, RenderCfg &R) {
     }
     R.cell_copies = 1;
     mt.ncells = (int32_t)cell;
+}
+
+// Environment gradient: the map as entry ZDR_ENV_ENTRY of a material table whose materials material_cell_layout has laid out.
+// The map's cells follow every copy of the materials' cells, with copies of their own (scene.h, table_cell_env): most light
+// samples go to the map's few brightest texels, whatever the map's size, so even a large map gets copies — up to
+// ZDR_ENV_CELL_BUDGET cells in all (16 MiB per copy for a 512 x 512 map: 15 copies).  Entry ZDR_ENV_ENTRY = {copies, h, w, first cell};
+// env_cells_total = the map's cells, all their copies.
+static int env_cell_layout(const zdr_scene *s, MaterialTable &mt, const RenderCfg &R, size_t &env_cells_total) {
+    const size_t mat_cells = (size_t)R.cell_copies * (size_t)mt.ncells;
+    const size_t one = (size_t)(s->ds.env_h + 1) * (size_t)(s->ds.env_w + 1);
+    size_t copies = std::min<size_t>(ZDR_MAX_CELL_COPIES, std::max<size_t>(1, ZDR_ENV_CELL_BUDGET / one));
+    if (mat_cells + one >= (1ull << 26)) return fail(ZDR_E_UNSUPPORTED, "materials and environment map too large for one call (2^26 staging cells)");
+    copies = std::min<size_t>(copies, ((1ull << 26) - 1 - mat_cells) / one);
+    mt.m[ZDR_ENV_ENTRY].texel = (int32_t)copies; mt.m[ZDR_ENV_ENTRY].h = s->ds.env_h; mt.m[ZDR_ENV_ENTRY].w = s->ds.env_w;
+    mt.m[ZDR_ENV_ENTRY].cell = (int32_t)mat_cells;
+    env_cells_total = copies * one;
+    return ZDR_OK;
 }
 
 // One render call as the entry points describe it to render_common.
@@ -1292,19 +1315,7 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const RenderC
         R.tex_h = R.tex_w = 0;                          // (unused in material-table mode)
         material_cell_layout(mt, R);                    // the materials' copies: as in the call without the map
     }
-    if (env_grad) {
-        // The map's cells follow every copy of the materials' cells, with copies of their own (scene.h, table_cell_env): most light
-        // samples go to the map's few brightest texels, whatever the map's size, so even a large map gets copies — up to
-        // ZDR_ENV_CELL_BUDGET cells in all (16 MiB per copy for a 512 x 512 map: 15 copies).  Entry ZDR_ENV_ENTRY = {copies, h, w, first cell}.
-        const size_t mat_cells = (size_t)R.cell_copies * (size_t)mt.ncells;
-        const size_t one = (size_t)(s->ds.env_h + 1) * (size_t)(s->ds.env_w + 1);
-        size_t copies = std::min<size_t>(ZDR_MAX_CELL_COPIES, std::max<size_t>(1, ZDR_ENV_CELL_BUDGET / one));
-        if (mat_cells + one >= (1ull << 26)) return fail(ZDR_E_UNSUPPORTED, "materials and environment map too large for one call (2^26 staging cells)");
-        copies = std::min<size_t>(copies, ((1ull << 26) - 1 - mat_cells) / one);
-        mt.m[ZDR_ENV_ENTRY].texel = (int32_t)copies; mt.m[ZDR_ENV_ENTRY].h = s->ds.env_h; mt.m[ZDR_ENV_ENTRY].w = s->ds.env_w;
-        mt.m[ZDR_ENV_ENTRY].cell = (int32_t)mat_cells;
-        env_cells_total = copies * one;
-    }
+    if (env_grad) { rc = env_cell_layout(s, mt, R, env_cells_total); if (rc) return rc; }
     if (capturing) s->captured = true;                  // sticky: a graph may name this handle's buffers from now on (zdr_scene)
     if (backward) { rc = ensure_cells(s, R, table_form ? (size_t)mt.ncells : (size_t)(R.tex_h + 1) * (R.tex_w + 1), st, capturing,
                                       env_cells_total); if (rc) return rc; }
@@ -1708,6 +1719,80 @@ extern "C" int zdr_shading_dump(zdr_scene *s, int32_t mode, const float *in, uin
     if (!in || !out) return fail(ZDR_E_INVALID, "null argument");
     HIPCHK(hipSetDevice(s->device));
     if (zdr_launch_shading_dump(mode, in, n, out, (hipStream_t)stream)) return fail(ZDR_E_HIP, "shading dump launch failed");
+    return ZDR_OK;
+}
+
+// The rows of a texture hook, read back and checked on the host before anything is launched: every material index names a material
+// of the table (or, env_entry, the map's entry; negative = an inactive row, where the hook has such rows).  stride: floats per row.
+static int check_texture_rows(const float *rows, uint32_t n, int stride, int mat_at, uint32_t nmat, bool inactive_ok, bool env_entry, hipStream_t st) {
+    std::vector<float> h((size_t)n * stride);
+    HIPCHK(hipMemcpyAsync(h.data(), rows, h.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < n; i++) {
+        int32_t k; memcpy(&k, &h[(size_t)i * stride + mat_at], sizeof k);
+        if (k < 0 && inactive_ok) continue;
+        if (env_entry && k == ZDR_ENV_ENTRY) continue;
+        if (k < 0 || (uint32_t)k >= nmat) return fail(ZDR_E_INVALID, "row " + std::to_string(i) + " names material " + std::to_string(k) + ", but " + std::to_string(nmat) + " materials were passed");
+    }
+    return ZDR_OK;
+}
+
+extern "C" int zdr_texture_lookup(zdr_scene *s, const float *materials, const int32_t *dims, uint32_t nmat, const float *rows, uint32_t n,
+                                  float *out, void *stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (!s) return fail(ZDR_E_INVALID, "null argument");
+    if (int rc = check_table_args(true, dims, nmat)) return rc;
+    MaterialTable mt;
+    if (int rc = pack_material_table(dims, nmat, mt)) return rc;
+    if (n == 0) return ZDR_OK;
+    if (!materials || !rows || !out) return fail(ZDR_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(s->device));
+    if (stream_is_capturing(st)) return fail(ZDR_E_UNSUPPORTED, "the texture hooks read their rows back to check them: they cannot be captured");
+    if (int rc = check_texture_rows(rows, n, 4, 2, nmat, false, false, st)) return rc;
+    if (zdr_launch_texture_lookup(s->ds, materials, mt, rows, n, out, st)) return fail(ZDR_E_HIP, "texture lookup launch failed");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_texture_scatter(zdr_scene *s, int32_t form, const int32_t *dims, uint32_t nmat, const float *rows, uint32_t n, uint32_t rounds,
+                                   float *d_materials, float *d_env, int32_t *copies, void *stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (!s) return fail(ZDR_E_INVALID, "null argument");
+    if (form != ZDR_SCATTER_SINGLE && form != ZDR_SCATTER_TABLE && form != ZDR_SCATTER_TABLE_ENV) return fail(ZDR_E_INVALID, "unknown texture scatter form");
+    if (int rc = check_table_args(true, dims, nmat)) return rc;
+    if (form == ZDR_SCATTER_SINGLE && nmat != 1) return fail(ZDR_E_INVALID, "the single-material form takes one material");
+    if (form == ZDR_SCATTER_TABLE_ENV) {                // what render_common and render_backward_call ask of an environment-gradient call
+        if (nmat > ZDR_ENV_ENTRY) return fail(ZDR_E_INVALID, "the form with the environment map takes at most " + std::to_string(ZDR_ENV_ENTRY) + " materials (the map is the last entry of the material table)");
+        if (s->ds.env_count == 0) return fail(ZDR_E_INVALID, "the form with the environment map was asked for, but the scene has no environment map");
+    }
+    if (rounds < 1 || rounds > 65536) return fail(ZDR_E_INVALID, "rounds must lie in [1, 65536]");
+    HIPCHK(hipSetDevice(s->device));
+    RenderCfg R; memset(&R, 0, sizeof R);
+    KernelIO io; memset(&io, 0, sizeof io);
+    MaterialTable mt;
+    if (int rc = pack_material_table(dims, nmat, mt)) return rc;
+    size_t ncells = (size_t)mt.ncells, env_cells_total = 0;
+    if (form == ZDR_SCATTER_SINGLE) {                   // zdr_render_backward: make_render_cfg, no table
+        R.tex_h = dims[0]; R.tex_w = dims[1];
+        R.cell_copies = cell_copies_for(ncells);
+        memset(&mt, 0, sizeof mt);
+    } else {                                            // zdr_render_backward_materials[_env]: render_common
+        material_cell_layout(mt, R);
+        ncells = (size_t)mt.ncells;
+        if (form == ZDR_SCATTER_TABLE_ENV) { if (int rc = env_cell_layout(s, mt, R, env_cells_total)) return rc; }
+    }
+    if (copies) {
+        for (int k = 0; k < ZDR_MAX_MATERIALS; k++) copies[k] = (k < (int)nmat) ? (form == ZDR_SCATTER_SINGLE ? R.cell_copies : mt.m[k].copies) : 0;
+        if (form == ZDR_SCATTER_TABLE_ENV) copies[ZDR_ENV_ENTRY] = mt.m[ZDR_ENV_ENTRY].texel;
+    }
+    if (n == 0) return ZDR_OK;
+    if (!rows || !d_materials || (form == ZDR_SCATTER_TABLE_ENV && !d_env)) return fail(ZDR_E_INVALID, "null argument");
+    const bool capturing = stream_is_capturing(st);
+    if (capturing) return fail(ZDR_E_UNSUPPORTED, "the texture hooks read their rows back to check them: they cannot be captured");
+    if (int rc = check_texture_rows(rows, n, 8, 6, nmat, true, form == ZDR_SCATTER_TABLE_ENV, st)) return rc;
+    if (int rc = ensure_cells(s, R, ncells, st, capturing, env_cells_total)) return rc;
+    io.cells = s->d_cells; io.d_material = d_materials; io.mt = mt;
+    if (zdr_launch_texture_scatter(R, io, form != ZDR_SCATTER_SINGLE, form == ZDR_SCATTER_TABLE_ENV ? d_env : nullptr, rows, n, rounds, st))
+        return fail(ZDR_E_HIP, "texture scatter launch failed");
     return ZDR_OK;
 }
 

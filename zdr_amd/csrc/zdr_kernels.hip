@@ -1159,6 +1159,29 @@ static bool launch_simple(const KernelForm &k, dim3 grid, size_t dyn, hipStream_
     return true;
 }
 
+// What a backward call launches behind its kernel: the staging cells into the gradient buffers (+=).  io.mt.nmat > 0: a material-table
+// call, d_env its map's gradient or NULL; else the single material of R.tex_h x R.tex_w.  (zdr_launch_render and the test hook
+// zdr_launch_texture_scatter.)
+static void launch_cells_fold(const RenderCfg &R, const KernelIO &io, float *d_env, hipStream_t st) {
+    if (io.mt.nmat > 0) {   // every material's cells into its range of d_material (+=)
+        int mh = 1, mw = 1;
+        for (int k = 0; k < io.mt.nmat; k++) { mh = std::max(mh, (int)io.mt.m[k].h); mw = std::max(mw, (int)io.mt.m[k].w); }
+        dim3 g((mw + 63) / 64, mh, io.mt.nmat);
+        hipLaunchKernelGGL(k_material_cells_to_grad, g, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)io.d_material, io.mt);
+        if (d_env) {   // the map's cells into d_env (+=): the same gather, a table whose only material is the map, with the map's own copies
+            const MaterialSlot e = io.mt.m[ZDR_ENV_ENTRY];    // {copies, h, w, first cell}
+            MaterialTable me = io.mt;
+            me.m[0] = e; me.m[0].texel = 0;
+            me.m[0].copies = e.texel; me.m[0].stride = (e.h + 1) * (e.w + 1);
+            dim3 ge((e.w + 63) / 64, e.h, 1);
+            hipLaunchKernelGGL(k_material_cells_to_grad, ge, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)d_env, me);
+        }
+    } else {   // fold the staging cells into d_material (+=)
+        dim3 g((R.tex_w + 63) / 64, R.tex_h);
+        hipLaunchKernelGGL(k_cells_to_grad, g, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)io.d_material, R.tex_h, R.tex_w, R.cell_copies);
+    }
+}
+
 int zdr_launch_render(const DScene &S_in, const RenderCfg &R, const SamplerCfg &C, const KernelIO &io, const RenderLaunch &L, hipStream_t st) {
     DScene S = S_in;
     const int integrator = L.integrator, backward = L.backward, stats = L.stats;
@@ -1182,24 +1205,10 @@ int zdr_launch_render(const DScene &S_in, const RenderCfg &R, const SamplerCfg &
         else launched = launch_simple<ZDR_COLLOCATED, SK, A>(k, grid, dyn, st, S, R, C, io);
     });
     if (!launched) return -1;   // no kernel of that form: nothing wrote the cells, so nothing is gathered
-    if (backward && io.mt.nmat > 0) {   // every material's cells into its range of d_material (+=)
-        int mh = 1, mw = 1;
-        for (int k = 0; k < io.mt.nmat; k++) { mh = std::max(mh, (int)io.mt.m[k].h); mw = std::max(mw, (int)io.mt.m[k].w); }
-        dim3 g((mw + 63) / 64, mh, io.mt.nmat);
-        hipLaunchKernelGGL(k_material_cells_to_grad, g, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)io.d_material, io.mt);
-        if (d_env) {   // the map's cells into d_env (+=): the same gather, a table whose only material is the map, with the map's own copies
-            const MaterialSlot e = io.mt.m[ZDR_ENV_ENTRY];    // {copies, h, w, first cell}
-            MaterialTable me = io.mt;
-            me.m[0] = e; me.m[0].texel = 0;
-            me.m[0].copies = e.texel; me.m[0].stride = (e.h + 1) * (e.w + 1);
-            dim3 ge((e.w + 63) / 64, e.h, 1);
-            hipLaunchKernelGGL(k_material_cells_to_grad, ge, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)d_env, me);
-        }
-        if (d_emission)      // the accumulator's rows into d_emission (+=), each light into its instance's row
+    if (backward) {
+        launch_cells_fold(R, io, d_env, st);
+        if (io.mt.nmat > 0 && d_emission)      // the accumulator's rows into d_emission (+=), each light into its instance's row
             hipLaunchKernelGGL(k_emission_gather, dim3((3 * S.light_count + 63) / 64), dim3(64), 0, st, (const float *)io.emit_acc, ZDR_EMISSION_COPIES, S.light_count, S.light_insts, d_emission);
-    } else if (backward) {   // fold the staging cells into d_material (+=)
-        dim3 g((R.tex_w + 63) / 64, R.tex_h);
-        hipLaunchKernelGGL(k_cells_to_grad, g, dim3(64), 0, st, (const float4 *)io.cells, (float4 *)io.d_material, R.tex_h, R.tex_w, R.cell_copies);
     }
     if (!backward && !stats && R.nchunks > 1) {
         dim3 g((R.x1 - R.x0 + 63) / 64, R.y1 - R.y0);
@@ -1417,6 +1426,71 @@ __global__ void k_shading_dump(int mode, const float *in, uint32_t n, float *out
 int zdr_launch_shading_dump(int mode, const float *in, uint32_t n, float *out, hipStream_t st) {
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_shading_dump, dim3((n + 63) / 64), dim3(64), 0, st, mode, in, n, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ------------------------------------------------------------------- texture lookup and scatter
+// Test hooks (zdr_texture_lookup, zdr_texture_scatter, include/zdr.h): the bilinear lookup and its adjoint on rows the caller chooses,
+// through the device functions of scene.h — read_bsdf, read_bsdf_in, env_lookup; scatter_queue_init[_cells], scatter_push,
+// scatter_finish with scatter_cell, env_cell and table_cell_env behind them — and the folds above.  Like k_shading_dump these are
+// kernels of their own: they run the functions as compiled here, not the instances inlined into k_path_bwd / k_simple / k_aov_bwd.
+//
+// Lookup: lane i is row i {u, v, bits(material), -}.  read_bsdf takes its material's size wave-uniform, as every kernel that calls it
+// does (RenderCfg), so the wave walks the table and a lane keeps the result of its own material; read_bsdf_in takes the lane's entry.
+// 20 floats out: read_bsdf narrow, wide; read_bsdf_in narrow, wide; env_lookup (zeros without a map), 0.
+__global__ void k_texture_lookup(DScene S, const float4 *materials, MaterialTable mt, const float4 *rows, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const float4 row = rows[i < n ? i : n - 1];
+    f2 uv; uv.x = row.x; uv.y = row.y;
+    const int mat = __float_as_int(row.z);
+    float4 r[4];
+    for (int k = 0; k < 4; k++) r[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int k = 0; k < mt.nmat; k++) {                        // k and the size are wave-uniform
+        const MaterialSlot m = mt.m[k];
+        const float4 a = read_bsdf(materials + m.texel, uv, m.h, m.w, false), b = read_bsdf(materials + m.texel, uv, m.h, m.w, true);
+        if (k == mat) { r[0] = a; r[1] = b; }
+    }
+    r[2] = read_bsdf_in(materials, mt.m[mat], uv, false);
+    r[3] = read_bsdf_in(materials, mt.m[mat], uv, true);
+    const f3 e = (S.env_count > 0) ? env_lookup(S, uv) : mk3(0.0f);
+    if (i >= n) return;
+    float4 *o = (float4 *)(out + 20 * (size_t)i);
+    for (int k = 0; k < 4; k++) o[k] = r[k];
+    o[4] = make_float4(e.x, e.y, e.z, 0.0f);
+}
+
+int zdr_launch_texture_lookup(const DScene &S, const float *materials, const MaterialTable &mt, const float *rows, uint32_t n, float *out, hipStream_t st) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_texture_lookup, dim3((n + 63) / 64), dim3(64), 0, st, S, (const float4 *)materials, mt, (const float4 *)rows, n, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// Scatter: one wave per block; in round r lane l of wave b holds row 64 (b rounds + r) + l {u, v, g[4], bits(material), -} and the
+// whole wave calls scatter_push with `active` = the row exists and its material is >= 0: the caller decides every ballot, and with it
+// when the queue flushes.  MT, EG: the template instances of the backward kernels (single material / table / table with the map).
+template <bool MT, bool EG>
+__global__ __launch_bounds__(WAVE) void k_texture_scatter(RenderCfg R, KernelIO io, const float4 *rows, uint32_t n, int rounds) {
+    __shared__ __attribute__((aligned(16))) float lds_q[ZDR_SCATTER_LDS_FLOATS];   // the queue writes g as one float4
+    ScatterQueue q = MT ? scatter_queue_init_cells(lds_q, io.mt.ncells, R.cell_copies) : scatter_queue_init(lds_q, R.tex_h, R.tex_w, R.cell_copies);
+    if constexpr (EG) q.lds_cells = nullptr;                // the map's cells are never in LDS (table_cell_env)
+    for (int r = 0; r < rounds; r++) {
+        const size_t i = 64 * ((size_t)blockIdx.x * rounds + r) + threadIdx.x;
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, __int_as_float(-1), 0.0f);
+        if (i < n) { a = rows[2 * i]; b = rows[2 * i + 1]; }
+        f2 uv; uv.x = a.x; uv.y = a.y;
+        const int mat = __float_as_int(b.z);
+        scatter_push<MT, EG>(q, io.cells, mat >= 0, uv, make_float4(a.z, a.w, b.x, b.y), R.tex_h, R.tex_w, 0, mat >= 0 ? mat : 0, io.mt.m);
+    }
+    scatter_finish<MT, EG>(q, io.cells, R.tex_h, R.tex_w, 0, io.mt.m);
+}
+
+int zdr_launch_texture_scatter(const RenderCfg &R, const KernelIO &io, int table, float *d_env, const float *rows, uint32_t n, uint32_t rounds, hipStream_t st) {
+    if (n == 0) return 0;
+    const dim3 grid((uint32_t)(((size_t)n + 64 * (size_t)rounds - 1) / (64 * (size_t)rounds)));
+    if (d_env) hipLaunchKernelGGL((k_texture_scatter<true, true>), grid, dim3(WAVE), 0, st, R, io, (const float4 *)rows, n, (int)rounds);
+    else if (table) hipLaunchKernelGGL((k_texture_scatter<true, false>), grid, dim3(WAVE), 0, st, R, io, (const float4 *)rows, n, (int)rounds);
+    else hipLaunchKernelGGL((k_texture_scatter<false, false>), grid, dim3(WAVE), 0, st, R, io, (const float4 *)rows, n, (int)rounds);
+    launch_cells_fold(R, io, d_env, st);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

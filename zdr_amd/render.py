@@ -877,6 +877,39 @@ class Scene:
         N.check(N.lib().zdr_shading_dump(self._handle, self.SHADING_MODES[mode], rows.data_ptr(), rows.shape[0], out.data_ptr(), self._stream()))
         return out
 
+    SCATTER_FORMS = {"single": 0, "table": 1, "table_env": 2}
+
+    def _texture_table(self, sizes):
+        dims = np.ascontiguousarray(np.array(sizes, np.int32).reshape(-1, 2))
+        return dims, int(sum(int(h) * int(w) for h, w in dims))
+
+    def texture_lookup(self, materials, sizes, rows):
+        """The bilinear lookups row by row (include/zdr.h, zdr_texture_lookup): ``materials`` the packed texels ((sum h w, 4) float32) of the
+        table ``sizes`` [(h, w), ...], ``rows`` (n, 3 or 4) float32 {u, v, bits(material index)} -> (n, 20) float32 {read_bsdf narrow, wide,
+        read_bsdf_in narrow, wide, env_lookup[3], 0}."""
+        dims, texels = self._texture_table(sizes)
+        materials = materials.to(device=self.device, dtype=torch.float32).contiguous()
+        assert materials.numel() == 4 * texels, (materials.shape, texels)
+        r = torch.zeros((rows.shape[0], 4), dtype=torch.int32, device=self.device)        # (bits, not values: the index is no number)
+        r[:, :3] = rows.to(device=self.device, dtype=torch.float32).contiguous().view(torch.int32)[:, :3]
+        out = torch.empty((r.shape[0], 20), dtype=torch.float32, device=self.device)
+        N.check(N.lib().zdr_texture_lookup(self._handle, materials.data_ptr(), dims.ctypes.data, dims.shape[0], r.data_ptr(), r.shape[0], out.data_ptr(), self._stream()))
+        return out
+
+    def texture_scatter(self, form, sizes, rows, rounds, d_materials, d_env=None):
+        """The staging-cell scatter and the fold row by row (include/zdr.h, zdr_texture_scatter): ``form`` "single" | "table" | "table_env",
+        ``rows`` (n, 7 or 8) float32 {u, v, g[4], bits(material index)}; adds into ``d_materials`` ((sum h w, 4) float32 cuda, in place) and,
+        third form, into ``d_env`` ((env_h, env_w, 4)) -> the copies of the staging cells each of the 16 table entries was given."""
+        dims, texels = self._texture_table(sizes)
+        assert d_materials.is_cuda and d_materials.dtype == torch.float32 and d_materials.is_contiguous() and d_materials.numel() == 4 * texels
+        assert d_env is None or (d_env.is_cuda and d_env.dtype == torch.float32 and d_env.is_contiguous())
+        r = torch.zeros((rows.shape[0], 8), dtype=torch.int32, device=self.device)        # (bits, not values: the index is no number)
+        r[:, :7] = rows.to(device=self.device, dtype=torch.float32).contiguous().view(torch.int32)[:, :7]
+        copies = np.zeros(N.MAX_MATERIALS, np.int32)
+        N.check(N.lib().zdr_texture_scatter(self._handle, self.SCATTER_FORMS[form], dims.ctypes.data, dims.shape[0], r.data_ptr(), r.shape[0], int(rounds),
+                                            d_materials.data_ptr(), None if d_env is None else d_env.data_ptr(), copies.ctypes.data, self._stream()))
+        return copies
+
     def sampler_dump(self, queries, spp, seed=0, nvert=3, rr_depth=RR_DEPTH):
         """queries: (n, 3) int32 cuda {px, py, sample_index} -> (n, 2 + 8*nvert) float32 sampler draws."""
         q = queries.reshape(-1, 3).to(device=self.device, dtype=torch.int32).contiguous()
