@@ -463,70 +463,95 @@ static int build_accel(const std::vector<h3> &pos, uint32_t ntris, bool use_bvh,
     return ZDR_OK;
 }
 
-// ----------------------------------------------------------------------------------- scene
-struct zdr_scene {
-    int device = 0;
-    int accel_is_bvh = 0;
-    uint32_t ntris = 0, nverts = 0, ninst = 0;
-    uint32_t bvh_nodes = 0, bvh_depth = 0, stack_entries = 8;
-    std::vector<int32_t> inst_tri_begin;
-    std::vector<float> emission;
-    float4 *d_isect = nullptr, *d_pairs = nullptr, *d_shade = nullptr, *d_nodes = nullptr;
-    bool isect_in_nodes = false;            // BVH: d_isect points into the d_nodes allocation (freed once)
-    std::vector<int> slot_tri;              // brute force: slot -> input triangle
-    unsigned long long shadow_pairs = ~0ull;   // brute force: the pairs of the pair walk a shadow segment can meet (never_occluders; rebuilt when the lights change)
-    uint32_t nquads = 0, nquads2 = 0, npar = 0;   // brute force: primitives of the pair walk, how many of them are merged quads (find_quads), how many of those parallelograms
-    float4 *d_ppairs = nullptr;
-    float *d_emission = nullptr;
-    // flat light table (scene.h): one 80-byte entry per triangle of every emitting instance + {first entry, count} per light
-    std::vector<float4> tri_geo;            // host copy, 4 float4 per INPUT triangle: p0, p1, p2, {ng, area} (lights may change)
-    float4 *d_light_tris = nullptr; size_t light_tris_cap = 0;
-    int32_t *d_light_range = nullptr;       // 2 ints per instance slot
-    float4 *d_emission4 = nullptr;          // ninst x {e.rgb, bits(light index | -1)}
-    int32_t *d_light_insts = nullptr, *d_inst_tri_begin = nullptr, *d_slot_of_tri = nullptr;
-    uint32_t *d_pmj = nullptr; uint16_t *d_bn = nullptr; SamplerTables tab{};
-    float4 *d_env_tex = nullptr; float *d_alias_prob = nullptr, *d_env_pdf = nullptr; int32_t *d_alias_idx = nullptr;
-    EnvSamplingScratch *d_env_scratch = nullptr;            // workspace of zdr_scene_update_envmap_sampling: allocated by its first call, kept until zdr_scene_destroy
-    float4 *d_partial = nullptr; size_t partial_bytes = 0;
-    unsigned long long *d_tile_masks = nullptr; size_t tile_mask_bytes = 0;   // camera-ray candidate pairs per tile (k_tile_masks)
-    float tile_mask_key[24]; bool tile_mask_key_set = false;                  // camera + tile grid the masks in the buffer were built for (all tiles of the rectangle, whatever the shard)
-    unsigned int *d_work_counters = nullptr;
-    float4 *d_ring = nullptr; size_t ring_bytes = 0;     // primary rings of the path kernels (integrators.h)
-    float *d_cells = nullptr; size_t cells_bytes = 0;       // backward staging cells, (tex_h+1) x (tex_w+1) x 16 floats
-    unsigned long long *d_counters = nullptr;
-    std::vector<int32_t> inst_slot;                         // material slot of each instance (zdr_scene_set_material_slots), -1 = none; empty = never set
-    int32_t *d_inst_slot = nullptr;                         // its device copy, allocated by the first call that needs it
-    int32_t *d_inst_slot0 = nullptr;                        // {0, -1, -1, ...}: the slot table of a single-material environment-gradient call (render_common)
-    float *d_emit_acc = nullptr; size_t emit_acc_bytes = 0; // emission-gradient accumulator: ZDR_EMISSION_COPIES rows of light_count x 3 floats (render_common)
-    unsigned int *d_error = nullptr;                        // device error word (scene.h, ZDR_DEVERR_*), sticky until read
-    uint64_t device_bytes = 0;
-    // A render call recorded while its stream was CAPTURING (hipStreamBeginCapture; torch.cuda.graph) bakes this handle's workspace
-    // pointers into a graph that may be replayed at any later time.  From then on the handle never frees a buffer a kernel can read or
-    // write — one that has to grow is retired (kept until zdr_scene_destroy) and replaced — and never trusts the tile masks in the
-    // buffer, which a replay rebuilds for ITS view behind the host's back (render_common).
-    bool captured = false;
-    std::vector<void *> retired;
-    DScene ds{};
-};
-
+// --------------------------------------------------------------------------- device memory
 static bool stream_is_capturing(hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
     return cs != hipStreamCaptureStatusNone;
 }
 
-// frees a buffer of the handle that no kernel in flight reads — unless a captured graph may still name it
-static void release_buffer(zdr_scene *s, void *p) {
-    if (!p) return;
-    if (s->captured) s->retired.push_back(p); else (void)hipFree(p);
+// A workspace that has to grow: not while the stream is capturing (an allocation cannot be recorded, and the capture would name a
+// buffer that does not exist yet) — one eager call of the same kind and size beforehand sizes everything.
+static int may_allocate(bool capturing, const char *what) {
+    if (!capturing) return ZDR_OK;
+    return fail(ZDR_E_UNSUPPORTED, std::string("the ") + what + " workspace would have to be allocated while the stream is capturing: make one eager call of this kind, resolution and spp on the handle first");
 }
 
-template <class T>
-static hipError_t upload(T **dst, const void *src, size_t bytes, uint64_t *acc) {
-    hipError_t e = hipMalloc((void **)dst, std::max<size_t>(bytes, 16));
+// The device memory of a scene handle (zdr_scene derives from it): every buffer is a DevBuf member of the handle, which registers
+// itself here, so that a buffer's life is written once — alloc / reserve / release below, free_all at zdr_scene_destroy.
+// A render call recorded while its stream was CAPTURING (hipStreamBeginCapture; torch.cuda.graph) bakes the handle's workspace
+// pointers into a graph that may be replayed at any later time.  From then on the handle never frees a buffer a kernel can read or
+// write — one that has to grow is retired (kept until zdr_scene_destroy) and replaced — and never trusts the tile masks in the
+// buffer, which a replay rebuilds for ITS view behind the host's back (render_common).
+struct DevMem { bool captured = false; std::vector<struct DevBuf *> owned; std::vector<void *> retired; };
+struct DevBuf {
+    DevMem &mem; void *p = nullptr; size_t bytes = 0;      // bytes: as allocated
+    explicit DevBuf(DevMem &m) : mem(m) { m.owned.push_back(this); }
+    DevBuf(const DevBuf &) = delete;
+    hipError_t alloc(size_t n) { const hipError_t e = hipMalloc(&p, n); if (e != hipSuccess) p = nullptr; bytes = p ? n : 0; return e; }   // (of an empty buffer)
+    void release() {                        // of a buffer that no kernel in flight reads: freed — unless a captured graph may still name it
+        if (p) { if (mem.captured) mem.retired.push_back(p); else (void)hipFree(p); }
+        p = nullptr; bytes = 0;
+    }
+    int reserve(size_t need, bool capturing, const char *what) {   // grow-only; the contents do not survive growing
+        if (need <= bytes) return ZDR_OK;
+        if (int rc = may_allocate(capturing, what)) return rc;
+        release();
+        const hipError_t e = alloc(need);
+        return e == hipSuccess ? ZDR_OK : fail(ZDR_E_HIP, std::string("hipMalloc of the ") + what + " workspace, " + std::to_string(need) + " bytes: " + hipGetErrorString(e));
+    }
+    static void free_all(DevMem &m) {       // zdr_scene_destroy
+        for (DevBuf *b : m.owned) (void)hipFree(b->p);
+        for (void *q : m.retired) (void)hipFree(q);
+    }
+};
+template <class T> struct Dev : DevBuf { using DevBuf::DevBuf; operator T *() const { return (T *)p; } };   // reads as the T * it holds
+
+// ----------------------------------------------------------------------------------- scene
+struct zdr_scene : DevMem {
+    int device = 0;
+    int accel_is_bvh = 0;
+    uint32_t ntris = 0, nverts = 0, ninst = 0;
+    uint32_t bvh_nodes = 0, bvh_depth = 0, stack_entries = 8;
+    std::vector<int32_t> inst_tri_begin;
+    std::vector<float> emission;
+    Dev<float4> d_isect{*this}, d_pairs{*this}, d_shade{*this}, d_nodes{*this};   // (BVH: the plane records lie in d_nodes, d_isect stays empty)
+    std::vector<int> slot_tri;              // brute force: slot -> input triangle
+    unsigned long long shadow_pairs = ~0ull;   // brute force: the pairs of the pair walk a shadow segment can meet (never_occluders; rebuilt when the lights change)
+    uint32_t nquads = 0, nquads2 = 0, npar = 0;   // brute force: primitives of the pair walk, how many of them are merged quads (find_quads), how many of those parallelograms
+    Dev<float4> d_ppairs{*this};
+    Dev<float> d_emission{*this};
+    // flat light table (scene.h): one 80-byte entry per triangle of every emitting instance + {first entry, count} per light
+    std::vector<float4> tri_geo;            // host copy, 4 float4 per INPUT triangle: p0, p1, p2, {ng, area} (lights may change)
+    Dev<float4> d_light_tris{*this};
+    Dev<int32_t> d_light_range{*this};      // 2 ints per instance slot
+    Dev<float4> d_emission4{*this};         // ninst x {e.rgb, bits(light index | -1)}
+    Dev<int32_t> d_light_insts{*this}, d_inst_tri_begin{*this}, d_slot_of_tri{*this};
+    Dev<uint32_t> d_pmj{*this}; Dev<uint16_t> d_bn{*this}; SamplerTables tab{};
+    Dev<float4> d_env_tex{*this}; Dev<float> d_alias_prob{*this}, d_env_pdf{*this}; Dev<int32_t> d_alias_idx{*this};
+    Dev<EnvSamplingScratch> d_env_scratch{*this};           // workspace of zdr_scene_update_envmap_sampling: allocated by its first call, kept until zdr_scene_destroy
+    Dev<float4> d_partial{*this};
+    Dev<unsigned long long> d_tile_masks{*this};                              // camera-ray candidate pairs per tile (k_tile_masks)
+    float tile_mask_key[24]; bool tile_mask_key_set = false;                  // camera + tile grid the masks in the buffer were built for (all tiles of the rectangle, whatever the shard)
+    Dev<unsigned int> d_work_counters{*this};
+    Dev<float4> d_ring{*this};                              // primary rings of the path kernels (integrators.h)
+    Dev<float> d_cells{*this};                              // backward staging cells, (tex_h+1) x (tex_w+1) x 16 floats
+    Dev<unsigned long long> d_counters{*this};
+    std::vector<int32_t> inst_slot;                         // material slot of each instance (zdr_scene_set_material_slots), -1 = none; empty = never set
+    Dev<int32_t> d_inst_slot{*this};                        // its device copy, allocated by the first call that needs it
+    Dev<int32_t> d_inst_slot0{*this};                       // {0, -1, -1, ...}: the slot table of a single-material environment-gradient call (render_common)
+    Dev<float> d_emit_acc{*this};                           // emission-gradient accumulator: ZDR_EMISSION_COPIES rows of light_count x 3 floats (render_common)
+    Dev<unsigned int> d_error{*this};                       // device error word (scene.h, ZDR_DEVERR_*), sticky until read
+    uint64_t device_bytes = 0;                              // uploads, the slot table and the environment scratch; not the per-call workspaces
+    DScene ds{};
+};
+
+// a new buffer with a copy of `bytes` host bytes; counted in *acc (zdr_scene_info_t::device_bytes)
+static hipError_t upload(DevBuf &dst, const void *src, size_t bytes, uint64_t *acc) {
+    hipError_t e = dst.alloc(std::max<size_t>(bytes, 16));
     if (e != hipSuccess) return e;
     if (acc) *acc += bytes;
-    return bytes ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    return bytes ? hipMemcpy(dst.p, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
 }
 
 static void light_list(const std::vector<float> &em, uint32_t ninst, std::vector<int32_t> &out, int &count) {
@@ -535,6 +560,15 @@ static void light_list(const std::vector<float> &em, uint32_t ninst, std::vector
         if (em[3 * i] > 0.0f || em[3 * i + 1] > 0.0f || em[3 * i + 2] > 0.0f) out[count++] = (int32_t)i;
 }
 
+// The corners of `ntris` triangles as the builders take them: three floats each, `corner` floats from one corner to the next and
+// `tri` floats from one triangle to the next — (3, 9) for packed positions, (4, 16) for zdr_scene::tri_geo.
+static std::vector<h3> triangle_corners(const float *xyz, uint32_t ntris, size_t corner, size_t tri) {
+    std::vector<h3> pos(3 * (size_t)ntris);
+    for (uint32_t t = 0; t < ntris; t++) for (int k = 0; k < 3; k++) { const float *c = xyz + tri * t + corner * k; pos[3 * (size_t)t + k] = H3(c[0], c[1], c[2]); }
+    return pos;
+}
+static bool wants_bvh(int accel, uint32_t ntris) { return accel == ZDR_ACCEL_BVH || (accel == ZDR_ACCEL_AUTO && ntris > 64); }
+
 // Light table for sample_light (scene.h): the reference walks light -> instance -> triangle range -> triangle ->
 // emission through four dependent lookups (light.py:33-48); on the GPU that is four memory round trips and eleven
 // per-lane loads per path vertex.  Flattened here to {first entry, T} per light and one 80-byte entry per light
@@ -542,8 +576,7 @@ static void light_list(const std::vector<float> &em, uint32_t ninst, std::vector
 // the pairs of the brute-force walk that hold at least one primitive a shadow segment can meet, for the current lights
 static unsigned long long shadow_pair_mask(const zdr_scene *s, const std::vector<int32_t> &lights, int count) {
     if (s->accel_is_bvh || s->slot_tri.empty() || s->ntris > 128 || getenv("ZDR_NO_SHADOW_MASK")) return ~0ull;
-    std::vector<h3> pos(3 * (size_t)s->ntris);
-    for (uint32_t t = 0; t < s->ntris; t++) for (int k = 0; k < 3; k++) { const float4 &g = s->tri_geo[4 * (size_t)t + k]; pos[3 * (size_t)t + k] = H3(g.x, g.y, g.z); }
+    const std::vector<h3> pos = triangle_corners((const float *)s->tri_geo.data(), s->ntris, 4, 16);
     std::vector<uint8_t> is_light(s->ntris, 0), never;
     for (int l = 0; l < count; l++) for (int t = s->inst_tri_begin[lights[l]]; t < s->inst_tri_begin[lights[l] + 1]; t++) is_light[t] = 1;
     never_occluders(pos, s->ntris, is_light, never);
@@ -570,14 +603,11 @@ static int upload_light_table(zdr_scene *s, const std::vector<int32_t> &lights, 
     }
     if (tab.empty()) tab.push_back(make_float4(0, 0, 0, 0));
     if (tab.size() * sizeof(float4) > (1ull << 32)) return fail(ZDR_E_UNSUPPORTED, "light table above 4 GiB: the kernels address its entries with 32-bit byte offsets");
-    if (tab.size() > s->light_tris_cap) {
-        HIPCHK(hipStreamSynchronize(st));
-        release_buffer(s, s->d_light_tris); s->d_light_tris = nullptr; s->light_tris_cap = 0;
-        HIPCHK(hipMalloc((void **)&s->d_light_tris, tab.size() * sizeof(float4)));
-        s->light_tris_cap = tab.size();
-    }
-    if (!s->d_light_range) HIPCHK(hipMalloc((void **)&s->d_light_range, range.size() * sizeof(int32_t)));
-    if (!s->d_emission4) HIPCHK(hipMalloc((void **)&s->d_emission4, (size_t)s->ninst * sizeof(float4)));
+    // (no capture check, hence `false`: this call synchronises the stream, which a capturing stream refuses by itself)
+    if (tab.size() * sizeof(float4) > s->d_light_tris.bytes) HIPCHK(hipStreamSynchronize(st));   // nothing in flight may still read the table that goes
+    if (int rc = s->d_light_tris.reserve(tab.size() * sizeof(float4), false, "light-table")) return rc;
+    if (int rc = s->d_light_range.reserve(range.size() * sizeof(int32_t), false, "light-table")) return rc;
+    if (int rc = s->d_emission4.reserve((size_t)s->ninst * sizeof(float4), false, "light-table")) return rc;
     std::vector<float4> e4(s->ninst);
     // .w: bits of the instance's index in the light list, -1 = not a light (read by the emission-gradient kernels only, as an int)
     std::vector<int32_t> light_of(s->ninst, -1);
@@ -593,6 +623,155 @@ static int upload_light_table(zdr_scene *s, const std::vector<int32_t> &lights, 
     s->ds.light_tris = s->d_light_tris; s->ds.light_range = s->d_light_range; s->ds.emission4 = s->d_emission4;
     s->ds.light0_T = count > 0 ? range[1] : 0;
     return ZDR_OK;
+}
+
+// ---- zdr_scene_create, step by step: what the steps hand on, on the host
+struct TriRec { h3 p[3], n[3]; float uv[3][2]; h3 ng; float area; int inst, prim; };
+struct SceneBuild {
+    std::vector<TriRec> rec;                // world-space records, input order
+    bool use_bvh = false;
+    std::vector<int> order, rot;            // slot -> input triangle; input triangle -> the input corner that is its slot's corner 0 (find_quads)
+    std::vector<float4> nodes, isect, shade, wedge;   // wedge: third edge function of every slot (single triangles of the brute-force walk)
+    std::vector<int32_t> slot_of_tri;
+    std::vector<float> pairs, ppairs;       // brute force: the records of the pair walk
+};
+
+// 1. world-space per-triangle records in input order (and the handle's copy of their geometry, zdr_scene::tri_geo)
+static void world_records(zdr_scene *s, const float *verts8, const int32_t *tris, const float *inst_xform, SceneBuild &B) {
+    B.rec.resize(s->ntris);
+    static const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    for (uint32_t i = 0; i < s->ninst; i++) {
+        const float *m = inst_xform ? inst_xform + 16 * (size_t)i : ident;
+        float nm[9]; normal_matrix(m, nm);
+        for (int t = s->inst_tri_begin[i]; t < s->inst_tri_begin[i + 1]; t++) {
+            TriRec &r = B.rec[t];
+            for (int k = 0; k < 3; k++) {
+                const float *v = verts8 + 8 * (size_t)tris[3 * (size_t)t + k];
+                r.p[k] = xform_point(m, H3(v[0], v[1], v[2]));
+                r.uv[k][0] = v[3]; r.uv[k][1] = v[4];
+                r.n[k] = H3(nm[0] * v[5] + nm[1] * v[6] + nm[2] * v[7], nm[3] * v[5] + nm[4] * v[6] + nm[5] * v[7], nm[6] * v[5] + nm[7] * v[6] + nm[8] * v[7]);
+            }
+            h3 c = hcross(hsub(r.p[1], r.p[0]), hsub(r.p[2], r.p[0]));
+            r.ng = hnormalize(c);                       // interaction.py:29, light.py:68
+            r.area = sqrtf(hdot(c, c)) / 2.0f;          // light.py:72
+            r.inst = (int)i; r.prim = t - s->inst_tri_begin[i];
+        }
+    }
+    s->tri_geo.resize(4 * (size_t)s->ntris);
+    for (uint32_t t = 0; t < s->ntris; t++) {
+        const TriRec &r = B.rec[t];
+        for (int k = 0; k < 3; k++) s->tri_geo[4 * (size_t)t + k] = make_float4(r.p[k].x, r.p[k].y, r.p[k].z, 0.0f);
+        s->tri_geo[4 * (size_t)t + 3] = make_float4(r.ng.x, r.ng.y, r.ng.z, r.area);
+    }
+}
+
+// 2. acceleration structure: slot order + nodes
+static int accel_and_slot_order(zdr_scene *s, int accel, SceneBuild &B) {
+    const uint32_t ntris = s->ntris;
+    const std::vector<h3> pos = triangle_corners((const float *)s->tri_geo.data(), ntris, 4, 16);
+    B.use_bvh = wants_bvh(accel, ntris);
+    if (int rc = build_accel(pos, ntris, B.use_bvh, B.order, B.nodes, s->bvh_nodes, s->bvh_depth, s->stack_entries)) return rc;
+    s->accel_is_bvh = B.use_bvh ? 1 : 0;
+    // brute force: merge coplanar triangle pairs into quads; slots 2q, 2q + 1 = quad q, the single triangles follow
+    B.rot.assign(ntris, 0);
+    if (!B.use_bvh) {
+        std::vector<uint8_t> is_light(ntris, 0), never;       // (the lights of the moment only ORDER the primitives; the mask itself follows update_lights)
+        for (uint32_t t = 0; t < ntris; t++) { const float *e = &s->emission[3 * (size_t)B.rec[t].inst]; is_light[t] = (e[0] > 0.0f || e[1] > 0.0f || e[2] > 0.0f) ? 1 : 0; }
+        never_occluders(pos, ntris, is_light, never);
+        s->nquads2 = brute_slot_order(pos, ntris, B.order, B.rot, &s->npar, &never); s->nquads = ntris - s->nquads2;
+        s->slot_tri = B.order;
+    }
+    return ZDR_OK;
+}
+
+// 3. per-slot records: plane records, shade records, third edge functions; brute force: the pair records made of them
+static void slot_records(zdr_scene *s, SceneBuild &B) {
+    const uint32_t ntris = s->ntris;
+    B.isect.assign(3 * (size_t)ntris + 3, make_float4(0, 0, 0, 0)); B.shade.resize(8 * (size_t)ntris);   // + one record: the BVH walk fetches four float4 behind a leaf's first triangle
+    B.slot_of_tri.resize(ntris); B.wedge.resize(ntris);
+    for (uint32_t slot = 0; slot < ntris; slot++) {
+        TriRec r = B.rec[B.order[slot]];
+        B.slot_of_tri[B.order[slot]] = (int32_t)slot;
+        const int ro = B.rot[B.order[slot]];     // the slot's corner 0 is input corner `ro` (cyclic: same triangle, same orientation)
+        if (ro) {
+            const TriRec in = r;
+            for (int k = 0; k < 3; k++) { r.p[k] = in.p[(k + ro) % 3]; r.n[k] = in.n[(k + ro) % 3]; r.uv[k][0] = in.uv[(k + ro) % 3][0]; r.uv[k][1] = in.uv[(k + ro) % 3][1]; }
+        }
+        plane_record(r.p, &B.isect[3 * (size_t)slot], &B.wedge[slot]);
+        float4 *q = &B.shade[8 * (size_t)slot];
+        q[0] = make_float4(r.p[0].x, r.p[0].y, r.p[0].z, r.uv[0][0]);
+        q[1] = make_float4(r.p[1].x, r.p[1].y, r.p[1].z, r.uv[0][1]);
+        q[2] = make_float4(r.p[2].x, r.p[2].y, r.p[2].z, r.uv[1][0]);
+        q[3] = make_float4(r.n[0].x, r.n[0].y, r.n[0].z, r.uv[1][1]);
+        q[4] = make_float4(r.n[1].x, r.n[1].y, r.n[1].z, r.uv[2][0]);
+        q[5] = make_float4(r.n[2].x, r.n[2].y, r.n[2].z, r.uv[2][1]);
+        float fi, fp; memcpy(&fi, &r.inst, 4); memcpy(&fp, &r.prim, 4);
+        q[6] = make_float4(r.ng.x, r.ng.y, r.ng.z, fi);
+        float fr; memcpy(&fr, &ro, 4);
+        q[7] = make_float4(r.area, fp, fr, 0.0f);          // .z: rotation of the slot's corners against the input triangle's
+    }
+    if (B.use_bvh) return;
+    // brute-force loops test two PRIMITIVES per trip with packed fp32 math, a primitive being a quad (slots 2q, 2q + 1)
+    // or a single triangle: plane N of the (first) triangle and four edge functions — u and v of both triangles of a quad,
+    // or u, v, w, w of a single triangle — five float4, interleaved for the two halves of a float2
+    B.pairs.assign(40 * (((size_t)s->nquads + 1) / 2), 0.0f);
+    for (uint32_t q = 0; q < s->nquads; q++) {
+        const uint32_t a = q < s->nquads2 ? 2 * q : q + s->nquads2;
+        float4 src[5] = {B.isect[3 * (size_t)a], B.isect[3 * (size_t)a + 1], B.isect[3 * (size_t)a + 2], B.wedge[a], B.wedge[a]};
+        if (q < s->nquads2) { src[3] = B.isect[3 * (size_t)(a + 1) + 1]; src[4] = B.isect[3 * (size_t)(a + 1) + 2]; }
+        float *dst = &B.pairs[40 * (size_t)(q / 2) + (q & 1)];
+        for (int k = 0; k < 20; k++) dst[2 * k] = ((const float *)src)[k];
+    }
+    // pairs of two PARALLELOGRAMS (they come first): the outer edges of the second triangle are 1 - u and 1 - v of the first,
+    // so the record is the plane and two edge functions — six float4
+    const size_t nppairs = s->npar / 2;
+    B.ppairs.assign(24 * std::max<size_t>(nppairs, 1), 0.0f);
+    for (uint32_t q = 0; q < 2 * nppairs; q++) {
+        const float *src = (const float *)&B.isect[3 * (size_t)(2 * q)];
+        float *dst = &B.ppairs[24 * (size_t)(q / 2) + (q & 1)];
+        for (int k = 0; k < 12; k++) dst[2 * k] = src[k];
+    }
+    s->ds.nppairs = getenv("ZDR_NO_PARALLELOGRAMS") ? 0 : (int32_t)nppairs;
+}
+
+// 4. upload, and the device's view of the scene (DScene)
+static int upload_scene(zdr_scene *s, const SceneBuild &B) {
+    std::vector<int32_t> lights; int light_count = 0;
+    light_list(s->emission, s->ninst, lights, light_count);
+    hipError_t e = hipSuccess;
+    auto up = [&](DevBuf &dst, const void *src, size_t bytes) { if (e == hipSuccess) e = upload(dst, src, bytes, &s->device_bytes); };
+    // BVH: nodes and plane records share ONE allocation, nodes first — the walk then addresses whatever a lane stands on as
+    // base + a 32-bit byte offset (accel.h, fetch): no 64-bit address arithmetic, no branch between "node" and "triangle" pointers.
+    const bool one_block = B.use_bvh;
+    if (one_block) {
+        if ((B.nodes.size() + B.isect.size()) * sizeof(float4) >= (1ull << 32)) return fail(ZDR_E_UNSUPPORTED, "BVH nodes and triangle records exceed 4 GiB");
+        std::vector<float4> both(B.nodes); both.insert(both.end(), B.isect.begin(), B.isect.end());
+        up(s->d_nodes, both.data(), both.size() * sizeof(float4));
+    } else {
+        up(s->d_isect, B.isect.data(), B.isect.size() * sizeof(float4));
+        up(s->d_pairs, B.pairs.data(), B.pairs.size() * sizeof(float));
+        up(s->d_ppairs, B.ppairs.data(), B.ppairs.size() * sizeof(float));
+    }
+    up(s->d_shade, B.shade.data(), B.shade.size() * sizeof(float4));
+    if (!one_block) up(s->d_nodes, B.nodes.data(), B.nodes.size() * sizeof(float4));
+    up(s->d_emission, s->emission.data(), s->emission.size() * sizeof(float));
+    up(s->d_light_insts, lights.data(), lights.size() * sizeof(int32_t));
+    up(s->d_inst_tri_begin, s->inst_tri_begin.data(), s->inst_tri_begin.size() * sizeof(int32_t));
+    up(s->d_slot_of_tri, B.slot_of_tri.data(), B.slot_of_tri.size() * sizeof(int32_t));
+    if (e == hipSuccess) e = s->d_counters.alloc(8 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = s->d_error.alloc(sizeof(unsigned int));
+    if (e == hipSuccess) e = hipMemset(s->d_error, 0, sizeof(unsigned int));
+    if (e != hipSuccess) return fail(ZDR_E_HIP, std::string("scene upload: ") + hipGetErrorString(e));
+    s->ds.isect = one_block ? s->d_nodes + B.nodes.size() : s->d_isect;
+    s->ds.pairs = s->d_pairs; s->ds.ppairs = s->d_ppairs; s->ds.shade = s->d_shade; s->ds.nodes = s->d_nodes; s->ds.emission = s->d_emission;
+    s->ds.light_insts = s->d_light_insts; s->ds.inst_tri_begin = s->d_inst_tri_begin; s->ds.slot_of_tri = s->d_slot_of_tri;
+    s->ds.error_word = s->d_error;
+    if (const char *e = getenv("ZDR_DEBUG_BVH_BUDGET")) s->ds.debug_bvh_budget = atoi(e);
+    s->ds.nquads = (int32_t)s->nquads; s->ds.nquads2 = (int32_t)s->nquads2;
+    s->ds.ntris = (int32_t)s->ntris; s->ds.ninst = (int32_t)s->ninst; s->ds.light_count = light_count; s->ds.nnodes = (int32_t)s->bvh_nodes; s->ds.stack_entries = (int32_t)s->stack_entries;
+    const float4 *walk_base = one_block ? s->d_nodes : s->d_isect;
+    s->ds.walk_base = (const char *)walk_base; s->ds.isect_off = one_block ? (uint32_t)(B.nodes.size() * sizeof(float4)) : 0u;   // accel.h, fetch
+    return upload_light_table(s, lights, light_count, nullptr);
 }
 
 extern "C" int zdr_scene_create(const float *verts8, uint32_t nverts, const int32_t *tris, uint32_t ntris,
@@ -614,146 +793,11 @@ extern "C" int zdr_scene_create(const float *verts8, uint32_t nverts, const int3
     s->device = device; s->ntris = ntris; s->nverts = nverts; s->ninst = ninst;
     s->inst_tri_begin.assign(inst_tri_begin, inst_tri_begin + ninst + 1);
     s->emission.assign(inst_emission, inst_emission + 3 * (size_t)ninst);
-
-    // world-space per-triangle records in input order
-    struct TriRec { h3 p[3], n[3]; float uv[3][2]; h3 ng; float area; int inst, prim; };
-    std::vector<TriRec> rec(ntris);
-    static const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    float slo[3] = {3e38f, 3e38f, 3e38f}, shi[3] = {-3e38f, -3e38f, -3e38f};
-    for (uint32_t i = 0; i < ninst; i++) {
-        const float *m = inst_xform ? inst_xform + 16 * (size_t)i : ident;
-        float nm[9]; normal_matrix(m, nm);
-        for (int t = inst_tri_begin[i]; t < inst_tri_begin[i + 1]; t++) {
-            TriRec &r = rec[t];
-            for (int k = 0; k < 3; k++) {
-                const float *v = verts8 + 8 * (size_t)tris[3 * (size_t)t + k];
-                r.p[k] = xform_point(m, H3(v[0], v[1], v[2]));
-                r.uv[k][0] = v[3]; r.uv[k][1] = v[4];
-                r.n[k] = H3(nm[0] * v[5] + nm[1] * v[6] + nm[2] * v[7], nm[3] * v[5] + nm[4] * v[6] + nm[5] * v[7], nm[6] * v[5] + nm[7] * v[6] + nm[8] * v[7]);
-                const float pc[3] = {r.p[k].x, r.p[k].y, r.p[k].z};
-                BvhBuilder::grow(slo, shi, pc, pc);
-            }
-            h3 c = hcross(hsub(r.p[1], r.p[0]), hsub(r.p[2], r.p[0]));
-            r.ng = hnormalize(c);                       // interaction.py:29, light.py:68
-            r.area = sqrtf(hdot(c, c)) / 2.0f;          // light.py:72
-            r.inst = (int)i; r.prim = t - inst_tri_begin[i];
-        }
-    }
-
-    // acceleration structure: slot order + nodes
-    std::vector<int> order;
-    std::vector<float4> nodes;
-    bool use_bvh = (accel == ZDR_ACCEL_BVH) || (accel == ZDR_ACCEL_AUTO && ntris > 64);
-    {
-        std::vector<h3> pos(3 * (size_t)ntris);
-        for (uint32_t t = 0; t < ntris; t++) for (int k = 0; k < 3; k++) pos[3 * (size_t)t + k] = rec[t].p[k];
-        int rc = build_accel(pos, ntris, use_bvh, order, nodes, s->bvh_nodes, s->bvh_depth, s->stack_entries);
-        if (rc) { delete s; return rc; }
-    }
-    s->accel_is_bvh = use_bvh ? 1 : 0;
-    // brute force: merge coplanar triangle pairs into quads; slots 2q, 2q + 1 = quad q, the single triangles follow
-    std::vector<int> rot(ntris, 0);
-    if (!use_bvh) {
-        std::vector<h3> pos(3 * (size_t)ntris);
-        for (uint32_t t = 0; t < ntris; t++) for (int k = 0; k < 3; k++) pos[3 * (size_t)t + k] = rec[t].p[k];
-        std::vector<uint8_t> is_light(ntris, 0), never;       // (the lights of the moment only ORDER the primitives; the mask itself follows update_lights)
-        for (uint32_t t = 0; t < ntris; t++) { const float *e = &s->emission[3 * (size_t)rec[t].inst]; is_light[t] = (e[0] > 0.0f || e[1] > 0.0f || e[2] > 0.0f) ? 1 : 0; }
-        never_occluders(pos, ntris, is_light, never);
-        s->nquads2 = brute_slot_order(pos, ntris, order, rot, &s->npar, &never); s->nquads = ntris - s->nquads2;
-        s->slot_tri = order;
-    }
-
-    std::vector<float4> isect(3 * (size_t)ntris + 3, make_float4(0, 0, 0, 0)), shade(8 * (size_t)ntris);   // + one record: the BVH walk fetches four float4 behind a leaf's first triangle
-    std::vector<int32_t> slot_of_tri(ntris);
-    std::vector<float4> wedge(ntris);       // third edge function of every slot (single triangles of the brute-force walk)
-    for (uint32_t slot = 0; slot < ntris; slot++) {
-        TriRec r = rec[order[slot]];
-        slot_of_tri[order[slot]] = (int32_t)slot;
-        const int ro = rot[order[slot]];     // the slot's corner 0 is input corner `ro` (cyclic: same triangle, same orientation)
-        if (ro) {
-            const TriRec in = r;
-            for (int k = 0; k < 3; k++) { r.p[k] = in.p[(k + ro) % 3]; r.n[k] = in.n[(k + ro) % 3]; r.uv[k][0] = in.uv[(k + ro) % 3][0]; r.uv[k][1] = in.uv[(k + ro) % 3][1]; }
-        }
-        plane_record(r.p, &isect[3 * (size_t)slot], &wedge[slot]);
-        float4 *q = &shade[8 * (size_t)slot];
-        q[0] = make_float4(r.p[0].x, r.p[0].y, r.p[0].z, r.uv[0][0]);
-        q[1] = make_float4(r.p[1].x, r.p[1].y, r.p[1].z, r.uv[0][1]);
-        q[2] = make_float4(r.p[2].x, r.p[2].y, r.p[2].z, r.uv[1][0]);
-        q[3] = make_float4(r.n[0].x, r.n[0].y, r.n[0].z, r.uv[1][1]);
-        q[4] = make_float4(r.n[1].x, r.n[1].y, r.n[1].z, r.uv[2][0]);
-        q[5] = make_float4(r.n[2].x, r.n[2].y, r.n[2].z, r.uv[2][1]);
-        float fi, fp; memcpy(&fi, &r.inst, 4); memcpy(&fp, &r.prim, 4);
-        q[6] = make_float4(r.ng.x, r.ng.y, r.ng.z, fi);
-        float fr; memcpy(&fr, &ro, 4);
-        q[7] = make_float4(r.area, fp, fr, 0.0f);          // .z: rotation of the slot's corners against the input triangle's
-    }
-    std::vector<int32_t> lights; int light_count = 0;
-    light_list(s->emission, ninst, lights, light_count);
-    s->tri_geo.resize(4 * (size_t)ntris);
-    for (uint32_t t = 0; t < ntris; t++) {
-        const TriRec &r = rec[t];
-        s->tri_geo[4 * (size_t)t] = make_float4(r.p[0].x, r.p[0].y, r.p[0].z, 0.0f);
-        s->tri_geo[4 * (size_t)t + 1] = make_float4(r.p[1].x, r.p[1].y, r.p[1].z, 0.0f);
-        s->tri_geo[4 * (size_t)t + 2] = make_float4(r.p[2].x, r.p[2].y, r.p[2].z, 0.0f);
-        s->tri_geo[4 * (size_t)t + 3] = make_float4(r.ng.x, r.ng.y, r.ng.z, r.area);
-    }
-
-    hipError_t e = hipSuccess;
-    auto up = [&](auto **dst, const void *src, size_t bytes) { if (e == hipSuccess) e = upload(dst, src, bytes, &s->device_bytes); };
-    // BVH: nodes and plane records share ONE allocation, nodes first — the walk then addresses whatever a lane stands on as
-    // base + a 32-bit byte offset (accel.h, fetch): no 64-bit address arithmetic, no branch between "node" and "triangle" pointers.
-    const bool one_block = use_bvh;
-    if (one_block) {
-        if ((nodes.size() + isect.size()) * sizeof(float4) >= (1ull << 32)) { zdr_scene_destroy(s); return fail(ZDR_E_UNSUPPORTED, "BVH nodes and triangle records exceed 4 GiB"); }
-        std::vector<float4> both(nodes); both.insert(both.end(), isect.begin(), isect.end());
-        up(&s->d_nodes, both.data(), both.size() * sizeof(float4));
-        s->d_isect = s->d_nodes ? s->d_nodes + nodes.size() : nullptr;
-        s->isect_in_nodes = true;
-    } else up(&s->d_isect, isect.data(), isect.size() * sizeof(float4));
-    if (!use_bvh) {
-        // brute-force loops test two PRIMITIVES per trip with packed fp32 math, a primitive being a quad (slots 2q, 2q + 1)
-        // or a single triangle: plane N of the (first) triangle and four edge functions — u and v of both triangles of a quad,
-        // or u, v, w, w of a single triangle — five float4, interleaved for the two halves of a float2
-        size_t npairs = ((size_t)s->nquads + 1) / 2;
-        std::vector<float> pr(40 * npairs, 0.0f);
-        for (uint32_t q = 0; q < s->nquads; q++) {
-            const uint32_t a = q < s->nquads2 ? 2 * q : q + s->nquads2;
-            float4 src[5] = {isect[3 * (size_t)a], isect[3 * (size_t)a + 1], isect[3 * (size_t)a + 2], wedge[a], wedge[a]};
-            if (q < s->nquads2) { src[3] = isect[3 * (size_t)(a + 1) + 1]; src[4] = isect[3 * (size_t)(a + 1) + 2]; }
-            float *dst = &pr[40 * (size_t)(q / 2) + (q & 1)];
-            for (int k = 0; k < 20; k++) dst[2 * k] = ((const float *)src)[k];
-        }
-        up(&s->d_pairs, pr.data(), pr.size() * sizeof(float));
-        // pairs of two PARALLELOGRAMS (they come first): the outer edges of the second triangle are 1 - u and 1 - v of the first,
-        // so the record is the plane and two edge functions — six float4
-        const size_t nppairs = s->npar / 2;
-        std::vector<float> ppr(24 * std::max<size_t>(nppairs, 1), 0.0f);
-        for (uint32_t q = 0; q < 2 * nppairs; q++) {
-            const float *src = (const float *)&isect[3 * (size_t)(2 * q)];
-            float *dst = &ppr[24 * (size_t)(q / 2) + (q & 1)];
-            for (int k = 0; k < 12; k++) dst[2 * k] = src[k];
-        }
-        up(&s->d_ppairs, ppr.data(), ppr.size() * sizeof(float));
-        s->ds.nppairs = getenv("ZDR_NO_PARALLELOGRAMS") ? 0 : (int32_t)nppairs;
-    }
-    up(&s->d_shade, shade.data(), shade.size() * sizeof(float4));
-    if (!one_block) up(&s->d_nodes, nodes.data(), nodes.size() * sizeof(float4));
-    up(&s->d_emission, s->emission.data(), s->emission.size() * sizeof(float));
-    up(&s->d_light_insts, lights.data(), lights.size() * sizeof(int32_t));
-    up(&s->d_inst_tri_begin, s->inst_tri_begin.data(), s->inst_tri_begin.size() * sizeof(int32_t));
-    up(&s->d_slot_of_tri, slot_of_tri.data(), slot_of_tri.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_counters, 8 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_error, sizeof(unsigned int));
-    if (e == hipSuccess) e = hipMemset(s->d_error, 0, sizeof(unsigned int));
-    if (e != hipSuccess) { std::string m = hipGetErrorString(e); zdr_scene_destroy(s); return fail(ZDR_E_HIP, "scene upload: " + m); }
-    s->ds.isect = s->d_isect; s->ds.pairs = s->d_pairs; s->ds.ppairs = s->d_ppairs; s->ds.shade = s->d_shade; s->ds.nodes = s->d_nodes; s->ds.emission = s->d_emission;
-    s->ds.light_insts = s->d_light_insts; s->ds.inst_tri_begin = s->d_inst_tri_begin; s->ds.slot_of_tri = s->d_slot_of_tri;
-    s->ds.error_word = s->d_error;
-    if (const char *e = getenv("ZDR_DEBUG_BVH_BUDGET")) s->ds.debug_bvh_budget = atoi(e);
-    s->ds.nquads = (int32_t)s->nquads; s->ds.nquads2 = (int32_t)s->nquads2;
-    s->ds.ntris = (int32_t)ntris; s->ds.ninst = (int32_t)ninst; s->ds.light_count = light_count; s->ds.nnodes = (int32_t)s->bvh_nodes; s->ds.stack_entries = (int32_t)s->stack_entries;
-    s->ds.walk_base = (const char *)(one_block ? s->d_nodes : s->d_isect); s->ds.isect_off = one_block ? (uint32_t)(nodes.size() * sizeof(float4)) : 0u;   // accel.h, fetch
-    { int rc = upload_light_table(s, lights, light_count, nullptr); if (rc) { zdr_scene_destroy(s); return rc; } }
+    SceneBuild B;
+    world_records(s, verts8, tris, inst_xform, B);
+    int rc = accel_and_slot_order(s, accel, B);
+    if (!rc) { slot_records(s, B); rc = upload_scene(s, B); }
+    if (rc) { zdr_scene_destroy(s); return rc; }
     *out = s;
     return ZDR_OK;
 }
@@ -763,10 +807,9 @@ extern "C" int zdr_scene_create(const float *verts8, uint32_t nverts, const int3
 extern "C" int zdr_debug_build_accel(const float *tri_xyz, uint32_t ntris, int accel, float *nodes_out, uint32_t nodes_cap,
                                      uint32_t *nnodes, uint32_t *stack_entries, int32_t *order_out, float *isect_out) {
     if (!tri_xyz || !ntris || !nnodes || !order_out || !isect_out) return fail(ZDR_E_INVALID, "null argument");
-    std::vector<h3> pos(3 * (size_t)ntris);
-    for (size_t i = 0; i < 3 * (size_t)ntris; i++) pos[i] = H3(tri_xyz[3 * i], tri_xyz[3 * i + 1], tri_xyz[3 * i + 2]);
+    const std::vector<h3> pos = triangle_corners(tri_xyz, ntris, 3, 9);
     std::vector<int> order; std::vector<float4> nodes; uint32_t nn = 0, depth = 0, se = 8;
-    bool use_bvh = (accel == ZDR_ACCEL_BVH) || (accel == ZDR_ACCEL_AUTO && ntris > 64);
+    const bool use_bvh = wants_bvh(accel, ntris);
     int rc = build_accel(pos, ntris, use_bvh, order, nodes, nn, depth, se); if (rc) return rc;
     std::vector<int> rot(ntris, 0);
     uint32_t npar = 0;
@@ -790,8 +833,7 @@ extern "C" int zdr_debug_build_accel(const float *tri_xyz, uint32_t ntris, int a
 // Host-only: the classification behind the shadow walk's pair mask (never_occluders above), for the CPU test-suite.
 extern "C" int zdr_debug_never_occluders(const float *tri_xyz, uint32_t ntris, const uint8_t *is_light_tri, uint8_t *never_out) {
     if (!tri_xyz || !ntris || !is_light_tri || !never_out) return fail(ZDR_E_INVALID, "null argument");
-    std::vector<h3> pos(3 * (size_t)ntris);
-    for (size_t i = 0; i < 3 * (size_t)ntris; i++) pos[i] = H3(tri_xyz[3 * i], tri_xyz[3 * i + 1], tri_xyz[3 * i + 2]);
+    const std::vector<h3> pos = triangle_corners(tri_xyz, ntris, 3, 9);
     std::vector<uint8_t> light(is_light_tri, is_light_tri + ntris), never;
     never_occluders(pos, ntris, light, never);
     memcpy(never_out, never.data(), ntris);
@@ -801,9 +843,7 @@ extern "C" int zdr_debug_never_occluders(const float *tri_xyz, uint32_t ntris, c
 extern "C" int zdr_scene_destroy(zdr_scene *s) {
     if (!s) return ZDR_OK;
     (void)hipSetDevice(s->device);
-    if (!s->isect_in_nodes) (void)hipFree(s->d_isect); (void)hipFree(s->d_pairs); (void)hipFree(s->d_ppairs); (void)hipFree(s->d_shade); (void)hipFree(s->d_nodes); (void)hipFree(s->d_emission); (void)hipFree(s->d_light_insts); (void)hipFree(s->d_light_tris); (void)hipFree(s->d_light_range); (void)hipFree(s->d_emission4);
-    (void)hipFree(s->d_inst_tri_begin); (void)hipFree(s->d_slot_of_tri); (void)hipFree(s->d_pmj); (void)hipFree(s->d_bn); (void)hipFree(s->d_env_tex); (void)hipFree(s->d_alias_prob); (void)hipFree(s->d_alias_idx); (void)hipFree(s->d_env_pdf); (void)hipFree(s->d_env_scratch); (void)hipFree(s->d_partial); (void)hipFree(s->d_ring); (void)hipFree(s->d_work_counters); (void)hipFree(s->d_tile_masks); (void)hipFree(s->d_cells); (void)hipFree(s->d_counters); (void)hipFree(s->d_error); (void)hipFree(s->d_inst_slot); (void)hipFree(s->d_inst_slot0); (void)hipFree(s->d_emit_acc);
-    for (void *p : s->retired) (void)hipFree(p);
+    DevBuf::free_all(*s);
     delete s;
     return ZDR_OK;
 }
@@ -850,7 +890,7 @@ extern "C" int zdr_scene_set_material_slots(zdr_scene *s, const int32_t *inst_sl
     hipStream_t st = (hipStream_t)stream;
     if (!s->d_inst_slot) {
         if (stream_is_capturing(st)) return fail(ZDR_E_UNSUPPORTED, "the material-slot table would have to be allocated while the stream is capturing");
-        HIPCHK(hipMalloc((void **)&s->d_inst_slot, std::max<size_t>(16, (size_t)s->ninst * sizeof(int32_t))));
+        if (int rc = s->d_inst_slot.reserve(std::max<size_t>(16, (size_t)s->ninst * sizeof(int32_t)), false, "material-slot")) return rc;   // (`false`: refused above, in this call's own words)
         s->device_bytes += (size_t)s->ninst * sizeof(int32_t);
     }
     s->inst_slot.assign(inst_slot, inst_slot + s->ninst);
@@ -864,8 +904,7 @@ extern "C" int zdr_scene_set_envmap(zdr_scene *s, const float *tex, uint32_t tex
     if (!s) return fail(ZDR_E_INVALID, "null scene");
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipDeviceSynchronize());     // nothing in flight may still read the old tables
-    release_buffer(s, s->d_env_tex); release_buffer(s, s->d_alias_prob); release_buffer(s, s->d_alias_idx); release_buffer(s, s->d_env_pdf);
-    s->d_env_tex = nullptr; s->d_alias_prob = nullptr; s->d_alias_idx = nullptr; s->d_env_pdf = nullptr;
+    s->d_env_tex.release(); s->d_alias_prob.release(); s->d_alias_idx.release(); s->d_env_pdf.release();
     s->ds.env_count = 0; s->ds.env_tex = nullptr; s->ds.alias_prob = nullptr; s->ds.alias_idx = nullptr; s->ds.env_pdf = nullptr;
     if (!tex) return ZDR_OK;
     if (!alias_prob || !alias_idx || !pdf || !tex_h || !tex_w || !map_w || !map_h) return fail(ZDR_E_INVALID, "bad envmap arguments");
@@ -874,10 +913,10 @@ extern "C" int zdr_scene_set_envmap(zdr_scene *s, const float *tex, uint32_t tex
         size_t lim = i < map_h ? map_h : map_w;
         if (alias_idx[i] < 0 || (size_t)alias_idx[i] >= lim) return fail(ZDR_E_INVALID, "alias index out of range");
     }
-    HIPCHK(upload(&s->d_env_tex, tex, (size_t)tex_h * tex_w * sizeof(float4), &s->device_bytes));
-    HIPCHK(upload(&s->d_alias_prob, alias_prob, n_alias * sizeof(float), &s->device_bytes));
-    HIPCHK(upload(&s->d_alias_idx, alias_idx, n_alias * sizeof(int32_t), &s->device_bytes));
-    HIPCHK(upload(&s->d_env_pdf, pdf, (size_t)map_w * map_h * sizeof(float), &s->device_bytes));
+    HIPCHK(upload(s->d_env_tex, tex, (size_t)tex_h * tex_w * sizeof(float4), &s->device_bytes));
+    HIPCHK(upload(s->d_alias_prob, alias_prob, n_alias * sizeof(float), &s->device_bytes));
+    HIPCHK(upload(s->d_alias_idx, alias_idx, n_alias * sizeof(int32_t), &s->device_bytes));
+    HIPCHK(upload(s->d_env_pdf, pdf, (size_t)map_w * map_h * sizeof(float), &s->device_bytes));
     s->ds.env_tex = s->d_env_tex; s->ds.alias_prob = s->d_alias_prob; s->ds.alias_idx = s->d_alias_idx; s->ds.env_pdf = s->d_env_pdf;
     s->ds.env_h = (int32_t)tex_h; s->ds.env_w = (int32_t)tex_w; s->ds.map_w = (int32_t)map_w; s->ds.map_h = (int32_t)map_h;
     s->ds.env_count = 1;
@@ -931,12 +970,11 @@ extern "C" int zdr_scene_update_envmap_sampling(zdr_scene *s, int compensate_mis
         if (capturing) return fail(ZDR_E_INVALID, "the workspace of zdr_scene_update_envmap_sampling would have to be allocated while the stream is capturing: call it once on the handle before capturing");
         std::vector<double> row_factor; std::vector<float> taps;
         envmap_sampling_constants(row_factor, taps);
-        EnvSamplingScratch *d = nullptr;
-        HIPCHK(hipMalloc((void **)&d, sizeof(EnvSamplingScratch)));
+        HIPCHK(s->d_env_scratch.alloc(sizeof(EnvSamplingScratch)));
+        EnvSamplingScratch *d = s->d_env_scratch;
         hipError_t e = hipMemcpy(d->row_factor, row_factor.data(), sizeof d->row_factor, hipMemcpyHostToDevice);   // (device addresses only: d is not read here)
         if (e == hipSuccess) e = hipMemcpy(d->taps, taps.data(), sizeof d->taps, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d); return fail(ZDR_E_HIP, std::string("envmap sampling constants: ") + hipGetErrorString(e)); }
-        s->d_env_scratch = d;
+        if (e != hipSuccess) { s->d_env_scratch.release(); return fail(ZDR_E_HIP, std::string("envmap sampling constants: ") + hipGetErrorString(e)); }
         s->device_bytes += sizeof(EnvSamplingScratch);
     }
     if (capturing) s->captured = true;                              // a graph names the tables and the workspace from now on (zdr_scene)
@@ -967,10 +1005,10 @@ extern "C" int zdr_scene_set_pmj02bn_tables(zdr_scene *s, const uint32_t *pmj, u
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipDeviceSynchronize());     // nothing in flight may still read the old tables
     // only the sampler tables belong to this setter (the environment buffers are zdr_scene_set_envmap's)
-    release_buffer(s, s->d_pmj); release_buffer(s, s->d_bn); s->d_pmj = nullptr; s->d_bn = nullptr;
+    s->d_pmj.release(); s->d_bn.release();
     memset(&s->tab, 0, sizeof s->tab);
-    HIPCHK(upload(&s->d_pmj, pmj, (size_t)nsets * nsamples * 2 * sizeof(uint32_t), &s->device_bytes));
-    HIPCHK(upload(&s->d_bn, bn, (size_t)ntex * bnres * bnres * sizeof(uint16_t), &s->device_bytes));
+    HIPCHK(upload(s->d_pmj, pmj, (size_t)nsets * nsamples * 2 * sizeof(uint32_t), &s->device_bytes));
+    HIPCHK(upload(s->d_bn, bn, (size_t)ntex * bnres * bnres * sizeof(uint16_t), &s->device_bytes));
     s->tab.pmj = s->d_pmj; s->tab.bn = s->d_bn; s->tab.nsets = nsets; s->tab.nsamples = nsamples; s->tab.ntex = ntex; s->tab.bnres = bnres;
     return ZDR_OK;
 }
@@ -1084,65 +1122,22 @@ static int make_render_cfg(const zdr_render_params *p, bool backward, RenderCfg 
     return ZDR_OK;
 }
 
-// A workspace that has to grow: not while the stream is capturing (an allocation cannot be recorded, and the capture would name a
-// buffer that does not exist yet) — one eager call of the same kind and size beforehand sizes everything.
-static int may_allocate(bool capturing, const char *what) {
-    if (!capturing) return ZDR_OK;
-    return fail(ZDR_E_UNSUPPORTED, std::string("the ") + what + " workspace would have to be allocated while the stream is capturing: make one eager call of this kind, resolution and spp on the handle first");
-}
-
-static int ensure_partial(zdr_scene *s, const RenderCfg &R, bool capturing) {
-    if (R.nchunks <= 1) return ZDR_OK;
-    size_t need = (size_t)R.nchunks * (size_t)R.ntiles * 64 * sizeof(float4);   // [chunk][tile of the shard][lane]
-    if (need > s->partial_bytes) {
-        if (int rc = may_allocate(capturing, "chunk-partial")) return rc;
-        release_buffer(s, s->d_partial); s->d_partial = nullptr; s->partial_bytes = 0;
-        HIPCHK(hipMalloc((void **)&s->d_partial, need));
-        s->partial_bytes = need;
-    }
-    return ZDR_OK;
-}
+static int zero_fill(void *p, size_t bytes, hipStream_t st) { return zdr_launch_zero(p, bytes, st) ? fail(ZDR_E_HIP, "zero-fill launch failed") : ZDR_OK; }
 
 // Workspace of the path kernels: one FIFO of ZDR_RING_CAP x 64 parked camera-ray vertices (two float4 each,
 // 32 KiB) per persistent workgroup, and the eight item counters the workgroups draw from (zeroed per launch).
 static int ensure_ring(zdr_scene *s, hipStream_t st, bool capturing) {
-    size_t need = (size_t)ZDR_MAX_PERSISTENT_BLOCKS * ZDR_RING_CAP * 2 * 64 * sizeof(float4);
-    if (need > s->ring_bytes) {
-        if (int rc = may_allocate(capturing, "parked-vertex FIFO")) return rc;
-        release_buffer(s, s->d_ring); s->d_ring = nullptr; s->ring_bytes = 0;
-        HIPCHK(hipMalloc((void **)&s->d_ring, need));
-        s->ring_bytes = need;
-    }
-    if (!s->d_work_counters) { if (int rc = may_allocate(capturing, "work-counter")) return rc; HIPCHK(hipMalloc((void **)&s->d_work_counters, 8 * sizeof(unsigned int))); }
-    if (zdr_launch_zero(s->d_work_counters, 8 * sizeof(unsigned int), st)) return fail(ZDR_E_HIP, "zero-fill launch failed");
-    return ZDR_OK;
+    if (int rc = s->d_ring.reserve((size_t)ZDR_MAX_PERSISTENT_BLOCKS * ZDR_RING_CAP * 2 * 64 * sizeof(float4), capturing, "parked-vertex FIFO")) return rc;
+    if (int rc = s->d_work_counters.reserve(8 * sizeof(unsigned int), capturing, "work-counter")) return rc;
+    return zero_fill(s->d_work_counters, 8 * sizeof(unsigned int), st);
 }
 
 // ncells: cells of one copy ((tex_h + 1) x (tex_w + 1), or MaterialTable::ncells)
 // extra_cells: cells behind all copies (the environment map's, zdr_render_backward_env)
 static int ensure_cells(zdr_scene *s, const RenderCfg &R, size_t ncells, hipStream_t st, bool capturing, size_t extra_cells = 0) {
     size_t need = ((size_t)R.cell_copies * ncells + extra_cells) * 16 * sizeof(float);
-    if (need > s->cells_bytes) {
-        if (int rc = may_allocate(capturing, "staging-cell")) return rc;
-        release_buffer(s, s->d_cells); s->d_cells = nullptr; s->cells_bytes = 0;
-        HIPCHK(hipMalloc((void **)&s->d_cells, need));
-        s->cells_bytes = need;
-    }
-    if (zdr_launch_zero(s->d_cells, need, st)) return fail(ZDR_E_HIP, "zero-fill launch failed");
-    return ZDR_OK;
-}
-
-// The emission-gradient accumulator (internal.h, KernelIO::emit_acc): sized once for every light list the scene can have, zeroed per call
-static int ensure_emit_acc(zdr_scene *s, hipStream_t st, bool capturing) {
-    const size_t need = (size_t)ZDR_EMISSION_COPIES * 3 * (size_t)s->ninst * sizeof(float);
-    if (need > s->emit_acc_bytes) {
-        if (int rc = may_allocate(capturing, "emission-accumulator")) return rc;
-        release_buffer(s, s->d_emit_acc); s->d_emit_acc = nullptr; s->emit_acc_bytes = 0;
-        HIPCHK(hipMalloc((void **)&s->d_emit_acc, need));
-        s->emit_acc_bytes = need;
-    }
-    if (zdr_launch_zero(s->d_emit_acc, (size_t)ZDR_EMISSION_COPIES * 3 * (size_t)s->ds.light_count * sizeof(float), st)) return fail(ZDR_E_HIP, "zero-fill launch failed");
-    return ZDR_OK;
+    if (int rc = s->d_cells.reserve(need, capturing, "staging-cell")) return rc;
+    return zero_fill(s->d_cells, need, st);
 }
 
 // Reads (and clears) the device error word; the stream is synchronised first.  A set bit means a watchdog ended
@@ -1211,7 +1206,7 @@ static int single_material_slots(zdr_scene *s, bool capturing, const int32_t *&o
         if (int rc = may_allocate(capturing, "material-slot")) return rc;
         std::vector<int32_t> t(s->ninst, -1);
         t[0] = 0;
-        HIPCHK(upload(&s->d_inst_slot0, t.data(), (size_t)s->ninst * sizeof(int32_t), &s->device_bytes));
+        HIPCHK(upload(s->d_inst_slot0, t.data(), (size_t)s->ninst * sizeof(int32_t), &s->device_bytes));
     }
     out = s->d_inst_slot0;
     return ZDR_OK;
@@ -1319,24 +1314,26 @@ static int render_common(zdr_scene *s, const zdr_render_params *p, const RenderC
     if (capturing) s->captured = true;                  // sticky: a graph may name this handle's buffers from now on (zdr_scene)
     if (backward) { rc = ensure_cells(s, R, table_form ? (size_t)mt.ncells : (size_t)(R.tex_h + 1) * (R.tex_w + 1), st, capturing,
                                       env_cells_total); if (rc) return rc; }
-    else if (!stats) { rc = ensure_partial(s, R, capturing); if (rc) return rc; }
+    else if (!stats && R.nchunks > 1) {                 // [chunk][tile of the shard][lane]
+        rc = s->d_partial.reserve((size_t)R.nchunks * (size_t)R.ntiles * 64 * sizeof(float4), capturing, "chunk-partial"); if (rc) return rc;
+    }
     if (p->integrator == ZDR_PATH) {
         if (p->spp > (1u << 25)) return fail(ZDR_E_UNSUPPORTED, "path integrator: spp above 2^25");   // queue entries pack pixel << 26 | bank << 25 | sample
         rc = ensure_ring(s, st, capturing); if (rc) return rc;
     }
     KernelIO io; memset(&io, 0, sizeof io);
-    if (emit_grad) { rc = ensure_emit_acc(s, st, capturing); if (rc) return rc; }
+    if (emit_grad) {    // the emission-gradient accumulator (internal.h, KernelIO::emit_acc): sized once for every light list the scene can have, zeroed per call
+        rc = s->d_emit_acc.reserve((size_t)ZDR_EMISSION_COPIES * 3 * (size_t)s->ninst * sizeof(float), capturing, "emission-accumulator"); if (rc) return rc;
+        rc = zero_fill(s->d_emit_acc, (size_t)ZDR_EMISSION_COPIES * 3 * (size_t)s->ds.light_count * sizeof(float), st); if (rc) return rc;
+    }
     io.ring = s->d_ring; io.work_counters = s->d_work_counters;
     // brute-force scenes of at most 64 triangle pairs: camera rays test only the pairs their tile can see
     const bool masks = !s->accel_is_bvh && s->ds.ntris <= 128 && p->integrator != ZDR_UVGRAD && !getenv("ZDR_NO_TILE_MASKS");
     if (masks) {
-        size_t need = (size_t)R.tiles_x * R.tiles_y * sizeof(unsigned long long);
-        if (need > s->tile_mask_bytes) {
-            if (int rc2 = may_allocate(capturing, "tile-mask")) return rc2;
-            release_buffer(s, s->d_tile_masks); s->d_tile_masks = nullptr; s->tile_mask_bytes = 0; s->tile_mask_key_set = false;
-            HIPCHK(hipMalloc((void **)&s->d_tile_masks, need));
-            s->tile_mask_bytes = need;
-        }
+        const size_t need = (size_t)R.tiles_x * R.tiles_y * sizeof(unsigned long long);
+        const bool replaced = need > s->d_tile_masks.bytes;
+        rc = s->d_tile_masks.reserve(need, capturing, "tile-mask"); if (rc) return rc;
+        if (replaced) s->tile_mask_key_set = false;
         io.tile_masks = s->d_tile_masks;
         // the masks depend on the camera and the tile grid only (the geometry of a scene handle never changes):
         // an optimisation loop that renders the same view again does not rebuild them

@@ -109,7 +109,21 @@ class EmissionValues(list):
         self.values = values
 
 
-class Aovs:
+class _ChannelViews:
+    """``data``, an (H, W, 16) tensor, with each entry of the subclass's ``CHANNELS`` as an attribute: a view into it."""
+    CHANNELS = {}
+
+    def __init__(self, data):
+        self.data = data
+
+    def __getattr__(self, name):                       # (reached for names that are not attributes: the channels)
+        if name not in self.CHANNELS:
+            raise AttributeError(name)
+        a, b = self.CHANNELS[name]
+        return self.data[..., a] if b - a == 1 else self.data[..., a:b]
+
+
+class Aovs(_ChannelViews):
     """First-hit feature buffers of ``Scene.render_aovs`` (include/zdr.h, zdr_render_aovs): ``data`` is the (H, W, 16) tensor, the
     attributes are views into it.  Every averaged channel is premultiplied by ``coverage`` (divide by it for the mean over the
     samples that hit); ``instance`` and ``slot`` are those of the pixel's first sample that hit, -1 where none did.  ``albedo`` and
@@ -117,17 +131,8 @@ class Aovs:
     CHANNELS = {"albedo": (0, 3), "roughness": (3, 4), "normal": (4, 7), "depth": (7, 8), "position": (8, 11), "coverage": (11, 12),
                 "uv": (12, 14), "instance": (14, 15), "slot": (15, 16)}
 
-    def __init__(self, data):
-        self.data = data
 
-    def __getattr__(self, name):                       # (reached for names that are not attributes: the channels)
-        if name not in Aovs.CHANNELS:
-            raise AttributeError(name)
-        a, b = Aovs.CHANNELS[name]
-        return self.data[..., a] if b - a == 1 else self.data[..., a:b]
-
-
-class TexelAovs:
+class TexelAovs(_ChannelViews):
     """Texture-space feature buffers of ``Scene.texel_aovs`` (include/zdr.h, zdr_scene_texel_aovs): ``data`` is the (H, W, 16) tensor of
     one material's texels, the attributes are views into it.  ``coverage``: the texel's lattice point lies on a model; ``reach``: a
     bilinear lookup somewhere on a model can read the texel (so it can receive gradient); ``position``, ``normal``: of the surface at
@@ -136,15 +141,6 @@ class TexelAovs:
     depend on the geometry and the slot table only and carry no gradient.  The layout is ``Aovs``'s, so ``denoise`` takes them as guides."""
     CHANNELS = {"normal": (4, 7), "texel_size": (7, 8), "position": (8, 11), "coverage": (11, 12), "reach": (12, 13),
                 "instance": (14, 15), "slot": (15, 16)}
-
-    def __init__(self, data):
-        self.data = data
-
-    def __getattr__(self, name):
-        if name not in TexelAovs.CHANNELS:
-            raise AttributeError(name)
-        a, b = TexelAovs.CHANNELS[name]
-        return self.data[..., a] if b - a == 1 else self.data[..., a:b]
 
     def as_guides(self, reached=True):
         """A copy of ``data`` for ``denoise``, which reads channel 11 as its coverage: with ``reached`` that channel holds ``reach``, so
@@ -373,6 +369,12 @@ class Scene:
         N.check(N.lib().zdr_scene_set_pmj02bn_tables(self._handle, pmj.ctypes.data, pmj.shape[0], pmj.shape[1], bn.ctypes.data, bn.shape[0], bn.shape[1]))
         self._pmj_tables_set = True
 
+    def _ensure_pmj_tables(self):
+        """The reference's pbrt tables are not shipped: without tables of the caller's, generated ones (zdr_amd/pmj02bn_tables.py)."""
+        if not getattr(self, "_pmj_tables_set", False):
+            from . import pmj02bn_tables
+            self.set_pmj02bn_tables(*pmj02bn_tables.default_tables(verbose=True))
+
     # -------------------------------------------------------------------------- materials
     @property
     def material_slots(self):
@@ -393,6 +395,25 @@ class Scene:
         table = np.array([-1 if k is None else k for k in slots], np.int32)
         N.check(N.lib().zdr_scene_set_material_slots(self._handle, table.ctypes.data, self._stream()))
         self._uploaded_slots = slots
+
+    def _call_slots(self, nmat, model0=False):
+        """The slot table of a call with ``nmat`` materials: ``material_slots``, or the default mapping — or, ``model0`` and
+        ``material_slots`` unset, material 0 on model 0 alone."""
+        if model0 and self._material_slots is None:
+            return (0,) + (None,) * (self.inst_count - 1)
+        return resolve_material_slots(self._material_slots, self.emissions, nmat)
+
+    def _resolve_materials(self, material, single_is_model0=False, pack=True):
+        """(mats, slots, dims, packed) of ``material`` as ``render`` takes it, a tensor or a list of tensors: the list, the slot table
+        that goes with it, the sizes, and (``pack``; else None) the texels as one tensor, which carries the graph: a copy when there
+        are several.  ``single_is_model0``: with ``material_slots`` unset a single tensor belongs to model 0 alone."""
+        mats = list(material) if isinstance(material, (list, tuple)) else [material]
+        for m in mats:
+            self._check_material(m)
+        slots = self._call_slots(len(mats), single_is_model0 and not isinstance(material, (list, tuple)))
+        dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
+        packed = None if not pack else mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
+        return mats, slots, dims, packed
 
     def _material_call(self, materials, dims, slots=None):
         """(packed material tensor, int32 dims array, slot table) of a material-table call: ``materials`` is a list / tuple of
@@ -417,6 +438,24 @@ class Scene:
         self._upload_slots(tuple(slots))
         return packed, np.ascontiguousarray(np.array(dims, np.int32).reshape(-1, 2)), tuple(slots)
 
+    def _pack_grads(self, d_materials, packed):
+        """``d_materials`` — a list shaped like the materials, or one tensor — as the one tensor a native backward accumulates into:
+        a copy when the list holds several, which _unpack_grads copies back."""
+        listed = isinstance(d_materials, (list, tuple))
+        dpacked = (torch.cat([g.reshape(-1, 4) for g in d_materials]) if len(d_materials) > 1 else d_materials[0]) if listed else d_materials
+        if dpacked.numel() != packed.numel() or not dpacked.is_contiguous() or dpacked.device != self.device or dpacked.dtype != torch.float32:
+            raise ValueError(f"d_materials must be contiguous float32 on {self.device}, shaped like the materials")
+        return dpacked
+
+    @staticmethod
+    def _unpack_grads(dpacked, d_materials):
+        if isinstance(d_materials, (list, tuple)) and len(d_materials) > 1:
+            off = 0
+            for t in d_materials:
+                t.copy_(dpacked[off:off + t.numel() // 4].reshape(t.shape))
+                off += t.numel() // 4
+        return d_materials
+
     def render_forward_materials(self, materials, res, spp, seed, *, dims=None, rect=None, samples=None, out=None, tile_shard=None, slots=None):
         """``render_forward`` with one material per slot (include/zdr.h, zdr_render_forward_materials).  ``materials``: a list of
         (H_k, W_k, 4) tensors, or their packed texels with ``dims``.  ``slots``: the slot table to use (default: ``material_slots``,
@@ -432,19 +471,11 @@ class Scene:
         """``render_backward`` with one material per slot: accumulates into ``d_materials`` (a list shaped like ``materials``, or
         one packed tensor); uses ``seed + 1`` like render_backward.  ``d_env``, ``d_emission``: as in render_backward."""
         packed, d, _ = self._material_call(materials, dims, slots)
-        listed = isinstance(d_materials, (list, tuple))
-        dpacked = (torch.cat([g.reshape(-1, 4) for g in d_materials]) if len(d_materials) > 1 else d_materials[0]) if listed else d_materials
-        if dpacked.numel() != packed.numel() or not dpacked.is_contiguous() or dpacked.device != self.device or dpacked.dtype != torch.float32:
-            raise ValueError(f"d_materials must be contiguous float32 on {self.device}, shaped like the materials")
+        dpacked = self._pack_grads(d_materials, packed)
         g = grad_output.reshape(res[1], res[0], 4).to(device=self.device, dtype=torch.float32).contiguous()
         p = self._params(res, spp, seed + 1, (1, 1), rect, samples, camera, tile_shard=tile_shard)
         self._native_backward(p, g, packed, d, dpacked, d_env, d_emission)
-        if listed and len(d_materials) > 1:
-            off = 0
-            for t in d_materials:
-                t.copy_(dpacked[off:off + t.numel() // 4].reshape(t.shape))
-                off += t.numel() // 4
-        return d_materials
+        return self._unpack_grads(dpacked, d_materials)
 
     # --------------------------------------------------------------------- feature buffers
     def _aov_call(self, materials, dims, slots):
@@ -452,8 +483,8 @@ class Scene:
         one material belongs to model 0 alone — what the path and the direct integrator do with a single material."""
         if isinstance(materials, torch.Tensor) and dims is None:
             materials = [materials]
-        if slots is None and self._material_slots is None and (len(dims) if dims is not None else len(materials)) == 1:
-            slots = (0,) + (None,) * (self.inst_count - 1)
+        if slots is None and (len(dims) if dims is not None else len(materials)) == 1:
+            slots = self._call_slots(1, model0=True)
         return self._material_call(materials, dims, slots)
 
     def render_aovs_forward(self, materials, res, spp, seed, *, dims=None, slots=None, rect=None, tile_shard=None, out=None):
@@ -462,11 +493,7 @@ class Scene:
         0 unless ``material_slots`` says otherwise).  With ``rect`` / ``tile_shard`` only that shard is written; other pixels of
         ``out`` keep their value, a fresh buffer is zero-filled."""
         packed, d, _ = self._aov_call(materials, dims, slots)
-        shape = (int(res[1]), int(res[0]), N.AOV_CHANNELS)
-        if out is None:
-            out = torch.zeros(shape, dtype=torch.float32, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
+        out = self._out_tensor(out, (int(res[1]), int(res[0]), N.AOV_CHANNELS), True)
         p = self._params(res, spp, seed, (1, 1), rect, None, tile_shard=tile_shard)
         N.check(N.lib().zdr_render_aovs(self._handle, C.byref(p), packed.data_ptr(), d.ctypes.data, d.shape[0], out.data_ptr(), self._stream()))
         return out
@@ -476,20 +503,12 @@ class Scene:
         like ``materials``, one tensor, or the packed texels).  ``grad`` is the (H, W, 16) cotangent, of which floats 0..3 are read.
         The SAME ``seed`` as the forward: this is its exact transpose."""
         packed, d, _ = self._aov_call(materials, dims, slots)
-        listed = isinstance(d_materials, (list, tuple))
-        dpacked = (torch.cat([g.reshape(-1, 4) for g in d_materials]) if len(d_materials) > 1 else d_materials[0]) if listed else d_materials
-        if dpacked.numel() != packed.numel() or not dpacked.is_contiguous() or dpacked.device != self.device or dpacked.dtype != torch.float32:
-            raise ValueError(f"d_materials must be contiguous float32 on {self.device}, shaped like the materials")
+        dpacked = self._pack_grads(d_materials, packed)
         g = grad.reshape(res[1], res[0], N.AOV_CHANNELS).to(device=self.device, dtype=torch.float32).contiguous()
         p = self._params(res, spp, seed, (1, 1), rect, None, camera, tile_shard=tile_shard)
         N.check(N.lib().zdr_render_aovs_backward(self._handle, C.byref(p), g.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
                                                  dpacked.data_ptr(), self._stream()))
-        if listed and len(d_materials) > 1:
-            off = 0
-            for t in d_materials:
-                t.copy_(dpacked[off:off + t.numel() // 4].reshape(t.shape))
-                off += t.numel() // 4
-        return d_materials
+        return self._unpack_grads(dpacked, d_materials)
 
     class AovOperator(torch.autograd.Function):
         """render_aovs() of the packed texels of its materials: returns the (H, W, 16) buffers and, backward, the packed gradient
@@ -518,16 +537,7 @@ class Scene:
         or a list exactly as ``render`` takes it; albedo and roughness are differentiable with respect to it (to each tensor of a
         list).  The scene's integrator does not matter.  With one tensor and ``material_slots`` unset only model 0 has a material
         (slot 0), as in the path and direct integrators; every other model reads albedo 0 and slot -1."""
-        if not isinstance(material, (list, tuple)) and self._material_slots is None:
-            mats = [material]
-            slots = (0,) + (None,) * (self.inst_count - 1)
-        else:
-            mats = list(material) if isinstance(material, (list, tuple)) else [material]
-            slots = resolve_material_slots(self._material_slots, self.emissions, len(mats))
-        for m in mats:
-            self._check_material(m)
-        dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
-        packed = mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
+        _, slots, dims, packed = self._resolve_materials(material, True)
         return Aovs(Scene.AovOperator.apply(packed, self, res, spp, seed, dims, slots))
 
     # ------------------------------------------------------------- texture-space buffers
@@ -538,18 +548,8 @@ class Scene:
         H, W = int(tex_hw[0]), int(tex_hw[1])
         if slots is not None:
             self._upload_slots(check_material_slots(slots, self.inst_count))
-        need = int(N.lib().zdr_texel_aovs_workspace_bytes(H, W))
-        if need == 0:
-            raise N.ZdrError(f"libzdr_hip error: {N.lib().zdr_last_error().decode()}")
-        shape = (H, W, N.AOV_CHANNELS)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        elif workspace.device != self.device or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
-            raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {self.device}")
+        workspace = self._workspace(workspace, int(N.lib().zdr_texel_aovs_workspace_bytes(H, W)))
+        out = self._out_tensor(out, (H, W, N.AOV_CHANNELS), False)
         N.check(N.lib().zdr_scene_texel_aovs(self._handle, int(index), H, W, out.data_ptr(), workspace.data_ptr(), self._stream()))
         return out
 
@@ -558,18 +558,10 @@ class Scene:
         zdr_scene_texel_aovs, at that material's size — coverage, reach, world position, normal, texel size, instance and slot, with a
         named view for each.  ``material`` is a tensor or a list exactly as ``render_aovs`` takes it; it is used for its sizes and to
         resolve the slots only (with one tensor and ``material_slots`` unset only model 0 has material 0).  No gradient."""
-        if not isinstance(material, (list, tuple)) and self._material_slots is None:
-            mats = [material]
-            slots = (0,) + (None,) * (self.inst_count - 1)
-        else:
-            mats = list(material) if isinstance(material, (list, tuple)) else [material]
-            slots = resolve_material_slots(self._material_slots, self.emissions, len(mats))
-        for m in mats:
-            self._check_material(m)
-        if not 0 <= int(index) < len(mats):
-            raise ValueError(f"index {index}: {len(mats)} materials were given")
-        m = mats[int(index)]
-        return TexelAovs(self.texel_aovs_forward(int(index), (int(m.shape[0]), int(m.shape[1])), slots=slots))
+        _, slots, dims, _ = self._resolve_materials(material, True, pack=False)
+        if not 0 <= int(index) < len(dims):
+            raise ValueError(f"index {index}: {len(dims)} materials were given")
+        return TexelAovs(self.texel_aovs_forward(int(index), dims[int(index)], slots=slots))
 
     # ------------------------------------------------------------- texture-space lighting
     def texel_lighting_forward(self, texel_data, *, spp, seed=0, samples=None, max_distance=None, sampler=None, out=None, workspace=None):
@@ -586,21 +578,10 @@ class Scene:
         sampler = self.sampler if sampler is None else sampler
         if sampler not in N.SAMPLERS:
             raise ValueError(f"unknown sampler {sampler!r}")
-        if sampler == "pmj02bn" and not getattr(self, "_pmj_tables_set", False):
-            from . import pmj02bn_tables                                # (as _params: generated tables when none were set)
-            self.set_pmj02bn_tables(*pmj02bn_tables.default_tables(verbose=True))
-        need = int(N.lib().zdr_texel_lighting_workspace_bytes(H, W))
-        if need == 0:
-            raise N.ZdrError(f"libzdr_hip error: {N.lib().zdr_last_error().decode()}")
-        shape = (H, W, 4)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        elif workspace.device != self.device or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
-            raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {self.device}")
+        if sampler == "pmj02bn":
+            self._ensure_pmj_tables()
+        workspace = self._workspace(workspace, int(N.lib().zdr_texel_lighting_workspace_bytes(H, W)))
+        out = self._out_tensor(out, (H, W, 4), False)
         p = N.TexelLightingParams()
         p.struct_size = C.sizeof(N.TexelLightingParams)
         p.tex_h, p.tex_w, p.spp, p.seed, p.sampler = H, W, int(spp), int(seed) & 0xFFFFFFFF, N.SAMPLERS[sampler]
@@ -636,10 +617,8 @@ class Scene:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _params(self, res, spp, seed, tex_hw, rect=None, samples=None, camera=None, integrator=None, tile_shard=None) -> N.RenderParams:
-        if self.sampler == "pmj02bn" and not getattr(self, "_pmj_tables_set", False):
-            # the reference's pbrt tables are not shipped: fall back to generated ones (zdr_amd/pmj02bn_tables.py)
-            from . import pmj02bn_tables
-            self.set_pmj02bn_tables(*pmj02bn_tables.default_tables(verbose=True))
+        if self.sampler == "pmj02bn":
+            self._ensure_pmj_tables()
         p = N.RenderParams()
         p.struct_size = C.sizeof(N.RenderParams)
         p.integrator, p.sampler = self._integrator if integrator is None else integrator, N.SAMPLERS[self.sampler]
@@ -655,14 +634,29 @@ class Scene:
         p.prb_mode = N.PRB_MODES[self.prb_mode]
         return p
 
-    def _image_out(self, out, res):
-        """The image a forward call writes: ``out`` once checked, or a fresh one — zero-filled even when the call covers every pixel: a
-        dropped work item must never surface as uninitialised memory."""
+    def _out_tensor(self, out, shape, zero):
+        """The tensor a call writes: ``out`` once checked, or a fresh one of ``shape`` (``zero``: zero-filled)."""
         if out is None:
-            return torch.zeros((res[1], res[0], 4), dtype=torch.float32, device=self.device)
-        if out.shape != (res[1], res[0], 4) or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 ({res[1]}, {res[0]}, 4) tensor on {self.device}")
+            return (torch.zeros if zero else torch.empty)(shape, dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
         return out
+
+    def _workspace(self, workspace, need):
+        """The workspace of a call that needs ``need`` bytes (what its ``*_workspace_bytes`` returned: 0 = the sizes were refused):
+        ``workspace`` once checked, or a fresh one."""
+        if need == 0:
+            raise N.ZdrError(f"libzdr_hip error: {N.lib().zdr_last_error().decode()}")
+        if workspace is None:
+            return torch.empty(need, dtype=torch.uint8, device=self.device)
+        if workspace.device != self.device or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {self.device}")
+        return workspace
+
+    def _image_out(self, out, res):
+        """The image a forward call writes — zero-filled even when the call covers every pixel: a dropped work item must never
+        surface as uninitialised memory."""
+        return self._out_tensor(out, (int(res[1]), int(res[0]), 4), True)
 
     def _native_backward(self, p, g, material, dims, d_material, d_env, d_emission):
         """The native backward call of render_backward (``dims`` None) and render_backward_materials (``dims``: the int32 array of
@@ -809,14 +803,10 @@ class Scene:
         env = None if envmap is None else self._prepare_envmap(envmap)
         if not isinstance(material, (list, tuple)) and self._material_slots is None:
             return Scene.RenderOperator.apply(material, self, res, spp, seed, env, emissions, None, None, bool(update_sampling))
-        mats = list(material) if isinstance(material, (list, tuple)) else [material]
-        if env is not None and len(mats) > N.MAX_MATERIALS - 1:
-            raise ValueError(f"{len(mats)} materials given with envmap=: at most {N.MAX_MATERIALS - 1} (the map takes the last entry of the material table)")
-        for m in mats:
-            self._check_material(m)
-        slots = resolve_material_slots(self._material_slots, self.emissions, len(mats))
-        dims = tuple((int(m.shape[0]), int(m.shape[1])) for m in mats)
-        packed = mats[0] if len(mats) == 1 else torch.cat([m.reshape(-1, 4) for m in mats])
+        nmat = len(material) if isinstance(material, (list, tuple)) else 1
+        if env is not None and nmat > N.MAX_MATERIALS - 1:
+            raise ValueError(f"{nmat} materials given with envmap=: at most {N.MAX_MATERIALS - 1} (the map takes the last entry of the material table)")
+        _, slots, dims, packed = self._resolve_materials(material)
         return Scene.RenderOperator.apply(packed, self, res, spp, seed, env, emissions, dims, slots, bool(update_sampling))
 
     def render_duvdxy(self, material, *, res, spp, seed=0):
@@ -910,9 +900,13 @@ class Scene:
                                             d_materials.data_ptr(), None if d_env is None else d_env.data_ptr(), copies.ctypes.data, self._stream()))
         return copies
 
+    def _queries(self, queries):
+        """(n, 3) int32 {px, py, sample_index} on the scene's device, contiguous."""
+        return queries.reshape(-1, 3).to(device=self.device, dtype=torch.int32).contiguous()
+
     def sampler_dump(self, queries, spp, seed=0, nvert=3, rr_depth=RR_DEPTH):
         """queries: (n, 3) int32 cuda {px, py, sample_index} -> (n, 2 + 8*nvert) float32 sampler draws."""
-        q = queries.reshape(-1, 3).to(device=self.device, dtype=torch.int32).contiguous()
+        q = self._queries(queries)
         out = torch.empty((q.shape[0], 2 + 8 * nvert), dtype=torch.float32, device=self.device)
         N.check(N.lib().zdr_sampler_dump(self._handle, N.SAMPLERS[self.sampler], int(seed) & 0xFFFFFFFF, int(spp), q.data_ptr(), q.shape[0], nvert, rr_depth, out.data_ptr(), self._stream()))
         return out
@@ -920,7 +914,7 @@ class Scene:
     def vertex_sampler_dump(self, queries, spp, seed=0, nvert=3, rr_depth=RR_DEPTH, integrator="path"):
         """As sampler_dump, but drawn the way the path (or the direct) kernels draw (include/zdr.h, zdr_vertex_sampler_dump).
         Returns (draws, batched): batched is True when the packed two-permutations-per-register route ran."""
-        q = queries.reshape(-1, 3).to(device=self.device, dtype=torch.int32).contiguous()
+        q = self._queries(queries)
         out = torch.empty((q.shape[0], 2 + 8 * nvert), dtype=torch.float32, device=self.device)
         b = C.c_int32(-1)
         N.check(N.lib().zdr_vertex_sampler_dump(self._handle, N.INTEGRATORS[integrator], N.SAMPLERS[self.sampler], int(seed) & 0xFFFFFFFF, int(spp), q.data_ptr(), q.shape[0], nvert, rr_depth, out.data_ptr(), C.byref(b), self._stream()))
@@ -931,7 +925,7 @@ class Scene:
         (n, 8 + 24 maxv) float32.  ``seed`` is used as it is (pass seed + 1 for the paths of a backward pass)."""
         self._check_material(material)
         material = material.detach().contiguous()
-        q = queries.reshape(-1, 3).to(device=self.device, dtype=torch.int32).contiguous()
+        q = self._queries(queries)
         out = torch.empty((q.shape[0], 8 + 24 * maxv), dtype=torch.float32, device=self.device)
         p = self._params(res, spp, seed, material.shape[0:2])
         g = None if d_image is None else d_image.reshape(res[1], res[0], 4).to(device=self.device, dtype=torch.float32).contiguous()
