@@ -14,6 +14,11 @@ render is a biased estimate of the loss of the converged image, the filtered ren
 of the surface the texel lies on (seam padding included: texels that a lookup reaches take part).
 --mask-unreached writes texture_diffuse.png with the texels that no lookup can ever read (reach 0: they never receive gradient and
 stay random noise) black.
+--fill-unreached writes texture_diffuse.png with every texel that lies on no model (coverage 0: the padding ring of each chart, which
+gets only the bilinear spill of its neighbours' gradient, and the texels nothing reaches) filled from the covered texels by push-pull
+(zdr_amd.push_pull): the covered texels stay as they are.  It takes precedence over --mask-unreached for the texels it fills.
+--fill-param optimises theta with material = push_pull(theta, coverage): the holes are always the smooth continuation of their chart,
+and the gradient that spills onto them is carried back to the covered texels (theta.grad is 0 elsewhere).
 --save-lighting writes irradiance.png and openness.png, the texture-space lighting of the material (scene.texel_lighting: direct
 irradiance and the open fraction of the hemisphere per texel), and prints the share of the reached texels that no light sample reached:
 a texel in shadow gets only noise for a gradient, whatever its reach.
@@ -30,7 +35,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from zdr_amd import Camera, Scene, denoise as zdr_denoise, float3
+from zdr_amd import Camera, Scene, denoise as zdr_denoise, float3, push_pull
 
 ASSETS = os.path.join(ROOT, "tests", "golden", "assets")
 
@@ -62,7 +67,7 @@ def texel_prior_loss(material, f, guides):
 
 
 def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0, denoise=False,
-        texel_prior=0.0, mask_unreached=False, save_lighting=False):
+        texel_prior=0.0, mask_unreached=False, save_lighting=False, fill_unreached=False, fill_param=False):
     scene = Scene([(os.path.join(ASSETS, "cboxuv.obj"), None, float3(0.0)),
                    (os.path.join(ASSETS, "cbox-light.obj"), None, float3(17, 12, 4))], integrator=integrator)
     scene.camera = Camera(fov=50 / 180 * 3.1415926, origin=float3(-0.2, 2.6, 6.0), target=float3(-0.2, 2.6, -2.5), up=float3(0.0, 1.0, 0.0))
@@ -70,13 +75,16 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
     image_gt = scene.render(material_gt, res=(res, res), spp=max(256, 4 * spp))          # seed defaults to 0
     rng = random.Random(seed)
     g = torch.Generator(device="cuda").manual_seed(seed)
-    material = torch.rand((tex, tex, 4), device="cuda", generator=g).requires_grad_()
-    opt = torch.optim.Adam([material], lr=0.02)
+    theta = torch.rand((tex, tex, 4), device="cuda", generator=g).requires_grad_()
+    opt = torch.optim.Adam([theta], lr=0.02)
     losses = []
-    texels = scene.texel_aovs(material.detach()) if (texel_prior > 0.0 or mask_unreached or save_lighting) else None   # geometry only: once
+    texels = scene.texel_aovs(theta.detach()) if (texel_prior > 0.0 or mask_unreached or save_lighting or fill_unreached or fill_param) else None   # geometry only: once
     guides = texels.as_guides() if texel_prior > 0.0 else None
+    material = theta
     for it in range(iters):
         opt.zero_grad()
+        if fill_param:
+            material = push_pull(theta, texels.coverage)
         step_seed = rng.randint(0, 2147483646)
         image = (scene.render_denoised if denoise else scene.render)(material, res=(res, res), spp=spp, seed=step_seed)
         loss = (image[..., :3] - image_gt[..., :3]).abs().mean()
@@ -87,10 +95,11 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
         loss.backward()
         opt.step()
         with torch.no_grad():
-            material.clamp_(1e-3, 1.0)                                                     # roughness / albedo stay physical
+            theta.clamp_(1e-3, 1.0)                                                        # roughness / albedo stay physical
         losses.append(float(loss))
         if verbose and (it % 20 == 0 or it == iters - 1):
             print(f"iteration {it:4d}  L1 image loss {losses[-1]:.5f}", flush=True)
+    material = push_pull(theta.detach(), texels.coverage) if fill_param else theta.detach()   # (a convex combination: stays within the clamp)
     if save_lighting:                                              # printed with or without --out; the images need it
         light = scene.texel_lighting(material.detach(), spp=max(64, spp), texels=texels)
         reached = texels.reach == 1
@@ -102,7 +111,10 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
         os.makedirs(out, exist_ok=True)
         save_png(os.path.join(out, "target.png"), image_gt)
         save_png(os.path.join(out, "result.png"), scene.render(material.detach(), res=(res, res), spp=max(256, 4 * spp)))
-        save_png(os.path.join(out, "texture_diffuse.png"), material.detach() * (texels.reach[..., None] if mask_unreached else 1.0))
+        if fill_unreached:
+            save_png(os.path.join(out, "texture_diffuse.png"), texels.fill(material))
+        else:
+            save_png(os.path.join(out, "texture_diffuse.png"), material * (texels.reach[..., None] if mask_unreached else 1.0))
         if save_lighting:
             save_png(os.path.join(out, "irradiance.png"), light.irradiance / light.irradiance.max().clamp_min(1e-8))
             save_png(os.path.join(out, "openness.png"), light.openness[..., None].expand(-1, -1, 3))
@@ -125,6 +137,9 @@ if __name__ == "__main__":
     ap.add_argument("--texel-prior", type=float, default=0.0)
     ap.add_argument("--mask-unreached", action="store_true")
     ap.add_argument("--save-lighting", action="store_true")
+    ap.add_argument("--fill-unreached", action="store_true")
+    ap.add_argument("--fill-param", action="store_true")
     a = ap.parse_args()
     run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness, denoise=a.denoise,
-        texel_prior=a.texel_prior, mask_unreached=a.mask_unreached, save_lighting=a.save_lighting)
+        texel_prior=a.texel_prior, mask_unreached=a.mask_unreached, save_lighting=a.save_lighting, fill_unreached=a.fill_unreached,
+        fill_param=a.fill_param)

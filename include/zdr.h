@@ -406,6 +406,50 @@ size_t zdr_texel_lighting_workspace_bytes(int32_t tex_h, int32_t tex_w);   /* 0 
 int zdr_scene_texel_lighting(zdr_scene *scene, const zdr_texel_lighting_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
                              float *out /* DEVICE tex_h x tex_w x 4 */, void *workspace, void *stream);
 
+/* Push-pull: fills the texels of a texture that a weight marks as unknown from the ones it marks as known, through a weighted pyramid — a
+ * baker's seam padding — and the adjoint of that map with respect to the texture.  No scene handle.  The known texels come out bit for
+ * bit as they went in; with the weights held fixed the map is linear in the texture, so y = K x is also a reparameterisation of a
+ * material whose holes are always the smooth continuation of their chart, and d_x = K^T g carries the gradient that lands on a hole back
+ * to the known texels that determine it.
+ *
+ * Inputs: a texture x (H, W, 4) and a weight w (H, W), such as the coverage of zdr_scene_texel_aovs.  The output y has the shape of x.
+ * Level sizes.  (H_0, W_0) = (H, W);  (H_{l+1}, W_{l+1}) = (ceil(H_l / 2), ceil(W_l / 2));  L is the first level of size 1 x 1, and
+ * min(that, levels) if levels > 0.
+ * Level 0.  a_0 = w clamped to [0, 1], NaN -> 0;  p_0 = a_0 x where a_0 > 0, else 0.  A texel of weight 0 is never read into the result,
+ * whatever it holds, NaN and infinity included.
+ * Push, l = 0 .. L - 1.  The children of (i, j) are (2i + {0, 1}, 2j + {0, 1}); children outside the level count as 0.
+ *   S = (a_00 + a_01) + (a_10 + a_11),  P = (p_00 + p_01) + (p_10 + p_11),
+ *   a_{l+1} = min(S, 1),  r_{l+1} = a_{l+1} / S where S > 0, else 0,  p_{l+1} = P r_{l+1}.
+ * Top.  y_L = p_L / a_L where a_L > 0, else 0.
+ * Pull, l = L - 1 .. 0.  y_l = p_l + (1 - a_l) U(y_{l+1});  at level 0, y = x (the same bits, by selection) where a_0 = 1.
+ * Upsampling.  U is bilinear from the coarser level, applied separably: for fine index i of an axis, c = i >> 1 and nb = c + 1 if i is
+ * odd, else c - 1, clamped to the coarser level; the value is 0.75 v[c] + 0.25 v[nb].  Along the row (x) first, then across rows.
+ * It follows that every output texel is a convex combination of the inputs whose weight is positive, that a texture which is constant
+ * where w > 0 comes out constant everywhere, that w = 1 everywhere gives y = x bit for bit and w = 0 everywhere gives y = 0.  Holes that
+ * a pyramid cut short by `levels` cannot reach are 0.
+ * Adjoint, d_x = K^T g for the same w:  G_0 = g;  G_{l+1} = U^T((1 - a_l) G_l);  q_L = G_L / a_L where a_L > 0, else 0;
+ * q_l = G_l + r_{l+1}[parent] q_{l+1}[parent];  d_x = a_0 q_0 (0 where a_0 = 0).  U^T is a gather: a coarse index c collects from the fine
+ * indices 2c - 1 .. 2c + 2 of each axis, the taps a clamped border folds onto it included; no atomic is needed.  The adjoint rebuilds
+ * a_l and r_l from w itself: it needs nothing that a forward call left behind.  The WEIGHTS receive NO gradient: they are held fixed.
+ * The kernels are compiled without contraction, so the result is defined by the operation order above.
+ *
+ * All pointers are DEVICE pointers, 16-byte aligned; weight is H x W, x / out / d_out / d_x are H x W x 4.  The caller provides
+ * `workspace`, at least zdr_push_pull_workspace_bytes(params) bytes (0 = invalid params; never 0 otherwise): the levels >= 1.  Both
+ * calls only enqueue on `stream`: they never allocate and never synchronise, so they can be captured in a HIP graph without a call
+ * before.  No float atomic: the same bits from run to run, whatever the workspace held; one workspace may serve both calls, one call in
+ * flight at a time.  out and d_x are overwritten and must not overlap an input or the workspace.
+ * ZDR_E_INVALID: struct_size other than sizeof(zdr_push_pull_params), a width or height <= 0, levels < 0, a null or misaligned pointer,
+ * an output that overlaps an input or the workspace, a workspace that overlaps an input (byte ranges as the parameters size them).
+ * ZDR_E_UNSUPPORTED: more than 2^26 texels, the cap of zdr_scene_texel_aovs; a library linked without these kernels. */
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_push_pull_params) */
+    int32_t width, height, levels;     /* levels: 0 = down to 1 x 1 */
+} zdr_push_pull_params;
+size_t zdr_push_pull_workspace_bytes(const zdr_push_pull_params *params);   /* 0 = invalid */
+int zdr_push_pull(const zdr_push_pull_params *params, const float *weight, const float *x, float *out, void *workspace, void *stream);
+int zdr_push_pull_backward(const zdr_push_pull_params *params, const float *weight, const float *d_out, float *d_x, void *workspace,
+                           void *stream);
+
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,
  * shadow rays (one per shaded vertex, prb.py:59), shaded vertices, emitter hits via BSDF sampling, NaN-dropped samples,

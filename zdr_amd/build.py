@@ -20,6 +20,8 @@ LIB = os.path.join(CSRC, "libzdr_hip.so")
 TEXEL_LIB = os.path.join(CSRC, "libzdr_texel.so")
 # The texture-space light baker (zdr_bake.hip) likewise: a third library, so that libzdr_texel.so keeps exactly its three kernels too.
 BAKE_LIB = os.path.join(CSRC, "libzdr_bake.so")
+# Push-pull hole filling (zdr_pushpull.hip): a fourth library, for the same reason.
+PUSHPULL_LIB = os.path.join(CSRC, "libzdr_pushpull.so")
 ARCH = "gfx950"
 
 
@@ -49,7 +51,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not os.path.exists(LIB) or not os.path.exists(TEXEL_LIB) or not os.path.exists(BAKE_LIB):
+    if not os.path.exists(LIB) or not os.path.exists(TEXEL_LIB) or not os.path.exists(BAKE_LIB) or not os.path.exists(PUSHPULL_LIB):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -82,6 +84,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # the texture-space light baker, linked into libzdr_bake.so: the path kernels' device code (sample_light, the any-hit walks)
         # under the path kernels' flags, without the atomics option (it has no float atomic)
         ("zdr_bake.hip", ["-O3", "-fno-slp-vectorize"]),
+        # push-pull hole filling, linked into libzdr_pushpull.so; no contraction: the result is defined by the operation order of
+        # include/zdr.h (zdr_push_pull), and a level computes the same bits in the fused tail as in a launch of its own
+        ("zdr_pushpull.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -95,11 +100,13 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    bake_obj = objs.pop()                                   # (zdr_bake.o: the last job)
-    texel_obj = objs.pop()                                  # (zdr_texel.o: the one before)
+    pushpull_obj = objs.pop()                               # (zdr_pushpull.o: the last job)
+    bake_obj = objs.pop()                                   # (zdr_bake.o: the one before)
+    texel_obj = objs.pop()                                  # (zdr_texel.o: the one before that)
     links = [[hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", TEXEL_LIB, texel_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BAKE_LIB, bake_obj],
-             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake",
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PUSHPULL_LIB, pushpull_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake", "-lzdr_pushpull",
               "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)

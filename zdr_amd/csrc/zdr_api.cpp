@@ -19,6 +19,8 @@
 #include "texel.h"
 #define ZDR_BAKE_LAUNCHER_REF __attribute__((weak))      // (csrc/bake.h)
 #include "bake.h"
+#define ZDR_PUSHPULL_LAUNCHER_REF __attribute__((weak))  // (csrc/pushpull.h)
+#include "pushpull.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1649,6 +1651,54 @@ extern "C" int zdr_scene_texel_lighting(zdr_scene *s, const zdr_texel_lighting_p
     B.inv_spp = 1.0f / (float)p->spp; B.spp_f = (float)p->spp; B.max_distance = p->max_distance;
     if (zdr_launch_texel_lighting(S, s->accel_is_bvh, C, B, (hipStream_t)stream)) return fail(ZDR_E_HIP, "texel lighting launch failed");
     return ZDR_OK;
+}
+
+// ------------------------------------------------------------------------------- push-pull
+// zdr_push_pull / zdr_push_pull_backward (include/zdr.h): no scene handle, no allocation, no synchronisation — argument checks, then the
+// launches of zdr_pushpull.hip on the caller's stream.  The workspace holds the pyramid's levels >= 1 (csrc/pushpull.h); neither call
+// reads what another left in it.
+static int push_pull_check(const zdr_push_pull_params *p) {
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (p->struct_size != sizeof(zdr_push_pull_params))
+        return fail(ZDR_E_INVALID, "zdr_push_pull_params.struct_size is " + std::to_string(p->struct_size) + ", this library expects " +
+                                   std::to_string(sizeof(zdr_push_pull_params)) + ": caller and library were built from different include/zdr.h");
+    if (p->width <= 0 || p->height <= 0) return fail(ZDR_E_INVALID, "zdr_push_pull_params: width and height must be positive");
+    if (p->levels < 0) return fail(ZDR_E_INVALID, "zdr_push_pull_params.levels is " + std::to_string(p->levels) + ": 0 (down to 1 x 1) or a positive count");
+    if ((uint64_t)p->width * (uint64_t)p->height > ZDR_PUSHPULL_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, "zdr_push_pull: more than 2^26 texels");
+    return ZDR_OK;
+}
+
+extern "C" size_t zdr_push_pull_workspace_bytes(const zdr_push_pull_params *p) {
+    if (push_pull_check(p)) return 0;
+    return zdr_push_pull_plan(p->width, p->height, p->levels).bytes;
+}
+
+static int push_pull_call(const char *name, const zdr_push_pull_params *p, const float *weight, const float *in, float *out, void *workspace, void *stream, int backward) {
+    if (int rc = push_pull_check(p)) return rc;
+    for (const void *q : {(const void *)weight, (const void *)in, (const void *)out, (const void *)workspace}) {
+        if (!q) return fail(ZDR_E_INVALID, "null argument");
+        if ((uintptr_t)q % 16) return fail(ZDR_E_INVALID, std::string(name) + ": every pointer must be 16-byte aligned");
+    }
+    const size_t n = (size_t)p->width * (size_t)p->height, wbytes = zdr_push_pull_plan(p->width, p->height, p->levels).bytes;
+    if (denoise_overlap(out, 16 * n, {{in, 16 * n}, {weight, 4 * n}, {workspace, wbytes}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": the output must not alias or overlap an input or the workspace");
+    if (denoise_overlap(workspace, wbytes, {{in, 16 * n}, {weight, 4 * n}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": the workspace must not overlap an input");
+    if (!zdr_launch_push_pull)                                       // (weak: csrc/pushpull.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the push-pull kernels (zdr_pushpull.hip)");
+    PushPullArgs A;
+    A.width = p->width; A.height = p->height; A.levels = p->levels;
+    A.weight = weight; A.in = (const float4 *)in; A.out = (float4 *)out; A.workspace = workspace;
+    if (zdr_launch_push_pull(A, backward, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": a launch failed");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_push_pull(const zdr_push_pull_params *p, const float *weight, const float *x, float *out, void *workspace, void *stream) {
+    return push_pull_call("zdr_push_pull", p, weight, x, out, workspace, stream, 0);
+}
+
+extern "C" int zdr_push_pull_backward(const zdr_push_pull_params *p, const float *weight, const float *d_out, float *d_x, void *workspace, void *stream) {
+    return push_pull_call("zdr_push_pull_backward", p, weight, d_out, d_x, workspace, stream, 1);
 }
 
 extern "C" int zdr_render_stats(zdr_scene *s, const zdr_render_params *p, const float *material, uint64_t counters[8], void *stream) {

@@ -150,6 +150,14 @@ class TexelAovs(_ChannelViews):
             g[..., 11] = self.data[..., 12]
         return g
 
+    def fill(self, x, by="coverage"):
+        """``push_pull(x, self.coverage)``, or with ``by="reach"`` ``push_pull(x, self.reach)``: the (H, W, 4) texture ``x`` with every
+        texel outside that mask filled from the ones inside it (zdr_amd/pushpull.py), differentiable in ``x``."""
+        if by not in ("coverage", "reach"):
+            raise ValueError(f'by must be "coverage" or "reach", not {by!r}')
+        from .pushpull import push_pull
+        return push_pull(x, getattr(self, by))
+
 
 class TexelLighting:
     """Texture-space lighting of ``Scene.texel_lighting`` (include/zdr.h, zdr_scene_texel_lighting): ``data`` is the (H, W, 4) tensor of
