@@ -542,6 +542,35 @@ int zdr_trace_fused(zdr_scene *scene, const float *shadow_rays, const float *nex
 enum { ZDR_SHADING_EVAL = 0, ZDR_SHADING_SAMPLE = 1, ZDR_SHADING_FRAME = 2 };
 int zdr_shading_dump(zdr_scene *scene, int32_t mode, const float *in, uint32_t n, float *out, void *stream);
 
+/* The light side of a path vertex point by point (test hook): row i (lane i of a kernel of its own, k_light_dump) calls the device
+ * functions the kernels sample and weigh lights with — csrc/scene.h: sample_light (sample_uniform_triangle, light_pdf, sample_alias_table
+ * behind it), sample_light_pdf, env_sampled_light_pdf, env_lookup, uv_to_direction, direction_to_uv, env_pdf_scale, balanced_heuristic,
+ * offset_ray_origin, surface_interact; csrc/integrators.h: tent_warp1 — on inputs the caller chooses, with the scene's own light table,
+ * environment map and acceleration structure.  in / out: DEVICE float32, n rows of 16 floats each; floats not listed are ignored (in)
+ * or written as 0 (out); rows n and beyond are not touched.  Nothing is normalised on the way in.
+ *   ZDR_LIGHT_SAMPLE    in  {origin[3], u_pick, u_prim, u_pt[2]}
+ *                       out {wi[3], dist, pdf, eval[3], env_uv[2] (the map coordinates of an environment sample; -1, -1 when the mesh
+ *                            branch or the no-light branch ran), bits(mesh_light) (list index of a mesh light sampled from its front, else -1)}
+ *                       sample_light<ENV, true> with the row's numbers as its draws; ENV = the scene has a map.  A scene without any
+ *                       light takes the n <= 0 branch.
+ *   ZDR_LIGHT_PDF       in  {origin[3], p[3], bits(inst), bits(tri)}   tri: index of the triangle in the scene's input order
+ *                       out {sample_light_pdf<ENV, true>, sample_light_pdf<ENV, false>, bits(slot)} at the slot the scene keeps the
+ *                            triangle in; {NaN, NaN, -1} and nothing read when inst or tri names nothing of the scene
+ *   ZDR_LIGHT_ENV       in  {d[3], u, v}   (scenes with a map only)
+ *                       out {direction_to_uv(d)[2], env_sampled_light_pdf(d), env_lookup(direction_to_uv(d))[3], uv_to_direction(u, v)[3],
+ *                            direction_to_uv(uv_to_direction(u, v))[2], env_pdf_scale(v, number of lights)}
+ *   ZDR_LIGHT_MISC      in  {a, b, p[3], n[3], u[2], t}
+ *                       out {balanced_heuristic(a, b), offset_ray_origin(p, n)[3], sample_uniform_triangle(u)[3], tent_warp1(t)}
+ *   ZDR_LIGHT_INTERACT  in  {o[3], d[3], tmin, tmax}
+ *                       out {bits(inst), bits(prim), u, v, t, p[3], uv[2], ns[3], ng[3]}: the closest hit of the scene's acceleration
+ *                            structure, reported as zdr_trace_closest reports it (-1, -1, 0, 0, tmax and zeros on a miss), and
+ *                            surface_interact<true> at it.  ZDR_LIGHT_INTERACT_WIDE: the same with surface_interact<false>.
+ * The call only enqueues on `stream`.  ZDR_E_INVALID for a null scene, an unknown mode, ZDR_LIGHT_ENV on a scene without a map, or null
+ * in / out with n > 0; n = 0 does nothing.  It checks the functions as compiled into this kernel, not the instances inlined into the
+ * render kernels (the path-by-path and image parity tests run those). */
+enum { ZDR_LIGHT_SAMPLE = 0, ZDR_LIGHT_PDF = 1, ZDR_LIGHT_ENV = 2, ZDR_LIGHT_MISC = 3, ZDR_LIGHT_INTERACT = 4, ZDR_LIGHT_INTERACT_WIDE = 5 };
+int zdr_light_dump(zdr_scene *scene, int32_t mode, const float *in, uint32_t n, float *out, void *stream);
+
 /* The bilinear texture lookup row by row (test hook): row i (lane i of a kernel of its own) calls the device functions the kernels shade
  * with — read_bsdf and read_bsdf_in, each with 32-bit byte offsets ("narrow") and with 64-bit addresses ("wide"), and env_lookup of the
  * scene's environment map — at a uv the caller chooses, outside [0, 1] included.  materials / dims / nmat: as zdr_render_*_materials takes

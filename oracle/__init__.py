@@ -88,6 +88,9 @@ def lib(variant: str = "ieee"):
         L.zdro_offset_ray_origin.argtypes = [fp, fp, fp]
         L.zdro_read_bsdf.argtypes = [fp, C.c_int, C.c_int, C.c_float, C.c_float, fp]
         L.zdro_write_bsdf_grad.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int, fp, C.c_int]
+        for name in ("zdro_sample_light", "zdro_sample_light_pdf", "zdro_env_dir_uv", "zdro_surface_interact"):
+            getattr(L, name).argtypes = [C.c_void_p, fp, C.c_int, fp]
+        L.zdro_light_misc.argtypes = [fp, C.c_int, fp]
         L.zdro_debug_force_brute.argtypes = [C.c_int]
         L.zdro_set_pmj02bn_tables.argtypes = [C.POINTER(C.c_uint32), C.c_int, C.c_int, C.POINTER(C.c_uint16), C.c_int, C.c_int]
         _LIBS[variant] = L
@@ -239,6 +242,20 @@ class OracleScene:
         bt = np.zeros((n, 3), np.float32)
         self._L.zdro_trace_closest(self.h, _f(rays), n, _i(ip), _f(bt))
         return ip, bt
+
+    LIGHT_ROWS = {"sample": "zdro_sample_light", "pdf": "zdro_sample_light_pdf", "env": "zdro_env_dir_uv", "interact": "zdro_surface_interact"}
+
+    def light_rows(self, what: str, rows: np.ndarray) -> np.ndarray:
+        """The oracle's copies of the light-side functions row by row (zdr_oracle.c, zdro_sample_light ...): (n, 16) float32 in the
+        layout of the kernels' zdr_light_dump -> (n, 16) float32; "misc" needs no scene; "interact" takes {bits(inst), bits(prim), u, v}
+        and returns {p[3], uv[2], ns[3], ng[3]}."""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 16)
+        out = np.zeros_like(rows)
+        if what == "misc":
+            self._L.zdro_light_misc(_f(rows), rows.shape[0], _f(out))
+        else:
+            getattr(self._L, self.LIGHT_ROWS[what])(self.h, _f(rows), rows.shape[0], _f(out))
+        return out
 
     def trace_any(self, rays: np.ndarray):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)

@@ -848,7 +848,10 @@ static v3 uv_to_direction(v2 uv) { /* envmap.py:206-214 */
     return vnormalize(V3(sinf(phi) * st, y, cosf(phi) * st));
 }
 static v2 direction_to_uv(v3 d) { /* envmap.py:216-220 */
-    v2 uv; uv.x = 1.0f - atan2f(d.x, d.z) / (2.0f * PI_F); uv.y = acosf(d.y) / PI_F;
+    /* The reference returns 1 - a, which lies in [0.5, 1.5): for d.x < 0 it is 1 + the u that uv_to_direction started from, and every
+     * clamped lookup then reads the last column.  Here u is wrapped into [0, 1): unchanged for a > 0, -a (exact) otherwise. */
+    float a = atan2f(d.x, d.z) / (2.0f * PI_F);
+    v2 uv; uv.x = a > 0.0f ? 1.0f - a : -a; uv.y = acosf(d.y) / PI_F;
     return uv;
 }
 static void sample_alias_table(const zdro_scene *s, int n, float u_in, int offset, int *index, float *uu) { /* envmap.py:85-106 */
@@ -905,6 +908,25 @@ static float light_pdf_core(const zdro_scene *s, int n, int inst, int prim, v3 o
     return sqr_dist / ((float)(n * trig_count) * area * cos_light);
 }
 
+/* light.py:33-81: mesh light `idx` of the light list, chosen among n lights; *front (may be NULL) receives whether the sample sees its front */
+static light_sample_t sample_mesh_light(const zdro_scene *s, v3 origin, int idx, int n, float u_prim, v2 u_pt, int *front) {
+    light_sample_t L;
+    int inst = s->light_insts[idx];
+    int trig_count = s->tri_begin[inst + 1] - s->tri_begin[inst];
+    int prim = clampi((int)(u_prim * (float)trig_count), 0, trig_count - 1);
+    int t = s->tri_begin[inst] + prim;
+    v3 p0 = s->wp[3 * (size_t)t], p1 = s->wp[3 * (size_t)t + 1], p2 = s->wp[3 * (size_t)t + 2];
+    v3 abc = sample_uniform_triangle(u_pt);
+    v3 p = vadd(vadd(vscale(p0, abc.x), vscale(p1, abc.y)), vscale(p2, abc.z));
+    float cos_light, sqr_dist; v3 wi;
+    float pdf = light_pdf_core(s, n, inst, prim, origin, p, &cos_light, &wi, &sqr_dist);
+    const float *e = s->emission + 3 * inst;
+    L.wi = wi; L.dist = 0.9999f * sqrtf(sqr_dist); L.pdf = pdf;
+    L.eval = cos_light > 1e-4f ? V3(e[0], e[1], e[2]) : V3(0, 0, 0);
+    if (front) *front = cos_light > 1e-4f;
+    return L;
+}
+
 static light_sample_t sample_light(const zdro_scene *s, v3 origin, sampler_t *smp) { /* light.py:23-81, mesh lights only */
     light_sample_t L; memset(&L, 0, sizeof L);
     float u = sampler_next(smp);
@@ -916,20 +938,8 @@ static light_sample_t sample_light(const zdro_scene *s, v3 origin, sampler_t *sm
     }
     int idx = clampi((int)(u * (float)n), 0, n - 1);
     if (idx < s->env_count) return sample_envmap(s, sampler_next2(smp), n); /* light.py:29-31: only next2f() is drawn */
-    idx -= s->env_count;
-    int inst = s->light_insts[idx];
-    int trig_count = s->tri_begin[inst + 1] - s->tri_begin[inst];
-    int prim = clampi((int)(sampler_next(smp) * (float)trig_count), 0, trig_count - 1);
-    int t = s->tri_begin[inst] + prim;
-    v3 p0 = s->wp[3 * (size_t)t], p1 = s->wp[3 * (size_t)t + 1], p2 = s->wp[3 * (size_t)t + 2];
-    v3 abc = sample_uniform_triangle(sampler_next2(smp));
-    v3 p = vadd(vadd(vscale(p0, abc.x), vscale(p1, abc.y)), vscale(p2, abc.z));
-    float cos_light, sqr_dist; v3 wi;
-    float pdf = light_pdf_core(s, n, inst, prim, origin, p, &cos_light, &wi, &sqr_dist);
-    const float *e = s->emission + 3 * inst;
-    L.wi = wi; L.dist = 0.9999f * sqrtf(sqr_dist); L.pdf = pdf;
-    L.eval = cos_light > 1e-4f ? V3(e[0], e[1], e[2]) : V3(0, 0, 0);
-    return L;
+    float u_prim = sampler_next(smp);
+    return sample_mesh_light(s, origin, idx - s->env_count, n, u_prim, sampler_next2(smp), 0);
 }
 
 static float sample_light_pdf(const zdro_scene *s, v3 origin, int inst, int prim, v3 p) { /* light.py:84-111 */
@@ -937,6 +947,83 @@ static float sample_light_pdf(const zdro_scene *s, v3 origin, int inst, int prim
 }
 
 static float balanced_heuristic(float a, float b) { return a / fmaxf(a + b, 1e-4f); } /* prb.py:12-13 */
+
+/* The light side row by row, for tests/light_cases.py: rows of 16 floats in and out, laid out as the kernels' zdr_light_dump takes and
+ * returns them (include/zdr.h), so that a test's float64 restatement can be pinned against these copies before it judges the kernels. */
+static void put3(float *o, v3 a) { o[0] = a.x; o[1] = a.y; o[2] = a.z; }
+static int32_t bits_i(float f) { int32_t i; memcpy(&i, &f, 4); return i; }
+static float bits_f(int32_t i) { float f; memcpy(&f, &i, 4); return f; }
+void zdro_sample_light(const zdro_scene *s, const float *in, int nrows, float *out) {
+    for (int r = 0; r < nrows; r++) {
+        const float *a = in + 16 * (size_t)r; float *o = out + 16 * (size_t)r;
+        memset(o, 0, 16 * sizeof(float));
+        v3 origin = V3(a[0], a[1], a[2]); v2 u_pt = {a[5], a[6]};
+        int n = s->env_count + s->light_count, mesh_light = -1;
+        light_sample_t L; o[8] = o[9] = -1.0f;
+        if (n <= 0) { L.wi = V3(0, 0, 1); L.dist = 0; L.pdf = 1.0f; L.eval = V3(0, 0, 0); }
+        else {
+            int idx = clampi((int)(a[3] * (float)n), 0, n - 1);
+            if (idx < s->env_count) {
+                L = sample_envmap(s, u_pt, n);
+                int iy, ix; float uy, ux;       /* the map coordinates sample_envmap drew, once more */
+                sample_alias_table(s, s->map_h, u_pt.y, 0, &iy, &uy);
+                sample_alias_table(s, s->map_w, u_pt.x, s->map_h + iy * s->map_w, &ix, &ux);
+                o[8] = ((float)ix + ux) / (float)s->map_w; o[9] = ((float)iy + uy) / (float)s->map_h;
+            } else {
+                int front = 0;
+                L = sample_mesh_light(s, origin, idx - s->env_count, n, a[4], u_pt, &front);
+                if (front) mesh_light = idx - s->env_count;
+            }
+        }
+        put3(o, L.wi); o[3] = L.dist; o[4] = L.pdf; put3(o + 5, L.eval); o[10] = bits_f(mesh_light);
+    }
+}
+/* in {origin[3], p[3], bits(inst), bits(tri)}: tri in the scene's input order -> out {pdf, pdf, bits(tri)} */
+void zdro_sample_light_pdf(const zdro_scene *s, const float *in, int nrows, float *out) {
+    for (int r = 0; r < nrows; r++) {
+        const float *a = in + 16 * (size_t)r; float *o = out + 16 * (size_t)r;
+        memset(o, 0, 16 * sizeof(float));
+        int inst = bits_i(a[6]), tri = bits_i(a[7]);
+        o[0] = o[1] = sample_light_pdf(s, V3(a[0], a[1], a[2]), inst, tri - s->tri_begin[inst], V3(a[3], a[4], a[5]));
+        o[2] = a[7];
+    }
+}
+void zdro_env_dir_uv(const zdro_scene *s, const float *in, int nrows, float *out) {
+    for (int r = 0; r < nrows; r++) {
+        const float *a = in + 16 * (size_t)r; float *o = out + 16 * (size_t)r;
+        memset(o, 0, 16 * sizeof(float));
+        v3 d = V3(a[0], a[1], a[2]); v2 uv = {a[3], a[4]};
+        int n = s->env_count + s->light_count;
+        v2 duv = direction_to_uv(d);
+        v3 w = uv_to_direction(uv);
+        v2 back = direction_to_uv(w);
+        o[0] = duv.x; o[1] = duv.y; o[2] = env_sampled_light_pdf(s, d, n); put3(o + 3, env_lookup(s, duv));
+        put3(o + 6, w); o[9] = back.x; o[10] = back.y;
+        float sn = sinf(PI_F * uv.y), inv_s = sn > 0 ? 1.0f / sn : 0.0f;
+        o[11] = inv_s / (2.0f * PI_F * PI_F) / (float)n;
+    }
+}
+void zdro_light_misc(const float *in, int nrows, float *out) {
+    for (int r = 0; r < nrows; r++) {
+        const float *a = in + 16 * (size_t)r; float *o = out + 16 * (size_t)r;
+        memset(o, 0, 16 * sizeof(float));
+        v2 u = {a[8], a[9]};
+        o[0] = balanced_heuristic(a[0], a[1]);
+        put3(o + 1, offset_ray_origin(V3(a[2], a[3], a[4]), V3(a[5], a[6], a[7])));
+        put3(o + 4, sample_uniform_triangle(u));
+        o[7] = tent_warp1(a[10], 1.0f);
+    }
+}
+/* in {bits(inst), bits(prim), u, v}: a hit as zdro_trace_closest reports it -> out {p[3], uv[2], ns[3], ng[3]} */
+void zdro_surface_interact(const zdro_scene *s, const float *in, int nrows, float *out) {
+    for (int r = 0; r < nrows; r++) {
+        const float *a = in + 16 * (size_t)r; float *o = out + 16 * (size_t)r;
+        memset(o, 0, 16 * sizeof(float));
+        hit_t h; memset(&h, 0, sizeof h); h.inst = bits_i(a[0]); h.prim = bits_i(a[1]); h.u = a[2]; h.v = a[3];
+        interaction_t it = surface_interact(s, &h);
+        put3(o, it.p); o[3] = it.uv.x; o[4] = it.uv.y; put3(o + 5, it.ns); put3(o + 8, it.ng);
+    }
+}
 
 /* ---------------------------------------------------------------- counters */
 typedef struct { uint64_t c[8]; } counters_t;

@@ -10,11 +10,14 @@ from test_oracle_render import quad_scene
 from zdr_amd import envmap, geometry
 
 
-def sun_sky(seed=0):
+def sun_sky(seed=0, column=40):
     rng = np.random.default_rng(seed)
     img = rng.uniform(0.05, 0.6, (32, 64, 3)).astype(np.float32)
-    img[5:8, 40:44] = (300.0, 260.0, 200.0)
+    img[5:8, column:column + 4] = (300.0, 260.0, 200.0)
     return img
+
+
+SUN_COLUMNS = (10, 20, 40)      # u = 0.17, 0.33 (d.x < 0: the half of the map direction_to_uv used to send past u = 1) and 0.65
 
 
 @pytest.fixture(scope="module")
@@ -69,12 +72,23 @@ def test_constant_environment_gives_the_hemispherical_albedo():
 
 
 def test_light_sampling_and_bsdf_sampling_agree_under_a_sun(sky_tables):
+    suns_agree(*sky_tables)
+
+
+@pytest.mark.parametrize("column", SUN_COLUMNS)
+def test_light_sampling_and_bsdf_sampling_agree_wherever_the_sun_stands(column):
+    """the same with the sun in either half of the map: with u left in [0.5, 1.5) a miss ray or BSDF sample towards column 10 or 20 read
+    the map's last column and its pdf while the light sample read the true texel, and the two estimators differed by 0.648"""
+    I = envmap.prepare_image(sun_sky(column=column))
+    suns_agree(I, *envmap.build_tables(I))
+
+
+def suns_agree(I, prob, alias, pdf):
     # MIS combines both; an estimator that only ever finds the sun through BSDF sampling (no envmap importance
     # sampling: a uniform 'sampling map') must converge to the same value, with far more noise
     S = oracle.OracleScene.from_arrays(quad_scene())
     cam = (0.5, (0.0, 2.0, 0.001), (0.0, 0.0, 0.0), (0.0, 0.0, -1.0))
     mat = np.zeros((4, 4, 4), np.float32); mat[..., :3] = 0.6; mat[..., 3] = 0.8
-    I, prob, alias, pdf = sky_tables
     W = 6
     S.set_envmap(I, prob, alias, pdf)
     good = np.mean([S.render_forward(oracle.make_params("path", W, W, 1024, s, cam, (4, 4), max_depth=2), mat)[..., :3].mean() for s in range(4)])
@@ -82,6 +96,7 @@ def test_light_sampling_and_bsdf_sampling_agree_under_a_sun(sky_tables):
     uprob = np.ones(Hm + Hm * Wm, np.float32); ualias = np.concatenate([np.arange(Hm), np.tile(np.arange(Wm), Hm)]).astype(np.int32)
     S.set_envmap(I, uprob, ualias, np.ones(Hm * Wm, np.float32))
     flat = np.mean([S.render_forward(oracle.make_params("path", W, W, 16384, s, cam, (4, 4), max_depth=2), mat)[..., :3].mean() for s in range(4)])
+    print(f"[envmap] tabled estimator {good:.5f}, uniform-table estimator {flat:.5f}, relative difference {abs(good - flat) / good:.5f}")
     assert abs(good - flat) / good < 0.03, (good, flat)
 
 
@@ -111,6 +126,33 @@ def test_hip_environment_lighting_matches_oracle(integrator, accel, cbox_arrays,
     scene.add_envmap(None)
     plain = make_scene(integrator, accel=accel).render(m.detach(), res=(32, 32), spp=4)
     assert torch.equal(scene.render(m.detach(), res=(32, 32), spp=4), plain)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("column", SUN_COLUMNS)
+def test_hip_environment_lighting_matches_oracle_wherever_the_sun_stands(column, cbox_arrays):
+    """test_hip_environment_lighting_matches_oracle (path, BVH) at its size, the sun in either half of the map"""
+    import torch
+    from gpu_util import assert_grad_parity, assert_image_parity, make_scene, oracle_params
+    sky = sun_sky(column=column)
+    I = envmap.prepare_image(sky)
+    prob, alias, pdf = envmap.build_tables(I)
+    scene = make_scene("path", accel="bvh")
+    scene.add_envmap(sky)
+    assert np.array_equal(scene._envmap[1], prob)
+    S = oracle.OracleScene.from_arrays(cbox_arrays); Sf = oracle.OracleScene.from_arrays(cbox_arrays, variant="fma")
+    S.set_envmap(I, prob, alias, pdf); Sf.set_envmap(I, prob, alias, pdf)
+    mat = fd_material_np(256, 0)
+    W, spp = 96, 16
+    m = torch.from_numpy(mat).cuda().requires_grad_()
+    img = scene.render(m, res=(W, W), spp=spp, seed=2)
+    p = oracle_params(scene, W, W, spp, 2, mat.shape[:2])
+    ref = S.render_forward(p, mat)
+    assert ref[..., :3].mean() > 0.05
+    assert_image_parity(img.detach().cpu().numpy()[..., :3], ref[..., :3], f"envmap sun at {column} forward", floor=Sf.render_forward(p, mat)[..., :3])
+    img.sum().backward()
+    pb = oracle_params(scene, W, W, spp, 3, mat.shape[:2]); ones = np.ones((W, W, 4), np.float32)
+    assert_grad_parity(m.grad.cpu().numpy(), S.render_backward(pb, ones, mat), f"envmap sun at {column} backward", floor=Sf.render_backward(pb, ones, mat))
 
 
 @pytest.mark.gpu

@@ -31,7 +31,7 @@ COUNTER_NAMES = ("samples", "closest_rays", "closest_hits", "shadow_rays", "shad
 # every symbol include/zdr.h declares
 EXPORTS = ("zdr_version", "zdr_abi_version", "zdr_last_error", "zdr_scene_create", "zdr_scene_destroy", "zdr_scene_info",
            "zdr_scene_set_emissions", "zdr_scene_set_envmap", "zdr_scene_set_pmj02bn_tables", "zdr_render_forward", "zdr_render_backward",
-           "zdr_render_stats", "zdr_scene_check", "zdr_trace_closest", "zdr_trace_any", "zdr_sampler_dump", "zdr_vertex_sampler_dump", "zdr_path_dump", "zdr_trace_fused", "zdr_shading_dump", "zdr_texture_lookup", "zdr_texture_scatter", "zdr_debug_build_accel", "zdr_debug_never_occluders",
+           "zdr_render_stats", "zdr_scene_check", "zdr_trace_closest", "zdr_trace_any", "zdr_sampler_dump", "zdr_vertex_sampler_dump", "zdr_path_dump", "zdr_trace_fused", "zdr_shading_dump", "zdr_light_dump", "zdr_texture_lookup", "zdr_texture_scatter", "zdr_debug_build_accel", "zdr_debug_never_occluders",
            "zdr_scene_set_material_slots", "zdr_render_forward_materials", "zdr_render_backward_materials",
            "zdr_scene_set_envmap_texture", "zdr_scene_update_envmap_sampling", "zdr_scene_get_envmap_sampling", "zdr_render_backward_env", "zdr_render_backward_materials_env",
            "zdr_scene_set_emission_values", "zdr_render_backward_emission", "zdr_render_backward_materials_emission",
@@ -144,6 +144,7 @@ def lib():
     L.zdr_path_dump.argtypes = [vp, C.POINTER(RenderParams), fp, fp, ip, C.c_uint32, C.c_int32, fp, vp]
     L.zdr_trace_fused.argtypes = [vp, fp, fp, ip, C.c_uint32, C.c_int32, ip, ip, fp, vp]
     L.zdr_shading_dump.argtypes = [vp, C.c_int32, fp, C.c_uint32, fp, vp]
+    L.zdr_light_dump.argtypes = [vp, C.c_int32, fp, C.c_uint32, fp, vp]
     L.zdr_texture_lookup.argtypes = [vp, fp, ip, C.c_uint32, fp, C.c_uint32, fp, vp]
     L.zdr_texture_scatter.argtypes = [vp, C.c_int32, ip, C.c_uint32, fp, C.c_uint32, C.c_uint32, fp, fp, ip, vp]
     L.zdr_debug_build_accel.argtypes = [fp, C.c_uint32, C.c_int, fp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), ip, fp]

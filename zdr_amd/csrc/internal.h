@@ -90,6 +90,7 @@ int zdr_launch_trace(const DScene &S, int accel_is_bvh, int any, const float *ra
 int zdr_launch_trace_fused(const DScene &S, const float *shadow, const float *next, const int32_t *need, uint32_t n, int backward_layout,
                            int32_t *occluded, int32_t *out_i, float *out_f, hipStream_t stream);   // BVH scenes only
 int zdr_launch_shading_dump(int mode, const float *in, uint32_t n, float *out, hipStream_t stream);   // rows of 16 floats, include/zdr.h
+int zdr_launch_light_dump(const DScene &S, int accel_is_bvh, int mode, const float *in, uint32_t n, float *out, hipStream_t stream);   // rows of 16 floats, include/zdr.h
 int zdr_launch_texture_lookup(const DScene &S, const float *materials, const MaterialTable &mt, const float *rows, uint32_t n, float *out, hipStream_t stream);   // include/zdr.h, zdr_texture_lookup
 // zdr_texture_scatter: the push kernel over `rows` (R and io laid out as for a backward call: cells zeroed, io.mt.nmat = 0 for the single
 // material; table: the material-table instance; d_env: the one with the map as entry ZDR_ENV_ENTRY), then the folds of a backward call

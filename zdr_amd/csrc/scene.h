@@ -442,8 +442,12 @@ ZD f3 uv_to_direction(f2 uv) {                                   // envmap.py:20
     float st = sinf(theta);
     return normalize(mk3(sinf(phi) * st, cosf(theta), cosf(phi) * st));
 }
-ZD f2 direction_to_uv(f3 d) {                                    // envmap.py:216-220
-    f2 uv; uv.x = 1.0f - atan2f(d.x, d.z) * (1.0f / (2.0f * ZDR_PI)); uv.y = acosf(d.y) * ZDR_INV_PI;
+// envmap.py:216-220 returns u = 1 - a, which lies in [0.5, 1.5): for d.x < 0 that is 1 + the u uv_to_direction started from, and the
+// clamped lookups (env_lookup, the pdf index, env_cell) all read the map's last column there.  u is wrapped into [0, 1) instead:
+// 1 - a for a > 0 (the reference's value, bit for bit), -a (exact) otherwise.  DESIGN.md, deviations from the literal reference.
+ZD f2 direction_to_uv(f3 d) {
+    const float a = atan2f(d.x, d.z) * (1.0f / (2.0f * ZDR_PI));
+    f2 uv; uv.x = (a > 0.0f) ? 1.0f - a : -a; uv.y = acosf(d.y) * ZDR_INV_PI;
     return uv;
 }
 ZD void sample_alias_table(const DScene &S, int n, float u_in, int offset, int &index, float &uu) {   // envmap.py:85-106

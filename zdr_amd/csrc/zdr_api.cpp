@@ -1769,6 +1769,17 @@ extern "C" int zdr_shading_dump(zdr_scene *s, int32_t mode, const float *in, uin
     return ZDR_OK;
 }
 
+extern "C" int zdr_light_dump(zdr_scene *s, int32_t mode, const float *in, uint32_t n, float *out, void *stream) {
+    if (!s) return fail(ZDR_E_INVALID, "null argument");
+    if (mode < ZDR_LIGHT_SAMPLE || mode > ZDR_LIGHT_INTERACT_WIDE) return fail(ZDR_E_INVALID, "unknown light dump mode");
+    if (mode == ZDR_LIGHT_ENV && s->ds.env_count == 0) return fail(ZDR_E_INVALID, "the environment mode was asked for, but the scene has no environment map");
+    if (n == 0) return ZDR_OK;
+    if (!in || !out) return fail(ZDR_E_INVALID, "null argument");
+    HIPCHK(hipSetDevice(s->device));
+    if (zdr_launch_light_dump(s->ds, s->accel_is_bvh, mode, in, n, out, (hipStream_t)stream)) return fail(ZDR_E_HIP, "light dump launch failed");
+    return ZDR_OK;
+}
+
 // The rows of a texture hook, read back and checked on the host before anything is launched: every material index names a material
 // of the table (or, env_entry, the map's entry; negative = an inactive row, where the hook has such rows).  stride: floats per row.
 static int check_texture_rows(const float *rows, uint32_t n, int stride, int mat_at, uint32_t nmat, bool inactive_ok, bool env_entry, hipStream_t st) {

@@ -1429,6 +1429,88 @@ int zdr_launch_shading_dump(int mode, const float *in, uint32_t n, float *out, h
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ------------------------------------------------------------------------------ light dump
+// Test hook (zdr_light_dump, include/zdr.h): lane i is row i and calls the light-side device functions of scene.h — sample_light with
+// sample_uniform_triangle, light_pdf and sample_alias_table behind it, sample_light_pdf, env_sampled_light_pdf, env_lookup,
+// uv_to_direction, direction_to_uv, env_pdf_scale, balanced_heuristic, offset_ray_origin, surface_interact — and tent_warp1
+// (integrators.h), on the scene's own light table, environment map and acceleration structure.  Like k_shading_dump this is a kernel of
+// its own: it runs the functions as compiled here, not the instances inlined into the render kernels (the parity tests run those).
+// Every lane stays to the end (A::closest is called by the whole wave, as in k_trace); lanes beyond n work on row n - 1 and write nothing.
+template <class A, bool ENV>
+__global__ __launch_bounds__(WAVE) void k_light_dump(DScene S, int mode, const float *in, uint32_t n, float *out) {
+    extern __shared__ int lds[];        // BvhAccel: traversal stacks (sized at launch); unused otherwise
+    const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+    const bool valid = i < n;
+    const float *a = in + 16 * (size_t)(valid ? i : n - 1);
+    float r[16];
+    for (int k = 0; k < 16; k++) r[k] = 0.0f;
+    if (mode == ZDR_LIGHT_SAMPLE) {
+        const f3 origin = ld3(a);
+        const float u_pick = a[3], u_prim = a[4];
+        f2 u_pt; u_pt.x = a[5]; u_pt.y = a[6];
+        f2 env_uv; env_uv.x = -1.0f; env_uv.y = -1.0f;
+        int mesh_light = -1;
+        const LightSample L = sample_light<ENV, true>(S, origin, u_pick, [&]() { return u_prim; }, [&]() { return u_pt; }, &env_uv, &mesh_light);
+        r[0] = L.wi.x; r[1] = L.wi.y; r[2] = L.wi.z; r[3] = L.dist; r[4] = L.pdf; r[5] = L.eval.x; r[6] = L.eval.y; r[7] = L.eval.z;
+        r[8] = env_uv.x; r[9] = env_uv.y; r[10] = __int_as_float(mesh_light);
+    } else if (mode == ZDR_LIGHT_PDF) {
+        const f3 origin = ld3(a), p = ld3(a + 3);
+        const int inst = __float_as_int(a[6]), tri = __float_as_int(a[7]);
+        r[0] = r[1] = __int_as_float(0x7fc00000); r[2] = __int_as_float(-1);      // a row that names no triangle of the scene reads nothing
+        if (inst >= 0 && inst < S.ninst && tri >= 0 && tri < S.ntris) {
+            const int slot = S.slot_of_tri[tri];
+            r[0] = sample_light_pdf<ENV, true>(S, origin, inst, slot, p);
+            r[1] = sample_light_pdf<ENV, false>(S, origin, inst, slot, p);
+            r[2] = __int_as_float(slot);
+        }
+    } else if (mode == ZDR_LIGHT_ENV) {
+        if constexpr (ENV) {
+            const f3 d = ld3(a);
+            f2 uv; uv.x = a[3]; uv.y = a[4];
+            const int nl = S.env_count + S.light_count;
+            const f2 duv = direction_to_uv(d);
+            const f3 e = env_lookup(S, duv), w = uv_to_direction(uv);
+            const f2 back = direction_to_uv(w);
+            r[0] = duv.x; r[1] = duv.y; r[2] = env_sampled_light_pdf(S, d, nl); r[3] = e.x; r[4] = e.y; r[5] = e.z;
+            r[6] = w.x; r[7] = w.y; r[8] = w.z; r[9] = back.x; r[10] = back.y; r[11] = env_pdf_scale(uv.y, nl);
+        }
+    } else if (mode == ZDR_LIGHT_MISC) {
+        const f3 p = ld3(a + 2), nrm = ld3(a + 5);
+        f2 u; u.x = a[8]; u.y = a[9];
+        const f3 o = offset_ray_origin(p, nrm), abc = sample_uniform_triangle(u);
+        r[0] = balanced_heuristic(a[0], a[1]); r[1] = o.x; r[2] = o.y; r[3] = o.z; r[4] = abc.x; r[5] = abc.y; r[6] = abc.z; r[7] = tent_warp1(a[10]);
+    } else {                                                   // ZDR_LIGHT_INTERACT, ZDR_LIGHT_INTERACT_WIDE
+        const Hit h = A::closest(S, lds, ld3(a), ld3(a + 3), a[6], a[7]);
+        r[0] = r[1] = __int_as_float(-1); r[4] = a[7];
+        if (h.slot >= 0) {
+            const Interaction it = (mode == ZDR_LIGHT_INTERACT) ? surface_interact<true>(S, h) : surface_interact<false>(S, h);
+            float hu = h.u, hv = h.v;                          // as k_trace reports a hit: prim from the record, the barycentrics of the INPUT corners 1 and 2
+            const int ro = __float_as_int(S.shade[8 * (size_t)h.slot + 7].z);
+            const float hw = 1.0f - h.u - h.v;
+            if (ro == 1) { hu = hw; hv = h.u; } else if (ro == 2) { hu = h.v; hv = hw; }
+            r[0] = __int_as_float(it.inst); r[1] = S.shade[8 * (size_t)h.slot + 7].y; r[2] = hu; r[3] = hv; r[4] = h.t;
+            r[5] = it.p.x; r[6] = it.p.y; r[7] = it.p.z; r[8] = it.uv.x; r[9] = it.uv.y;
+            r[10] = it.ns.x; r[11] = it.ns.y; r[12] = it.ns.z; r[13] = it.ng.x; r[14] = it.ng.y; r[15] = it.ng.z;
+        }
+    }
+    if (!valid) return;
+    float *o = out + 16 * (size_t)i;
+    for (int k = 0; k < 16; k++) o[k] = r[k];
+}
+
+int zdr_launch_light_dump(const DScene &S_in, int accel_is_bvh, int mode, const float *in, uint32_t n, float *out, hipStream_t st) {
+    DScene S = S_in;
+    if (n == 0) return 0;
+    const dim3 grid((n + WAVE - 1) / WAVE);
+    const size_t dyn = accel_is_bvh ? bvh_dyn_lds(S, false, false) : 0;
+    with_accel(accel_is_bvh, [&](auto acc) {
+        with_bool(S.env_count > 0, [&](auto env) {
+            hipLaunchKernelGGL((k_light_dump<typename decltype(acc)::type, decltype(env)::value>), grid, dim3(WAVE), dyn, st, S, mode, in, n, out);
+        });
+    });
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ------------------------------------------------------------------- texture lookup and scatter
 // Test hooks (zdr_texture_lookup, zdr_texture_scatter, include/zdr.h): the bilinear lookup and its adjoint on rows the caller chooses,
 // through the device functions of scene.h — read_bsdf, read_bsdf_in, env_lookup; scatter_queue_init[_cells], scatter_push,

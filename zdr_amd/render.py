@@ -875,6 +875,18 @@ class Scene:
         N.check(N.lib().zdr_shading_dump(self._handle, self.SHADING_MODES[mode], rows.data_ptr(), rows.shape[0], out.data_ptr(), self._stream()))
         return out
 
+    LIGHT_MODES = {"sample": 0, "pdf": 1, "env": 2, "misc": 3, "interact": 4, "interact_wide": 5}
+
+    def light_dump(self, mode, rows):
+        """The light side of a path vertex point by point (include/zdr.h, zdr_light_dump): ``mode`` "sample" | "pdf" | "env" | "misc" |
+        "interact" | "interact_wide", ``rows`` (n, 16) float32 laid out as the header says -> (n, 16) float32, computed with this
+        scene's light table, environment map and acceleration structure."""
+        rows = rows.to(device=self.device, dtype=torch.float32).contiguous()
+        assert rows.ndim == 2 and rows.shape[1] == 16, rows.shape
+        out = torch.empty_like(rows)
+        N.check(N.lib().zdr_light_dump(self._handle, self.LIGHT_MODES[mode], rows.data_ptr(), rows.shape[0], out.data_ptr(), self._stream()))
+        return out
+
     SCATTER_FORMS = {"single": 0, "table": 1, "table_env": 2}
 
     def _texture_table(self, sizes):
