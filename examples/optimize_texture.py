@@ -22,8 +22,14 @@ and the gradient that spills onto them is carried back to the covered texels (th
 --save-lighting writes irradiance.png and openness.png, the texture-space lighting of the material (scene.texel_lighting: direct
 irradiance and the open fraction of the hemisphere per texel), and prints the share of the reached texels that no light sample reached:
 a texel in shadow gets only noise for a gradient, whatever its reach.
+--init-from-target starts from the target photograph instead of from noise: the target is projected into texture space through the
+camera (scene.texel_project) and divided by the direct irradiance of scene.texel_lighting — albedo = pi * color / irradiance, a
+Lambertian guess that ignores indirect light — on the texels the camera sees and a light sample reached; every other texel is filled
+from those by push-pull.  Roughness starts as it would have.  Prints the share of the reached texels that the camera sees and the
+first iteration's loss.
 """
 import argparse
+import math
 import os
 import random
 import sys
@@ -67,7 +73,7 @@ def texel_prior_loss(material, f, guides):
 
 
 def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0, denoise=False,
-        texel_prior=0.0, mask_unreached=False, save_lighting=False, fill_unreached=False, fill_param=False):
+        texel_prior=0.0, mask_unreached=False, save_lighting=False, fill_unreached=False, fill_param=False, init_from_target=False):
     scene = Scene([(os.path.join(ASSETS, "cboxuv.obj"), None, float3(0.0)),
                    (os.path.join(ASSETS, "cbox-light.obj"), None, float3(17, 12, 4))], integrator=integrator)
     scene.camera = Camera(fov=50 / 180 * 3.1415926, origin=float3(-0.2, 2.6, 6.0), target=float3(-0.2, 2.6, -2.5), up=float3(0.0, 1.0, 0.0))
@@ -78,8 +84,20 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
     theta = torch.rand((tex, tex, 4), device="cuda", generator=g).requires_grad_()
     opt = torch.optim.Adam([theta], lr=0.02)
     losses = []
-    texels = scene.texel_aovs(theta.detach()) if (texel_prior > 0.0 or mask_unreached or save_lighting or fill_unreached or fill_param) else None   # geometry only: once
+    texels = scene.texel_aovs(theta.detach()) if (texel_prior > 0.0 or mask_unreached or save_lighting or fill_unreached or fill_param or init_from_target) else None   # geometry only: once
     guides = texels.as_guides() if texel_prior > 0.0 else None
+    if init_from_target:
+        with torch.no_grad():
+            photo = scene.texel_project([(scene.camera, image_gt)], theta.detach(), texels=texels)
+            irradiance = scene.texel_lighting(theta.detach(), spp=max(64, spp), texels=texels).irradiance
+            known = (photo.weight > 0) & (irradiance.sum(-1) > 0)
+            guess = torch.zeros_like(theta)
+            guess[..., :3] = (math.pi * photo.color[..., :3] / irradiance.clamp_min(1e-8)).clamp(1e-3, 1.0)
+            theta[..., :3] = push_pull(guess, known)[..., :3].clamp(1e-3, 1.0)
+            reached = texels.reach == 1
+            if verbose:
+                print(f"initialised from the target: the camera sees {int((reached & (photo.weight > 0)).sum())} of {int(reached.sum())} reached texels "
+                      f"({float((reached & (photo.weight > 0)).sum()) / max(int(reached.sum()), 1):.1%}); {int(known.sum())} of them were lit", flush=True)
     material = theta
     for it in range(iters):
         opt.zero_grad()
@@ -99,6 +117,8 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
         losses.append(float(loss))
         if verbose and (it % 20 == 0 or it == iters - 1):
             print(f"iteration {it:4d}  L1 image loss {losses[-1]:.5f}", flush=True)
+    if init_from_target and verbose and losses:
+        print(f"first iteration's loss after the initialisation from the target: {losses[0]:.5f}", flush=True)
     material = push_pull(theta.detach(), texels.coverage) if fill_param else theta.detach()   # (a convex combination: stays within the clamp)
     if save_lighting:                                              # printed with or without --out; the images need it
         light = scene.texel_lighting(material.detach(), spp=max(64, spp), texels=texels)
@@ -139,7 +159,8 @@ if __name__ == "__main__":
     ap.add_argument("--save-lighting", action="store_true")
     ap.add_argument("--fill-unreached", action="store_true")
     ap.add_argument("--fill-param", action="store_true")
+    ap.add_argument("--init-from-target", action="store_true")
     a = ap.parse_args()
     run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness, denoise=a.denoise,
         texel_prior=a.texel_prior, mask_unreached=a.mask_unreached, save_lighting=a.save_lighting, fill_unreached=a.fill_unreached,
-        fill_param=a.fill_param)
+        fill_param=a.fill_param, init_from_target=a.init_from_target)

@@ -450,6 +450,66 @@ int zdr_push_pull(const zdr_push_pull_params *params, const float *weight, const
 int zdr_push_pull_backward(const zdr_push_pull_params *params, const float *weight, const float *d_out, float *d_x, void *workspace,
                            void *stream);
 
+/* Texture-space views (projective texturing): what a camera sees of each texel, the photograph it took gathered into texture space, and
+ * the adjoint of that gather.  Two halves, split where the cost and the differentiability split.
+ *
+ * 1. zdr_scene_texel_view: geometry.  Needs the scene, costs one any-hit ray per texel, carries no gradient.
+ * texel_aovs: a tex_h x tex_w x 16 buffer in the layout of zdr_scene_texel_aovs, of which only the normal (floats 4..6), texel_size (7),
+ * the position (8..10) and reach (12) are read — any set of surface points is valid input, as for zdr_scene_texel_lighting.  A texel is
+ * SHADED iff reach == 1 and neither its normal nor its position holds a NaN; every other texel gets eight zeros.  The camera's frame
+ * o, fwd, right, upp, tan = tan(fov / 2), aspect = height / width is the one a render with `camera`, `width` and `height` uses.
+ * With v = p - o, z = v . fwd, dist = |v|, a shaded texel gets
+ *   float 0     visible    1 iff z > 0 (in front), 0 <= X < width and 0 <= Y < height (inside) and the segment to the camera is free, else 0
+ *   float 1     cosine     n . wi, wi = (o - p) / dist, signed.  A weight, not a test: the renderer has no facing test, `visible` has none
+ *   floats 2, 3 pixel      X = ((v . right) / z / tan + 1) width / 2,  Y = (-(v . upp) / z / (tan aspect) + 1) height / 2: the exact inverse
+ *                          of the camera ray with the pixel jitter as the fractional part; pixel x covers [x, x + 1).  0 when z <= 0
+ *   floats 4, 5 depth, distance   z and dist
+ *   float 6     scale      on-screen length of one texel in pixels, texel_size (width / 2) / (tan z); 0 when z <= 0.
+ *                          scale^2 |cosine| approximates the texel's area in pixels
+ *   float 7                0
+ * The segment starts at p with direction wi and the interval (1e-4, dist); it is tested against every primitive (the any-hit query of
+ * zdr_trace_any), and only for texels in front and inside.  Products and sums are float32 in the order written (dot products from x to
+ * z), divisions and the square root IEEE, nothing contracted.  No float atomic and no dependence on the order of the work: the same bits
+ * from run to run.  `workspace`: at least zdr_texel_view_workspace_bytes(tex_h, tex_w) bytes (0 = invalid size), contents irrelevant.
+ * The call only enqueues on `stream`; it never allocates and never synchronises, and can be captured in a HIP graph without a call
+ * before.
+ * ZDR_E_INVALID: a null or misaligned (16 bytes) pointer, struct_size other than sizeof(zdr_texel_view_params), a size <= 0, a fov that
+ * is not finite or not in (0, pi), an output that overlaps the workspace or the input, a workspace that overlaps the input.
+ * ZDR_E_UNSUPPORTED: more than 2^26 texels or 2^28 pixels; a library linked without these kernels.
+ *
+ * 2. zdr_texel_gather, zdr_texel_gather_backward: the gather and its adjoint.  No scene handle, no workspace.
+ * view: a tex_h x tex_w x 8 view buffer, of which only floats 0 (visible), 2 and 3 (X, Y) are read; image: height x width x 4.
+ * Forward, color (tex_h x tex_w x 4, overwritten).  Where visible is 0 (or NaN) the colour is 0 and the image is NOT read: what lies
+ * behind an invisible texel, NaN included, never reaches the result, and X, Y may hold anything there.  Otherwise, in this order:
+ *   fx = X - 0.5, fy = Y - 0.5;  x0 = floor(fx), y0 = floor(fy);  tx = fx - x0, ty = fy - y0;
+ *   taps x0 and x0 + 1 clamped to [0, width - 1], y0 and y0 + 1 clamped to [0, height - 1] (the weights come from the unclamped fraction);
+ *   top = c(y0, x0) + (c(y0, x1) - c(y0, x0)) tx,  bot = c(y1, x0) + (c(y1, x1) - c(y1, x0)) tx,  color = visible (top + (bot - top) ty)
+ * per channel, uncontracted: X, Y at a pixel's centre return that pixel bit for bit, and a 1 x 1 image returns its pixel.  The gather
+ * POINT-SAMPLES: a texel that covers many pixels (scale >> 1) aliases unless the caller prefilters the image.
+ * Adjoint, d_image (height x width x 4) ADDED INTO — the caller zeroes it: for the same four taps
+ *   d_image[tap] += (w visible) d_color,  w = (1 - tx)(1 - ty), tx (1 - ty), (1 - tx) ty, tx ty,
+ * one float atomic per tap and channel.  With the view held fixed the map is linear in the image and this is its transpose, up to the
+ * rounding of the four products and the order of the additions (which varies from run to run).  The VIEW BUFFER receives NO gradient.
+ * Both calls only enqueue on `stream` and can be captured without a call before.
+ * ZDR_E_INVALID: struct_size other than sizeof(zdr_texel_gather_params), a size <= 0, a null or misaligned (16 bytes) pointer, an output
+ * that overlaps an input.  ZDR_E_UNSUPPORTED: more than 2^26 texels or 2^28 pixels; a library linked without these kernels. */
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_texel_view_params) */
+    int32_t tex_h, tex_w;
+    int32_t width, height;             /* of the camera's image */
+    zdr_camera camera;
+} zdr_texel_view_params;
+size_t zdr_texel_view_workspace_bytes(int32_t tex_h, int32_t tex_w);   /* 0 = invalid size */
+int zdr_scene_texel_view(zdr_scene *scene, const zdr_texel_view_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
+                         float *out /* DEVICE tex_h x tex_w x 8 */, void *workspace, void *stream);
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_texel_gather_params) */
+    int32_t tex_h, tex_w;
+    int32_t width, height;             /* of the image */
+} zdr_texel_gather_params;
+int zdr_texel_gather(const zdr_texel_gather_params *params, const float *view, const float *image, float *color, void *stream);
+int zdr_texel_gather_backward(const zdr_texel_gather_params *params, const float *view, const float *d_color, float *d_image, void *stream);
+
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,
  * shadow rays (one per shaded vertex, prb.py:59), shaded vertices, emitter hits via BSDF sampling, NaN-dropped samples,

@@ -1,8 +1,10 @@
 """zdr_amd — MI355X-native differentiable path tracer behind the reference's Python API
 (``from zdr import Scene, Camera, float3``; /root/reference/__init__.py:1)."""
 from .denoiser import denoise
+from .project import texel_gather, texel_gather_backward, texel_gather_forward
 from .pushpull import push_pull
 from .mathtypes import Camera, float3, float4x4
-from .render import Aovs, Scene, TexelAovs, TexelLighting
+from .render import Aovs, Scene, TexelAovs, TexelLighting, TexelProjection, TexelView
 
-__all__ = ["Scene", "Aovs", "TexelAovs", "TexelLighting", "Camera", "float3", "float4x4", "denoise", "push_pull"]
+__all__ = ["Scene", "Aovs", "TexelAovs", "TexelLighting", "Camera", "float3", "float4x4", "denoise", "push_pull",
+           "TexelView", "TexelProjection", "texel_gather", "texel_gather_forward", "texel_gather_backward"]

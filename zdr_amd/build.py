@@ -22,6 +22,8 @@ TEXEL_LIB = os.path.join(CSRC, "libzdr_texel.so")
 BAKE_LIB = os.path.join(CSRC, "libzdr_bake.so")
 # Push-pull hole filling (zdr_pushpull.hip): a fourth library, for the same reason.
 PUSHPULL_LIB = os.path.join(CSRC, "libzdr_pushpull.so")
+# Texture-space views of a camera, the gather through them and its adjoint (zdr_project.hip): a fifth library, for the same reason.
+PROJECT_LIB = os.path.join(CSRC, "libzdr_project.so")
 ARCH = "gfx950"
 
 
@@ -51,7 +53,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not os.path.exists(LIB) or not os.path.exists(TEXEL_LIB) or not os.path.exists(BAKE_LIB) or not os.path.exists(PUSHPULL_LIB):
+    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB)):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -87,6 +89,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # push-pull hole filling, linked into libzdr_pushpull.so; no contraction: the result is defined by the operation order of
         # include/zdr.h (zdr_push_pull), and a level computes the same bits in the fused tail as in a launch of its own
         ("zdr_pushpull.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
+        # texture-space views, linked into libzdr_project.so; no contraction: the gather's bits are defined by the operation order of
+        # include/zdr.h (zdr_texel_gather), and the projection inverts the camera ray in plain float32; its adjoint scatters with float
+        # atomics, which the option turns into global_atomic_add_f32 as in the path kernels
+        ("zdr_project.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off", "-munsafe-fp-atomics"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -100,13 +106,16 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    pushpull_obj = objs.pop()                               # (zdr_pushpull.o: the last job)
+    project_obj = objs.pop()                                # (zdr_project.o: the last job)
+    pushpull_obj = objs.pop()                               # (zdr_pushpull.o: the one before)
     bake_obj = objs.pop()                                   # (zdr_bake.o: the one before)
     texel_obj = objs.pop()                                  # (zdr_texel.o: the one before that)
     links = [[hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", TEXEL_LIB, texel_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BAKE_LIB, bake_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PUSHPULL_LIB, pushpull_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PROJECT_LIB, project_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake", "-lzdr_pushpull",
+              "-lzdr_project",
               "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -21,6 +21,8 @@
 #include "bake.h"
 #define ZDR_PUSHPULL_LAUNCHER_REF __attribute__((weak))  // (csrc/pushpull.h)
 #include "pushpull.h"
+#define ZDR_PROJECT_LAUNCHER_REF __attribute__((weak))   // (csrc/project.h)
+#include "project.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1064,6 +1066,22 @@ static int32_t wide_offsets_for(size_t texels, size_t pixels) {
     return wide;
 }
 
+// The camera's frame as every kernel takes it: a render (RenderCfg) and the view buffer of zdr_scene_texel_view (ProjViewArgs), which
+// inverts pixel_ray and must do so with the very floats the ray was made from.
+static void camera_frame(const zdr_camera &cam, float o[3], float f[3], float r[3], float u[3], float &tan_half) {
+    h3 origin = H3(cam.origin[0], cam.origin[1], cam.origin[2]);
+    h3 target = H3(cam.target[0], cam.target[1], cam.target[2]);
+    h3 up = H3(cam.up[0], cam.up[1], cam.up[2]);
+    h3 fwd = hnormalize(hsub(target, origin));                    // camera.py:12-14
+    h3 right = hnormalize(hcross(fwd, up));
+    h3 upp = hcross(right, fwd);
+    o[0] = origin.x; o[1] = origin.y; o[2] = origin.z;
+    f[0] = fwd.x; f[1] = fwd.y; f[2] = fwd.z;
+    r[0] = right.x; r[1] = right.y; r[2] = right.z;
+    u[0] = upp.x; u[1] = upp.y; u[2] = upp.z;
+    tan_half = tanf(0.5f * cam.fov);                              // camera.py:15
+}
+
 static int make_render_cfg(const zdr_render_params *p, bool backward, RenderCfg &R) {
     { int rc = check_params_abi(p); if (rc) return rc; }
     if (p->integrator < 0 || p->integrator > ZDR_UVGRAD) return fail(ZDR_E_INVALID, "unknown integrator");
@@ -1085,17 +1103,7 @@ static int make_render_cfg(const zdr_render_params *p, bool backward, RenderCfg 
     R.aspect = (float)p->height / (float)p->width;
     R.inv_spp = 1.0f / (float)p->spp;
     R.alpha = (float)(p->sample_end - p->sample_begin) / (float)p->spp;
-    h3 origin = H3(p->camera.origin[0], p->camera.origin[1], p->camera.origin[2]);
-    h3 target = H3(p->camera.target[0], p->camera.target[1], p->camera.target[2]);
-    h3 up = H3(p->camera.up[0], p->camera.up[1], p->camera.up[2]);
-    h3 fwd = hnormalize(hsub(target, origin));                    // camera.py:12-14
-    h3 right = hnormalize(hcross(fwd, up));
-    h3 upp = hcross(right, fwd);
-    R.cam_o[0] = origin.x; R.cam_o[1] = origin.y; R.cam_o[2] = origin.z;
-    R.cam_fwd[0] = fwd.x; R.cam_fwd[1] = fwd.y; R.cam_fwd[2] = fwd.z;
-    R.cam_right[0] = right.x; R.cam_right[1] = right.y; R.cam_right[2] = right.z;
-    R.cam_upp[0] = upp.x; R.cam_upp[1] = upp.y; R.cam_upp[2] = upp.z;
-    R.cam_tan = tanf(0.5f * p->camera.fov);                       // camera.py:15
+    camera_frame(p->camera, R.cam_o, R.cam_fwd, R.cam_right, R.cam_upp, R.cam_tan);
     // work decomposition: 8x8 pixel tiles x sample chunks, enough single-wave workgroups to keep
     // 256 CUs x 4 SIMDs busy with several waves each and to let the dispatcher balance uneven tiles
     R.tiles_x = (p->x1 - p->x0 + 7) / 8; R.tiles_y = (p->y1 - p->y0 + 7) / 8;
@@ -1699,6 +1707,86 @@ extern "C" int zdr_push_pull(const zdr_push_pull_params *p, const float *weight,
 
 extern "C" int zdr_push_pull_backward(const zdr_push_pull_params *p, const float *weight, const float *d_out, float *d_x, void *workspace, void *stream) {
     return push_pull_call("zdr_push_pull_backward", p, weight, d_out, d_x, workspace, stream, 1);
+}
+
+// ------------------------------------------------------------------- texture-space views
+// zdr_scene_texel_view (include/zdr.h): argument checks, then the three launches of zdr_project.hip on the caller's stream.  The handle is
+// only read — the acceleration structure as it is — so nothing is allocated and the call can be captured without a call before.
+static int project_check_size(int32_t tex_h, int32_t tex_w) {
+    if (tex_h <= 0 || tex_w <= 0) return fail(ZDR_E_INVALID, "zdr_scene_texel_view: the texture size must be positive");
+    if ((uint64_t)tex_h * (uint64_t)tex_w > ZDR_PROJECT_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, "zdr_scene_texel_view: more than 2^26 texels");
+    return ZDR_OK;
+}
+
+static int project_check_image(const char *name, int32_t width, int32_t height) {
+    if (width <= 0 || height <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the image size must be positive");
+    if ((uint64_t)width * (uint64_t)height > ZDR_PROJECT_MAX_PIXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^28 pixels");
+    return ZDR_OK;
+}
+
+extern "C" size_t zdr_texel_view_workspace_bytes(int32_t tex_h, int32_t tex_w) {
+    if (project_check_size(tex_h, tex_w)) return 0;
+    return ZDR_PROJECT_HEADER_BYTES + (((size_t)tex_h * (size_t)tex_w * sizeof(uint32_t) + 15) & ~(size_t)15);
+}
+
+extern "C" int zdr_scene_texel_view(zdr_scene *s, const zdr_texel_view_params *p, const float *texel_aovs, float *out, void *workspace, void *stream) {
+    if (!s || !p || !texel_aovs || !out || !workspace) return fail(ZDR_E_INVALID, "null argument");
+    if (p->struct_size != sizeof(zdr_texel_view_params))
+        return fail(ZDR_E_INVALID, "zdr_texel_view_params.struct_size is " + std::to_string(p->struct_size) + ", this library expects " + std::to_string(sizeof(zdr_texel_view_params)));
+    if ((uintptr_t)texel_aovs % 16 || (uintptr_t)out % 16 || (uintptr_t)workspace % 16)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_view: texel_aovs, out and workspace must be 16-byte aligned");
+    if (int rc = project_check_size(p->tex_h, p->tex_w)) return rc;
+    if (int rc = project_check_image("zdr_scene_texel_view", p->width, p->height)) return rc;
+    if (!(p->camera.fov > 0.0f && p->camera.fov < 3.14159265358979323846f))       // (false for a NaN)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_view: camera.fov must be finite and lie in (0, pi)");
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, wbytes = zdr_texel_view_workspace_bytes(p->tex_h, p->tex_w);
+    if (denoise_overlap(out, 32 * n, {{workspace, wbytes}, {texel_aovs, 64 * n}})) return fail(ZDR_E_INVALID, "zdr_scene_texel_view: out must not overlap the workspace or texel_aovs");
+    if (denoise_overlap(workspace, wbytes, {{texel_aovs, 64 * n}})) return fail(ZDR_E_INVALID, "zdr_scene_texel_view: the workspace must not overlap texel_aovs");
+    if (!zdr_launch_texel_view)                                      // (weak: csrc/project.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the texture-space view kernels (zdr_project.hip)");
+    HIPCHK(hipSetDevice(s->device));
+    ProjViewArgs V;
+    V.texels = (const float4 *)texel_aovs; V.out = (float4 *)out;
+    V.count = (uint32_t *)workspace; V.list = (uint32_t *)((char *)workspace + ZDR_PROJECT_HEADER_BYTES);
+    V.ntexels = (uint32_t)n; V.tex_w = p->tex_w; V.tex_h = p->tex_h;
+    V.width =(float)p->width; V.height = (float)p->height; V.half_w = 0.5f * (float)p->width; V.half_h = 0.5f * (float)p->height;
+    V.aspect = (float)p->height / (float)p->width;                   // (as make_render_cfg)
+    camera_frame(p->camera, V.cam_o, V.cam_fwd, V.cam_right, V.cam_upp, V.cam_tan);
+    if (zdr_launch_texel_view(s->ds, s->accel_is_bvh, V, (hipStream_t)stream)) return fail(ZDR_E_HIP, "texel view launch failed");
+    return ZDR_OK;
+}
+
+// zdr_texel_gather / zdr_texel_gather_backward (include/zdr.h): no scene handle, no workspace, no allocation, no synchronisation —
+// argument checks, then one launch of zdr_project.hip on the caller's stream.
+static int texel_gather_call(const char *name, const zdr_texel_gather_params *p, const float *view, const float *in, float *out, void *stream, int backward) {
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (p->struct_size != sizeof(zdr_texel_gather_params))
+        return fail(ZDR_E_INVALID, "zdr_texel_gather_params.struct_size is " + std::to_string(p->struct_size) + ", this library expects " + std::to_string(sizeof(zdr_texel_gather_params)));
+    if (p->tex_h <= 0 || p->tex_w <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the texture size must be positive");
+    if ((uint64_t)p->tex_h * (uint64_t)p->tex_w > ZDR_PROJECT_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
+    if (int rc = project_check_image(name, p->width, p->height)) return rc;
+    for (const void *q : {(const void *)view, (const void *)in, (const void *)out}) {
+        if (!q) return fail(ZDR_E_INVALID, "null argument");
+        if ((uintptr_t)q % 16) return fail(ZDR_E_INVALID, std::string(name) + ": every pointer must be 16-byte aligned");
+    }
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
+    if (denoise_overlap(out, 16 * (backward ? npix : n), {{view, 32 * n}, {in, 16 * (backward ? n : npix)}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": the output must not alias or overlap an input");
+    if (!zdr_launch_texel_gather)                                    // (weak: csrc/project.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the texture-space view kernels (zdr_project.hip)");
+    ProjGatherArgs G;
+    G.view = (const float4 *)view; G.in = (const float4 *)in; G.out = (float4 *)out;
+    G.ntexels = (uint32_t)n; G.width = p->width; G.height = p->height;
+    if (zdr_launch_texel_gather(G, backward, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_texel_gather(const zdr_texel_gather_params *p, const float *view, const float *image, float *color, void *stream) {
+    return texel_gather_call("zdr_texel_gather", p, view, image, color, stream, 0);
+}
+
+extern "C" int zdr_texel_gather_backward(const zdr_texel_gather_params *p, const float *view, const float *d_color, float *d_image, void *stream) {
+    return texel_gather_call("zdr_texel_gather_backward", p, view, d_color, d_image, stream, 1);
 }
 
 extern "C" int zdr_render_stats(zdr_scene *s, const zdr_render_params *p, const float *material, uint64_t counters[8], void *stream) {

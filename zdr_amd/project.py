@@ -1,0 +1,106 @@
+"""Projective texturing, the gather half (include/zdr.h, zdr_texel_gather): a camera's image read into texture space through the view
+buffer of ``Scene.texel_view`` — for every texel the camera sees, the bilinear value of the image at the texel's pixel position — and
+the adjoint of that map, which scatters a texture-space gradient back onto the image.
+
+    view = scene.texel_view(theta, res=(w, h))               # geometry: one ray per texel, no gradient
+    color = texel_gather(photo, view)                        # (H, W, 4), differentiable in photo
+    loss = (view.weight()[..., None] * (color - theta)).square().sum()     # a loss in texture space
+
+With the view held fixed the map is linear in the image.  The VIEW BUFFER receives no gradient.  The gather point-samples: a texel that
+covers many pixels (``view.scale`` >> 1) aliases unless the image is prefiltered.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _native as N
+
+VIEW_CHANNELS = 8
+
+
+def _view_data(view):
+    data = getattr(view, "data", view)                        # a TexelView or the (H, W, 8) tensor itself
+    if not isinstance(data, torch.Tensor) or data.dim() != 3 or data.shape[2] != VIEW_CHANNELS or data.dtype != torch.float32 or data.shape[0] < 1 or data.shape[1] < 1:
+        raise ValueError(f"view must be a TexelView or a float32 (H, W, {VIEW_CHANNELS}) tensor")
+    if not data.is_cuda:
+        raise ValueError(f"the view buffer must be on a GPU, not on {data.device}")
+    return data.detach().contiguous()
+
+
+def _check_image(x, what, device):
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[2] != 4 or x.shape[0] < 1 or x.shape[1] < 1 or x.dtype != torch.float32:
+        raise ValueError(f"{what} must be a float32 (height, width, 4) tensor, not {tuple(getattr(x, 'shape', ()))} {getattr(x, 'dtype', type(x))}")
+    if x.device != device:
+        raise ValueError(f"{what} must be on the view buffer's device {device}, not on {x.device}")
+
+
+def _out(out, shape, device, what):
+    if out is None:
+        return None
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 {shape} tensor on {device}")
+    return out
+
+
+def _call(fn, view, src, dst, res):
+    p = N.TexelGatherParams()
+    p.struct_size = C.sizeof(N.TexelGatherParams)
+    p.tex_h, p.tex_w, p.width, p.height = int(view.shape[0]), int(view.shape[1]), int(res[0]), int(res[1])
+    with torch.cuda.device(view.device):
+        stream = C.c_void_p(torch.cuda.current_stream(view.device).cuda_stream)
+        N.check(fn(C.byref(p), view.data_ptr(), src.data_ptr(), dst.data_ptr(), stream))
+    return dst
+
+
+def texel_gather_forward(image, view, *, out=None):
+    """zdr_texel_gather: ``color[t] = visible[t] * bilinear(image, X[t] - 0.5, Y[t] - 0.5)``, (H, W, 4).  ``image`` is (height, width, 4)
+    float32, ``view`` a ``TexelView`` or its (H, W, 8) tensor; ``out`` is allocated when not given.  Only enqueues, on torch's current
+    stream."""
+    view = _view_data(view)
+    _check_image(image, "image", view.device)
+    shape = (int(view.shape[0]), int(view.shape[1]), 4)
+    out = _out(out, shape, view.device, "out")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=view.device)
+    return _call(N.lib().zdr_texel_gather, view, image.detach().contiguous(), out, (image.shape[1], image.shape[0]))
+
+
+def texel_gather_backward(d_color, view, res, *, d_image=None):
+    """zdr_texel_gather_backward: the adjoint of ``texel_gather_forward`` for an image of ``res = (width, height)``, ADDED INTO
+    ``d_image`` ((height, width, 4); a zero tensor when not given) with float atomics.  The view receives no gradient."""
+    view = _view_data(view)
+    w, h = int(res[0]), int(res[1])
+    if w < 1 or h < 1:
+        raise ValueError(f"res must be a positive (width, height), not {res}")
+    _check_image(d_color, "d_color", view.device)
+    if tuple(d_color.shape[:2]) != tuple(view.shape[:2]):
+        raise ValueError(f"d_color must have the view's size {tuple(view.shape[:2])}, not {tuple(d_color.shape[:2])}")
+    d_image = _out(d_image, (h, w, 4), view.device, "d_image")
+    if d_image is None:
+        d_image = torch.zeros((h, w, 4), dtype=torch.float32, device=view.device)
+    return _call(N.lib().zdr_texel_gather_backward, view, d_color.detach().contiguous(), d_image, (w, h))
+
+
+class TexelGatherOperator(torch.autograd.Function):
+    """The linear map color = K image.  Gradient with respect to the image only; keeps nothing but the detached view buffer."""
+    @staticmethod
+    def forward(ctx, image, view):
+        ctx.save_for_backward(view)
+        ctx.res = (int(image.shape[1]), int(image.shape[0]))
+        return texel_gather_forward(image, view)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        view, = ctx.saved_tensors
+        return texel_gather_backward(grad_output, view, ctx.res), None
+
+
+def texel_gather(image, view):
+    """The image gathered into texture space: (H, W, 4), 0 on the texels the camera does not see.  Differentiable in ``image`` only:
+    ``image.grad`` is the scatter of the texture-space gradient onto the four pixels each visible texel reads, exactly 0 on pixels
+    that no visible texel taps."""
+    view = _view_data(view)
+    _check_image(image, "image", view.device)
+    return TexelGatherOperator.apply(image, view)

@@ -177,6 +177,46 @@ class TexelLighting:
         return self.data[..., 3]
 
 
+class TexelView:
+    """What a camera sees of each texel, from ``Scene.texel_view`` (include/zdr.h, zdr_scene_texel_view): ``data`` is the (H, W, 8) view
+    buffer of one material's texels for an image of ``res`` = (width, height).  ``visible`` (H, W): 1 where the texel lies in front of the
+    camera, inside its image and the segment to the camera is free; ``cosine``: n . wi towards the camera, signed (a weight, not a test);
+    ``pixel`` (H, W, 2): the texel's position (X, Y) in the image, pixel x covering [x, x + 1); ``depth``, ``distance``: along the
+    camera's axis and along the segment; ``scale``: the on-screen length of one texel in pixels.  Eight zeros where ``reach`` is 0.
+    No gradient."""
+
+    def __init__(self, data, res):
+        self.data = data
+        self.res = (int(res[0]), int(res[1]))
+
+    visible = property(lambda self: self.data[..., 0])
+    cosine = property(lambda self: self.data[..., 1])
+    pixel = property(lambda self: self.data[..., 2:4])
+    depth = property(lambda self: self.data[..., 4])
+    distance = property(lambda self: self.data[..., 5])
+    scale = property(lambda self: self.data[..., 6])
+
+    def gather(self, image):
+        """``texel_gather(image, self)`` (zdr_amd/project.py): the (height, width, 4) image of this view's size read into texture space,
+        (H, W, 4), differentiable in ``image``."""
+        from .project import texel_gather
+        if tuple(image.shape[:2]) != (self.res[1], self.res[0]):
+            raise ValueError(f"the image must be ({self.res[1]}, {self.res[0]}, 4), the size the view was made for, not {tuple(image.shape)}")
+        return texel_gather(image, self.data)
+
+    def weight(self, cosine_power=1.0):
+        """``visible * |cosine| ** cosine_power`` (H, W): how much this view should count for each texel."""
+        return self.visible * self.cosine.abs() ** float(cosine_power)
+
+
+class TexelProjection:
+    """Several photographs merged in texture space, from ``Scene.texel_project``: ``color`` (H, W, 4) = sum w_i c_i / sum w_i (0 where no
+    view sees the texel), ``weight`` (H, W) = sum w_i, ``count`` (H, W): the number of views that see each texel."""
+
+    def __init__(self, color, weight, count):
+        self.color, self.weight, self.count = color, weight, count
+
+
 def _camera_pod(cam: Camera) -> N.CameraPOD:
     return N.CameraPOD(float(cam.fov), (C.c_float * 3)(*cam.origin), (C.c_float * 3)(*cam.target), (C.c_float * 3)(*cam.up))
 
@@ -610,6 +650,65 @@ class Scene:
         if texels is None:
             texels = self.texel_aovs(material, index)
         return TexelLighting(self.texel_lighting_forward(texels.data, spp=spp, seed=seed, samples=samples, max_distance=max_distance))
+
+    # ------------------------------------------------------------- texture-space views
+    def texel_view_forward(self, texel_data, res, *, camera=None, out=None, workspace=None):
+        """The (H, W, 8) view buffer of include/zdr.h, zdr_scene_texel_view — visible, cosine, pixel x / y, depth, distance, scale, 0 —
+        of ``camera`` (default: ``scene.camera``) with an image of ``res`` = (width, height), for the surface points of ``texel_data``,
+        an (H, W, 16) tensor in the layout of ``texel_aovs_forward`` of which the normal, the texel size, the position and ``reach``
+        are read.  ``out`` and ``workspace`` (any tensor of at least ``zdr_texel_view_workspace_bytes`` bytes) are allocated when not
+        given.  Only enqueues, on torch's current stream."""
+        if texel_data.ndim != 3 or texel_data.shape[2] != N.AOV_CHANNELS or texel_data.dtype != torch.float32 or texel_data.device != self.device:
+            raise ValueError(f"texel_data must be a float32 (H, W, {N.AOV_CHANNELS}) tensor on {self.device}")
+        width, height = int(res[0]), int(res[1])
+        if width < 1 or height < 1:
+            raise ValueError(f"res must be a positive (width, height), not {res}")
+        texel_data = texel_data.detach().contiguous()
+        H, W = int(texel_data.shape[0]), int(texel_data.shape[1])
+        workspace = self._workspace(workspace, int(N.lib().zdr_texel_view_workspace_bytes(H, W)))
+        out = self._out_tensor(out, (H, W, 8), False)
+        p = N.TexelViewParams()
+        p.struct_size = C.sizeof(N.TexelViewParams)
+        p.tex_h, p.tex_w, p.width, p.height = H, W, width, height
+        p.camera = _camera_pod(camera if camera is not None else self.camera)
+        N.check(N.lib().zdr_scene_texel_view(self._handle, C.byref(p), texel_data.data_ptr(), out.data_ptr(), workspace.data_ptr(), self._stream()))
+        return out
+
+    def texel_view(self, material, index=0, *, res, camera=None, texels=None) -> TexelView:
+        """What ``camera`` (default: ``scene.camera``) sees of each texel of ``material[index]`` in an image of ``res`` = (width,
+        height): a ``TexelView``.  ``material`` and ``index`` are taken as ``texel_aovs`` takes them; ``texels``: a ``TexelAovs``
+        already computed for them (without it one is computed here).  No gradient."""
+        if texels is None:
+            texels = self.texel_aovs(material, index)
+        return TexelView(self.texel_view_forward(texels.data, res, camera=camera), res)
+
+    def texel_project(self, views, material, index=0, *, cosine_power=1.0, fill=False, texels=None) -> TexelProjection:
+        """Photographs into texture space ("bake from photographs"): ``views`` is a list of (camera, image) pairs, each image (h, w, 4)
+        of the size the camera took it at (sizes may differ from view to view).  Every view is gathered through its ``texel_view`` and
+        weighted with ``view.weight(cosine_power)``; the result has ``color`` = sum w_i c_i / sum w_i (0 where the sum is 0),
+        ``weight`` = sum w_i and ``count``, the number of views that see each texel, accumulated in list order.  Differentiable in
+        the images.  ``fill=True``: ``color`` is push-pull-filled from the texels some view sees (zdr_amd/pushpull.py), which stay
+        bit for bit.  ``material``, ``index``, ``texels``: as ``texel_view`` takes them."""
+        from .pushpull import push_pull
+        if len(views) == 0:
+            raise ValueError("texel_project needs at least one (camera, image) pair")
+        if texels is None:
+            texels = self.texel_aovs(material, index)
+        num = weight = count = None
+        for camera, image in views:
+            if image.dim() != 3 or image.shape[2] != 4:
+                raise ValueError(f"every image must be (height, width, 4), not {tuple(image.shape)}")
+            view = self.texel_view(material, index, res=(int(image.shape[1]), int(image.shape[0])), camera=camera, texels=texels)
+            w = view.weight(cosine_power)
+            term = w[..., None] * view.gather(image)
+            num = term if num is None else num + term
+            weight = w if weight is None else weight + w
+            count = view.visible.clone() if count is None else count + view.visible
+        seen = weight > 0
+        color = torch.where(seen[..., None], num / torch.where(seen, weight, torch.ones_like(weight))[..., None], torch.zeros_like(num))
+        if fill:
+            color = push_pull(color, seen)
+        return TexelProjection(color, weight, count)
 
     def render_denoised(self, material, *, res, spp, seed=0, **denoise_kwargs):
         """``render`` followed by the feature-guided denoiser: ``denoise(render(material), render_aovs(material), **denoise_kwargs)``
