@@ -26,7 +26,8 @@ a texel in shadow gets only noise for a gradient, whatever its reach.
 camera (scene.texel_project) and divided by the direct irradiance of scene.texel_lighting — albedo = pi * color / irradiance, a
 Lambertian guess that ignores indirect light — on the texels the camera sees and a light sample reached; every other texel is filled
 from those by push-pull.  Roughness starts as it would have.  Prints the share of the reached texels that the camera sees and the
-first iteration's loss.
+first iteration's loss.  --project-filter mip prefilters the photograph for that projection (a mip pyramid, the level taken from each
+texel's on-screen size: scene.texel_project(..., filter="mip")), so that a texel that covers many pixels reads their mean, not one.
 """
 import argparse
 import math
@@ -73,7 +74,8 @@ def texel_prior_loss(material, f, guides):
 
 
 def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0, denoise=False,
-        texel_prior=0.0, mask_unreached=False, save_lighting=False, fill_unreached=False, fill_param=False, init_from_target=False):
+        texel_prior=0.0, mask_unreached=False, save_lighting=False, fill_unreached=False, fill_param=False, init_from_target=False,
+        project_filter="bilinear"):
     scene = Scene([(os.path.join(ASSETS, "cboxuv.obj"), None, float3(0.0)),
                    (os.path.join(ASSETS, "cbox-light.obj"), None, float3(17, 12, 4))], integrator=integrator)
     scene.camera = Camera(fov=50 / 180 * 3.1415926, origin=float3(-0.2, 2.6, 6.0), target=float3(-0.2, 2.6, -2.5), up=float3(0.0, 1.0, 0.0))
@@ -88,7 +90,7 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
     guides = texels.as_guides() if texel_prior > 0.0 else None
     if init_from_target:
         with torch.no_grad():
-            photo = scene.texel_project([(scene.camera, image_gt)], theta.detach(), texels=texels)
+            photo = scene.texel_project([(scene.camera, image_gt)], theta.detach(), texels=texels, filter=project_filter)
             irradiance = scene.texel_lighting(theta.detach(), spp=max(64, spp), texels=texels).irradiance
             known = (photo.weight > 0) & (irradiance.sum(-1) > 0)
             guess = torch.zeros_like(theta)
@@ -160,7 +162,8 @@ if __name__ == "__main__":
     ap.add_argument("--fill-unreached", action="store_true")
     ap.add_argument("--fill-param", action="store_true")
     ap.add_argument("--init-from-target", action="store_true")
+    ap.add_argument("--project-filter", choices=("bilinear", "mip"), default="bilinear")
     a = ap.parse_args()
     run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness, denoise=a.denoise,
         texel_prior=a.texel_prior, mask_unreached=a.mask_unreached, save_lighting=a.save_lighting, fill_unreached=a.fill_unreached,
-        fill_param=a.fill_param, init_from_target=a.init_from_target)
+        fill_param=a.fill_param, init_from_target=a.init_from_target, project_filter=a.project_filter)

@@ -485,7 +485,7 @@ int zdr_push_pull_backward(const zdr_push_pull_params *params, const float *weig
  *   taps x0 and x0 + 1 clamped to [0, width - 1], y0 and y0 + 1 clamped to [0, height - 1] (the weights come from the unclamped fraction);
  *   top = c(y0, x0) + (c(y0, x1) - c(y0, x0)) tx,  bot = c(y1, x0) + (c(y1, x1) - c(y1, x0)) tx,  color = visible (top + (bot - top) ty)
  * per channel, uncontracted: X, Y at a pixel's centre return that pixel bit for bit, and a 1 x 1 image returns its pixel.  The gather
- * POINT-SAMPLES: a texel that covers many pixels (scale >> 1) aliases unless the caller prefilters the image.
+ * POINT-SAMPLES: a texel that covers many pixels (scale >> 1) aliases; zdr_texel_gather_mip below ("Prefiltered gather") is the remedy.
  * Adjoint, d_image (height x width x 4) ADDED INTO — the caller zeroes it: for the same four taps
  *   d_image[tap] += (w visible) d_color,  w = (1 - tx)(1 - ty), tx (1 - ty), (1 - tx) ty, tx ty,
  * one float atomic per tap and channel.  With the view held fixed the map is linear in the image and this is its transpose, up to the
@@ -509,6 +509,65 @@ typedef struct {
 } zdr_texel_gather_params;
 int zdr_texel_gather(const zdr_texel_gather_params *params, const float *view, const float *image, float *color, void *stream);
 int zdr_texel_gather_backward(const zdr_texel_gather_params *params, const float *view, const float *d_color, float *d_image, void *stream);
+
+/* Prefiltered gather: a mip pyramid of the image, a trilinear gather that takes the level from each texel's on-screen footprint (float 6
+ * of the view buffer, scale), and the exact transposes of both, so that a gradient reaches every pixel under a texel's footprint.  No
+ * scene handle.
+ *
+ * Pyramid.  Level 0 is the image, height x width x 4.  (w_{l+1}, h_{l+1}) = (ceil(w_l / 2), ceil(h_l / 2));  L is the first level of size
+ * 1 x 1, and min(that, levels) if levels > 0.  The image is thought of as continued by its border pixels: pixel (row i, column j) of
+ * level l + 1 is
+ *   ((a00 + a01) + (a10 + a11)) * 0.25,   a_rc = level l at (row min(2i + r, h_l - 1), column min(2j + c, w_l - 1)),
+ * per channel, uncontracted, in that order.  So for an odd size the last coarse pixel counts the last fine pixel twice and the corner
+ * pixel counts it four times, and a constant image has constant levels of the same bits.  The levels >= 1 are packed one after another
+ * (level 1 first, rows of float4) into one buffer, the PYRAMID, of zdr_image_pyramid_bytes(params) bytes: 0 = invalid parameters, never 0
+ * otherwise (16 when L = 0).  Level 0 is never copied.
+ * Pyramid adjoint, zdr_image_pyramid_backward.  d_pyramid holds cotangents G_1 .. G_L in the pyramid's layout.  T_L = G_L;
+ *   T_l[y, x] = G_l[y, x] + (0.25 m_l(y, x)) T_{l+1}[y >> 1, x >> 1],   m_l = mx my,
+ * mx = 2 if x is the last index of an odd-width level, else 1, my likewise for rows;  d_image[y, x] += (0.25 m_0(y, x)) T_1[y >> 1, x >> 1],
+ * ADDED INTO as zdr_texel_gather_backward adds.  A gather (every fine pixel has one parent): no atomic, the same bits from run to run.
+ * d_pyramid is a WORKSPACE: its contents after the call are unspecified.
+ *
+ * Level of a texel.  s = scale * footprint (a float32 product; footprint: finite, > 0, 1 by default; 0.5 sharpens by one level);
+ * s = max(s, 1), NaN -> 1;  l0 = the binary exponent of s, taken from its bits;  m = s 2^-l0 in [1, 2);  f = 0 if m == 1 (by selection),
+ * else min(log2f(m), 1);  if l0 >= L then l0 = L and f = 0.  The split is exact integer work; only f carries rounding, and the result is
+ * continuous in it.
+ * Mip gather, zdr_texel_gather_mip: color (tex_h x tex_w x 4, overwritten).  Where visible is 0 or NaN the colour is 0 and neither the
+ * image nor the pyramid is read for that texel.  Otherwise lo = the bilinear sample of level l0 at (X 2^-l0, Y 2^-l0) — the scaling is
+ * exact — by the tap rule of zdr_texel_gather with that level's width and height, operation for operation.  If f == 0 the upper level is
+ * NOT READ and c = lo; otherwise hi is the same sample of level l0 + 1 and c = lo + (hi - lo) f.  color = visible c.
+ * It follows that wherever s <= 1 the result is zdr_texel_gather's bit for bit; that where scale is 2^k (k <= L) and footprint is 1 it is,
+ * bit for bit, zdr_texel_gather of level k with X, Y scaled by 2^-k; and that a constant image comes out as visible times that constant.
+ * Mip gather adjoint, zdr_texel_gather_mip_backward: ADDED INTO d_image (level 0) and d_pyramid (the levels >= 1, the pyramid's layout; the
+ * caller zeroes it), one float atomic per tap and channel.  Each lower tap receives ((w (1 - f)) visible) d_color, each upper tap, only
+ * where f != 0, ((w f) visible) d_color, w the four bilinear products of zdr_texel_gather_backward; with f == 0 that is the very product
+ * zdr_texel_gather_backward adds.  The VIEW BUFFER receives NO gradient.  The full image gradient is this call followed by
+ * zdr_image_pyramid_backward on d_pyramid.
+ * The filter is ISOTROPIC: scale is the footprint's long axis, so grazing texels (|cosine| << 1) are over-blurred across the short one;
+ * anisotropic filtering needs footprint axes that the view buffer does not carry.
+ *
+ * All pointers are DEVICE pointers, 16-byte aligned.  The calls only enqueue on `stream`: they never allocate and never synchronise, and
+ * can be captured in a HIP graph without a call before.
+ * ZDR_E_INVALID: a wrong struct_size, a size <= 0, levels < 0, a footprint that is not finite or not > 0, a null or misaligned pointer, an
+ * output that overlaps an input or another output (byte ranges as the parameters size them).
+ * ZDR_E_UNSUPPORTED: more than 2^26 texels or 2^28 pixels; a library linked without these kernels. */
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_image_pyramid_params) */
+    int32_t width, height, levels;     /* levels: 0 = down to 1 x 1 */
+} zdr_image_pyramid_params;
+size_t zdr_image_pyramid_bytes(const zdr_image_pyramid_params *params);   /* 0 = invalid */
+int zdr_image_pyramid(const zdr_image_pyramid_params *params, const float *image, float *pyramid, void *stream);
+int zdr_image_pyramid_backward(const zdr_image_pyramid_params *params, float *d_pyramid, float *d_image, void *stream);
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_texel_gather_mip_params) */
+    int32_t tex_h, tex_w;
+    int32_t width, height, levels;     /* of the image; levels as zdr_image_pyramid_params.levels */
+    float footprint;
+} zdr_texel_gather_mip_params;
+int zdr_texel_gather_mip(const zdr_texel_gather_mip_params *params, const float *view, const float *image, const float *pyramid, float *color,
+                         void *stream);
+int zdr_texel_gather_mip_backward(const zdr_texel_gather_mip_params *params, const float *view, const float *d_color, float *d_image,
+                                  float *d_pyramid, void *stream);
 
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,

@@ -1,7 +1,8 @@
 """zdr_amd — MI355X-native differentiable path tracer behind the reference's Python API
 (``from zdr import Scene, Camera, float3``; /root/reference/__init__.py:1)."""
 from .denoiser import denoise
-from .project import texel_gather, texel_gather_backward, texel_gather_forward
+from .mip import ImagePyramid, image_pyramid, image_pyramid_backward, image_pyramid_forward, pyramid_layout
+from .project import texel_gather, texel_gather_backward, texel_gather_forward, texel_gather_mip_backward, texel_gather_mip_forward
 from .pushpull import push_pull
 from .mathtypes import Camera, float3, float4x4
 from .render import Aovs, Scene, TexelAovs, TexelLighting, TexelProjection, TexelView

@@ -24,6 +24,8 @@ BAKE_LIB = os.path.join(CSRC, "libzdr_bake.so")
 PUSHPULL_LIB = os.path.join(CSRC, "libzdr_pushpull.so")
 # Texture-space views of a camera, the gather through them and its adjoint (zdr_project.hip): a fifth library, for the same reason.
 PROJECT_LIB = os.path.join(CSRC, "libzdr_project.so")
+# The image pyramid, the mip gather and their adjoints (zdr_mip.hip): a sixth library, for the same reason.
+MIP_LIB = os.path.join(CSRC, "libzdr_mip.so")
 ARCH = "gfx950"
 
 
@@ -53,7 +55,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB)):
+    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB)):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -93,6 +95,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # include/zdr.h (zdr_texel_gather), and the projection inverts the camera ray in plain float32; its adjoint scatters with float
         # atomics, which the option turns into global_atomic_add_f32 as in the path kernels
         ("zdr_project.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off", "-munsafe-fp-atomics"]),
+        # the image pyramid and the mip gather, linked into libzdr_mip.so, under the flags of zdr_project.hip: the operation order of
+        # include/zdr.h defines the bits (a level is the same in a fused launch as in one of its own), and the scatter's atomics
+        # become global_atomic_add_f32
+        ("zdr_mip.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off", "-munsafe-fp-atomics"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -106,7 +112,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    project_obj = objs.pop()                                # (zdr_project.o: the last job)
+    mip_obj = objs.pop()                                    # (zdr_mip.o: the last job)
+    project_obj = objs.pop()                                # (zdr_project.o: the one before)
     pushpull_obj = objs.pop()                               # (zdr_pushpull.o: the one before)
     bake_obj = objs.pop()                                   # (zdr_bake.o: the one before)
     texel_obj = objs.pop()                                  # (zdr_texel.o: the one before that)
@@ -114,8 +121,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BAKE_LIB, bake_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PUSHPULL_LIB, pushpull_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PROJECT_LIB, project_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", MIP_LIB, mip_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake", "-lzdr_pushpull",
-              "-lzdr_project",
+              "-lzdr_project", "-lzdr_mip",
               "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)

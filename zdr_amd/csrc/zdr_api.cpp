@@ -23,6 +23,8 @@
 #include "pushpull.h"
 #define ZDR_PROJECT_LAUNCHER_REF __attribute__((weak))   // (csrc/project.h)
 #include "project.h"
+#define ZDR_MIP_LAUNCHER_REF __attribute__((weak))       // (csrc/mip.h)
+#include "mip.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1787,6 +1789,101 @@ extern "C" int zdr_texel_gather(const zdr_texel_gather_params *p, const float *v
 
 extern "C" int zdr_texel_gather_backward(const zdr_texel_gather_params *p, const float *view, const float *d_color, float *d_image, void *stream) {
     return texel_gather_call("zdr_texel_gather_backward", p, view, d_color, d_image, stream, 1);
+}
+
+// ------------------------------------------------------------------- prefiltered gather
+// zdr_image_pyramid, zdr_image_pyramid_backward, zdr_texel_gather_mip, zdr_texel_gather_mip_backward (include/zdr.h): no scene handle, no
+// allocation, no synchronisation — argument checks, then the launches of zdr_mip.hip on the caller's stream.
+static int mip_check_image(const char *name, uint32_t struct_size, size_t expect, int32_t width, int32_t height, int32_t levels) {
+    if (struct_size != expect)
+        return fail(ZDR_E_INVALID, std::string(name) + ": struct_size is " + std::to_string(struct_size) + ", this library expects " + std::to_string(expect));
+    if (width <= 0 || height <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the image size must be positive");
+    if (levels < 0) return fail(ZDR_E_INVALID, std::string(name) + ": levels is " + std::to_string(levels) + ": 0 (down to 1 x 1) or a positive count");
+    if ((uint64_t)width * (uint64_t)height > ZDR_MIP_MAX_PIXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^28 pixels");
+    return ZDR_OK;
+}
+
+static int mip_check_pointers(const char *name, std::initializer_list<const void *> ptrs) {
+    for (const void *q : ptrs) {
+        if (!q) return fail(ZDR_E_INVALID, "null argument");
+        if ((uintptr_t)q % 16) return fail(ZDR_E_INVALID, std::string(name) + ": every pointer must be 16-byte aligned");
+    }
+    return ZDR_OK;
+}
+
+extern "C" size_t zdr_image_pyramid_bytes(const zdr_image_pyramid_params *p) {
+    if (!p) { fail(ZDR_E_INVALID, "null argument"); return 0; }
+    if (mip_check_image("zdr_image_pyramid_params", p->struct_size, sizeof(zdr_image_pyramid_params), p->width, p->height, p->levels)) return 0;
+    return zdr_mip_plan(p->width, p->height, p->levels).bytes;
+}
+
+static int image_pyramid_call(const char *name, const zdr_image_pyramid_params *p, const float *image, float *d_image, float *pyramid, void *stream, int backward) {
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (int rc = mip_check_image(name, p->struct_size, sizeof(zdr_image_pyramid_params), p->width, p->height, p->levels)) return rc;
+    const void *level0 = backward ? (const void *)d_image : (const void *)image;
+    if (int rc = mip_check_pointers(name, {level0, (const void *)pyramid})) return rc;
+    const size_t npix = (size_t)p->width * (size_t)p->height, pbytes = zdr_mip_plan(p->width, p->height, p->levels).bytes;
+    if (denoise_overlap(pyramid, pbytes, {{level0, 16 * npix}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": the pyramid must not alias or overlap the image");
+    if (!zdr_launch_image_pyramid)                                   // (weak: csrc/mip.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the prefiltering kernels (zdr_mip.hip)");
+    MipPyramidArgs A;
+    A.width = p->width; A.height = p->height; A.levels = p->levels;
+    A.image = (const float4 *)image; A.d_image = (float4 *)d_image; A.pyramid = (float4 *)pyramid;
+    if (zdr_launch_image_pyramid(A, backward, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": a launch failed");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_image_pyramid(const zdr_image_pyramid_params *p, const float *image, float *pyramid, void *stream) {
+    return image_pyramid_call("zdr_image_pyramid", p, image, nullptr, pyramid, stream, 0);
+}
+
+extern "C" int zdr_image_pyramid_backward(const zdr_image_pyramid_params *p, float *d_pyramid, float *d_image, void *stream) {
+    return image_pyramid_call("zdr_image_pyramid_backward", p, nullptr, d_image, d_pyramid, stream, 1);
+}
+
+static int texel_gather_mip_check(const char *name, const zdr_texel_gather_mip_params *p) {
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (int rc = mip_check_image(name, p->struct_size, sizeof(zdr_texel_gather_mip_params), p->width, p->height, p->levels)) return rc;
+    if (p->tex_h <= 0 || p->tex_w <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the texture size must be positive");
+    if (!(p->footprint > 0.0f && p->footprint <= 3.402823466e38f))    // (false for a NaN)
+        return fail(ZDR_E_INVALID, std::string(name) + ": footprint must be finite and > 0");
+    if ((uint64_t)p->tex_h * (uint64_t)p->tex_w > ZDR_MIP_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_texel_gather_mip(const zdr_texel_gather_mip_params *p, const float *view, const float *image, const float *pyramid, float *color, void *stream) {
+    const char *name = "zdr_texel_gather_mip";
+    if (int rc = texel_gather_mip_check(name, p)) return rc;
+    if (int rc = mip_check_pointers(name, {(const void *)view, (const void *)image, (const void *)pyramid, (const void *)color})) return rc;
+    const MipPlan P = zdr_mip_plan(p->width, p->height, p->levels);
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
+    if (denoise_overlap(color, 16 * n, {{view, 32 * n}, {image, 16 * npix}, {pyramid, P.bytes}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": the output must not alias or overlap an input");
+    if (!zdr_launch_texel_gather_mip)                                // (weak: csrc/mip.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the prefiltering kernels (zdr_mip.hip)");
+    MipGatherArgs G;
+    G.view = (const float4 *)view; G.in = (const float4 *)image; G.pyramid = (const float4 *)pyramid; G.out = (float4 *)color; G.d_pyramid = nullptr;
+    G.ntexels = (uint32_t)n; G.width = p->width; G.height = p->height; G.L = P.L; G.footprint = p->footprint;
+    if (zdr_launch_texel_gather_mip(G, 0, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_texel_gather_mip_backward(const zdr_texel_gather_mip_params *p, const float *view, const float *d_color, float *d_image, float *d_pyramid, void *stream) {
+    const char *name = "zdr_texel_gather_mip_backward";
+    if (int rc = texel_gather_mip_check(name, p)) return rc;
+    if (int rc = mip_check_pointers(name, {(const void *)view, (const void *)d_color, (const void *)d_image, (const void *)d_pyramid})) return rc;
+    const MipPlan P = zdr_mip_plan(p->width, p->height, p->levels);
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
+    if (denoise_overlap(d_image, 16 * npix, {{view, 32 * n}, {d_color, 16 * n}, {d_pyramid, P.bytes}}) || denoise_overlap(d_pyramid, P.bytes, {{view, 32 * n}, {d_color, 16 * n}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": an output must not alias or overlap an input or the other output");
+    if (!zdr_launch_texel_gather_mip)                                // (weak: csrc/mip.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the prefiltering kernels (zdr_mip.hip)");
+    MipGatherArgs G;
+    G.view = (const float4 *)view; G.in = (const float4 *)d_color; G.pyramid = nullptr; G.out = (float4 *)d_image; G.d_pyramid = (float4 *)d_pyramid;
+    G.ntexels = (uint32_t)n; G.width = p->width; G.height = p->height; G.L = P.L; G.footprint = p->footprint;
+    if (zdr_launch_texel_gather_mip(G, 1, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
+    return ZDR_OK;
 }
 
 extern "C" int zdr_render_stats(zdr_scene *s, const zdr_render_params *p, const float *material, uint64_t counters[8], void *stream) {

@@ -6,8 +6,10 @@ the adjoint of that map, which scatters a texture-space gradient back onto the i
     color = texel_gather(photo, view)                        # (H, W, 4), differentiable in photo
     loss = (view.weight()[..., None] * (color - theta)).square().sum()     # a loss in texture space
 
-With the view held fixed the map is linear in the image.  The VIEW BUFFER receives no gradient.  The gather point-samples: a texel that
-covers many pixels (``view.scale`` >> 1) aliases unless the image is prefiltered.
+With the view held fixed the map is linear in the image.  The VIEW BUFFER receives no gradient.  The bilinear gather point-samples: a
+texel that covers many pixels (``view.scale`` >> 1) aliases.  ``texel_gather(photo, view, filter="mip")`` is the remedy (README,
+"Prefiltered gather"): a mip pyramid of the image (zdr_amd/mip.py) and a trilinear gather whose level comes from ``view.scale``, with
+the exact transposes of both, so that the gradient reaches every pixel under a texel's footprint.
 """
 from __future__ import annotations
 
@@ -83,6 +85,66 @@ def texel_gather_backward(d_color, view, res, *, d_image=None):
     return _call(N.lib().zdr_texel_gather_backward, view, d_color.detach().contiguous(), d_image, (w, h))
 
 
+def _mip_params(view, res, levels, footprint) -> N.TexelGatherMipParams:
+    footprint = float(footprint)
+    if not (0.0 < footprint < float("inf")):
+        raise ValueError(f"footprint must be finite and > 0, not {footprint}")
+    p = N.TexelGatherMipParams()
+    p.struct_size = C.sizeof(N.TexelGatherMipParams)
+    p.tex_h, p.tex_w, p.width, p.height = int(view.shape[0]), int(view.shape[1]), int(res[0]), int(res[1])
+    p.levels, p.footprint = levels, footprint
+    return p
+
+
+def texel_gather_mip_forward(image, pyramid, view, footprint=1.0, levels=0, *, out=None):
+    """zdr_texel_gather_mip: the trilinear gather of ``image`` and its packed levels >= 1 ``pyramid`` (``image_pyramid_forward`` of the
+    same ``levels``), (H, W, 4): the level of a texel is log2(max(view.scale * footprint, 1)), split into a level and a fraction.
+    ``out`` is allocated when not given.  Only enqueues, on torch's current stream."""
+    from . import mip as M
+    view = _view_data(view)
+    _check_image(image, "image", view.device)
+    levels, res = M._levels_arg(levels), (int(image.shape[1]), int(image.shape[0]))
+    M._check_packed(pyramid, "pyramid", res, levels, view.device)
+    p = _mip_params(view, res, levels, footprint)
+    shape = (int(view.shape[0]), int(view.shape[1]), 4)
+    out = _out(out, shape, view.device, "out")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=view.device)
+    image = image.detach().contiguous()
+    with torch.cuda.device(view.device):
+        stream = C.c_void_p(torch.cuda.current_stream(view.device).cuda_stream)
+        N.check(N.lib().zdr_texel_gather_mip(C.byref(p), view.data_ptr(), image.data_ptr(), pyramid.data_ptr(), out.data_ptr(), stream))
+    return out
+
+
+def texel_gather_mip_backward(d_color, view, res, footprint=1.0, levels=0, *, d_image=None, d_pyramid=None):
+    """zdr_texel_gather_mip_backward: the adjoint of ``texel_gather_mip_forward`` for an image of ``res = (width, height)``, ADDED INTO
+    ``d_image`` ((height, width, 4)) and ``d_pyramid`` (the packed levels >= 1), zero tensors when not given, with float atomics.
+    Returns ``(d_image, d_pyramid)``; ``image_pyramid_backward(d_pyramid, res, levels, d_image=d_image)`` completes the image's
+    gradient.  The view receives no gradient."""
+    from . import mip as M
+    view = _view_data(view)
+    w, h = int(res[0]), int(res[1])
+    if w < 1 or h < 1:
+        raise ValueError(f"res must be a positive (width, height), not {res}")
+    levels = M._levels_arg(levels)
+    _check_image(d_color, "d_color", view.device)
+    if tuple(d_color.shape[:2]) != tuple(view.shape[:2]):
+        raise ValueError(f"d_color must have the view's size {tuple(view.shape[:2])}, not {tuple(d_color.shape[:2])}")
+    p = _mip_params(view, (w, h), levels, footprint)
+    d_image = _out(d_image, (h, w, 4), view.device, "d_image")
+    if d_image is None:
+        d_image = torch.zeros((h, w, 4), dtype=torch.float32, device=view.device)
+    if d_pyramid is None:
+        d_pyramid = torch.zeros((M.pyramid_pixels((w, h), levels), 4), dtype=torch.float32, device=view.device)
+    M._check_packed(d_pyramid, "d_pyramid", (w, h), levels, view.device)
+    d_color = d_color.detach().contiguous()
+    with torch.cuda.device(view.device):
+        stream = C.c_void_p(torch.cuda.current_stream(view.device).cuda_stream)
+        N.check(N.lib().zdr_texel_gather_mip_backward(C.byref(p), view.data_ptr(), d_color.data_ptr(), d_image.data_ptr(), d_pyramid.data_ptr(), stream))
+    return d_image, d_pyramid
+
+
 class TexelGatherOperator(torch.autograd.Function):
     """The linear map color = K image.  Gradient with respect to the image only; keeps nothing but the detached view buffer."""
     @staticmethod
@@ -97,10 +159,43 @@ class TexelGatherOperator(torch.autograd.Function):
         return texel_gather_backward(grad_output, view, ctx.res), None
 
 
-def texel_gather(image, view):
-    """The image gathered into texture space: (H, W, 4), 0 on the texels the camera does not see.  Differentiable in ``image`` only:
-    ``image.grad`` is the scatter of the texture-space gradient onto the four pixels each visible texel reads, exactly 0 on pixels
-    that no visible texel taps."""
+class TexelGatherMipOperator(torch.autograd.Function):
+    """The linear map color = K image with K = (mip gather) o (image, pyramid): four calls, two each way.  Gradient with respect to the
+    image only; keeps nothing but the detached view buffer."""
+    @staticmethod
+    def forward(ctx, image, view, footprint):
+        from .mip import image_pyramid_forward
+        ctx.save_for_backward(view)
+        ctx.res, ctx.footprint = (int(image.shape[1]), int(image.shape[0])), footprint
+        return texel_gather_mip_forward(image, image_pyramid_forward(image), view, footprint)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from .mip import image_pyramid_backward
+        view, = ctx.saved_tensors
+        d_image, d_pyramid = texel_gather_mip_backward(grad_output, view, ctx.res, ctx.footprint)
+        return image_pyramid_backward(d_pyramid, ctx.res, d_image=d_image), None, None
+
+
+FILTERS = ("bilinear", "mip")
+
+
+def texel_gather(image, view, *, filter="bilinear", footprint=1.0):
+    """The image gathered into texture space: (H, W, 4), 0 on the texels the camera does not see.  Differentiable in ``image`` only.
+
+    ``filter="bilinear"`` (the default): four taps of the image at the texel's pixel position; ``image.grad`` is the scatter of the
+    texture-space gradient onto the four pixels each visible texel reads, exactly 0 on pixels that no visible texel taps.  It
+    point-samples: where ``view.scale`` >> 1 it aliases.
+    ``filter="mip"``: the prefiltered gather (README, "Prefiltered gather").  A mip pyramid of the image is built and every texel reads
+    the two levels around log2(max(view.scale * footprint, 1)), blended by the fraction; where that is 0 (``scale * footprint <= 1``)
+    the result is the bilinear one bit for bit.  ``footprint`` (finite, > 0) scales the footprint: 0.5 sharpens by one level.
+    ``image.grad`` reaches every pixel under a texel's footprint, through the exact transposes of the gather and of the pyramid.  The
+    filter is isotropic: grazing texels are over-blurred across their short axis."""
+    if filter not in FILTERS:
+        raise ValueError(f"filter must be one of {FILTERS}, not {filter!r}")
     view = _view_data(view)
     _check_image(image, "image", view.device)
+    if filter == "mip":
+        _mip_params(view, (int(image.shape[1]), int(image.shape[0])), 0, footprint)     # (raises on a bad footprint)
+        return TexelGatherMipOperator.apply(image, view, float(footprint))
     return TexelGatherOperator.apply(image, view)

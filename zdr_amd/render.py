@@ -196,13 +196,13 @@ class TexelView:
     distance = property(lambda self: self.data[..., 5])
     scale = property(lambda self: self.data[..., 6])
 
-    def gather(self, image):
+    def gather(self, image, filter="bilinear", footprint=1.0):
         """``texel_gather(image, self)`` (zdr_amd/project.py): the (height, width, 4) image of this view's size read into texture space,
-        (H, W, 4), differentiable in ``image``."""
+        (H, W, 4), differentiable in ``image``.  ``filter``, ``footprint``: as ``texel_gather`` takes them ("mip": prefiltered)."""
         from .project import texel_gather
         if tuple(image.shape[:2]) != (self.res[1], self.res[0]):
             raise ValueError(f"the image must be ({self.res[1]}, {self.res[0]}, 4), the size the view was made for, not {tuple(image.shape)}")
-        return texel_gather(image, self.data)
+        return texel_gather(image, self.data, filter=filter, footprint=footprint)
 
     def weight(self, cosine_power=1.0):
         """``visible * |cosine| ** cosine_power`` (H, W): how much this view should count for each texel."""
@@ -682,13 +682,15 @@ class Scene:
             texels = self.texel_aovs(material, index)
         return TexelView(self.texel_view_forward(texels.data, res, camera=camera), res)
 
-    def texel_project(self, views, material, index=0, *, cosine_power=1.0, fill=False, texels=None) -> TexelProjection:
+    def texel_project(self, views, material, index=0, *, cosine_power=1.0, fill=False, texels=None, filter="bilinear", footprint=1.0) -> TexelProjection:
         """Photographs into texture space ("bake from photographs"): ``views`` is a list of (camera, image) pairs, each image (h, w, 4)
         of the size the camera took it at (sizes may differ from view to view).  Every view is gathered through its ``texel_view`` and
         weighted with ``view.weight(cosine_power)``; the result has ``color`` = sum w_i c_i / sum w_i (0 where the sum is 0),
         ``weight`` = sum w_i and ``count``, the number of views that see each texel, accumulated in list order.  Differentiable in
         the images.  ``fill=True``: ``color`` is push-pull-filled from the texels some view sees (zdr_amd/pushpull.py), which stay
-        bit for bit.  ``material``, ``index``, ``texels``: as ``texel_view`` takes them."""
+        bit for bit.  ``material``, ``index``, ``texels``: as ``texel_view`` takes them.  ``filter``, ``footprint``: how each view is
+        gathered, as ``texel_gather`` takes them; "mip" prefilters the photographs, so that a texel that covers many pixels reads all
+        of them (README, "Prefiltered gather")."""
         from .pushpull import push_pull
         if len(views) == 0:
             raise ValueError("texel_project needs at least one (camera, image) pair")
@@ -700,7 +702,7 @@ class Scene:
                 raise ValueError(f"every image must be (height, width, 4), not {tuple(image.shape)}")
             view = self.texel_view(material, index, res=(int(image.shape[1]), int(image.shape[0])), camera=camera, texels=texels)
             w = view.weight(cosine_power)
-            term = w[..., None] * view.gather(image)
+            term = w[..., None] * view.gather(image, filter=filter, footprint=footprint)
             num = term if num is None else num + term
             weight = w if weight is None else weight + w
             count = view.visible.clone() if count is None else count + view.visible
