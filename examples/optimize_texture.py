@@ -27,7 +27,9 @@ camera (scene.texel_project) and divided by the direct irradiance of scene.texel
 Lambertian guess that ignores indirect light — on the texels the camera sees and a light sample reached; every other texel is filled
 from those by push-pull.  Roughness starts as it would have.  Prints the share of the reached texels that the camera sees and the
 first iteration's loss.  --project-filter mip prefilters the photograph for that projection (a mip pyramid, the level taken from each
-texel's on-screen size: scene.texel_project(..., filter="mip")), so that a texel that covers many pixels reads their mean, not one.
+texel's on-screen size: scene.texel_project(..., filter="mip")), so that a texel that covers many pixels reads their mean, not one;
+--project-filter aniso takes the level from the short axis of each texel's on-screen ellipse and averages probes along the long one
+(filter="aniso"), which does not over-blur the walls seen at a grazing angle.
 """
 import argparse
 import math
@@ -162,7 +164,7 @@ if __name__ == "__main__":
     ap.add_argument("--fill-unreached", action="store_true")
     ap.add_argument("--fill-param", action="store_true")
     ap.add_argument("--init-from-target", action="store_true")
-    ap.add_argument("--project-filter", choices=("bilinear", "mip"), default="bilinear")
+    ap.add_argument("--project-filter", choices=("bilinear", "mip", "aniso"), default="bilinear")
     a = ap.parse_args()
     run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness, denoise=a.denoise,
         texel_prior=a.texel_prior, mask_unreached=a.mask_unreached, save_lighting=a.save_lighting, fill_unreached=a.fill_unreached,

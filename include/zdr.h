@@ -544,7 +544,7 @@ int zdr_texel_gather_backward(const zdr_texel_gather_params *params, const float
  * zdr_texel_gather_backward adds.  The VIEW BUFFER receives NO gradient.  The full image gradient is this call followed by
  * zdr_image_pyramid_backward on d_pyramid.
  * The filter is ISOTROPIC: scale is the footprint's long axis, so grazing texels (|cosine| << 1) are over-blurred across the short one;
- * anisotropic filtering needs footprint axes that the view buffer does not carry.
+ * anisotropic filtering needs footprint axes that the view buffer does not carry: zdr_texel_footprint and zdr_texel_gather_aniso below.
  *
  * All pointers are DEVICE pointers, 16-byte aligned.  The calls only enqueue on `stream`: they never allocate and never synchronise, and
  * can be captured in a HIP graph without a call before.
@@ -568,6 +568,75 @@ int zdr_texel_gather_mip(const zdr_texel_gather_mip_params *params, const float 
                          void *stream);
 int zdr_texel_gather_mip_backward(const zdr_texel_gather_mip_params *params, const float *view, const float *d_color, float *d_image,
                                   float *d_pyramid, void *stream);
+
+/* Anisotropic gather: the on-screen footprint ELLIPSE of every texel, a gather that places up to max_aniso trilinear probes of the mip
+ * gather along the ellipse's major axis — the way a texture unit filters anisotropically — and that gather's exact transpose.  The
+ * pyramid is zdr_image_pyramid's, unchanged.  No scene handle, no workspace, one launch per call.
+ *
+ * Footprint buffer, zdr_texel_footprint: out (tex_h x tex_w x 4, overwritten) from the texel buffer of zdr_scene_texel_aovs (normal n,
+ * texel_size, position p, reach) and a camera, whose frame (o, fwd, right, upp, tan, aspect, half_w = width / 2, half_h = height / 2) is
+ * exactly the one zdr_scene_texel_view derives.  A texel that is not shaded (the view's rule: reach == 1 and no NaN in normal or
+ * position), or that has z <= 0, or for which any of the four results is not finite, gets four zeros.  For the others, in float32,
+ * uncontracted, divisions and roots IEEE, dot products from x to z:
+ *   v = p - o,  z = v.fwd,  a = v.right,  b = v.upp
+ *   gX = (right z - fwd a) (half_w / (tan (z z))),   gY = -((upp z - fwd b) (half_h / ((tan aspect) (z z))))
+ * — the derivatives of the view buffer's X, Y with respect to the world position —, (t1, t2) = tangent and binormal of the kernels'
+ * make_onb(n),
+ *   m00 = texel_size (gX.t1), m01 = texel_size (gX.t2), m10 = texel_size (gY.t1), m11 = texel_size (gY.t2)
+ *   P = m00^2 + m01^2,  Q = m10^2 + m11^2,  R = m00 m10 + m01 m11,  hd = 0.5 (P - Q),  d = sqrt(hd^2 + R^2)
+ *   major = sqrt(0.5 (P + Q) + d),   minor = |m00 m11 - m01 m10| / major, 0 if major == 0
+ * (the determinant, not the smaller eigenvalue 0.5 (P + Q) - d, which cancels at grazing angles);  the direction e = (hd + d, R) if
+ * P >= Q, else (R, 0.5 (Q - P) + d) — no cancellation in the component that carries the length —, divided by sqrt(e.e), (1, 0) if that
+ * is 0.  Floats of a row: 0, 1 = major e (pixels), 2 = minor, 3 = major.  Because M M^T = texel_size^2 J (I - n n^T) J^T, the ellipse
+ * does not depend on the tangent basis that make_onb returns.  The texel is taken as a SQUARE PATCH of side texel_size in its tangent
+ * plane: the texel buffers carry no UV derivatives, so the stretch of the UV mapping itself is not modelled.  No atomic: the same bits
+ * from run to run.
+ *
+ * Probes of a texel.  A = major * footprint, B = minor * footprint (float32 products; footprint: finite, > 0; max_aniso: 1 .. 16).  If not
+ * A > 1 (a NaN too): N = 1, s = 1.  Else B' = max(B, A / max_aniso, 1) (a NaN B is passed over), q = ceil(A / B' - 0.125),
+ * N = q if 1 <= q <= max_aniso, max_aniso if q is larger, 1 otherwise (a NaN), s = B'.  The offset of 1/8: a plane parallel to the image
+ * plane projects by a similarity, its ratio is exactly 1 in exact arithmetic, and without the offset float32 would make N toggle between
+ * 1 and 2 across such a surface.  (l0, f) = the level split of zdr_texel_gather_mip applied to s with that routine's footprint at 1.
+ * Anisotropic gather, zdr_texel_gather_aniso: color (tex_h x tex_w x 4, overwritten).  Where visible is 0 or NaN the colour is 0 and
+ * NOTHING ELSE is read for that texel: no footprint row, no image, no pyramid.  Otherwise for probe i = 0 .. N - 1
+ *   t_i = (2 i + 1 - N) / (2 N)  (both exact as floats, one IEEE division),
+ *   X_i = X + (t_i footprint) major_x,   Y_i = Y + (t_i footprint) major_y,
+ *   c_i = the trilinear sample of zdr_texel_gather_mip at (X_i, Y_i) with (l0, f), operation for operation (the upper level is not
+ *         read where f == 0),
+ *   color = visible (((c_0 + c_1) + c_2 ...) (1 / N)),   1 / N one IEEE division.
+ * It follows that wherever A <= 1 the result is zdr_texel_gather's bit for bit; that a footprint row (scale, 0, scale, scale), or
+ * max_aniso = 1 with major = scale, gives zdr_texel_gather_mip's bits; and that a constant image comes out as visible times that
+ * constant up to the rounding of N (1 / N).
+ * Adjoint, zdr_texel_gather_aniso_backward: ADDED INTO d_image (level 0) and d_pyramid (the levels >= 1, the pyramid's layout; the
+ * caller zeroes it), one float atomic per tap, probe and channel.  Per probe each lower tap receives (((w (1 - f)) (1 / N)) visible)
+ * d_color, each upper tap, only where f != 0, (((w f) (1 / N)) visible) d_color, w the four bilinear products of
+ * zdr_texel_gather_backward.  The VIEW and FOOTPRINT buffers receive NO gradient.  The full image gradient is this call followed by
+ * zdr_image_pyramid_backward on d_pyramid.
+ *
+ * All pointers are DEVICE pointers, 16-byte aligned.  The calls only enqueue on `stream`: they never allocate and never synchronise, and
+ * can be captured in a HIP graph without a call before.
+ * ZDR_E_INVALID: a wrong struct_size, a size <= 0, levels < 0, a footprint that is not finite or not > 0, max_aniso outside 1 .. 16, a fov
+ * that is not finite or outside (0, pi), a null or misaligned pointer, an output that overlaps an input or another output.
+ * ZDR_E_UNSUPPORTED: more than 2^26 texels or 2^28 pixels; a library linked without these kernels. */
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_texel_footprint_params) */
+    int32_t tex_h, tex_w;
+    int32_t width, height;             /* of the camera's image */
+    zdr_camera camera;
+} zdr_texel_footprint_params;
+int zdr_texel_footprint(const zdr_texel_footprint_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
+                        float *out /* DEVICE tex_h x tex_w x 4 */, void *stream);
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_texel_gather_aniso_params) */
+    int32_t tex_h, tex_w;
+    int32_t width, height, levels;     /* of the image; levels as zdr_image_pyramid_params.levels */
+    float footprint;
+    int32_t max_aniso;                 /* 1 .. 16; 8 is the Python default */
+} zdr_texel_gather_aniso_params;
+int zdr_texel_gather_aniso(const zdr_texel_gather_aniso_params *params, const float *view, const float *footprint, const float *image,
+                           const float *pyramid, float *color, void *stream);
+int zdr_texel_gather_aniso_backward(const zdr_texel_gather_aniso_params *params, const float *view, const float *footprint,
+                                    const float *d_color, float *d_image, float *d_pyramid, void *stream);
 
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,

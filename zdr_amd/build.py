@@ -26,6 +26,8 @@ PUSHPULL_LIB = os.path.join(CSRC, "libzdr_pushpull.so")
 PROJECT_LIB = os.path.join(CSRC, "libzdr_project.so")
 # The image pyramid, the mip gather and their adjoints (zdr_mip.hip): a sixth library, for the same reason.
 MIP_LIB = os.path.join(CSRC, "libzdr_mip.so")
+# The footprint ellipse, the anisotropic gather and its adjoint (zdr_aniso.hip): a seventh library, for the same reason.
+ANISO_LIB = os.path.join(CSRC, "libzdr_aniso.so")
 ARCH = "gfx950"
 
 
@@ -55,7 +57,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB)):
+    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB)):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -99,6 +101,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # include/zdr.h defines the bits (a level is the same in a fused launch as in one of its own), and the scatter's atomics
         # become global_atomic_add_f32
         ("zdr_mip.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off", "-munsafe-fp-atomics"]),
+        # the footprint ellipse and the anisotropic gather, linked into libzdr_aniso.so, under the flags of zdr_mip.hip: a probe is the
+        # mip gather's trilinear sample operation for operation, and one probe must give that gather's bits
+        ("zdr_aniso.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off", "-munsafe-fp-atomics"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -112,7 +117,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    mip_obj = objs.pop()                                    # (zdr_mip.o: the last job)
+    aniso_obj = objs.pop()                                  # (zdr_aniso.o: the last job)
+    mip_obj = objs.pop()                                    # (zdr_mip.o: the one before)
     project_obj = objs.pop()                                # (zdr_project.o: the one before)
     pushpull_obj = objs.pop()                               # (zdr_pushpull.o: the one before)
     bake_obj = objs.pop()                                   # (zdr_bake.o: the one before)
@@ -122,8 +128,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PUSHPULL_LIB, pushpull_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PROJECT_LIB, project_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", MIP_LIB, mip_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", ANISO_LIB, aniso_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake", "-lzdr_pushpull",
-              "-lzdr_project", "-lzdr_mip",
+              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso",
               "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -25,6 +25,8 @@
 #include "project.h"
 #define ZDR_MIP_LAUNCHER_REF __attribute__((weak))       // (csrc/mip.h)
 #include "mip.h"
+#define ZDR_ANISO_LAUNCHER_REF __attribute__((weak))     // (csrc/aniso.h)
+#include "aniso.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1883,6 +1885,85 @@ extern "C" int zdr_texel_gather_mip_backward(const zdr_texel_gather_mip_params *
     G.view = (const float4 *)view; G.in = (const float4 *)d_color; G.pyramid = nullptr; G.out = (float4 *)d_image; G.d_pyramid = (float4 *)d_pyramid;
     G.ntexels = (uint32_t)n; G.width = p->width; G.height = p->height; G.L = P.L; G.footprint = p->footprint;
     if (zdr_launch_texel_gather_mip(G, 1, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
+    return ZDR_OK;
+}
+
+// ------------------------------------------------------------------- anisotropic gather
+// zdr_texel_footprint, zdr_texel_gather_aniso, zdr_texel_gather_aniso_backward (include/zdr.h): no scene handle, no workspace, no
+// allocation, no synchronisation — argument checks, then one launch of zdr_aniso.hip on the caller's stream.
+extern "C" int zdr_texel_footprint(const zdr_texel_footprint_params *p, const float *texel_aovs, float *out, void *stream) {
+    const char *name = "zdr_texel_footprint";
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (p->struct_size != sizeof(zdr_texel_footprint_params))
+        return fail(ZDR_E_INVALID, "zdr_texel_footprint_params.struct_size is " + std::to_string(p->struct_size) + ", this library expects " + std::to_string(sizeof(zdr_texel_footprint_params)));
+    if (p->tex_h <= 0 || p->tex_w <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the texture size must be positive");
+    if (p->width <= 0 || p->height <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the image size must be positive");
+    if (!(p->camera.fov > 0.0f && p->camera.fov < 3.14159265358979323846f))       // (false for a NaN)
+        return fail(ZDR_E_INVALID, std::string(name) + ": camera.fov must be finite and lie in (0, pi)");
+    if ((uint64_t)p->tex_h * (uint64_t)p->tex_w > ZDR_ANISO_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
+    if ((uint64_t)p->width * (uint64_t)p->height > ZDR_ANISO_MAX_PIXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^28 pixels");
+    if (int rc = mip_check_pointers(name, {(const void *)texel_aovs, (const void *)out})) return rc;
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w;
+    if (denoise_overlap(out, 16 * n, {{texel_aovs, 64 * n}})) return fail(ZDR_E_INVALID, std::string(name) + ": out must not alias or overlap texel_aovs");
+    if (!zdr_launch_texel_footprint)                                 // (weak: csrc/aniso.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the anisotropic-gather kernels (zdr_aniso.hip)");
+    AnisoFootprintArgs A;
+    A.texels = (const float4 *)texel_aovs; A.out = (float4 *)out; A.ntexels = (uint32_t)n;
+    A.half_w = 0.5f * (float)p->width; A.half_h = 0.5f * (float)p->height;
+    A.aspect = (float)p->height / (float)p->width;                   // (as zdr_scene_texel_view)
+    camera_frame(p->camera, A.cam_o, A.cam_fwd, A.cam_right, A.cam_upp, A.cam_tan);
+    if (zdr_launch_texel_footprint(A, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
+    return ZDR_OK;
+}
+
+static int texel_gather_aniso_check(const char *name, const zdr_texel_gather_aniso_params *p) {
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (int rc = mip_check_image(name, p->struct_size, sizeof(zdr_texel_gather_aniso_params), p->width, p->height, p->levels)) return rc;
+    if (p->tex_h <= 0 || p->tex_w <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the texture size must be positive");
+    if (!(p->footprint > 0.0f && p->footprint <= 3.402823466e38f))    // (false for a NaN)
+        return fail(ZDR_E_INVALID, std::string(name) + ": footprint must be finite and > 0");
+    if (p->max_aniso < 1 || p->max_aniso > ZDR_ANISO_MAX_PROBES)
+        return fail(ZDR_E_INVALID, std::string(name) + ": max_aniso is " + std::to_string(p->max_aniso) + ": it must lie in 1 .. " + std::to_string(ZDR_ANISO_MAX_PROBES));
+    if ((uint64_t)p->tex_h * (uint64_t)p->tex_w > ZDR_ANISO_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_texel_gather_aniso(const zdr_texel_gather_aniso_params *p, const float *view, const float *footprint, const float *image, const float *pyramid,
+                                      float *color, void *stream) {
+    const char *name = "zdr_texel_gather_aniso";
+    if (int rc = texel_gather_aniso_check(name, p)) return rc;
+    if (int rc = mip_check_pointers(name, {(const void *)view, (const void *)footprint, (const void *)image, (const void *)pyramid, (const void *)color})) return rc;
+    const MipPlan P = zdr_mip_plan(p->width, p->height, p->levels);
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
+    if (denoise_overlap(color, 16 * n, {{view, 32 * n}, {footprint, 16 * n}, {image, 16 * npix}, {pyramid, P.bytes}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": the output must not alias or overlap an input");
+    if (!zdr_launch_texel_gather_aniso)                              // (weak: csrc/aniso.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the anisotropic-gather kernels (zdr_aniso.hip)");
+    AnisoGatherArgs G;
+    G.view = (const float4 *)view; G.foot = (const float4 *)footprint; G.in = (const float4 *)image; G.pyramid = (const float4 *)pyramid;
+    G.out = (float4 *)color; G.d_pyramid = nullptr;
+    G.ntexels = (uint32_t)n; G.width = p->width; G.height = p->height; G.L = P.L; G.max_aniso = p->max_aniso; G.footprint = p->footprint;
+    if (zdr_launch_texel_gather_aniso(G, 0, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_texel_gather_aniso_backward(const zdr_texel_gather_aniso_params *p, const float *view, const float *footprint, const float *d_color, float *d_image,
+                                               float *d_pyramid, void *stream) {
+    const char *name = "zdr_texel_gather_aniso_backward";
+    if (int rc = texel_gather_aniso_check(name, p)) return rc;
+    if (int rc = mip_check_pointers(name, {(const void *)view, (const void *)footprint, (const void *)d_color, (const void *)d_image, (const void *)d_pyramid})) return rc;
+    const MipPlan P = zdr_mip_plan(p->width, p->height, p->levels);
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
+    if (denoise_overlap(d_image, 16 * npix, {{view, 32 * n}, {footprint, 16 * n}, {d_color, 16 * n}, {d_pyramid, P.bytes}}) ||
+        denoise_overlap(d_pyramid, P.bytes, {{view, 32 * n}, {footprint, 16 * n}, {d_color, 16 * n}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": an output must not alias or overlap an input or the other output");
+    if (!zdr_launch_texel_gather_aniso)                              // (weak: csrc/aniso.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the anisotropic-gather kernels (zdr_aniso.hip)");
+    AnisoGatherArgs G;
+    G.view = (const float4 *)view; G.foot = (const float4 *)footprint; G.in = (const float4 *)d_color; G.pyramid = nullptr;
+    G.out = (float4 *)d_image; G.d_pyramid = (float4 *)d_pyramid;
+    G.ntexels = (uint32_t)n; G.width = p->width; G.height = p->height; G.L = P.L; G.max_aniso = p->max_aniso; G.footprint = p->footprint;
+    if (zdr_launch_texel_gather_aniso(G, 1, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
     return ZDR_OK;
 }
 

@@ -9,7 +9,9 @@ the adjoint of that map, which scatters a texture-space gradient back onto the i
 With the view held fixed the map is linear in the image.  The VIEW BUFFER receives no gradient.  The bilinear gather point-samples: a
 texel that covers many pixels (``view.scale`` >> 1) aliases.  ``texel_gather(photo, view, filter="mip")`` is the remedy (README,
 "Prefiltered gather"): a mip pyramid of the image (zdr_amd/mip.py) and a trilinear gather whose level comes from ``view.scale``, with
-the exact transposes of both, so that the gradient reaches every pixel under a texel's footprint.
+the exact transposes of both, so that the gradient reaches every pixel under a texel's footprint.  That filter is isotropic;
+``texel_gather(photo, view, filter="aniso")`` (README, "Anisotropic gather") takes the level from the short axis of each texel's
+on-screen ellipse (``texel_footprint_forward``, ``scene.texel_view(..., footprint=True)``) and averages probes along the long one.
 """
 from __future__ import annotations
 
@@ -177,10 +179,136 @@ class TexelGatherMipOperator(torch.autograd.Function):
         return image_pyramid_backward(d_pyramid, ctx.res, d_image=d_image), None, None
 
 
-FILTERS = ("bilinear", "mip")
+FOOTPRINT_CHANNELS = 4
+MAX_ANISO = 16
 
 
-def texel_gather(image, view, *, filter="bilinear", footprint=1.0):
+def _footprint_data(data, view):
+    if not isinstance(data, torch.Tensor) or tuple(data.shape) != (int(view.shape[0]), int(view.shape[1]), FOOTPRINT_CHANNELS) or data.dtype != torch.float32:
+        raise ValueError(f"footprint_data must be a float32 {(int(view.shape[0]), int(view.shape[1]), FOOTPRINT_CHANNELS)} tensor, the footprint buffer of the view's texels")
+    if data.device != view.device:
+        raise ValueError(f"the footprint buffer must be on the view buffer's device {view.device}, not on {data.device}")
+    return data.detach().contiguous()
+
+
+def texel_footprint_forward(texel_data, res, camera, *, out=None):
+    """zdr_texel_footprint: the (H, W, 4) footprint buffer — the major axis of each texel's on-screen ellipse as a vector in pixels
+    (floats 0, 1), the lengths of the minor and of the major axis (floats 2, 3) — of ``camera`` with an image of ``res`` = (width, height),
+    for the surface points of ``texel_data``, an (H, W, 16) tensor in the layout of ``Scene.texel_aovs_forward`` of which the normal,
+    the texel size, the position and ``reach`` are read.  Four zeros where the texel is not shaded or lies behind the camera.  ``out``
+    is allocated when not given.  No scene, no workspace; only enqueues, on torch's current stream."""
+    from .render import _camera_pod
+    if not isinstance(texel_data, torch.Tensor) or texel_data.dim() != 3 or texel_data.shape[2] != N.AOV_CHANNELS or texel_data.dtype != torch.float32 \
+            or texel_data.shape[0] < 1 or texel_data.shape[1] < 1:
+        raise ValueError(f"texel_data must be a float32 (H, W, {N.AOV_CHANNELS}) tensor")
+    if not texel_data.is_cuda:
+        raise ValueError(f"texel_data must be on a GPU, not on {texel_data.device}")
+    width, height = int(res[0]), int(res[1])
+    if width < 1 or height < 1:
+        raise ValueError(f"res must be a positive (width, height), not {res}")
+    texel_data = texel_data.detach().contiguous()
+    shape = (int(texel_data.shape[0]), int(texel_data.shape[1]), FOOTPRINT_CHANNELS)
+    out = _out(out, shape, texel_data.device, "out")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=texel_data.device)
+    p = N.TexelFootprintParams()
+    p.struct_size = C.sizeof(N.TexelFootprintParams)
+    p.tex_h, p.tex_w, p.width, p.height = shape[0], shape[1], width, height
+    p.camera = _camera_pod(camera)
+    with torch.cuda.device(texel_data.device):
+        stream = C.c_void_p(torch.cuda.current_stream(texel_data.device).cuda_stream)
+        N.check(N.lib().zdr_texel_footprint(C.byref(p), texel_data.data_ptr(), out.data_ptr(), stream))
+    return out
+
+
+def _aniso_params(view, res, levels, footprint, max_aniso) -> N.TexelGatherAnisoParams:
+    footprint = float(footprint)
+    if not (0.0 < footprint < float("inf")):
+        raise ValueError(f"footprint must be finite and > 0, not {footprint}")
+    if isinstance(max_aniso, bool) or int(max_aniso) != max_aniso or not (1 <= int(max_aniso) <= MAX_ANISO):
+        raise ValueError(f"max_aniso must be an integer in 1 .. {MAX_ANISO}, not {max_aniso!r}")
+    p = N.TexelGatherAnisoParams()
+    p.struct_size = C.sizeof(N.TexelGatherAnisoParams)
+    p.tex_h, p.tex_w, p.width, p.height = int(view.shape[0]), int(view.shape[1]), int(res[0]), int(res[1])
+    p.levels, p.footprint, p.max_aniso = levels, footprint, int(max_aniso)
+    return p
+
+
+def texel_gather_aniso_forward(image, pyramid, view, footprint_data, footprint=1.0, max_aniso=8, levels=0, *, out=None):
+    """zdr_texel_gather_aniso: the anisotropic gather of ``image`` and its packed levels >= 1 ``pyramid`` (``image_pyramid_forward`` of
+    the same ``levels``), (H, W, 4): up to ``max_aniso`` trilinear probes along the major axis of each texel's ellipse in
+    ``footprint_data`` (``texel_footprint_forward``), at the level of the minor axis.  ``out`` is allocated when not given.  Only
+    enqueues, on torch's current stream."""
+    from . import mip as M
+    view = _view_data(view)
+    footprint_data = _footprint_data(footprint_data, view)
+    _check_image(image, "image", view.device)
+    levels, res = M._levels_arg(levels), (int(image.shape[1]), int(image.shape[0]))
+    M._check_packed(pyramid, "pyramid", res, levels, view.device)
+    p = _aniso_params(view, res, levels, footprint, max_aniso)
+    shape = (int(view.shape[0]), int(view.shape[1]), 4)
+    out = _out(out, shape, view.device, "out")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=view.device)
+    image = image.detach().contiguous()
+    with torch.cuda.device(view.device):
+        stream = C.c_void_p(torch.cuda.current_stream(view.device).cuda_stream)
+        N.check(N.lib().zdr_texel_gather_aniso(C.byref(p), view.data_ptr(), footprint_data.data_ptr(), image.data_ptr(), pyramid.data_ptr(), out.data_ptr(), stream))
+    return out
+
+
+def texel_gather_aniso_backward(d_color, view, footprint_data, res, footprint=1.0, max_aniso=8, levels=0, *, d_image=None, d_pyramid=None):
+    """zdr_texel_gather_aniso_backward: the adjoint of ``texel_gather_aniso_forward`` for an image of ``res = (width, height)``, ADDED
+    INTO ``d_image`` ((height, width, 4)) and ``d_pyramid`` (the packed levels >= 1), zero tensors when not given, with float atomics.
+    Returns ``(d_image, d_pyramid)``; ``image_pyramid_backward(d_pyramid, res, levels, d_image=d_image)`` completes the image's
+    gradient.  The view and the footprint buffer receive no gradient."""
+    from . import mip as M
+    view = _view_data(view)
+    footprint_data = _footprint_data(footprint_data, view)
+    w, h = int(res[0]), int(res[1])
+    if w < 1 or h < 1:
+        raise ValueError(f"res must be a positive (width, height), not {res}")
+    levels = M._levels_arg(levels)
+    _check_image(d_color, "d_color", view.device)
+    if tuple(d_color.shape[:2]) != tuple(view.shape[:2]):
+        raise ValueError(f"d_color must have the view's size {tuple(view.shape[:2])}, not {tuple(d_color.shape[:2])}")
+    p = _aniso_params(view, (w, h), levels, footprint, max_aniso)
+    d_image = _out(d_image, (h, w, 4), view.device, "d_image")
+    if d_image is None:
+        d_image = torch.zeros((h, w, 4), dtype=torch.float32, device=view.device)
+    if d_pyramid is None:
+        d_pyramid = torch.zeros((M.pyramid_pixels((w, h), levels), 4), dtype=torch.float32, device=view.device)
+    M._check_packed(d_pyramid, "d_pyramid", (w, h), levels, view.device)
+    d_color = d_color.detach().contiguous()
+    with torch.cuda.device(view.device):
+        stream = C.c_void_p(torch.cuda.current_stream(view.device).cuda_stream)
+        N.check(N.lib().zdr_texel_gather_aniso_backward(C.byref(p), view.data_ptr(), footprint_data.data_ptr(), d_color.data_ptr(), d_image.data_ptr(),
+                                                        d_pyramid.data_ptr(), stream))
+    return d_image, d_pyramid
+
+
+class TexelGatherAnisoOperator(torch.autograd.Function):
+    """The linear map color = K image with K = (anisotropic gather) o (image, pyramid): four calls, two each way.  Gradient with respect
+    to the image only; keeps nothing but the detached view and footprint buffers."""
+    @staticmethod
+    def forward(ctx, image, view, footprint_data, footprint, max_aniso):
+        from .mip import image_pyramid_forward
+        ctx.save_for_backward(view, footprint_data)
+        ctx.res, ctx.footprint, ctx.max_aniso = (int(image.shape[1]), int(image.shape[0])), footprint, max_aniso
+        return texel_gather_aniso_forward(image, image_pyramid_forward(image), view, footprint_data, footprint, max_aniso)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from .mip import image_pyramid_backward
+        view, footprint_data = ctx.saved_tensors
+        d_image, d_pyramid = texel_gather_aniso_backward(grad_output, view, footprint_data, ctx.res, ctx.footprint, ctx.max_aniso)
+        return image_pyramid_backward(d_pyramid, ctx.res, d_image=d_image), None, None, None, None
+
+
+FILTERS = ("bilinear", "mip", "aniso")
+
+
+def texel_gather(image, view, *, filter="bilinear", footprint=1.0, max_aniso=8):
     """The image gathered into texture space: (H, W, 4), 0 on the texels the camera does not see.  Differentiable in ``image`` only.
 
     ``filter="bilinear"`` (the default): four taps of the image at the texel's pixel position; ``image.grad`` is the scatter of the
@@ -190,11 +318,22 @@ def texel_gather(image, view, *, filter="bilinear", footprint=1.0):
     the two levels around log2(max(view.scale * footprint, 1)), blended by the fraction; where that is 0 (``scale * footprint <= 1``)
     the result is the bilinear one bit for bit.  ``footprint`` (finite, > 0) scales the footprint: 0.5 sharpens by one level.
     ``image.grad`` reaches every pixel under a texel's footprint, through the exact transposes of the gather and of the pyramid.  The
-    filter is isotropic: grazing texels are over-blurred across their short axis."""
+    filter is isotropic: grazing texels are over-blurred across their short axis.
+    ``filter="aniso"``: the anisotropic gather (README, "Anisotropic gather").  ``view`` must be a ``TexelView`` made with
+    ``footprint=True``: the level comes from the MINOR axis of each texel's on-screen ellipse, and up to ``max_aniso`` (1 .. 16)
+    trilinear probes are spread along the major axis and averaged.  ``footprint`` scales both axes.  Where the major axis times
+    ``footprint`` is at most 1 the result is the bilinear one bit for bit.  ``image.grad`` as for "mip"."""
     if filter not in FILTERS:
         raise ValueError(f"filter must be one of {FILTERS}, not {filter!r}")
+    footprint_data = getattr(view, "footprint_data", None)
     view = _view_data(view)
     _check_image(image, "image", view.device)
+    if filter == "aniso":
+        if footprint_data is None:
+            raise ValueError('filter="aniso" needs a view that carries a footprint buffer: scene.texel_view(..., footprint=True)')
+        footprint_data = _footprint_data(footprint_data, view)
+        _aniso_params(view, (int(image.shape[1]), int(image.shape[0])), 0, footprint, max_aniso)     # (raises on a bad footprint or max_aniso)
+        return TexelGatherAnisoOperator.apply(image, view, footprint_data, float(footprint), int(max_aniso))
     if filter == "mip":
         _mip_params(view, (int(image.shape[1]), int(image.shape[0])), 0, footprint)     # (raises on a bad footprint)
         return TexelGatherMipOperator.apply(image, view, float(footprint))

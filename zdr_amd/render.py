@@ -183,11 +183,13 @@ class TexelView:
     camera, inside its image and the segment to the camera is free; ``cosine``: n . wi towards the camera, signed (a weight, not a test);
     ``pixel`` (H, W, 2): the texel's position (X, Y) in the image, pixel x covering [x, x + 1); ``depth``, ``distance``: along the
     camera's axis and along the segment; ``scale``: the on-screen length of one texel in pixels.  Eight zeros where ``reach`` is 0.
-    No gradient."""
+    No gradient.  ``footprint_data``: the (H, W, 4) footprint buffer (include/zdr.h, zdr_texel_footprint) when the view was made with
+    ``footprint=True``, else None; ``footprint`` reads it."""
 
-    def __init__(self, data, res):
+    def __init__(self, data, res, footprint_data=None):
         self.data = data
         self.res = (int(res[0]), int(res[1]))
+        self.footprint_data = footprint_data
 
     visible = property(lambda self: self.data[..., 0])
     cosine = property(lambda self: self.data[..., 1])
@@ -196,17 +198,39 @@ class TexelView:
     distance = property(lambda self: self.data[..., 5])
     scale = property(lambda self: self.data[..., 6])
 
-    def gather(self, image, filter="bilinear", footprint=1.0):
+    @property
+    def footprint(self):
+        """The on-screen ellipse of each texel, a ``TexelFootprint`` (``major_axis`` (H, W, 2), ``minor``, ``major``), or None when the
+        view was made without ``footprint=True``."""
+        return None if self.footprint_data is None else TexelFootprint(self.footprint_data)
+
+    def gather(self, image, filter="bilinear", footprint=1.0, max_aniso=8):
         """``texel_gather(image, self)`` (zdr_amd/project.py): the (height, width, 4) image of this view's size read into texture space,
-        (H, W, 4), differentiable in ``image``.  ``filter``, ``footprint``: as ``texel_gather`` takes them ("mip": prefiltered)."""
+        (H, W, 4), differentiable in ``image``.  ``filter``, ``footprint``, ``max_aniso``: as ``texel_gather`` takes them ("mip":
+        prefiltered; "aniso": anisotropic, for a view made with ``footprint=True``)."""
         from .project import texel_gather
         if tuple(image.shape[:2]) != (self.res[1], self.res[0]):
             raise ValueError(f"the image must be ({self.res[1]}, {self.res[0]}, 4), the size the view was made for, not {tuple(image.shape)}")
+        if filter == "aniso":
+            return texel_gather(image, self, filter=filter, footprint=footprint, max_aniso=max_aniso)
         return texel_gather(image, self.data, filter=filter, footprint=footprint)
 
     def weight(self, cosine_power=1.0):
         """``visible * |cosine| ** cosine_power`` (H, W): how much this view should count for each texel."""
         return self.visible * self.cosine.abs() ** float(cosine_power)
+
+
+class TexelFootprint:
+    """The footprint buffer of a view (include/zdr.h, zdr_texel_footprint), ``data`` (H, W, 4): the on-screen ellipse of each texel's
+    square patch.  ``major_axis`` (H, W, 2): the long axis as a vector in pixels; ``minor``, ``major`` (H, W): the lengths of the two
+    axes (``major`` = |``major_axis``|).  Zeros where the texel is not shaded or lies behind the camera.  No gradient."""
+
+    def __init__(self, data):
+        self.data = data
+
+    major_axis = property(lambda self: self.data[..., 0:2])
+    minor = property(lambda self: self.data[..., 2])
+    major = property(lambda self: self.data[..., 3])
 
 
 class TexelProjection:
@@ -674,15 +698,21 @@ class Scene:
         N.check(N.lib().zdr_scene_texel_view(self._handle, C.byref(p), texel_data.data_ptr(), out.data_ptr(), workspace.data_ptr(), self._stream()))
         return out
 
-    def texel_view(self, material, index=0, *, res, camera=None, texels=None) -> TexelView:
+    def texel_view(self, material, index=0, *, res, camera=None, texels=None, footprint=False) -> TexelView:
         """What ``camera`` (default: ``scene.camera``) sees of each texel of ``material[index]`` in an image of ``res`` = (width,
         height): a ``TexelView``.  ``material`` and ``index`` are taken as ``texel_aovs`` takes them; ``texels``: a ``TexelAovs``
-        already computed for them (without it one is computed here).  No gradient."""
+        already computed for them (without it one is computed here).  ``footprint=True`` also computes the footprint buffer
+        (``texel_footprint_forward``) and attaches it as ``view.footprint_data``, which ``gather(..., filter="aniso")`` needs.  No
+        gradient."""
         if texels is None:
             texels = self.texel_aovs(material, index)
-        return TexelView(self.texel_view_forward(texels.data, res, camera=camera), res)
+        data = self.texel_view_forward(texels.data, res, camera=camera)
+        if not footprint:
+            return TexelView(data, res)
+        from .project import texel_footprint_forward
+        return TexelView(data, res, texel_footprint_forward(texels.data, res, camera if camera is not None else self.camera))
 
-    def texel_project(self, views, material, index=0, *, cosine_power=1.0, fill=False, texels=None, filter="bilinear", footprint=1.0) -> TexelProjection:
+    def texel_project(self, views, material, index=0, *, cosine_power=1.0, fill=False, texels=None, filter="bilinear", footprint=1.0, max_aniso=8) -> TexelProjection:
         """Photographs into texture space ("bake from photographs"): ``views`` is a list of (camera, image) pairs, each image (h, w, 4)
         of the size the camera took it at (sizes may differ from view to view).  Every view is gathered through its ``texel_view`` and
         weighted with ``view.weight(cosine_power)``; the result has ``color`` = sum w_i c_i / sum w_i (0 where the sum is 0),
@@ -690,7 +720,8 @@ class Scene:
         the images.  ``fill=True``: ``color`` is push-pull-filled from the texels some view sees (zdr_amd/pushpull.py), which stay
         bit for bit.  ``material``, ``index``, ``texels``: as ``texel_view`` takes them.  ``filter``, ``footprint``: how each view is
         gathered, as ``texel_gather`` takes them; "mip" prefilters the photographs, so that a texel that covers many pixels reads all
-        of them (README, "Prefiltered gather")."""
+        of them (README, "Prefiltered gather"); "aniso" computes each view's footprint buffer itself and gathers with up to
+        ``max_aniso`` probes along each texel's long axis (README, "Anisotropic gather")."""
         from .pushpull import push_pull
         if len(views) == 0:
             raise ValueError("texel_project needs at least one (camera, image) pair")
@@ -700,9 +731,9 @@ class Scene:
         for camera, image in views:
             if image.dim() != 3 or image.shape[2] != 4:
                 raise ValueError(f"every image must be (height, width, 4), not {tuple(image.shape)}")
-            view = self.texel_view(material, index, res=(int(image.shape[1]), int(image.shape[0])), camera=camera, texels=texels)
+            view = self.texel_view(material, index, res=(int(image.shape[1]), int(image.shape[0])), camera=camera, texels=texels, footprint=filter == "aniso")
             w = view.weight(cosine_power)
-            term = w[..., None] * view.gather(image, filter=filter, footprint=footprint)
+            term = w[..., None] * view.gather(image, filter=filter, footprint=footprint, max_aniso=max_aniso)
             num = term if num is None else num + term
             weight = w if weight is None else weight + w
             count = view.visible.clone() if count is None else count + view.visible
