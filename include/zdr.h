@@ -638,6 +638,70 @@ int zdr_texel_gather_aniso(const zdr_texel_gather_aniso_params *params, const fl
 int zdr_texel_gather_aniso_backward(const zdr_texel_gather_aniso_params *params, const float *view, const float *footprint,
                                     const float *d_color, float *d_image, float *d_pyramid, void *stream);
 
+/* Gather plan: the adjoint of the three gathers above without a float atomic.  With the view held fixed a gather is a sparse linear map
+ * from the image (and its pyramid) to the texture, and a view is fixed for as long as camera and geometry are.  A PLAN lays the
+ * transpose of that map out once, as rows per destination pixel, and is then applied as a gather: a defined summation order, the same
+ * bits from run to run, no hotspot where many texels tap one pixel.  The atomic adjoints above are unchanged.  No scene handle.
+ *
+ * Destinations (rows).  P0 = width height.  Pixel (x, y) of level 0 is row y width + x; pixel (x, y) of level l >= 1 is row
+ * P0 + offset_l + y w_l + x, offset_l the level's place in the packed pyramid in pixels.  P = zdr_gather_plan_rows(params): P0 for the
+ * bilinear filter, P0 + zdr_image_pyramid_bytes / 16 for mip and aniso (so an image without a level >= 1 has one row that stays empty).
+ * Entries.  An entry is (texel: uint32, weight: float32), 8 bytes.  Every texel, in texel index order, enumerates exactly the taps its
+ * scatter kernel touches, in this order, with the weight that kernel multiplies d_color by, operation for operation:
+ *   filter 0, bilinear (zdr_texel_gather_backward)        taps 00, 01, 10, 11;  (w visible)
+ *   filter 1, mip (zdr_texel_gather_mip_backward)         the four lower taps, ((w (1 - f)) visible); then, only where f != 0, the four
+ *                                                         upper taps, ((w f) visible)
+ *   filter 2, aniso (zdr_texel_gather_aniso_backward)     probe i = 0 .. N - 1 ascending, within a probe the lower taps, (((w (1 - f)) (1 / N))
+ *                                                         visible), then where f != 0 the upper ones, (((w f) (1 / N)) visible)
+ * w = (1 - tx)(1 - ty), tx (1 - ty), (1 - tx) ty, tx ty.  A texel whose visible is 0 or NaN has no entry; entries of weight 0 are kept;
+ * taps that clamp onto the same pixel stay separate entries.  The ENTRY ID is the position in this enumeration; nnz is their number.
+ * weight d_color[texel][c] is, bit for bit, the addend of the atomic adjoint.
+ * Layout, CSR by row: row_start, P + 1 uint32 (row r holds the entries row_start[r] .. row_start[r + 1] - 1; row_start[P] = nnz);
+ * entries, nnz x 8 bytes; within a row the entries are in ascending entry id.
+ * Apply, zdr_gather_plan_apply, per channel c of a row with the entries e_0 .. e_{R-1}, in float32, nothing contracted:
+ *   sixteen sub-sums: s_j = 0, then for k = j, j + 16, j + 32 .. in ascending order s_j = s_j + weight_k d_color[texel_k][c]
+ *   the tree: s_j = s_j + s_{j+8} (j < 8); s_j = s_j + s_{j+4} (j < 4); s_j = s_j + s_{j+2} (j < 2); s_0 = s_0 + s_1
+ *   a row of level 0 with R > 0: d_image[row] = d_image[row] + s_0 — ADDED INTO, as the atomic adjoints add; with R = 0 it is NOT
+ *   TOUCHED, whatever bits it holds;  a row of the pyramid: d_pyramid[row - P0] = s_0 — WRITTEN, 0 for an empty row: the caller need
+ *   not zero d_pyramid, and nothing in it is read.
+ * The payload of a NaN is unspecified.  The full image gradient of mip and aniso is this call followed by zdr_image_pyramid_backward on
+ * d_pyramid, as for the atomic adjoints.  d_pyramid may be null for the bilinear filter.
+ *
+ * Building a plan, once per (view, image size, filter and its parameters):
+ *   1. zdr_gather_plan_count with a workspace of zdr_gather_plan_workspace_bytes(params, 0) bytes leaves nnz, a uint64, at the start of
+ *      the workspace;
+ *   2. the caller reads it — the ONE SYNCHRONISATION of a build, and the caller's: none of these calls synchronises or allocates;
+ *   3. zdr_gather_plan_build with that nnz, a workspace of zdr_gather_plan_workspace_bytes(params, nnz) bytes (about 16 nnz plus what
+ *      the sort asks for; the count's workspace may be this one or another), row_start (4 (P + 1) bytes) and entries (8 nnz bytes;
+ *      non-null also when nnz is 0).  It counts again, writes the entries in entry-id order, sorts them STABLY by row and derives
+ *      row_start.  nnz is meant to be the count's.  One below it drops the entries beyond it — the plan is then not the transpose; one
+ *      above it still gives the right plan: the places no entry fills sort behind every row, row_start[P] is the true count and no
+ *      row reaches the tail of `entries`, whose contents are unspecified.
+ * The workspace's size needs a device to be present (the sort is asked for its own).  The same bits from build to build.
+ * zdr_gather_plan_apply only enqueues (two launches) and can be captured in a HIP graph without a call before.  footprint, levels and
+ * max_aniso are read as the filter's own call reads them (bilinear: none of them; mip: not max_aniso); `footprint_data` — the
+ * footprint buffer — is read, and must be non-null, for aniso only.
+ * All pointers are DEVICE pointers, 16-byte aligned.
+ * ZDR_E_INVALID: a wrong struct_size, a size <= 0, levels < 0, a filter outside 0 .. 2, a footprint that is not finite or not > 0 (mip,
+ * aniso), max_aniso outside 1 .. 16 (aniso), a null or misaligned pointer, an output or workspace that overlaps an input or another
+ * output.  ZDR_E_UNSUPPORTED: more than 2^26 texels or 2^28 pixels, nnz above 2^31 - 1; a library linked without these kernels. */
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_gather_plan_params) */
+    int32_t tex_h, tex_w;
+    int32_t width, height;             /* of the image */
+    int32_t filter;                    /* 0 bilinear, 1 mip, 2 aniso */
+    int32_t levels;                    /* as zdr_image_pyramid_params.levels */
+    float footprint;
+    int32_t max_aniso;
+} zdr_gather_plan_params;
+size_t zdr_gather_plan_rows(const zdr_gather_plan_params *params);                          /* P; 0 = invalid */
+size_t zdr_gather_plan_workspace_bytes(const zdr_gather_plan_params *params, uint64_t nnz);  /* 0 = invalid, or no device */
+int zdr_gather_plan_count(const zdr_gather_plan_params *params, const float *view, const float *footprint_data, void *workspace, void *stream);
+int zdr_gather_plan_build(const zdr_gather_plan_params *params, const float *view, const float *footprint_data, uint64_t nnz, void *workspace,
+                          uint32_t *row_start, void *entries, void *stream);
+int zdr_gather_plan_apply(const zdr_gather_plan_params *params, const uint32_t *row_start, const void *entries, const float *d_color,
+                          float *d_image, float *d_pyramid, void *stream);
+
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,
  * shadow rays (one per shaded vertex, prb.py:59), shaded vertices, emitter hits via BSDF sampling, NaN-dropped samples,

@@ -15,6 +15,7 @@ PUSHPULL_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_pushpull.so")   # push-pu
 PROJECT_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_project.so")     # texture-space views: likewise
 MIP_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_mip.so")             # the image pyramid and the mip gather: likewise
 ANISO_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_aniso.so")         # the footprint ellipse and the anisotropic gather: likewise
+PLAN_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_plan.so")           # the gather plan: likewise
 TEXEL_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_texel.so")   # the texture-space kernels: a dependency of libzdr_hip.so, found beside it
 
 COLLOCATED, DIRECT, PATH, UVGRAD = 0, 1, 2, 3
@@ -45,7 +46,8 @@ EXPORTS = ("zdr_version", "zdr_abi_version", "zdr_last_error", "zdr_scene_create
            "zdr_push_pull_workspace_bytes", "zdr_push_pull", "zdr_push_pull_backward",
            "zdr_texel_view_workspace_bytes", "zdr_scene_texel_view", "zdr_texel_gather", "zdr_texel_gather_backward",
            "zdr_image_pyramid_bytes", "zdr_image_pyramid", "zdr_image_pyramid_backward", "zdr_texel_gather_mip", "zdr_texel_gather_mip_backward",
-           "zdr_texel_footprint", "zdr_texel_gather_aniso", "zdr_texel_gather_aniso_backward")
+           "zdr_texel_footprint", "zdr_texel_gather_aniso", "zdr_texel_gather_aniso_backward",
+           "zdr_gather_plan_rows", "zdr_gather_plan_workspace_bytes", "zdr_gather_plan_count", "zdr_gather_plan_build", "zdr_gather_plan_apply")
 
 
 class CameraPOD(C.Structure):
@@ -106,6 +108,11 @@ class TexelGatherAnisoParams(C.Structure):
                 ("levels", C.c_int32), ("footprint", C.c_float), ("max_aniso", C.c_int32)]
 
 
+class GatherPlanParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("tex_h", C.c_int32), ("tex_w", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("filter", C.c_int32), ("levels", C.c_int32), ("footprint", C.c_float), ("max_aniso", C.c_int32)]
+
+
 class SceneInfo(C.Structure):
     _fields_ = [("ntris", C.c_uint32), ("nverts", C.c_uint32), ("ninst", C.c_uint32), ("light_count", C.c_uint32),
                 ("accel", C.c_int32), ("bvh_nodes", C.c_uint32), ("bvh_max_depth", C.c_uint32), ("bvh_stack_entries", C.c_uint32), ("device", C.c_int32),
@@ -127,7 +134,7 @@ def lib():
     from . import build as _build
     if _build.stale():
         _build.build()
-    for path in (LIB_PATH, TEXEL_LIB_PATH, BAKE_LIB_PATH, PUSHPULL_LIB_PATH, PROJECT_LIB_PATH, MIP_LIB_PATH, ANISO_LIB_PATH):
+    for path in (LIB_PATH, TEXEL_LIB_PATH, BAKE_LIB_PATH, PUSHPULL_LIB_PATH, PROJECT_LIB_PATH, MIP_LIB_PATH, ANISO_LIB_PATH, PLAN_LIB_PATH):
         if not os.path.exists(path):
             raise ZdrError(f"{path} is missing: the zdr HIP back end was not built (python -m zdr_amd.build)")
     L = C.CDLL(LIB_PATH)
@@ -183,6 +190,13 @@ def lib():
     L.zdr_texel_footprint.argtypes = [C.POINTER(TexelFootprintParams), fp, fp, vp]
     L.zdr_texel_gather_aniso.argtypes = [C.POINTER(TexelGatherAnisoParams), fp, fp, fp, fp, fp, vp]
     L.zdr_texel_gather_aniso_backward.argtypes = [C.POINTER(TexelGatherAnisoParams), fp, fp, fp, fp, fp, vp]
+    L.zdr_gather_plan_rows.argtypes = [C.POINTER(GatherPlanParams)]
+    L.zdr_gather_plan_rows.restype = C.c_size_t
+    L.zdr_gather_plan_workspace_bytes.argtypes = [C.POINTER(GatherPlanParams), C.c_uint64]
+    L.zdr_gather_plan_workspace_bytes.restype = C.c_size_t
+    L.zdr_gather_plan_count.argtypes = [C.POINTER(GatherPlanParams), fp, fp, vp, vp]
+    L.zdr_gather_plan_build.argtypes = [C.POINTER(GatherPlanParams), fp, fp, C.c_uint64, vp, vp, vp, vp]
+    L.zdr_gather_plan_apply.argtypes = [C.POINTER(GatherPlanParams), vp, vp, fp, fp, fp, vp]
     L.zdr_render_stats.argtypes = [vp, C.POINTER(RenderParams), fp, C.POINTER(C.c_uint64), vp]
     L.zdr_scene_check.argtypes = [vp, vp]
     L.zdr_trace_closest.argtypes = [vp, fp, C.c_uint32, ip, fp, vp]

@@ -28,6 +28,8 @@ PROJECT_LIB = os.path.join(CSRC, "libzdr_project.so")
 MIP_LIB = os.path.join(CSRC, "libzdr_mip.so")
 # The footprint ellipse, the anisotropic gather and its adjoint (zdr_aniso.hip): a seventh library, for the same reason.
 ANISO_LIB = os.path.join(CSRC, "libzdr_aniso.so")
+# The gather plan — the adjoints of the three gathers as CSR rows, built once and applied without atomics (zdr_plan.hip): an eighth library.
+PLAN_LIB = os.path.join(CSRC, "libzdr_plan.so")
 ARCH = "gfx950"
 
 
@@ -57,7 +59,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB)):
+    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB)):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -104,6 +106,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # the footprint ellipse and the anisotropic gather, linked into libzdr_aniso.so, under the flags of zdr_mip.hip: a probe is the
         # mip gather's trilinear sample operation for operation, and one probe must give that gather's bits
         ("zdr_aniso.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off", "-munsafe-fp-atomics"]),
+        # the gather plan, linked into libzdr_plan.so, under the flags of zdr_mip.hip without the atomics option (it has no float atomic):
+        # a weight is the scatter kernels' own product, and the sums follow the operation order of include/zdr.h
+        ("zdr_plan.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -117,7 +122,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    aniso_obj = objs.pop()                                  # (zdr_aniso.o: the last job)
+    plan_obj = objs.pop()                                   # (zdr_plan.o: the last job)
+    aniso_obj = objs.pop()                                  # (zdr_aniso.o: the one before)
     mip_obj = objs.pop()                                    # (zdr_mip.o: the one before)
     project_obj = objs.pop()                                # (zdr_project.o: the one before)
     pushpull_obj = objs.pop()                               # (zdr_pushpull.o: the one before)
@@ -129,8 +135,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PROJECT_LIB, project_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", MIP_LIB, mip_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", ANISO_LIB, aniso_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PLAN_LIB, plan_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake", "-lzdr_pushpull",
-              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso",
+              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan",
               "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -27,6 +27,8 @@
 #include "mip.h"
 #define ZDR_ANISO_LAUNCHER_REF __attribute__((weak))     // (csrc/aniso.h)
 #include "aniso.h"
+#define ZDR_PLAN_LAUNCHER_REF __attribute__((weak))      // (csrc/plan.h)
+#include "plan.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1964,6 +1966,137 @@ extern "C" int zdr_texel_gather_aniso_backward(const zdr_texel_gather_aniso_para
     G.out = (float4 *)d_image; G.d_pyramid = (float4 *)d_pyramid;
     G.ntexels = (uint32_t)n; G.width = p->width; G.height = p->height; G.L = P.L; G.max_aniso = p->max_aniso; G.footprint = p->footprint;
     if (zdr_launch_texel_gather_aniso(G, 1, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
+    return ZDR_OK;
+}
+
+// ------------------------------------------------------------------- gather plan
+// zdr_gather_plan_* (include/zdr.h): no scene handle, no allocation — argument checks, then the launches of zdr_plan.hip on the caller's
+// stream.  None of them synchronises: the ONE synchronisation of a plan's build is the caller's, between zdr_gather_plan_count and the
+// read of nnz from the workspace's header.
+static int plan_check(const char *name, const zdr_gather_plan_params *p) {
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (int rc = mip_check_image(name, p->struct_size, sizeof(zdr_gather_plan_params), p->width, p->height, p->levels)) return rc;
+    if (p->tex_h <= 0 || p->tex_w <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the texture size must be positive");
+    if (p->filter < ZDR_PLAN_BILINEAR || p->filter > ZDR_PLAN_ANISO)
+        return fail(ZDR_E_INVALID, std::string(name) + ": filter is " + std::to_string(p->filter) + ": 0 (bilinear), 1 (mip) or 2 (aniso)");
+    if (p->filter != ZDR_PLAN_BILINEAR && !(p->footprint > 0.0f && p->footprint <= 3.402823466e38f))    // (false for a NaN)
+        return fail(ZDR_E_INVALID, std::string(name) + ": footprint must be finite and > 0");
+    if (p->filter == ZDR_PLAN_ANISO && (p->max_aniso < 1 || p->max_aniso > ZDR_ANISO_MAX_PROBES))
+        return fail(ZDR_E_INVALID, std::string(name) + ": max_aniso is " + std::to_string(p->max_aniso) + ": it must lie in 1 .. " + std::to_string(ZDR_ANISO_MAX_PROBES));
+    if ((uint64_t)p->tex_h * (uint64_t)p->tex_w > ZDR_PLAN_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
+    return ZDR_OK;
+}
+
+// the rows of a plan: the pixels of level 0, then — mip and aniso — the packed levels >= 1 (one pixel where there is none, as the
+// pyramid's buffer has it)
+static uint32_t plan_rows(const zdr_gather_plan_params *p) {
+    const size_t p0 = (size_t)p->width * (size_t)p->height;
+    return (uint32_t)(p->filter == ZDR_PLAN_BILINEAR ? p0 : p0 + zdr_mip_plan(p->width, p->height, p->levels).bytes / sizeof(float4));
+}
+
+static size_t plan_round(size_t n) { return (n + 255) & ~(size_t)255; }
+
+static bool plan_workspace(const zdr_gather_plan_params *p, uint64_t nnz, void *base, PlanWorkspace &W) {
+    const size_t nblocks = ((size_t)p->tex_h * (size_t)p->tex_w + ZDR_PLAN_BLOCK - 1) / ZDR_PLAN_BLOCK;
+    int ok = 1;
+    W.sort_temp_bytes = zdr_plan_sort_temp_bytes(nnz, plan_rows(p), &ok);
+    if (!ok) return false;
+    char *at = (char *)base;
+    W.nnz = (uint64_t *)at; at += ZDR_PLAN_HEADER_BYTES;
+    W.block_off = (uint32_t *)at; at += plan_round(nblocks * sizeof(uint32_t));
+    W.keys = (uint32_t *)at; at += plan_round((size_t)nnz * sizeof(uint32_t));
+    W.keys_sorted = (uint32_t *)at; at += plan_round((size_t)nnz * sizeof(uint32_t));
+    W.vals = (uint64_t *)at; at += plan_round((size_t)nnz * sizeof(uint64_t));
+    W.sort_temp = (void *)at; at += plan_round(W.sort_temp_bytes);
+    W.bytes = (size_t)(at - (char *)base);
+    return true;
+}
+
+static PlanEnumArgs plan_enum_args(const zdr_gather_plan_params *p, const float *view, const float *footprint) {
+    PlanEnumArgs E;
+    E.view = (const float4 *)view; E.foot = (const float4 *)footprint;
+    E.ntexels = (uint32_t)((size_t)p->tex_h * (size_t)p->tex_w); E.nblocks = (E.ntexels + ZDR_PLAN_BLOCK - 1u) / ZDR_PLAN_BLOCK;
+    E.filter = p->filter; E.width = p->width; E.height = p->height;
+    E.L = p->filter == ZDR_PLAN_BILINEAR ? 0 : zdr_mip_plan(p->width, p->height, p->levels).L;
+    E.max_aniso = p->filter == ZDR_PLAN_ANISO ? p->max_aniso : 1;
+    E.footprint = p->filter == ZDR_PLAN_BILINEAR ? 1.0f : p->footprint;
+    E.p0 = (uint32_t)((size_t)p->width * (size_t)p->height);
+    return E;
+}
+
+extern "C" size_t zdr_gather_plan_rows(const zdr_gather_plan_params *p) {
+    if (plan_check("zdr_gather_plan_params", p)) return 0;
+    return plan_rows(p);
+}
+
+extern "C" size_t zdr_gather_plan_workspace_bytes(const zdr_gather_plan_params *p, uint64_t nnz) {
+    if (plan_check("zdr_gather_plan_params", p)) return 0;
+    if (nnz > ZDR_PLAN_MAX_NNZ) { fail(ZDR_E_UNSUPPORTED, "zdr_gather_plan_workspace_bytes: more than 2^31 - 1 entries"); return 0; }
+    if (!zdr_plan_sort_temp_bytes) { fail(ZDR_E_UNSUPPORTED, "this library was linked without the gather-plan kernels (zdr_plan.hip)"); return 0; }
+    PlanWorkspace W;
+    if (!plan_workspace(p, nnz, nullptr, W)) { fail(ZDR_E_HIP, "zdr_gather_plan_workspace_bytes: the sort's size query failed (no device?)"); return 0; }
+    return W.bytes;
+}
+
+static int plan_check_inputs(const char *name, const zdr_gather_plan_params *p, const float *view, const float *footprint, const void *workspace) {
+    if (int rc = plan_check(name, p)) return rc;
+    if (int rc = mip_check_pointers(name, {(const void *)view, workspace})) return rc;
+    if (p->filter == ZDR_PLAN_ANISO)
+        if (int rc = mip_check_pointers(name, {(const void *)footprint})) return rc;
+    if (!zdr_launch_plan_build)                                      // (weak: csrc/plan.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the gather-plan kernels (zdr_plan.hip)");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_gather_plan_count(const zdr_gather_plan_params *p, const float *view, const float *footprint, void *workspace, void *stream) {
+    const char *name = "zdr_gather_plan_count";
+    if (int rc = plan_check_inputs(name, p, view, footprint, workspace)) return rc;
+    PlanWorkspace W;
+    if (!plan_workspace(p, 0, workspace, W)) return fail(ZDR_E_HIP, std::string(name) + ": the sort's size query failed");
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w;
+    if (denoise_overlap(workspace, W.bytes, {{view, 32 * n}, {footprint, p->filter == ZDR_PLAN_ANISO ? 16 * n : 0}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": the workspace must not alias or overlap an input");
+    if (zdr_launch_plan_count(plan_enum_args(p, view, footprint), W, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": a launch failed");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_gather_plan_build(const zdr_gather_plan_params *p, const float *view, const float *footprint, uint64_t nnz, void *workspace, uint32_t *row_start,
+                                     void *entries, void *stream) {
+    const char *name = "zdr_gather_plan_build";
+    if (int rc = plan_check_inputs(name, p, view, footprint, workspace)) return rc;
+    if (int rc = mip_check_pointers(name, {(const void *)row_start, (const void *)entries})) return rc;
+    if (nnz > ZDR_PLAN_MAX_NNZ) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^31 - 1 entries");
+    PlanWorkspace W;
+    if (!plan_workspace(p, nnz, workspace, W)) return fail(ZDR_E_HIP, std::string(name) + ": the sort's size query failed");
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, rows = plan_rows(p);
+    const size_t fbytes = p->filter == ZDR_PLAN_ANISO ? 16 * n : 0;
+    if (denoise_overlap(workspace, W.bytes, {{view, 32 * n}, {footprint, fbytes}, {row_start, 4 * (rows + 1)}, {entries, 8 * (size_t)nnz}}) ||
+        denoise_overlap(row_start, 4 * (rows + 1), {{view, 32 * n}, {footprint, fbytes}, {entries, 8 * (size_t)nnz}}) ||
+        denoise_overlap(entries, 8 * (size_t)nnz, {{view, 32 * n}, {footprint, fbytes}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": the workspace and the outputs must not alias or overlap an input or one another");
+    if (zdr_launch_plan_build(plan_enum_args(p, view, footprint), W, (uint32_t)nnz, (uint32_t)rows, row_start, (uint64_t *)entries, (hipStream_t)stream))
+        return fail(ZDR_E_HIP, std::string(name) + ": a launch failed");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_gather_plan_apply(const zdr_gather_plan_params *p, const uint32_t *row_start, const void *entries, const float *d_color, float *d_image,
+                                     float *d_pyramid, void *stream) {
+    const char *name = "zdr_gather_plan_apply";
+    if (int rc = plan_check(name, p)) return rc;
+    if (int rc = mip_check_pointers(name, {(const void *)row_start, entries, (const void *)d_color, (const void *)d_image})) return rc;
+    if (p->filter != ZDR_PLAN_BILINEAR)
+        if (int rc = mip_check_pointers(name, {(const void *)d_pyramid})) return rc;
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height, rows = plan_rows(p);
+    const size_t pbytes = p->filter == ZDR_PLAN_BILINEAR ? 0 : 16 * (rows - npix);
+    if (denoise_overlap(d_image, 16 * npix, {{row_start, 4 * (rows + 1)}, {d_color, 16 * n}, {d_pyramid, pbytes}}) ||
+        denoise_overlap(d_pyramid, pbytes, {{row_start, 4 * (rows + 1)}, {d_color, 16 * n}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": an output must not alias or overlap an input or the other output");
+    if (!zdr_launch_plan_apply)                                      // (weak: csrc/plan.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the gather-plan kernels (zdr_plan.hip)");
+    PlanApplyArgs A;
+    A.row_start = row_start; A.entries = (const uint2 *)entries; A.d_color = d_color; A.d_image = d_image; A.d_pyramid = d_pyramid;
+    A.p0 = (uint32_t)npix; A.rows = (uint32_t)rows;
+    if (zdr_launch_plan_apply(A, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": a launch failed");
     return ZDR_OK;
 }
 

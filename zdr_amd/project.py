@@ -308,7 +308,7 @@ class TexelGatherAnisoOperator(torch.autograd.Function):
 FILTERS = ("bilinear", "mip", "aniso")
 
 
-def texel_gather(image, view, *, filter="bilinear", footprint=1.0, max_aniso=8):
+def texel_gather(image, view, *, filter="bilinear", footprint=1.0, max_aniso=8, plan=None):
     """The image gathered into texture space: (H, W, 4), 0 on the texels the camera does not see.  Differentiable in ``image`` only.
 
     ``filter="bilinear"`` (the default): four taps of the image at the texel's pixel position; ``image.grad`` is the scatter of the
@@ -322,12 +322,27 @@ def texel_gather(image, view, *, filter="bilinear", footprint=1.0, max_aniso=8):
     ``filter="aniso"``: the anisotropic gather (README, "Anisotropic gather").  ``view`` must be a ``TexelView`` made with
     ``footprint=True``: the level comes from the MINOR axis of each texel's on-screen ellipse, and up to ``max_aniso`` (1 .. 16)
     trilinear probes are spread along the major axis and averaged.  ``footprint`` scales both axes.  Where the major axis times
-    ``footprint`` is at most 1 the result is the bilinear one bit for bit.  ``image.grad`` as for "mip"."""
+    ``footprint`` is at most 1 the result is the bilinear one bit for bit.  ``image.grad`` as for "mip".
+    ``plan``: None (the default) scatters ``image.grad`` with float atomics, whose order of addition varies from run to run.  True, or
+    a ``GatherPlan`` made for this view, image size and filter (``view.gather_plan``; any other raises ``ValueError``), leaves the
+    forward as it is, bit for bit, and computes ``image.grad`` through the plan (README, "Gather plan"; zdr_amd/plan.py): no atomic,
+    the same bits from run to run.  True builds the plan on first use — one synchronisation — and keeps it on the ``TexelView``."""
     if filter not in FILTERS:
         raise ValueError(f"filter must be one of {FILTERS}, not {filter!r}")
     footprint_data = getattr(view, "footprint_data", None)
+    view_object = view
     view = _view_data(view)
     _check_image(image, "image", view.device)
+    if plan is not None:
+        from . import plan as GP
+        if filter == "aniso":
+            if footprint_data is None:
+                raise ValueError('filter="aniso" needs a view that carries a footprint buffer: scene.texel_view(..., footprint=True)')
+            footprint_data = _footprint_data(footprint_data, view)
+        key = GP.plan_key((int(image.shape[1]), int(image.shape[0])), filter, footprint, max_aniso, 0)
+        GP._params(view, key)                                        # (raises on a bad footprint or max_aniso)
+        plan = GP.resolve_plan(plan, view_object, view, key)
+        return GP.TexelGatherPlanOperator.apply(image, plan, view, footprint_data if filter == "aniso" else None)
     if filter == "aniso":
         if footprint_data is None:
             raise ValueError('filter="aniso" needs a view that carries a footprint buffer: scene.texel_view(..., footprint=True)')
