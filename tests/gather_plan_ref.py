@@ -37,7 +37,7 @@ def level_split32(s, L, log2=numpy_log2):
 
 
 def taps32(X, Y, w, h):
-    """proj_taps in float32: ((i00, i01, i10, i11) int64, tx, ty); a NaN or an infinity ends inside the level, as in the kernels"""
+    """tf_taps (csrc/texel_filter.h) in float32: ((i00, i01, i10, i11) int64, tx, ty); a NaN or an infinity ends inside the level, as in the kernels"""
     with np.errstate(invalid="ignore", over="ignore"):
         fx, fy = (X - F(0.5)).astype(F), (Y - F(0.5)).astype(F)
         x0f, y0f = np.floor(fx), np.floor(fy)

@@ -1,6 +1,7 @@
 """-m gpu: the gather plan (zdr_amd/plan.py; include/zdr.h, zdr_gather_plan_*) against the NumPy reference of tests/gather_plan_ref.py,
 for the three filters: the CSR structure and the weights bit for bit, the apply bit for bit against the float32 reference in the
-header's summation order, run-to-run equality, accuracy against float64 within the existing bars, the transpose, the buffer rules
+header's summation order, the atomic adjoints' own products bit for bit on the rows of one or two entries, run-to-run equality,
+accuracy against float64 within the existing bars, the transpose, the buffer rules
 (added into, untouched, written), autograd through ``plan=``, and the argument checks.
 
 Views: the kernels' own view and footprint buffers of cbox_16x16 and cbox_64x64 through the standard camera, for images of 96 x 64
@@ -214,6 +215,41 @@ def test_structure_and_apply_on_views_made_by_hand(kind, filter):
     if kind.startswith("rows_"):
         n = int(kind.split("_")[1])
         assert plan.nnz == 4 * n and int((counts == n).sum()) == 4 and int((counts == 0).sum()) == plan.rows - 4
+
+
+@pytest.mark.parametrize("filter", list(FILTERS))
+@pytest.mark.parametrize("kind", ["single", "half", "random"])
+def test_the_atomic_adjoints_add_the_plans_own_products(kind, filter):
+    """The tie between the two families: on a row of one or two entries the atomic adjoint, run onto zeros, leaves fl(w0 g0) or
+    fl(fl(w0 g0) + fl(w1 g1)) with the plan's weights — two addends onto a zero commute, so the order of the atomics cannot show — and
+    that is compared bit for bit, all four channels.  Rows of three or more entries are left out; an empty row holds +0.  Every
+    (kind, filter) pair must compare at least 60 % of its non-empty rows and at least two of them: asserted before the comparison."""
+    res, kw = (96, 64), FILTERS[filter]
+    view, fp = hand_view(kind, res)
+    ref = GR.plan_ref(view, fp, res, filter, log2=device_log2, **kw)
+    p0, rows, counts = ref["p0"], ref["rows"], GR.counts(ref)
+    g = np.random.default_rng(5).standard_normal(view.shape[:2] + (4,)).astype(F)
+    gt, vt, ft = torch.from_numpy(g).cuda(), torch.from_numpy(view).cuda(), torch.from_numpy(fp).cuda()
+    d_image = torch.zeros(res[1], res[0], 4, device="cuda")
+    d_pyr = torch.zeros(max(rows - p0, 1), 4, device="cuda")
+    if filter == "bilinear":
+        texel_gather_backward(gt, vt, res, d_image=d_image)
+    elif filter == "mip":
+        texel_gather_mip_backward(gt, vt, res, kw["footprint"], d_image=d_image, d_pyramid=d_pyr)
+    else:
+        texel_gather_aniso_backward(gt, vt, ft, res, kw["footprint"], kw["max_aniso"], d_image=d_image, d_pyramid=d_pyr)
+    got = np.concatenate([d_image.cpu().numpy().reshape(-1, 4), d_pyr.cpu().numpy()])[:rows]
+    nonempty, short = int((counts > 0).sum()), np.nonzero((counts == 1) | (counts == 2))[0]
+    print(f"[gather plan] atomic adjoint against the plan's products, {kind} {filter}: {short.size} rows compared of {nonempty} non-empty ones")
+    assert short.size >= 2 and short.size >= 0.6 * nonempty
+    with np.errstate(invalid="ignore", over="ignore"):
+        prod = (ref["weight"][:, None] * g.reshape(-1, 4)[ref["texel"]]).astype(F)
+        first, second = ref["row_start"][short], ref["row_start"][short] + 1
+        want = (np.zeros((short.size, 4), F) + prod[first]).astype(F)
+        two = counts[short] == 2
+        want[two] = (want[two] + prod[second[two]]).astype(F)
+    assert same_bits(got[short], want), (kind, filter)
+    assert (bits(got[counts == 0]) == 0).all()
 
 
 @pytest.mark.parametrize("filter", list(FILTERS))

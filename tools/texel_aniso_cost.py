@@ -74,6 +74,7 @@ def part_gather(args):
                         "mip_forward": lambda: texel_gather_mip_forward(image, pyr, view, footprint, out=color),
                         "aniso_adjoint": aniso_adjoint, "mip_adjoint": mip_adjoint}, args)
         vis = view[..., 0] == 1
+        # the probe count of tf_probes (csrc/texel_filter.h), over the whole buffer
         A, B = (fp[..., 3] * footprint)[vis], (fp[..., 2] * footprint)[vis]
         Bp = torch.maximum(torch.maximum(B, A / max_aniso), torch.ones_like(B))
         N = torch.where(A > 1, torch.ceil(A / Bp - 0.125).clamp(1, max_aniso), torch.ones_like(A))

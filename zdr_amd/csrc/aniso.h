@@ -7,8 +7,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define ZDR_ANISO_MAX_TEXELS (1u << 26)   // texel indices x 64-byte rows of the texel buffer within 4 GiB (as ZDR_MIP_MAX_TEXELS)
-#define ZDR_ANISO_MAX_PIXELS (1u << 28)   // pixel indices x 16-byte rows of the image within 4 GiB (as ZDR_MIP_MAX_PIXELS)
 #define ZDR_ANISO_MAX_PROBES 16           // the largest max_aniso
 
 // Wave-uniform arguments of the footprint kernel.  The camera frame is the one zdr_scene_texel_view derives (zdr_api.cpp, camera_frame).

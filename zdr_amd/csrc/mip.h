@@ -7,9 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define ZDR_MIP_MAX_TEXELS (1u << 26)   // texel indices x 32-byte rows of the view buffer within 4 GiB (as ZDR_PROJECT_MAX_TEXELS)
-#define ZDR_MIP_MAX_PIXELS (1u << 28)   // pixel indices x 16-byte rows of the image within 4 GiB (as ZDR_PROJECT_MAX_PIXELS)
-#define ZDR_MIP_MAX_LEVELS 32           // 2^28 pixels in one row end after 28 halvings
+#define ZDR_MIP_MAX_LEVELS 32           // 2^28 pixels (ZDR_FILTER_MAX_PIXELS, texel_filter.h) in one row end after 28 halvings
 #define ZDR_MIP_TAIL_DIM 32             // a level of at most 32 x 32 and everything above it is one workgroup's work, in LDS
 #define ZDR_MIP_TAIL_TEXELS 1368        // 32^2 + 16^2 + ... + 1 = 1365, rounded up to a multiple of 8
 

@@ -6,15 +6,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "texel_filter.h"                 // the filters' numbers; ZDR_FILTER_MAX_TEXELS and ZDR_FILTER_MAX_PIXELS bound a plan: a row index fits 32 bits
 
-#define ZDR_PLAN_MAX_TEXELS (1u << 26)    // as ZDR_MIP_MAX_TEXELS
-#define ZDR_PLAN_MAX_PIXELS (1u << 28)    // as ZDR_MIP_MAX_PIXELS: level 0; the levels >= 1 add less than half of it, so a row index fits 32 bits
 #define ZDR_PLAN_MAX_NNZ 0x7fffffffull    // entry ids fit an int32
 #define ZDR_PLAN_BLOCK 256                // texels of one workgroup of the enumeration
 #define ZDR_PLAN_HEADER_BYTES 256         // the workspace begins with nnz as a uint64
 #define ZDR_PLAN_LONG_ROW 64              // a row of at least this many entries is summed by a whole wave
 
-enum { ZDR_PLAN_BILINEAR = 0, ZDR_PLAN_MIP = 1, ZDR_PLAN_ANISO = 2 };
+enum { ZDR_PLAN_BILINEAR = TF_BILINEAR, ZDR_PLAN_MIP = TF_MIP, ZDR_PLAN_ANISO = TF_ANISO };   // zdr_gather_plan_params.filter
 
 // Wave-uniform arguments of the enumeration (the count and the fill).
 struct PlanEnumArgs {

@@ -5,9 +5,7 @@
 #pragma once
 #include "internal.h"
 
-#define ZDR_PROJECT_MAX_TEXELS (1u << 26)   // texel indices x 64-byte rows of the input within 4 GiB (as ZDR_BAKE_MAX_TEXELS)
-#define ZDR_PROJECT_MAX_PIXELS (1u << 28)   // pixel indices x 16-byte rows of the image within 4 GiB
-#define ZDR_PROJECT_HEADER_BYTES 16         // the workspace begins with the list's counter, padded to 16 bytes; the list follows
+#define ZDR_PROJECT_HEADER_BYTES 16        // the workspace begins with the list's counter, padded to 16 bytes; the list follows
 
 // Wave-uniform arguments of the three launches of the view buffer.  The camera frame is the one make_render_cfg gives a render
 // (zdr_api.cpp, camera_frame).

@@ -11,13 +11,12 @@
 //                      a probe is two bilinear samples and an addition; nothing per probe is kept, so nothing goes to scratch.
 //   k_aniso_scatter    thread = (texel, channel), for the reason given above k_proj_scatter (zdr_project.hip): one float atomic per tap,
 //                      probe and channel (-munsafe-fp-atomics: global_atomic_add_f32, no compare-and-swap loop).
-// The level split, the places, the taps and the trilinear sample are those of zdr_mip.hip operation for operation, copied (an_*) as
-// zdr_mip.hip copied proj_taps: the translation units share no object file.  With one probe (N = 1) the gather IS the mip gather of
-// s = B', and where major x footprint <= 1 the bilinear gather, bit for bit.
+// The probes, the level split, the places, the taps, the trilinear sample and the adjoint's walk are texel_filter.h's, the very functions
+// zdr_mip.hip and zdr_project.hip call.  With one probe (N = 1) the gather IS the mip gather of s = B', and where major x footprint <= 1 the
+// bilinear gather, bit for bit.
 #include "scene.h"
 #include "aniso.h"
-
-ZD int32_t an_clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : v > hi ? hi : v; }
+#include "texel_filter.h"
 
 // --------------------------------------------------------------------------------------------------------------------- the footprint
 __global__ __launch_bounds__(256) void k_aniso_footprint(AnisoFootprintArgs A) {
@@ -56,102 +55,24 @@ __global__ __launch_bounds__(256) void k_aniso_footprint(AnisoFootprintArgs A) {
     A.out[t] = out;
 }
 
-// ------------------------------------------------------------------------------------------------------------- the level of a texel
-// (zdr_mip.hip, mip_level with its footprint factor at 1)  s = max(s, 1), NaN -> 1;  l0 = its binary exponent, f = log2 of its mantissa
-struct AnLevel { int l0; float f; };
-ZD AnLevel an_level(float s, int L) {
-    s = s * 1.0f;
-    s = s > 1.0f ? s : 1.0f;
-    const uint32_t b = __float_as_uint(s);
-    AnLevel r;
-    r.l0 = (int)(b >> 23) - 127;
-    r.f = 0.0f;
-    if (r.l0 >= L) { r.l0 = L; return r; }
-    const float m = __uint_as_float((b & 0x007fffffu) | 0x3f800000u);
-    if (m != 1.0f) r.f = fminf(log2f(m), 1.0f);
-    return r;
-}
-
-struct AnPlace { int w, h; size_t off; };
-ZD AnPlace an_place(int width, int height, int l) {
-    AnPlace p;
-    p.w = width; p.h = height; p.off = 0;
-    for (int k = 1; k <= l; k++) {
-        if (k > 1) p.off += (size_t)p.w * (size_t)p.h;
-        p.w = (p.w + 1) >> 1; p.h = (p.h + 1) >> 1;
-    }
-    return p;
-}
-ZD AnPlace an_above(AnPlace p, int l) {                              // level l + 1 from level l
-    if (l >= 1) p.off += (size_t)p.w * (size_t)p.h;
-    p.w = (p.w + 1) >> 1; p.h = (p.h + 1) >> 1;
-    return p;
-}
-
-// The taps of one probe in a level: the rule of proj_taps (zdr_project.hip) with that level's size.  Whatever X and Y hold — a NaN, an
-// infinity, a probe far outside the image — the indices lie inside the level.
-struct AnTaps { int32_t i00, i01, i10, i11; float tx, ty; };
-ZD AnTaps an_taps(float X, float Y, int32_t width, int32_t height) {
-    const float fx = X - 0.5f, fy = Y - 0.5f;
-    const float x0f = floorf(fx), y0f = floorf(fy);
-    AnTaps T;
-    T.tx = fx - x0f; T.ty = fy - y0f;
-    const int32_t x0 = (int32_t)fminf(fmaxf(x0f, -1.0f), (float)width), y0 = (int32_t)fminf(fmaxf(y0f, -1.0f), (float)height);
-    const int32_t xa = an_clampi(x0, 0, width - 1), xb = an_clampi(x0 + 1, 0, width - 1);
-    const int32_t ya = an_clampi(y0, 0, height - 1), yb = an_clampi(y0 + 1, 0, height - 1);
-    T.i00 = ya * width + xa; T.i01 = ya * width + xb; T.i10 = yb * width + xa; T.i11 = yb * width + xb;
-    return T;
-}
-
-ZD float4 an_lerp(float4 a, float4 b, float t) {
-    return make_float4(a.x + (b.x - a.x) * t, a.y + (b.y - a.y) * t, a.z + (b.z - a.z) * t, a.w + (b.w - a.w) * t);
-}
-
-ZD float an_exp2_neg(int l) { return __uint_as_float((uint32_t)(127 - l) << 23); }   // 2^-l, l <= 31
-
-ZD float4 an_sample(const float4 *lvl, float X, float Y, int l, AnPlace p) {
-    const float inv = an_exp2_neg(l);
-    const AnTaps T = an_taps(X * inv, Y * inv, p.w, p.h);
-    const float4 top = an_lerp(lvl[T.i00], lvl[T.i01], T.tx), bot = an_lerp(lvl[T.i10], lvl[T.i11], T.tx);
-    return an_lerp(top, bot, T.ty);
-}
-
-// ------------------------------------------------------------------------------------------------------------- the probes of a texel
-// A = major footprint, B = minor footprint.  Not A > 1 (a NaN too): one probe at level 0.  Else B' = max(B, A / max_aniso, 1) (a NaN B is
-// passed over), N = clamp(ceil(A / B' - 0.125), 1, max_aniso) (a NaN gives 1), s = B'.
-struct AnProbes { int N; float s; };
-ZD AnProbes an_probes(float minor, float major, float footprint, int max_aniso) {
-    const float A = major * footprint, B = minor * footprint;
-    AnProbes r;
-    r.N = 1; r.s = 1.0f;
-    if (A > 1.0f) {
-        const float Bp = fmaxf(fmaxf(B, __fdiv_rn(A, (float)max_aniso)), 1.0f);
-        const float q = ceilf(__fdiv_rn(A, Bp) - 0.125f);
-        r.N = q >= 1.0f ? (q <= (float)max_aniso ? (int)q : max_aniso) : 1;
-        r.s = Bp;
-    }
-    return r;
-}
-
+// ------------------------------------------------------------------------------------------------------------------ the gather
 __global__ __launch_bounds__(256) void k_aniso_gather(AnisoGatherArgs G) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= G.ntexels) return;
     const float4 vw = G.view[2 * (size_t)t];                 // {visible, cosine, X, Y}
     float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (vw.x != 0.0f && vw.x == vw.x) {                      // an invisible texel reads nothing else: no footprint, no image, no pyramid
+    if (tf_on(vw.x)) {                                       // an invisible texel reads nothing else: no footprint, no image, no pyramid
         const float4 fp = G.foot[t];                         // {major axis x, y, minor, major}
-        const AnProbes pr = an_probes(fp.z, fp.w, G.footprint, G.max_aniso);
-        const AnLevel lv = an_level(pr.s, G.L);
-        const AnPlace lo = an_place(G.width, G.height, lv.l0);
-        const AnPlace hi = an_above(lo, lv.l0);              // (read only where f != 0: then l0 < L and the level exists)
-        const float4 *plo = lv.l0 ? G.pyramid + lo.off : G.in, *phi = G.pyramid + hi.off;
+        const tf_probes_t pr = tf_probes(fp.z, fp.w, G.footprint, G.max_aniso);
+        const tf_level_t lv = tf_level(pr.s, G.L);
+        const tf_place_t lo = tf_place(G.width, G.height, lv.l0);
+        const tf_place_t hi = tf_above(lo, lv.l0);
         const float fN = (float)pr.N, inv_n = __fdiv_rn(1.0f, fN), two_n = 2.0f * fN;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma nounroll                                             // (nor peeled for i == 0: one copy of the body, profiles/texel_filter_cost.txt)
         for (int i = 0; i < pr.N; i++) {
-            const float ti = __fdiv_rn((float)(2 * i + 1 - pr.N), two_n);
-            const float X = vw.z + (ti * G.footprint) * fp.x, Y = vw.w + (ti * G.footprint) * fp.y;
-            float4 r = an_sample(plo, X, Y, lv.l0, lo);
-            if (lv.f != 0.0f) r = an_lerp(r, an_sample(phi, X, Y, lv.l0 + 1, hi), lv.f);
+            const tf_xy_t q = tf_probe_xy(vw.z, vw.w, fp.x, fp.y, G.footprint, i, pr.N, two_n);
+            const float4 r = tf_trilinear(G.in, G.pyramid, q.X, q.Y, lv, lo, hi);
             acc = i == 0 ? r : make_float4(acc.x + r.x, acc.y + r.y, acc.z + r.z, acc.w + r.w);
         }
         c = make_float4(vw.x * (acc.x * inv_n), vw.x * (acc.y * inv_n), vw.x * (acc.z * inv_n), vw.x * (acc.w * inv_n));
@@ -159,36 +80,22 @@ __global__ __launch_bounds__(256) void k_aniso_gather(AnisoGatherArgs G) {
     G.out[t] = c;
 }
 
-ZD void an_scatter(float *d, float X, float Y, int l, AnPlace p, float share, float inv_n, float visible, float g) {
-    const float inv = an_exp2_neg(l);
-    const AnTaps T = an_taps(X * inv, Y * inv, p.w, p.h);
-    const float ux = 1.0f - T.tx, uy = 1.0f - T.ty;
-    atomicAdd(d + 4 * (size_t)T.i00, ((((ux * uy) * share) * inv_n) * visible) * g);
-    atomicAdd(d + 4 * (size_t)T.i01, ((((T.tx * uy) * share) * inv_n) * visible) * g);
-    atomicAdd(d + 4 * (size_t)T.i10, ((((ux * T.ty) * share) * inv_n) * visible) * g);
-    atomicAdd(d + 4 * (size_t)T.i11, ((((T.tx * T.ty) * share) * inv_n) * visible) * g);
-}
-
 __global__ __launch_bounds__(256) void k_aniso_scatter(AnisoGatherArgs G) {
     const uint32_t id = blockIdx.x * 256u + threadIdx.x, t = id >> 2, c = id & 3u;   // (id < 4 ntexels <= 2^28)
     if (t >= G.ntexels) return;
     const float4 vw = G.view[2 * (size_t)t];
-    if (!(vw.x != 0.0f && vw.x == vw.x)) return;
+    if (!tf_on(vw.x)) return;
     const float4 fp = G.foot[t];
-    const AnProbes pr = an_probes(fp.z, fp.w, G.footprint, G.max_aniso);
-    const AnLevel lv = an_level(pr.s, G.L);
-    const AnPlace lo = an_place(G.width, G.height, lv.l0);
-    const AnPlace hi = an_above(lo, lv.l0);
-    float *dlo = (lv.l0 ? (float *)(G.d_pyramid + lo.off) : (float *)G.out) + c, *dhi = (float *)(G.d_pyramid + hi.off) + c;
+    const tf_probes_t pr = tf_probes(fp.z, fp.w, G.footprint, G.max_aniso);
+    tf_texel_t x = tf_texel(vw.x, vw.z, vw.w);
+    x.ax = fp.x; x.ay = fp.y; x.N = pr.N;
+    x.lv = tf_level(pr.s, G.L);
     const float g = ((const float *)G.in)[id];
-    const float fN = (float)pr.N, inv_n = __fdiv_rn(1.0f, fN), two_n = 2.0f * fN, low = 1.0f - lv.f;
-    for (int i = 0; i < pr.N; i++) {
-        const float ti = __fdiv_rn((float)(2 * i + 1 - pr.N), two_n);
-        const float X = vw.z + (ti * G.footprint) * fp.x, Y = vw.w + (ti * G.footprint) * fp.y;
-        an_scatter(dlo, X, Y, lv.l0, lo, low, inv_n, vw.x, g);
-        if (lv.f != 0.0f) an_scatter(dhi, X, Y, lv.l0 + 1, hi, lv.f, inv_n, vw.x, g);
-    }
+    float *d_image = (float *)G.out + c, *d_pyramid = (float *)G.d_pyramid + c;
+    tf_enumerate(x, TF_ANISO, G.footprint, G.width, G.height,
+                 [&](bool pyramid, uint32_t pixel, float weight) { atomicAdd((pyramid ? d_pyramid : d_image) + 4 * (size_t)pixel, weight * g); });
 }
+
 
 // ------------------------------------------------------------------------------------------------------------------------ launchers
 int zdr_launch_texel_footprint(const AnisoFootprintArgs &A, hipStream_t st) {

@@ -1718,16 +1718,44 @@ extern "C" int zdr_push_pull_backward(const zdr_push_pull_params *p, const float
 // ------------------------------------------------------------------- texture-space views
 // zdr_scene_texel_view (include/zdr.h): argument checks, then the three launches of zdr_project.hip on the caller's stream.  The handle is
 // only read — the acceleration structure as it is — so nothing is allocated and the call can be captured without a call before.
-static int project_check_size(int32_t tex_h, int32_t tex_w) {
-    if (tex_h <= 0 || tex_w <= 0) return fail(ZDR_E_INVALID, "zdr_scene_texel_view: the texture size must be positive");
-    if ((uint64_t)tex_h * (uint64_t)tex_w > ZDR_PROJECT_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, "zdr_scene_texel_view: more than 2^26 texels");
+// The argument checks the texel-filter entry points share (views, gathers, pyramids, footprints, plans), one condition each; an entry
+// point calls them in the order in which its checks fire.
+static int filter_check_struct(const std::string &what, uint32_t struct_size, size_t expect) {      // what: "<struct>." or "<entry point>: "
+    if (struct_size != expect) return fail(ZDR_E_INVALID, what + "struct_size is " + std::to_string(struct_size) + ", this library expects " + std::to_string(expect));
     return ZDR_OK;
 }
 
-static int project_check_image(const char *name, int32_t width, int32_t height) {
-    if (width <= 0 || height <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the image size must be positive");
-    if ((uint64_t)width * (uint64_t)height > ZDR_PROJECT_MAX_PIXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^28 pixels");
+static int filter_check_positive(const char *name, const char *what, int32_t a, int32_t b) {         // what: "texture" or "image"
+    if (a <= 0 || b <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the " + what + " size must be positive");
     return ZDR_OK;
+}
+
+static int filter_check_texels(const char *name, int32_t tex_h, int32_t tex_w) {
+    if ((uint64_t)tex_h * (uint64_t)tex_w > ZDR_FILTER_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
+    return ZDR_OK;
+}
+
+static int filter_check_pixels(const char *name, int32_t width, int32_t height) {
+    if ((uint64_t)width * (uint64_t)height > ZDR_FILTER_MAX_PIXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^28 pixels");
+    return ZDR_OK;
+}
+
+static int filter_check_pointers(const char *name, std::initializer_list<const void *> ptrs) {
+    for (const void *q : ptrs) {
+        if (!q) return fail(ZDR_E_INVALID, "null argument");
+        if ((uintptr_t)q % 16) return fail(ZDR_E_INVALID, std::string(name) + ": every pointer must be 16-byte aligned");
+    }
+    return ZDR_OK;
+}
+
+static int project_check_size(int32_t tex_h, int32_t tex_w) {
+    if (int rc = filter_check_positive("zdr_scene_texel_view", "texture", tex_h, tex_w)) return rc;
+    return filter_check_texels("zdr_scene_texel_view", tex_h, tex_w);
+}
+
+static int project_check_image(const char *name, int32_t width, int32_t height) {
+    if (int rc = filter_check_positive(name, "image", width, height)) return rc;
+    return filter_check_pixels(name, width, height);
 }
 
 extern "C" size_t zdr_texel_view_workspace_bytes(int32_t tex_h, int32_t tex_w) {
@@ -1766,15 +1794,11 @@ extern "C" int zdr_scene_texel_view(zdr_scene *s, const zdr_texel_view_params *p
 // argument checks, then one launch of zdr_project.hip on the caller's stream.
 static int texel_gather_call(const char *name, const zdr_texel_gather_params *p, const float *view, const float *in, float *out, void *stream, int backward) {
     if (!p) return fail(ZDR_E_INVALID, "null argument");
-    if (p->struct_size != sizeof(zdr_texel_gather_params))
-        return fail(ZDR_E_INVALID, "zdr_texel_gather_params.struct_size is " + std::to_string(p->struct_size) + ", this library expects " + std::to_string(sizeof(zdr_texel_gather_params)));
-    if (p->tex_h <= 0 || p->tex_w <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the texture size must be positive");
-    if ((uint64_t)p->tex_h * (uint64_t)p->tex_w > ZDR_PROJECT_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
+    if (int rc = filter_check_struct("zdr_texel_gather_params.", p->struct_size, sizeof(zdr_texel_gather_params))) return rc;
+    if (int rc = filter_check_positive(name, "texture", p->tex_h, p->tex_w)) return rc;
+    if (int rc = filter_check_texels(name, p->tex_h, p->tex_w)) return rc;
     if (int rc = project_check_image(name, p->width, p->height)) return rc;
-    for (const void *q : {(const void *)view, (const void *)in, (const void *)out}) {
-        if (!q) return fail(ZDR_E_INVALID, "null argument");
-        if ((uintptr_t)q % 16) return fail(ZDR_E_INVALID, std::string(name) + ": every pointer must be 16-byte aligned");
-    }
+    if (int rc = filter_check_pointers(name, {(const void *)view, (const void *)in, (const void *)out})) return rc;
     const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
     if (denoise_overlap(out, 16 * (backward ? npix : n), {{view, 32 * n}, {in, 16 * (backward ? n : npix)}}))
         return fail(ZDR_E_INVALID, std::string(name) + ": the output must not alias or overlap an input");
@@ -1799,20 +1823,25 @@ extern "C" int zdr_texel_gather_backward(const zdr_texel_gather_params *p, const
 // zdr_image_pyramid, zdr_image_pyramid_backward, zdr_texel_gather_mip, zdr_texel_gather_mip_backward (include/zdr.h): no scene handle, no
 // allocation, no synchronisation — argument checks, then the launches of zdr_mip.hip on the caller's stream.
 static int mip_check_image(const char *name, uint32_t struct_size, size_t expect, int32_t width, int32_t height, int32_t levels) {
-    if (struct_size != expect)
-        return fail(ZDR_E_INVALID, std::string(name) + ": struct_size is " + std::to_string(struct_size) + ", this library expects " + std::to_string(expect));
-    if (width <= 0 || height <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the image size must be positive");
+    if (int rc = filter_check_struct(std::string(name) + ": ", struct_size, expect)) return rc;
+    if (int rc = filter_check_positive(name, "image", width, height)) return rc;
     if (levels < 0) return fail(ZDR_E_INVALID, std::string(name) + ": levels is " + std::to_string(levels) + ": 0 (down to 1 x 1) or a positive count");
-    if ((uint64_t)width * (uint64_t)height > ZDR_MIP_MAX_PIXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^28 pixels");
-    return ZDR_OK;
+    return filter_check_pixels(name, width, height);
 }
 
-static int mip_check_pointers(const char *name, std::initializer_list<const void *> ptrs) {
-    for (const void *q : ptrs) {
-        if (!q) return fail(ZDR_E_INVALID, "null argument");
-        if ((uintptr_t)q % 16) return fail(ZDR_E_INVALID, std::string(name) + ": every pointer must be 16-byte aligned");
-    }
-    return ZDR_OK;
+// What zdr_texel_gather_mip*, zdr_texel_gather_aniso* and zdr_gather_plan_* ask of their params: the image and its pyramid, the texture,
+// the filter (ZDR_PLAN_*; a plan's is the caller's) and what that filter reads of footprint and max_aniso.
+static int filter_check_gather(const char *name, uint32_t struct_size, size_t expect, int32_t tex_h, int32_t tex_w, int32_t width, int32_t height, int32_t levels,
+                               int32_t filter, float footprint, int32_t max_aniso) {
+    if (int rc = mip_check_image(name, struct_size, expect, width, height, levels)) return rc;
+    if (int rc = filter_check_positive(name, "texture", tex_h, tex_w)) return rc;
+    if (filter < ZDR_PLAN_BILINEAR || filter > ZDR_PLAN_ANISO)
+        return fail(ZDR_E_INVALID, std::string(name) + ": filter is " + std::to_string(filter) + ": 0 (bilinear), 1 (mip) or 2 (aniso)");
+    if (filter != ZDR_PLAN_BILINEAR && !(footprint > 0.0f && footprint <= 3.402823466e38f))    // (false for a NaN)
+        return fail(ZDR_E_INVALID, std::string(name) + ": footprint must be finite and > 0");
+    if (filter == ZDR_PLAN_ANISO && (max_aniso < 1 || max_aniso > ZDR_ANISO_MAX_PROBES))
+        return fail(ZDR_E_INVALID, std::string(name) + ": max_aniso is " + std::to_string(max_aniso) + ": it must lie in 1 .. " + std::to_string(ZDR_ANISO_MAX_PROBES));
+    return filter_check_texels(name, tex_h, tex_w);
 }
 
 extern "C" size_t zdr_image_pyramid_bytes(const zdr_image_pyramid_params *p) {
@@ -1825,7 +1854,7 @@ static int image_pyramid_call(const char *name, const zdr_image_pyramid_params *
     if (!p) return fail(ZDR_E_INVALID, "null argument");
     if (int rc = mip_check_image(name, p->struct_size, sizeof(zdr_image_pyramid_params), p->width, p->height, p->levels)) return rc;
     const void *level0 = backward ? (const void *)d_image : (const void *)image;
-    if (int rc = mip_check_pointers(name, {level0, (const void *)pyramid})) return rc;
+    if (int rc = filter_check_pointers(name, {level0, (const void *)pyramid})) return rc;
     const size_t npix = (size_t)p->width * (size_t)p->height, pbytes = zdr_mip_plan(p->width, p->height, p->levels).bytes;
     if (denoise_overlap(pyramid, pbytes, {{level0, 16 * npix}}))
         return fail(ZDR_E_INVALID, std::string(name) + ": the pyramid must not alias or overlap the image");
@@ -1848,18 +1877,13 @@ extern "C" int zdr_image_pyramid_backward(const zdr_image_pyramid_params *p, flo
 
 static int texel_gather_mip_check(const char *name, const zdr_texel_gather_mip_params *p) {
     if (!p) return fail(ZDR_E_INVALID, "null argument");
-    if (int rc = mip_check_image(name, p->struct_size, sizeof(zdr_texel_gather_mip_params), p->width, p->height, p->levels)) return rc;
-    if (p->tex_h <= 0 || p->tex_w <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the texture size must be positive");
-    if (!(p->footprint > 0.0f && p->footprint <= 3.402823466e38f))    // (false for a NaN)
-        return fail(ZDR_E_INVALID, std::string(name) + ": footprint must be finite and > 0");
-    if ((uint64_t)p->tex_h * (uint64_t)p->tex_w > ZDR_MIP_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
-    return ZDR_OK;
+    return filter_check_gather(name, p->struct_size, sizeof(*p), p->tex_h, p->tex_w, p->width, p->height, p->levels, ZDR_PLAN_MIP, p->footprint, 1);
 }
 
 extern "C" int zdr_texel_gather_mip(const zdr_texel_gather_mip_params *p, const float *view, const float *image, const float *pyramid, float *color, void *stream) {
     const char *name = "zdr_texel_gather_mip";
     if (int rc = texel_gather_mip_check(name, p)) return rc;
-    if (int rc = mip_check_pointers(name, {(const void *)view, (const void *)image, (const void *)pyramid, (const void *)color})) return rc;
+    if (int rc = filter_check_pointers(name, {(const void *)view, (const void *)image, (const void *)pyramid, (const void *)color})) return rc;
     const MipPlan P = zdr_mip_plan(p->width, p->height, p->levels);
     const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
     if (denoise_overlap(color, 16 * n, {{view, 32 * n}, {image, 16 * npix}, {pyramid, P.bytes}}))
@@ -1876,7 +1900,7 @@ extern "C" int zdr_texel_gather_mip(const zdr_texel_gather_mip_params *p, const 
 extern "C" int zdr_texel_gather_mip_backward(const zdr_texel_gather_mip_params *p, const float *view, const float *d_color, float *d_image, float *d_pyramid, void *stream) {
     const char *name = "zdr_texel_gather_mip_backward";
     if (int rc = texel_gather_mip_check(name, p)) return rc;
-    if (int rc = mip_check_pointers(name, {(const void *)view, (const void *)d_color, (const void *)d_image, (const void *)d_pyramid})) return rc;
+    if (int rc = filter_check_pointers(name, {(const void *)view, (const void *)d_color, (const void *)d_image, (const void *)d_pyramid})) return rc;
     const MipPlan P = zdr_mip_plan(p->width, p->height, p->levels);
     const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
     if (denoise_overlap(d_image, 16 * npix, {{view, 32 * n}, {d_color, 16 * n}, {d_pyramid, P.bytes}}) || denoise_overlap(d_pyramid, P.bytes, {{view, 32 * n}, {d_color, 16 * n}}))
@@ -1896,15 +1920,14 @@ extern "C" int zdr_texel_gather_mip_backward(const zdr_texel_gather_mip_params *
 extern "C" int zdr_texel_footprint(const zdr_texel_footprint_params *p, const float *texel_aovs, float *out, void *stream) {
     const char *name = "zdr_texel_footprint";
     if (!p) return fail(ZDR_E_INVALID, "null argument");
-    if (p->struct_size != sizeof(zdr_texel_footprint_params))
-        return fail(ZDR_E_INVALID, "zdr_texel_footprint_params.struct_size is " + std::to_string(p->struct_size) + ", this library expects " + std::to_string(sizeof(zdr_texel_footprint_params)));
-    if (p->tex_h <= 0 || p->tex_w <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the texture size must be positive");
-    if (p->width <= 0 || p->height <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the image size must be positive");
+    if (int rc = filter_check_struct("zdr_texel_footprint_params.", p->struct_size, sizeof(zdr_texel_footprint_params))) return rc;
+    if (int rc = filter_check_positive(name, "texture", p->tex_h, p->tex_w)) return rc;
+    if (int rc = filter_check_positive(name, "image", p->width, p->height)) return rc;
     if (!(p->camera.fov > 0.0f && p->camera.fov < 3.14159265358979323846f))       // (false for a NaN)
         return fail(ZDR_E_INVALID, std::string(name) + ": camera.fov must be finite and lie in (0, pi)");
-    if ((uint64_t)p->tex_h * (uint64_t)p->tex_w > ZDR_ANISO_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
-    if ((uint64_t)p->width * (uint64_t)p->height > ZDR_ANISO_MAX_PIXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^28 pixels");
-    if (int rc = mip_check_pointers(name, {(const void *)texel_aovs, (const void *)out})) return rc;
+    if (int rc = filter_check_texels(name, p->tex_h, p->tex_w)) return rc;
+    if (int rc = filter_check_pixels(name, p->width, p->height)) return rc;
+    if (int rc = filter_check_pointers(name, {(const void *)texel_aovs, (const void *)out})) return rc;
     const size_t n = (size_t)p->tex_h * (size_t)p->tex_w;
     if (denoise_overlap(out, 16 * n, {{texel_aovs, 64 * n}})) return fail(ZDR_E_INVALID, std::string(name) + ": out must not alias or overlap texel_aovs");
     if (!zdr_launch_texel_footprint)                                 // (weak: csrc/aniso.h)
@@ -1920,21 +1943,14 @@ extern "C" int zdr_texel_footprint(const zdr_texel_footprint_params *p, const fl
 
 static int texel_gather_aniso_check(const char *name, const zdr_texel_gather_aniso_params *p) {
     if (!p) return fail(ZDR_E_INVALID, "null argument");
-    if (int rc = mip_check_image(name, p->struct_size, sizeof(zdr_texel_gather_aniso_params), p->width, p->height, p->levels)) return rc;
-    if (p->tex_h <= 0 || p->tex_w <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the texture size must be positive");
-    if (!(p->footprint > 0.0f && p->footprint <= 3.402823466e38f))    // (false for a NaN)
-        return fail(ZDR_E_INVALID, std::string(name) + ": footprint must be finite and > 0");
-    if (p->max_aniso < 1 || p->max_aniso > ZDR_ANISO_MAX_PROBES)
-        return fail(ZDR_E_INVALID, std::string(name) + ": max_aniso is " + std::to_string(p->max_aniso) + ": it must lie in 1 .. " + std::to_string(ZDR_ANISO_MAX_PROBES));
-    if ((uint64_t)p->tex_h * (uint64_t)p->tex_w > ZDR_ANISO_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
-    return ZDR_OK;
+    return filter_check_gather(name, p->struct_size, sizeof(*p), p->tex_h, p->tex_w, p->width, p->height, p->levels, ZDR_PLAN_ANISO, p->footprint, p->max_aniso);
 }
 
 extern "C" int zdr_texel_gather_aniso(const zdr_texel_gather_aniso_params *p, const float *view, const float *footprint, const float *image, const float *pyramid,
                                       float *color, void *stream) {
     const char *name = "zdr_texel_gather_aniso";
     if (int rc = texel_gather_aniso_check(name, p)) return rc;
-    if (int rc = mip_check_pointers(name, {(const void *)view, (const void *)footprint, (const void *)image, (const void *)pyramid, (const void *)color})) return rc;
+    if (int rc = filter_check_pointers(name, {(const void *)view, (const void *)footprint, (const void *)image, (const void *)pyramid, (const void *)color})) return rc;
     const MipPlan P = zdr_mip_plan(p->width, p->height, p->levels);
     const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
     if (denoise_overlap(color, 16 * n, {{view, 32 * n}, {footprint, 16 * n}, {image, 16 * npix}, {pyramid, P.bytes}}))
@@ -1953,7 +1969,7 @@ extern "C" int zdr_texel_gather_aniso_backward(const zdr_texel_gather_aniso_para
                                                float *d_pyramid, void *stream) {
     const char *name = "zdr_texel_gather_aniso_backward";
     if (int rc = texel_gather_aniso_check(name, p)) return rc;
-    if (int rc = mip_check_pointers(name, {(const void *)view, (const void *)footprint, (const void *)d_color, (const void *)d_image, (const void *)d_pyramid})) return rc;
+    if (int rc = filter_check_pointers(name, {(const void *)view, (const void *)footprint, (const void *)d_color, (const void *)d_image, (const void *)d_pyramid})) return rc;
     const MipPlan P = zdr_mip_plan(p->width, p->height, p->levels);
     const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
     if (denoise_overlap(d_image, 16 * npix, {{view, 32 * n}, {footprint, 16 * n}, {d_color, 16 * n}, {d_pyramid, P.bytes}}) ||
@@ -1975,16 +1991,7 @@ extern "C" int zdr_texel_gather_aniso_backward(const zdr_texel_gather_aniso_para
 // read of nnz from the workspace's header.
 static int plan_check(const char *name, const zdr_gather_plan_params *p) {
     if (!p) return fail(ZDR_E_INVALID, "null argument");
-    if (int rc = mip_check_image(name, p->struct_size, sizeof(zdr_gather_plan_params), p->width, p->height, p->levels)) return rc;
-    if (p->tex_h <= 0 || p->tex_w <= 0) return fail(ZDR_E_INVALID, std::string(name) + ": the texture size must be positive");
-    if (p->filter < ZDR_PLAN_BILINEAR || p->filter > ZDR_PLAN_ANISO)
-        return fail(ZDR_E_INVALID, std::string(name) + ": filter is " + std::to_string(p->filter) + ": 0 (bilinear), 1 (mip) or 2 (aniso)");
-    if (p->filter != ZDR_PLAN_BILINEAR && !(p->footprint > 0.0f && p->footprint <= 3.402823466e38f))    // (false for a NaN)
-        return fail(ZDR_E_INVALID, std::string(name) + ": footprint must be finite and > 0");
-    if (p->filter == ZDR_PLAN_ANISO && (p->max_aniso < 1 || p->max_aniso > ZDR_ANISO_MAX_PROBES))
-        return fail(ZDR_E_INVALID, std::string(name) + ": max_aniso is " + std::to_string(p->max_aniso) + ": it must lie in 1 .. " + std::to_string(ZDR_ANISO_MAX_PROBES));
-    if ((uint64_t)p->tex_h * (uint64_t)p->tex_w > ZDR_PLAN_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^26 texels");
-    return ZDR_OK;
+    return filter_check_gather(name, p->struct_size, sizeof(*p), p->tex_h, p->tex_w, p->width, p->height, p->levels, p->filter, p->footprint, p->max_aniso);
 }
 
 // the rows of a plan: the pixels of level 0, then — mip and aniso — the packed levels >= 1 (one pixel where there is none, as the
@@ -2040,9 +2047,9 @@ extern "C" size_t zdr_gather_plan_workspace_bytes(const zdr_gather_plan_params *
 
 static int plan_check_inputs(const char *name, const zdr_gather_plan_params *p, const float *view, const float *footprint, const void *workspace) {
     if (int rc = plan_check(name, p)) return rc;
-    if (int rc = mip_check_pointers(name, {(const void *)view, workspace})) return rc;
+    if (int rc = filter_check_pointers(name, {(const void *)view, workspace})) return rc;
     if (p->filter == ZDR_PLAN_ANISO)
-        if (int rc = mip_check_pointers(name, {(const void *)footprint})) return rc;
+        if (int rc = filter_check_pointers(name, {(const void *)footprint})) return rc;
     if (!zdr_launch_plan_build)                                      // (weak: csrc/plan.h)
         return fail(ZDR_E_UNSUPPORTED, "this library was linked without the gather-plan kernels (zdr_plan.hip)");
     return ZDR_OK;
@@ -2064,7 +2071,7 @@ extern "C" int zdr_gather_plan_build(const zdr_gather_plan_params *p, const floa
                                      void *entries, void *stream) {
     const char *name = "zdr_gather_plan_build";
     if (int rc = plan_check_inputs(name, p, view, footprint, workspace)) return rc;
-    if (int rc = mip_check_pointers(name, {(const void *)row_start, (const void *)entries})) return rc;
+    if (int rc = filter_check_pointers(name, {(const void *)row_start, (const void *)entries})) return rc;
     if (nnz > ZDR_PLAN_MAX_NNZ) return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": more than 2^31 - 1 entries");
     PlanWorkspace W;
     if (!plan_workspace(p, nnz, workspace, W)) return fail(ZDR_E_HIP, std::string(name) + ": the sort's size query failed");
@@ -2083,9 +2090,9 @@ extern "C" int zdr_gather_plan_apply(const zdr_gather_plan_params *p, const uint
                                      float *d_pyramid, void *stream) {
     const char *name = "zdr_gather_plan_apply";
     if (int rc = plan_check(name, p)) return rc;
-    if (int rc = mip_check_pointers(name, {(const void *)row_start, entries, (const void *)d_color, (const void *)d_image})) return rc;
+    if (int rc = filter_check_pointers(name, {(const void *)row_start, entries, (const void *)d_color, (const void *)d_image})) return rc;
     if (p->filter != ZDR_PLAN_BILINEAR)
-        if (int rc = mip_check_pointers(name, {(const void *)d_pyramid})) return rc;
+        if (int rc = filter_check_pointers(name, {(const void *)d_pyramid})) return rc;
     const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height, rows = plan_rows(p);
     const size_t pbytes = p->filter == ZDR_PLAN_BILINEAR ? 0 : 16 * (rows - npix);
     if (denoise_overlap(d_image, 16 * npix, {{row_start, 4 * (rows + 1)}, {d_color, 16 * n}, {d_pyramid, pbytes}}) ||

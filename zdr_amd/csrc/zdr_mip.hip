@@ -22,8 +22,10 @@
 //
 // The gather (k_mip_gather) is thread = texel, like k_proj_gather; it reads both float4 of the view row (scale is float 6).  Its adjoint
 // (k_mip_scatter) is thread = (texel, channel), for the reason given above k_proj_scatter (zdr_project.hip): one float atomic per tap
-// and channel (-munsafe-fp-atomics: global_atomic_add_f32, no compare-and-swap loop).
+// and channel (-munsafe-fp-atomics: global_atomic_add_f32, no compare-and-swap loop).  The level split, the places, the taps, the
+// trilinear sample and the adjoint's walk are texel_filter.h's, shared with the other texel filters.
 #include "mip.h"
+#include "texel_filter.h"
 
 #define MIP_BLOCK 256
 #define ZD __device__ __forceinline__
@@ -31,7 +33,6 @@
 ZD float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 ZD float4 f4scale(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
 ZD int32_t mini(int32_t a, int32_t b) { return a < b ? a : b; }
-ZD int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // ---------------------------------------------------------------------------------------------------- the pyramid, value by value
 ZD float4 mip_box(float4 a00, float4 a01, float4 a10, float4 a11) { return f4scale(f4add(f4add(a00, a01), f4add(a10, a11)), 0.25f); }
@@ -151,112 +152,35 @@ __global__ __launch_bounds__(MIP_BLOCK) void k_mip_tail_bwd(int w0, int h0, int 
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------- the level of a texel
-// s = max(scale footprint, 1), NaN -> 1;  l0 = its binary exponent, f = log2 of its mantissa in [1, 2); at or beyond the top level: L, 0.
-// The split is integer work on the float's bits: only f carries rounding.
-struct MipLevel { int l0; float f; };
-ZD MipLevel mip_level(float scale, float footprint, int L) {
-    float s = scale * footprint;
-    s = s > 1.0f ? s : 1.0f;
-    const uint32_t b = __float_as_uint(s);
-    MipLevel r;
-    r.l0 = (int)(b >> 23) - 127;                                    // (s >= 1: no sign, an exponent field of at least 127; infinity: 128)
-    r.f = 0.0f;
-    if (r.l0 >= L) { r.l0 = L; return r; }
-    const float m = __uint_as_float((b & 0x007fffffu) | 0x3f800000u);
-    if (m != 1.0f) r.f = fminf(log2f(m), 1.0f);
-    return r;
-}
-
-// size of level l and where it begins in the packed buffer (float4; level 0 is the image and has no place there).  A loop, not a table
-// in the kernel's arguments: l differs from lane to lane, and l0 is small wherever the gather is worth calling.
-struct MipPlace { int w, h; size_t off; };
-ZD MipPlace mip_place(int width, int height, int l) {
-    MipPlace p;
-    p.w = width; p.h = height; p.off = 0;
-    for (int k = 1; k <= l; k++) {
-        if (k > 1) p.off += (size_t)p.w * (size_t)p.h;
-        p.w = (p.w + 1) >> 1; p.h = (p.h + 1) >> 1;
-    }
-    return p;
-}
-ZD MipPlace mip_above(MipPlace p, int l) {                           // level l + 1 from level l
-    if (l >= 1) p.off += (size_t)p.w * (size_t)p.h;
-    p.w = (p.w + 1) >> 1; p.h = (p.h + 1) >> 1;
-    return p;
-}
-
-// The taps of one texel in a level: the rule of proj_taps (zdr_project.hip; include/zdr.h, zdr_texel_gather) with that level's size.
-struct MipTaps { int32_t i00, i01, i10, i11; float tx, ty; };
-ZD MipTaps mip_taps(float X, float Y, int32_t width, int32_t height) {
-    const float fx = X - 0.5f, fy = Y - 0.5f;
-    const float x0f = floorf(fx), y0f = floorf(fy);
-    MipTaps T;
-    T.tx = fx - x0f; T.ty = fy - y0f;
-    const int32_t x0 = (int32_t)fminf(fmaxf(x0f, -1.0f), (float)width), y0 = (int32_t)fminf(fmaxf(y0f, -1.0f), (float)height);
-    const int32_t xa = clampi(x0, 0, width - 1), xb = clampi(x0 + 1, 0, width - 1);
-    const int32_t ya = clampi(y0, 0, height - 1), yb = clampi(y0 + 1, 0, height - 1);
-    T.i00 = ya * width + xa; T.i01 = ya * width + xb; T.i10 = yb * width + xa; T.i11 = yb * width + xb;
-    return T;
-}
-
-ZD float4 mip_lerp(float4 a, float4 b, float t) {
-    return make_float4(a.x + (b.x - a.x) * t, a.y + (b.y - a.y) * t, a.z + (b.z - a.z) * t, a.w + (b.w - a.w) * t);
-}
-
-ZD float mip_exp2_neg(int l) { return __uint_as_float((uint32_t)(127 - l) << 23); }   // 2^-l, l <= 31: the scaling of X, Y is exact
-
-ZD float4 mip_sample(const float4 *lvl, float X, float Y, int l, MipPlace p) {
-    const float inv = mip_exp2_neg(l);
-    const MipTaps T = mip_taps(X * inv, Y * inv, p.w, p.h);
-    const float4 top = mip_lerp(lvl[T.i00], lvl[T.i01], T.tx), bot = mip_lerp(lvl[T.i10], lvl[T.i11], T.tx);
-    return mip_lerp(top, bot, T.ty);
-}
-
+// ------------------------------------------------------------------------------------------------------------------ the gather
 __global__ __launch_bounds__(256) void k_mip_gather(MipGatherArgs G) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= G.ntexels) return;
     const float4 vw = G.view[2 * (size_t)t], vs = G.view[2 * (size_t)t + 1];   // {visible, cosine, X, Y}, {depth, distance, scale, 0}
     float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (vw.x != 0.0f && vw.x == vw.x) {                      // an invisible texel reads nothing of the image or the pyramid
-        const MipLevel lv = mip_level(vs.z, G.footprint, G.L);
-        const MipPlace lo = mip_place(G.width, G.height, lv.l0);
-        float4 r = mip_sample(lv.l0 ? G.pyramid + lo.off : G.in, vw.z, vw.w, lv.l0, lo);
-        if (lv.f != 0.0f) {                                  // (then l0 < L: the level above exists)
-            const MipPlace hi = mip_above(lo, lv.l0);
-            r = mip_lerp(r, mip_sample(G.pyramid + hi.off, vw.z, vw.w, lv.l0 + 1, hi), lv.f);
-        }
+    if (tf_on(vw.x)) {                                       // an invisible texel reads nothing of the image or the pyramid
+        const tf_level_t lv = tf_level(vs.z * G.footprint, G.L);
+        const tf_place_t lo = tf_place(G.width, G.height, lv.l0);
+        const float4 r = tf_trilinear(G.in, G.pyramid, vw.z, vw.w, lv, lo, tf_above(lo, lv.l0));
         c = make_float4(vw.x * r.x, vw.x * r.y, vw.x * r.z, vw.x * r.w);
     }
     G.out[t] = c;
-}
-
-ZD void mip_scatter(float *d, float X, float Y, int l, MipPlace p, float share, float visible, float g) {
-    const float inv = mip_exp2_neg(l);
-    const MipTaps T = mip_taps(X * inv, Y * inv, p.w, p.h);
-    const float ux = 1.0f - T.tx, uy = 1.0f - T.ty;
-    atomicAdd(d + 4 * (size_t)T.i00, (((ux * uy) * share) * visible) * g);
-    atomicAdd(d + 4 * (size_t)T.i01, (((T.tx * uy) * share) * visible) * g);
-    atomicAdd(d + 4 * (size_t)T.i10, (((ux * T.ty) * share) * visible) * g);
-    atomicAdd(d + 4 * (size_t)T.i11, (((T.tx * T.ty) * share) * visible) * g);
 }
 
 __global__ __launch_bounds__(256) void k_mip_scatter(MipGatherArgs G) {
     const uint32_t id = blockIdx.x * 256u + threadIdx.x, t = id >> 2, c = id & 3u;   // (id < 4 ntexels <= 2^28)
     if (t >= G.ntexels) return;
     const float4 vw = G.view[2 * (size_t)t];
-    if (!(vw.x != 0.0f && vw.x == vw.x)) return;
+    if (!tf_on(vw.x)) return;
     const float scale = ((const float *)G.view)[8 * (size_t)t + 6];
-    const MipLevel lv = mip_level(scale, G.footprint, G.L);
-    const MipPlace lo = mip_place(G.width, G.height, lv.l0);
+    tf_texel_t x = tf_texel(vw.x, vw.z, vw.w);
+    x.lv = tf_level(scale * G.footprint, G.L);
     const float g = ((const float *)G.in)[id];
-    // with f == 0 the share is 1 and (w 1) visible g is the very product k_proj_scatter adds
-    mip_scatter((lv.l0 ? (float *)(G.d_pyramid + lo.off) : (float *)G.out) + c, vw.z, vw.w, lv.l0, lo, 1.0f - lv.f, vw.x, g);
-    if (lv.f != 0.0f) {
-        const MipPlace hi = mip_above(lo, lv.l0);
-        mip_scatter((float *)(G.d_pyramid + hi.off) + c, vw.z, vw.w, lv.l0 + 1, hi, lv.f, vw.x, g);
-    }
+    float *d_image = (float *)G.out + c, *d_pyramid = (float *)G.d_pyramid + c;
+    tf_enumerate(x, TF_MIP, G.footprint, G.width, G.height,
+                 [&](bool pyramid, uint32_t pixel, float weight) { atomicAdd((pyramid ? d_pyramid : d_image) + 4 * (size_t)pixel, weight * g); });
 }
+
 
 // ------------------------------------------------------------------------------------------------------------------------ launchers
 static dim3 mip_grid(int w, int h) { return dim3((unsigned)(((size_t)w * (size_t)h + MIP_BLOCK - 1) / MIP_BLOCK)); }

@@ -22,131 +22,34 @@
 // grid and the launch order.  The four channel lanes of a sub-sum read the same entry (8 bytes, one request) and 16 contiguous bytes of
 // d_color.
 //
-// The taps, the level split and the probes are those of zdr_project.hip, zdr_mip.hip and zdr_aniso.hip operation for operation, restated
-// here (pl_*) as zdr_aniso.hip restated zdr_mip.hip's: the translation units share no object file.  One formula serves the three
-// filters: a weight is (((w share) (1 / N)) visible), and where a scatter kernel has no such factor it is 1 here — a product with 1 is
-// exact, so the bits are that kernel's.
+// The enumeration is tf_enumerate (texel_filter.h), the very walk the scatter kernels of zdr_project.hip, zdr_mip.hip and zdr_aniso.hip run
+// with an atomic add as its emit: the fill's emit stores (row, (texel, weight)) instead.  Why one weight formula has the bits of all
+// three kernels is argued there.
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include "plan.h"
 
 #define ZD __device__ __forceinline__
 
-ZD int32_t pl_clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-// ------------------------------------------------------------------------------------------------------------- the level of a texel
-// (zdr_mip.hip, mip_level, after its product scale * footprint)  s = max(s, 1), NaN -> 1;  l0 = its binary exponent, f = log2 of its mantissa
-struct PlLevel { int l0; float f; };
-ZD PlLevel pl_level(float s, int L) {
-    s = s > 1.0f ? s : 1.0f;
-    const uint32_t b = __float_as_uint(s);
-    PlLevel r;
-    r.l0 = (int)(b >> 23) - 127;
-    r.f = 0.0f;
-    if (r.l0 >= L) { r.l0 = L; return r; }
-    const float m = __uint_as_float((b & 0x007fffffu) | 0x3f800000u);
-    if (m != 1.0f) r.f = fminf(log2f(m), 1.0f);
-    return r;
-}
-
-struct PlPlace { int w, h; uint32_t off; };                          // off: pixels from the start of the packed levels >= 1
-ZD PlPlace pl_place(int width, int height, int l) {
-    PlPlace p;
-    p.w = width; p.h = height; p.off = 0;
-    for (int k = 1; k <= l; k++) {
-        if (k > 1) p.off += (uint32_t)p.w * (uint32_t)p.h;
-        p.w = (p.w + 1) >> 1; p.h = (p.h + 1) >> 1;
-    }
-    return p;
-}
-ZD PlPlace pl_above(PlPlace p, int l) {                              // level l + 1 from level l
-    if (l >= 1) p.off += (uint32_t)p.w * (uint32_t)p.h;
-    p.w = (p.w + 1) >> 1; p.h = (p.h + 1) >> 1;
-    return p;
-}
-
-// The taps of one position in a level: proj_taps (zdr_project.hip).  Whatever X and Y hold, the indices lie inside the level.
-struct PlTaps { int32_t i00, i01, i10, i11; float tx, ty; };
-ZD PlTaps pl_taps(float X, float Y, int32_t width, int32_t height) {
-    const float fx = X - 0.5f, fy = Y - 0.5f;
-    const float x0f = floorf(fx), y0f = floorf(fy);
-    PlTaps T;
-    T.tx = fx - x0f; T.ty = fy - y0f;
-    const int32_t x0 = (int32_t)fminf(fmaxf(x0f, -1.0f), (float)width), y0 = (int32_t)fminf(fmaxf(y0f, -1.0f), (float)height);
-    const int32_t xa = pl_clampi(x0, 0, width - 1), xb = pl_clampi(x0 + 1, 0, width - 1);
-    const int32_t ya = pl_clampi(y0, 0, height - 1), yb = pl_clampi(y0 + 1, 0, height - 1);
-    T.i00 = ya * width + xa; T.i01 = ya * width + xb; T.i10 = yb * width + xa; T.i11 = yb * width + xb;
-    return T;
-}
-
-ZD float pl_exp2_neg(int l) { return __uint_as_float((uint32_t)(127 - l) << 23); }   // 2^-l, l <= 31
-
-// ------------------------------------------------------------------------------------------------------------- the probes of a texel
-// (zdr_aniso.hip, an_probes)
-struct PlProbes { int N; float s; };
-ZD PlProbes pl_probes(float minor, float major, float footprint, int max_aniso) {
-    const float A = major * footprint, B = minor * footprint;
-    PlProbes r;
-    r.N = 1; r.s = 1.0f;
-    if (A > 1.0f) {
-        const float Bp = fmaxf(fmaxf(B, __fdiv_rn(A, (float)max_aniso)), 1.0f);
-        const float q = ceilf(__fdiv_rn(A, Bp) - 0.125f);
-        r.N = q >= 1.0f ? (q <= (float)max_aniso ? (int)q : max_aniso) : 1;
-        r.s = Bp;
-    }
-    return r;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- what a texel enumerates
-struct PlTexel { bool on; float visible, X, Y, ax, ay; int N; PlLevel lv; };
-ZD PlTexel pl_texel(const PlanEnumArgs &E, uint32_t t) {
-    PlTexel r;
+// the state the scatter kernel of E.filter forms for texel t (texel_filter.h); an invisible texel reads nothing else and has no entry
+ZD tf_texel_t pl_texel(const PlanEnumArgs &E, uint32_t t) {
     const float4 vw = E.view[2 * (size_t)t];                 // {visible, cosine, X, Y}
-    r.on = vw.x != 0.0f && vw.x == vw.x;                     // an invisible texel reads nothing else and has no entry
-    r.visible = vw.x; r.X = vw.z; r.Y = vw.w; r.ax = 0.0f; r.ay = 0.0f; r.N = 1; r.lv.l0 = 0; r.lv.f = 0.0f;
-    if (!r.on) return r;
+    tf_texel_t x = tf_texel(vw.x, vw.z, vw.w);
+    if (!tf_on(vw.x)) return x;
     if (E.filter == ZDR_PLAN_MIP) {
         const float scale = ((const float *)E.view)[8 * (size_t)t + 6];
-        r.lv = pl_level(scale * E.footprint, E.L);
+        x.lv = tf_level(scale * E.footprint, E.L);
     } else if (E.filter == ZDR_PLAN_ANISO) {
         const float4 fp = E.foot[t];                         // {major axis x, y, minor, major}
-        const PlProbes pr = pl_probes(fp.z, fp.w, E.footprint, E.max_aniso);
-        r.N = pr.N; r.ax = fp.x; r.ay = fp.y;
-        r.lv = pl_level(pr.s * 1.0f, E.L);
+        const tf_probes_t pr = tf_probes(fp.z, fp.w, E.footprint, E.max_aniso);
+        x.N = pr.N; x.ax = fp.x; x.ay = fp.y;
+        x.lv = tf_level(pr.s, E.L);
     }
-    return r;
+    return x;
 }
 
-ZD uint32_t pl_count(const PlTexel &x) { return x.on ? (uint32_t)x.N * (x.lv.f != 0.0f ? 8u : 4u) : 0u; }
-
-// the four taps of one probe in one level: rows first + index, weights (((w share) inv_n) visible)
-template <class Emit>
-ZD void pl_emit_taps(uint32_t first, float X, float Y, int l, PlPlace p, float share, float inv_n, float visible, Emit emit) {
-    const float inv = pl_exp2_neg(l);
-    const PlTaps T = pl_taps(X * inv, Y * inv, p.w, p.h);
-    const float ux = 1.0f - T.tx, uy = 1.0f - T.ty;
-    emit(first + (uint32_t)T.i00, (((ux * uy) * share) * inv_n) * visible);
-    emit(first + (uint32_t)T.i01, (((T.tx * uy) * share) * inv_n) * visible);
-    emit(first + (uint32_t)T.i10, (((ux * T.ty) * share) * inv_n) * visible);
-    emit(first + (uint32_t)T.i11, (((T.tx * T.ty) * share) * inv_n) * visible);
-}
-
-template <class Emit>
-ZD void pl_enumerate(const PlanEnumArgs &E, const PlTexel &x, Emit emit) {
-    const PlPlace lo = pl_place(E.width, E.height, x.lv.l0);
-    const PlPlace hi = pl_above(lo, x.lv.l0);
-    const uint32_t first_lo = x.lv.l0 ? E.p0 + lo.off : 0u, first_hi = E.p0 + hi.off;
-    const float fN = (float)x.N, inv_n = __fdiv_rn(1.0f, fN), two_n = 2.0f * fN, low = 1.0f - x.lv.f;
-    for (int i = 0; i < x.N; i++) {
-        float X = x.X, Y = x.Y;
-        if (E.filter == ZDR_PLAN_ANISO) {
-            const float ti = __fdiv_rn((float)(2 * i + 1 - x.N), two_n);
-            X = x.X + (ti * E.footprint) * x.ax; Y = x.Y + (ti * E.footprint) * x.ay;
-        }
-        pl_emit_taps(first_lo, X, Y, x.lv.l0, lo, low, inv_n, x.visible, emit);
-        if (x.lv.f != 0.0f) pl_emit_taps(first_hi, X, Y, x.lv.l0 + 1, hi, x.lv.f, inv_n, x.visible, emit);   // (then l0 < L: the level exists)
-    }
-}
+ZD uint32_t pl_count(const tf_texel_t &x) { return tf_on(x.visible) ? (uint32_t)x.N * (x.lv.f != 0.0f ? 8u : 4u) : 0u; }
 
 // ------------------------------------------------------------------------------------------------------------------------- the build
 __global__ __launch_bounds__(ZDR_PLAN_BLOCK) void k_plan_count(PlanEnumArgs E, uint32_t *block_off) {
@@ -179,17 +82,17 @@ __global__ __launch_bounds__(ZDR_PLAN_BLOCK) void k_plan_fill(PlanEnumArgs E, co
                                                               uint64_t *__restrict__ vals) {
     __shared__ uint32_t cnt[ZDR_PLAN_BLOCK];
     const uint32_t t = blockIdx.x * ZDR_PLAN_BLOCK + threadIdx.x;
-    PlTexel x;
-    x.on = false;
+    tf_texel_t x = tf_texel(0.0f, 0.0f, 0.0f);                       // (a thread beyond the last texel: invisible)
     if (t < E.ntexels) x = pl_texel(E, t);
-    cnt[threadIdx.x] = t < E.ntexels ? pl_count(x) : 0u;
+    cnt[threadIdx.x] = pl_count(x);
     __syncthreads();
-    if (!x.on) return;
+    if (!tf_on(x.visible)) return;
     uint32_t at = block_off[blockIdx.x];
     for (uint32_t k = 0; k < threadIdx.x; k++) at += cnt[k];
-    pl_enumerate(E, x, [&](uint32_t row, float weight) {
+    // a destination's row: the pixels of the image first, then, from p0 on, the pixels of the packed levels >= 1
+    tf_enumerate(x, E.filter, E.footprint, E.width, E.height, [&](bool pyramid, uint32_t pixel, float weight) {
         if (at < nnz) {                                              // (a caller's nnz below the true one: the entries beyond it are dropped, not written)
-            keys[at] = row;
+            keys[at] = (pyramid ? E.p0 : 0u) + pixel;
             vals[at] = (uint64_t)t | ((uint64_t)__float_as_uint(weight) << 32);
         }
         at++;

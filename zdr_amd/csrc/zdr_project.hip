@@ -16,9 +16,11 @@
 //                     sized for "every texel shaded"; workgroups beyond the list's end leave at once.  No float atomic: a texel's bits
 //                     depend on its own row and the camera alone.
 // The gather (k_proj_gather) is thread = texel, four loads and a store; its adjoint (k_proj_scatter) is thread = (texel, channel), one float atomic
-// per tap and channel into d_image (-munsafe-fp-atomics: global_atomic_add_f32, no compare-and-swap loop).
+// per tap and channel into d_image (-munsafe-fp-atomics: global_atomic_add_f32, no compare-and-swap loop).  The taps, the lerp and the
+// adjoint's walk are texel_filter.h's, which the mip gather, the anisotropic gather and the gather plan share.
 #include "accel.h"
 #include "project.h"
+#include "texel_filter.h"
 #include <algorithm>
 
 #define PROJ_WAVE 64
@@ -118,35 +120,13 @@ __global__ __launch_bounds__(PROJ_WAVE) void k_proj_view(DScene S, ProjViewArgs 
     }
 }
 
-// The taps of one texel (include/zdr.h, zdr_texel_gather): indices clamped to the image, weights from the unclamped fraction.  The floor
-// is clamped as a float before it becomes an integer, so that whatever X and Y hold — a caller's own view buffer — the indices lie
-// inside the image.
-struct ProjTaps { int32_t i00, i01, i10, i11; float tx, ty; };
-ZD ProjTaps proj_taps(float X, float Y, int32_t width, int32_t height) {
-    const float fx = X - 0.5f, fy = Y - 0.5f;
-    const float x0f = floorf(fx), y0f = floorf(fy);
-    ProjTaps T;
-    T.tx = fx - x0f; T.ty = fy - y0f;
-    const int32_t x0 = (int32_t)fminf(fmaxf(x0f, -1.0f), (float)width), y0 = (int32_t)fminf(fmaxf(y0f, -1.0f), (float)height);
-    const int32_t xa = clampi(x0, 0, width - 1), xb = clampi(x0 + 1, 0, width - 1);
-    const int32_t ya = clampi(y0, 0, height - 1), yb = clampi(y0 + 1, 0, height - 1);
-    T.i00 = ya * width + xa; T.i01 = ya * width + xb; T.i10 = yb * width + xa; T.i11 = yb * width + xb;
-    return T;
-}
-
-ZD float4 proj_lerp(float4 a, float4 b, float t) {
-    return make_float4(a.x + (b.x - a.x) * t, a.y + (b.y - a.y) * t, a.z + (b.z - a.z) * t, a.w + (b.w - a.w) * t);
-}
-
 __global__ __launch_bounds__(256) void k_proj_gather(ProjGatherArgs G) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= G.ntexels) return;
     const float4 vw = G.view[2 * (size_t)t];                 // {visible, cosine, X, Y}
     float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (vw.x != 0.0f && vw.x == vw.x) {                      // an invisible texel reads nothing of the image
-        const ProjTaps T = proj_taps(vw.z, vw.w, G.width, G.height);
-        const float4 top = proj_lerp(G.in[T.i00], G.in[T.i01], T.tx), bot = proj_lerp(G.in[T.i10], G.in[T.i11], T.tx);
-        const float4 r = proj_lerp(top, bot, T.ty);
+    if (tf_on(vw.x)) {                                       // an invisible texel reads nothing of the image
+        const float4 r = tf_sample(G.in, vw.z, vw.w, 0, tf_place(G.width, G.height, 0));
         c = make_float4(vw.x * r.x, vw.x * r.y, vw.x * r.z, vw.x * r.w);
     }
     G.out[t] = c;
@@ -159,15 +139,11 @@ __global__ __launch_bounds__(256) void k_proj_scatter(ProjGatherArgs G) {
     const uint32_t id = blockIdx.x * 256u + threadIdx.x, t = id >> 2, c = id & 3u;   // (id < 4 ntexels <= 2^28)
     if (t >= G.ntexels) return;
     const float4 vw = G.view[2 * (size_t)t];
-    if (!(vw.x != 0.0f && vw.x == vw.x)) return;
-    const ProjTaps T = proj_taps(vw.z, vw.w, G.width, G.height);
+    if (!tf_on(vw.x)) return;
     const float g = ((const float *)G.in)[id];
-    const float ux = 1.0f - T.tx, uy = 1.0f - T.ty;
     float *d = (float *)G.out + c;
-    atomicAdd(d + 4 * (size_t)T.i00, ((ux * uy) * vw.x) * g);
-    atomicAdd(d + 4 * (size_t)T.i01, ((T.tx * uy) * vw.x) * g);
-    atomicAdd(d + 4 * (size_t)T.i10, ((ux * T.ty) * vw.x) * g);
-    atomicAdd(d + 4 * (size_t)T.i11, ((T.tx * T.ty) * vw.x) * g);
+    tf_enumerate(tf_texel(vw.x, vw.z, vw.w), TF_BILINEAR, 1.0f, G.width, G.height,
+                 [&](bool, uint32_t pixel, float weight) { atomicAdd(d + 4 * (size_t)pixel, weight * g); });
 }
 
 int zdr_launch_texel_view(const DScene &S_in, int accel_is_bvh, const ProjViewArgs &V, hipStream_t st) {
