@@ -702,6 +702,71 @@ int zdr_gather_plan_build(const zdr_gather_plan_params *params, const float *vie
 int zdr_gather_plan_apply(const zdr_gather_plan_params *params, const uint32_t *row_start, const void *entries, const float *d_color,
                           float *d_image, float *d_pyramid, void *stream);
 
+/* Camera gradients: the derivative of a gather in the view buffer, and the adjoint of the view buffer in the camera.  VISIBLE IS HELD
+ * FIXED: neither the occlusion test nor the image-border test is differentiated (the interior derivative; biased where a silhouette
+ * sweeps over texels).  Everything else in the view buffer is smooth in the camera, and the gathers are piecewise smooth in X, Y and
+ * scale.  No scene handle, no ray, no float atomic; the calls above are unchanged.
+ *
+ * 1. zdr_texel_gather_dview: d_view (tex_h x tex_w x 8, every row OVERWRITTEN) from d_color (tex_h x tex_w x 4), for filter 0 (bilinear,
+ * zdr_texel_gather) or 1 (mip, zdr_texel_gather_mip; pyramid, footprint and levels as that call takes them, not read for filter 0, where
+ * pyramid may be null).  Filter 2 (aniso) is ZDR_E_UNSUPPORTED: its axis, N and B' would need derivatives of the footprint buffer.
+ * Floats 2 (d_X), 3 (d_Y) and, mip, 6 (d_scale) carry values, the rest are 0.  Where visible is 0 or NaN the row is eight zeros and
+ * neither the image, the pyramid nor d_color of that texel is read.  Otherwise, for a sample of level l with the taps c00, c01, c10, c11
+ * and the fractions tx, ty exactly as the forward forms them (X 2^-l, Y 2^-l; level 0 for the bilinear filter), per channel
+ *   a = c01 - c00,  b = c11 - c10,  gx = (a + (b - a) ty) 2^-l,  gy = (bot - top) 2^-l,   top, bot the forward's two lerps,
+ * the scaling exact.  Mip: g = lo + (hi - lo) f for gx and gy as the forward blends the colours; where f == 0 the upper level is not read.
+ *   d_X = visible (((d_color_0 gx_0 + d_color_1 gx_1) + d_color_2 gx_2) + d_color_3 gx_3),   d_Y likewise with gy,
+ * in float32, uncontracted.  Taps that clamp onto one pixel give a = 0 by themselves: this is the derivative of the forward as it is
+ * implemented, and at an integer fx the right-hand one, as the floor dictates.  Where the level split moves with scale — 0 < f < 1, which
+ * implies s = scale footprint > 1 and l0 < L; f == 1 is log2f's clamp —
+ *   d_scale = visible (dot(d_color, hi - lo) (footprint / (s ln 2))),   dot as above, hi and lo the two levels' colours, ln 2 as a float,
+ * so that the result is the derivative of the forward and not of a surrogate with frozen levels.  Where s <= 1 the mip result is the
+ * bilinear one bit for bit.  One thread per texel, no workspace: the same bits from run to run.
+ *
+ * 2. zdr_texel_view_backward: d_camera, 10 floats in zdr_camera's order (fov, origin, target, up), OVERWRITTEN, from d_view (tex_h x
+ * tex_w x 8) and the texel buffer the view was made from (normal n, texel_size, position p and reach are read, as in the forward), with
+ * the params of zdr_scene_texel_view.  For every SHADED texel (the forward's rule), with the frame and the quantities of that call,
+ * v = p - o, z, dist, wi, cosine, a = v.right, b = v.upp, and g_1 .. g_6 = floats 1 .. 6 of its d_view row (floats 0 and 7 are ignored;
+ * the row of a texel that is not shaded is not read):
+ *   kx = half_w / (z tan),  ky = half_h / (z (tan aspect)),  qx = a / z,  qy = b / z           dX/da = kx, dY/db = -ky
+ *   ga = g_2 kx,  gb = -(g_3 ky),  gxy = g_3 (ky qy) - g_2 (kx qx)                             dX/dz = -kx qx, dY/dz = ky qy
+ *   gz = (g_4 + gxy) - (g_6 scale) / z,   gt = (gxy z - g_6 scale) / tan                       dscale/dz = -scale / z, d./dtan = (z / tan) d./dz
+ * where z > 0, and ga = gb = gt = 0, gz = g_4 elsewhere (there X, Y and scale are the constant 0);
+ *   gv = ((gz fwd + ga right) + gb upp) - ((g_1 / dist) (n - cosine wi) + g_5 wi)               dcosine/dv = -(n - cosine wi) / dist, ddist/dv = -wi
+ * and the texel's 13 partial derivatives are  d_o = -gv,  d_fwd = gz v,  d_right = ga v,  d_upp = gb v,  d_tan = gt,  float32, uncontracted.
+ * Their sums over the texels are taken in FLOAT64 (the terms cancel, and the chain rule below differences the totals once more), in a
+ * fixed order: G = 256 R lanes, R = min(ceil(ntexels / 256), 1024); lane g adds the texels g, g + G, g + 2G .. in ascending order; within
+ * each wave of 64 consecutive lanes, lane i adds lane i + 32 to itself, then i + 16, 8, 4, 2, 1; the four waves of a workgroup of 256
+ * consecutive lanes are added in wave order, which gives one partial row per workgroup in the workspace; sixteen sub-sums add the rows
+ * r, r + 16, r + 32 .. ascending, and are added in order.  One lane takes the totals through the frame — d = target - origin, fwd = d / |d|,
+ * c = fwd x up, right = c / |c|, upp = right x fwd, tan = tan(fov / 2) — in float64, the frame formed once more in float64 from the
+ * camera's floats (the Jacobian of the exact map: what the projections remove, such as d_up along up, is then 0 to float64's rounding):
+ *   g_right += fwd x g_upp,  g_fwd += g_upp x right,  g_c = (g_right - right (right . g_right)) / |c|,  g_fwd += up x g_c,
+ *   d_up = g_c x fwd,  d_target = (g_fwd - fwd (fwd . g_fwd)) / |d|,  d_origin = g_o - d_target,  d_fov = g_tan (1 + tan^2) / 2,
+ * rounded to float32 once.  A degenerate frame (up parallel to fwd) gives NaN, as the forward does.  `workspace`: at least
+ * zdr_texel_view_backward_workspace_bytes(tex_h, tex_w) bytes (0 = invalid size; 128 R), contents irrelevant: nothing is read that
+ * the call did not write.  No float atomic, no dependence on the launch order: the same bits from run to run.
+ *
+ * All pointers are DEVICE pointers, 16-byte aligned.  The calls only enqueue on `stream` (one launch, two launches): they never allocate
+ * and never synchronise, and can be captured in a HIP graph without a call before.
+ * ZDR_E_INVALID: a null or misaligned pointer, a wrong struct_size, a size <= 0, levels < 0, a filter outside 0 .. 2, a footprint that is
+ * not finite or not > 0 (mip), a fov that is not finite or not in (0, pi), an output or workspace that overlaps an input or the other.
+ * ZDR_E_UNSUPPORTED: filter 2; more than 2^26 texels or 2^28 pixels; a library linked without these kernels. */
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_texel_gather_dview_params) */
+    int32_t tex_h, tex_w;
+    int32_t width, height;             /* of the image */
+    int32_t filter;                    /* 0 bilinear, 1 mip */
+    int32_t levels;                    /* as zdr_image_pyramid_params.levels */
+    float footprint;
+} zdr_texel_gather_dview_params;
+int zdr_texel_gather_dview(const zdr_texel_gather_dview_params *params, const float *view, const float *image, const float *pyramid,
+                           const float *d_color, float *d_view, void *stream);
+size_t zdr_texel_view_backward_workspace_bytes(int32_t tex_h, int32_t tex_w);   /* 0 = invalid size */
+int zdr_texel_view_backward(const zdr_texel_view_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
+                            const float *d_view /* DEVICE tex_h x tex_w x 8 */, float *d_camera /* DEVICE 10 floats */, void *workspace,
+                            void *stream);
+
 /* Path statistics of one forward pass over the shard: counters[8] (HOST, written
  * after an internal synchronise) = camera samples, closest-hit rays, closest rays that hit,
  * shadow rays (one per shaded vertex, prb.py:59), shaded vertices, emitter hits via BSDF sampling, NaN-dropped samples,

@@ -30,6 +30,8 @@ MIP_LIB = os.path.join(CSRC, "libzdr_mip.so")
 ANISO_LIB = os.path.join(CSRC, "libzdr_aniso.so")
 # The gather plan — the adjoints of the three gathers as CSR rows, built once and applied without atomics (zdr_plan.hip): an eighth library.
 PLAN_LIB = os.path.join(CSRC, "libzdr_plan.so")
+# Camera gradients — the derivative of a gather in the view buffer and the adjoint of the view buffer in the camera (zdr_viewgrad.hip): a ninth.
+VIEWGRAD_LIB = os.path.join(CSRC, "libzdr_viewgrad.so")
 ARCH = "gfx950"
 
 
@@ -59,7 +61,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB)):
+    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB, VIEWGRAD_LIB)):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -109,6 +111,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # the gather plan, linked into libzdr_plan.so, under the flags of zdr_mip.hip without the atomics option (it has no float atomic):
         # a weight is the scatter kernels' own product, and the sums follow the operation order of include/zdr.h
         ("zdr_plan.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
+        # camera gradients, linked into libzdr_viewgrad.so, under the flags of zdr_plan.hip (no float atomic here either): the taps and
+        # lerps are the gathers' own, and the sums follow the operation order of include/zdr.h
+        ("zdr_viewgrad.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -122,7 +127,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    plan_obj = objs.pop()                                   # (zdr_plan.o: the last job)
+    viewgrad_obj = objs.pop()                               # (zdr_viewgrad.o: the last job)
+    plan_obj = objs.pop()                                   # (zdr_plan.o: the one before)
     aniso_obj = objs.pop()                                  # (zdr_aniso.o: the one before)
     mip_obj = objs.pop()                                    # (zdr_mip.o: the one before)
     project_obj = objs.pop()                                # (zdr_project.o: the one before)
@@ -136,8 +142,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", MIP_LIB, mip_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", ANISO_LIB, aniso_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PLAN_LIB, plan_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", VIEWGRAD_LIB, viewgrad_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake", "-lzdr_pushpull",
-              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan",
+              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan", "-lzdr_viewgrad",
               "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -163,3 +163,50 @@ TF_D void tf_enumerate(const tf_texel_t &x, int filter, float footprint, int wid
         if (x.lv.f != 0.0f) tf_emit_taps(true, q.X, q.Y, x.lv.l0 + 1, hi, x.lv.f, inv_n, x.visible, emit);   // (then l0 < L: the level exists)
     }
 }
+
+// ------------------------------------------------------------------------------------------------- the derivative in the view buffer
+// What a gather's colour does when the view buffer moves (zdr_viewgrad.hip; include/zdr.h, zdr_texel_gather_dview): the derivative of
+// tf_sample and tf_trilinear in X, Y and — through the fractional level — in scale, from the taps the forward reads, formed as the
+// forward forms them.  The indices are held: the derivative is the one of the piece the position lies in, the right-hand one at an
+// integer fx.  Taps that clamp onto one pixel give a difference of 0 by themselves.
+struct tf_grad_t { float4 c, gx, gy; };            // the sample itself, and its derivative in the X and Y of level 0
+TF_D float4 tf_sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+TF_D float4 tf_mul(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
+TF_D float tf_dot4(float4 d, float4 g) { return ((d.x * g.x + d.y * g.y) + d.z * g.z) + d.w * g.w; }   // channels 0 .. 3 in order
+
+// a = c01 - c00, b = c11 - c10;  gx = a + (b - a) ty;  gy = bot - top;  both times 2^-l, which is exact (level 0: times 1)
+TF_D tf_grad_t tf_sample_grad(const float4 *lvl, float X, float Y, int l, tf_place_t p) {
+    const float inv = tf_exp2_neg(l);
+    const tf_taps_t T = tf_taps(X * inv, Y * inv, p.w, p.h);
+    const float4 c00 = lvl[T.i00], c01 = lvl[T.i01], c10 = lvl[T.i10], c11 = lvl[T.i11];
+    const float4 top = tf_lerp(c00, c01, T.tx), bot = tf_lerp(c10, c11, T.tx);
+    tf_grad_t r;
+    r.c = tf_lerp(top, bot, T.ty);
+    r.gx = tf_mul(tf_lerp(tf_sub(c01, c00), tf_sub(c11, c10), T.ty), inv);
+    r.gy = tf_mul(tf_sub(bot, top), inv);
+    return r;
+}
+
+#define TF_LN2 0.693147180559945309f
+
+// d_X, d_Y, d_scale of one visible texel with the colour's cotangent d.  s = scale * footprint, the product the forward hands to
+// tf_level (the bilinear filter: s = 1, L = 0, which folds the levels away).  The levels blend as tf_trilinear blends them, and the
+// upper one is not read where f == 0.  d_scale only where the level split moves with s: 0 < f < 1 (then s > 1 and l0 < L; f == 1 is
+// the clamp of log2f), f = log2(s) - l0, so df/dscale = footprint / (s ln 2).
+struct tf_dview_t { float dX, dY, dS; };
+TF_D tf_dview_t tf_dview(const float4 *image, const float4 *pyramid, float visible, float X, float Y, float s, float footprint, int L, int width,
+                         int height, float4 d) {
+    const tf_level_t lv = tf_level(s, L);
+    const tf_place_t lo = tf_place(width, height, lv.l0);
+    tf_grad_t g = tf_sample_grad(lv.l0 ? pyramid + (size_t)lo.off : image, X, Y, lv.l0, lo);
+    tf_dview_t r;
+    r.dS = 0.0f;
+    if (lv.f != 0.0f) {
+        const tf_place_t hi = tf_above(lo, lv.l0);
+        const tf_grad_t h = tf_sample_grad(pyramid + (size_t)hi.off, X, Y, lv.l0 + 1, hi);
+        if (lv.f < 1.0f) r.dS = visible * (tf_dot4(d, tf_sub(h.c, g.c)) * __fdiv_rn(footprint, s * TF_LN2));
+        g.gx = tf_lerp(g.gx, h.gx, lv.f); g.gy = tf_lerp(g.gy, h.gy, lv.f);
+    }
+    r.dX = visible * tf_dot4(d, g.gx); r.dY = visible * tf_dot4(d, g.gy);
+    return r;
+}

@@ -29,6 +29,8 @@
 #include "aniso.h"
 #define ZDR_PLAN_LAUNCHER_REF __attribute__((weak))      // (csrc/plan.h)
 #include "plan.h"
+#define ZDR_VIEWGRAD_LAUNCHER_REF __attribute__((weak))  // (csrc/viewgrad.h)
+#include "viewgrad.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -2104,6 +2106,67 @@ extern "C" int zdr_gather_plan_apply(const zdr_gather_plan_params *p, const uint
     A.row_start = row_start; A.entries = (const uint2 *)entries; A.d_color = d_color; A.d_image = d_image; A.d_pyramid = d_pyramid;
     A.p0 = (uint32_t)npix; A.rows = (uint32_t)rows;
     if (zdr_launch_plan_apply(A, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": a launch failed");
+    return ZDR_OK;
+}
+
+// ------------------------------------------------------------------- camera gradients
+// zdr_texel_gather_dview, zdr_texel_view_backward (include/zdr.h): no scene handle, no allocation, no synchronisation — argument checks,
+// then the launches of zdr_viewgrad.hip on the caller's stream.
+extern "C" int zdr_texel_gather_dview(const zdr_texel_gather_dview_params *p, const float *view, const float *image, const float *pyramid,
+                                      const float *d_color, float *d_view, void *stream) {
+    const char *name = "zdr_texel_gather_dview";
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (int rc = filter_check_gather(name, p->struct_size, sizeof(*p), p->tex_h, p->tex_w, p->width, p->height, p->levels, p->filter, p->footprint, 1)) return rc;
+    if (p->filter == ZDR_PLAN_ANISO)
+        return fail(ZDR_E_UNSUPPORTED, std::string(name) + ": the anisotropic gather has no derivative in the view buffer (its axis and probe count come from the footprint buffer)");
+    if (int rc = filter_check_pointers(name, {(const void *)view, (const void *)image, (const void *)d_color, (const void *)d_view})) return rc;
+    if (p->filter == ZDR_PLAN_MIP)
+        if (int rc = filter_check_pointers(name, {(const void *)pyramid})) return rc;
+    const MipPlan P = zdr_mip_plan(p->width, p->height, p->levels);
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, npix = (size_t)p->width * (size_t)p->height;
+    if (denoise_overlap(d_view, 32 * n, {{view, 32 * n}, {image, 16 * npix}, {d_color, 16 * n}, {pyramid, p->filter == ZDR_PLAN_MIP ? P.bytes : 0}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": the output must not alias or overlap an input");
+    if (!zdr_launch_texel_gather_dview)                              // (weak: csrc/viewgrad.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the camera-gradient kernels (zdr_viewgrad.hip)");
+    ViewGradDviewArgs G;
+    G.view = (const float4 *)view; G.image = (const float4 *)image; G.pyramid = (const float4 *)pyramid; G.d_color = (const float4 *)d_color;
+    G.out = (float4 *)d_view; G.ntexels = (uint32_t)n; G.width = p->width; G.height = p->height; G.L = P.L; G.filter = p->filter;
+    G.footprint = p->footprint;
+    if (zdr_launch_texel_gather_dview(G, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
+    return ZDR_OK;
+}
+
+extern "C" size_t zdr_texel_view_backward_workspace_bytes(int32_t tex_h, int32_t tex_w) {
+    if (project_check_size(tex_h, tex_w)) return 0;
+    return (size_t)zdr_viewgrad_rows((uint32_t)((size_t)tex_h * (size_t)tex_w)) * ZDR_VIEWGRAD_ROW * sizeof(double);
+}
+
+extern "C" int zdr_texel_view_backward(const zdr_texel_view_params *p, const float *texel_aovs, const float *d_view, float *d_camera, void *workspace,
+                                       void *stream) {
+    const char *name = "zdr_texel_view_backward";
+    if (!p || !texel_aovs || !d_view || !d_camera || !workspace) return fail(ZDR_E_INVALID, "null argument");
+    if (int rc = filter_check_struct("zdr_texel_view_params.", p->struct_size, sizeof(zdr_texel_view_params))) return rc;
+    if (int rc = filter_check_pointers(name, {(const void *)texel_aovs, (const void *)d_view, (const void *)d_camera, (const void *)workspace})) return rc;
+    if (int rc = project_check_size(p->tex_h, p->tex_w)) return rc;
+    if (int rc = project_check_image(name, p->width, p->height)) return rc;
+    if (!(p->camera.fov > 0.0f && p->camera.fov < 3.14159265358979323846f))       // (false for a NaN)
+        return fail(ZDR_E_INVALID, std::string(name) + ": camera.fov must be finite and lie in (0, pi)");
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, wbytes = zdr_texel_view_backward_workspace_bytes(p->tex_h, p->tex_w);
+    if (denoise_overlap(d_camera, 10 * sizeof(float), {{workspace, wbytes}, {texel_aovs, 64 * n}, {d_view, 32 * n}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": d_camera must not overlap the workspace or an input");
+    if (denoise_overlap(workspace, wbytes, {{texel_aovs, 64 * n}, {d_view, 32 * n}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": the workspace must not overlap an input");
+    if (!zdr_launch_texel_view_backward)                             // (weak: csrc/viewgrad.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the camera-gradient kernels (zdr_viewgrad.hip)");
+    ViewGradCameraArgs A;
+    A.texels = (const float4 *)texel_aovs; A.d_view = (const float4 *)d_view; A.rows = (double *)workspace; A.d_camera = d_camera;
+    A.ntexels = (uint32_t)n; A.nrows = zdr_viewgrad_rows((uint32_t)n);
+    A.half_w = 0.5f * (float)p->width; A.half_h = 0.5f * (float)p->height;
+    A.aspect = (float)p->height / (float)p->width;                   // (as zdr_scene_texel_view)
+    camera_frame(p->camera, A.cam_o, A.cam_fwd, A.cam_right, A.cam_upp, A.cam_tan);
+    for (int k = 0; k < 3; k++) { A.target[k] = p->camera.target[k]; A.up[k] = p->camera.up[k]; }
+    A.fov = p->camera.fov;
+    if (zdr_launch_texel_view_backward(A, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": a launch failed");
     return ZDR_OK;
 }
 

@@ -101,5 +101,19 @@ class Camera:
     def copy(self) -> "Camera":
         return Camera(self.fov, self.origin, self.target, self.up)
 
+    def to_tensor(self):
+        """The camera as 10 float32 values on the CPU, in the order of the C struct: fov, origin, target, up.  With
+        ``requires_grad_()`` this is a differentiable camera (README, "Camera gradients")."""
+        import torch
+        return torch.tensor([self.fov, *self.origin, *self.target, *self.up], dtype=torch.float32)
+
+    @staticmethod
+    def from_tensor(t) -> "Camera":
+        """The ``Camera`` of 10 values in ``to_tensor``'s order (any tensor or sequence; it is read on the host)."""
+        v = [float(x) for x in (t.detach().reshape(-1).tolist() if hasattr(t, "detach") else t)]
+        if len(v) != 10:
+            raise ValueError(f"a camera is 10 values (fov, origin, target, up), not {len(v)}")
+        return Camera(v[0], v[1:4], v[4:7], v[7:10])
+
     def __repr__(self):
         return f"Camera(fov={self.fov}, origin={self.origin}, target={self.target}, up={self.up})"

@@ -306,6 +306,79 @@ class TexelGatherAnisoOperator(torch.autograd.Function):
 
 
 FILTERS = ("bilinear", "mip", "aniso")
+DVIEW_FILTERS = {"bilinear": 0, "mip": 1}
+
+
+def texel_gather_dview(image, view, d_color, *, filter="bilinear", pyramid=None, footprint=1.0, levels=0, out=None):
+    """zdr_texel_gather_dview: the cotangent of the view buffer, (H, W, 8), from the cotangent ``d_color`` (H, W, 4) of
+    ``texel_gather_forward(image, view)`` (``filter="bilinear"``) or of ``texel_gather_mip_forward(image, pyramid, view, footprint,
+    levels)`` (``filter="mip"``; ``pyramid`` is built here when not given).  Floats 2, 3 (d_X, d_Y) and, for "mip", 6 (d_scale) carry
+    values, the rest are 0; eight zeros where the texel is not visible: visibility is held fixed.  ``filter="aniso"`` raises
+    ``ValueError``.  Every row of ``out`` is overwritten; it is allocated when not given.  No atomic, the same bits from run to run.
+    Only enqueues, on torch's current stream."""
+    from . import mip as M
+    if filter not in DVIEW_FILTERS:
+        raise ValueError(f'filter must be "bilinear" or "mip", not {filter!r}: the anisotropic gather has no derivative in the view buffer')
+    view = _view_data(view)
+    _check_image(image, "image", view.device)
+    _check_image(d_color, "d_color", view.device)
+    if tuple(d_color.shape[:2]) != tuple(view.shape[:2]):
+        raise ValueError(f"d_color must have the view's size {tuple(view.shape[:2])}, not {tuple(d_color.shape[:2])}")
+    res = (int(image.shape[1]), int(image.shape[0]))
+    image, d_color = image.detach().contiguous(), d_color.detach().contiguous()
+    p = N.TexelGatherDviewParams()
+    p.struct_size = C.sizeof(N.TexelGatherDviewParams)
+    p.tex_h, p.tex_w, p.width, p.height = int(view.shape[0]), int(view.shape[1]), res[0], res[1]
+    p.filter, p.levels, p.footprint = DVIEW_FILTERS[filter], 0, 1.0
+    pyramid_ptr = None
+    if filter == "mip":
+        m = _mip_params(view, res, M._levels_arg(levels), footprint)     # (raises on a bad footprint)
+        p.levels, p.footprint = m.levels, m.footprint
+        if pyramid is None:
+            pyramid = M.image_pyramid_forward(image, p.levels)
+        M._check_packed(pyramid, "pyramid", res, p.levels, view.device)
+        pyramid_ptr = pyramid.data_ptr()
+    shape = (int(view.shape[0]), int(view.shape[1]), VIEW_CHANNELS)
+    out = _out(out, shape, view.device, "out")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=view.device)
+    with torch.cuda.device(view.device):
+        stream = C.c_void_p(torch.cuda.current_stream(view.device).cuda_stream)
+        N.check(N.lib().zdr_texel_gather_dview(C.byref(p), view.data_ptr(), image.data_ptr(), pyramid_ptr, d_color.data_ptr(), out.data_ptr(), stream))
+    return out
+
+
+class TexelGatherViewOperator(torch.autograd.Function):
+    """color = gather(image, view) over BOTH arguments, for a view buffer that carries gradient (a differentiable camera; README,
+    "Camera gradients").  The forward is the gathers' own; the backward is their image adjoint plus ``texel_gather_dview``.  Visibility
+    is held fixed."""
+    @staticmethod
+    def forward(ctx, image, view, filter, footprint):
+        from .mip import image_pyramid_forward
+        view = view.detach().contiguous()
+        pyramid = image_pyramid_forward(image) if filter == "mip" else None
+        ctx.filter, ctx.footprint = filter, footprint
+        ctx.save_for_backward(image, view, *(() if pyramid is None else (pyramid,)))
+        if filter == "mip":
+            return texel_gather_mip_forward(image, pyramid, view, footprint)
+        return texel_gather_forward(image, view)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from .mip import image_pyramid_backward
+        image, view = ctx.saved_tensors[:2]
+        res = (int(image.shape[1]), int(image.shape[0]))
+        d_image = d_view = None
+        if ctx.needs_input_grad[0]:
+            if ctx.filter == "mip":
+                d_image, d_pyramid = texel_gather_mip_backward(grad_output, view, res, ctx.footprint)
+                d_image = image_pyramid_backward(d_pyramid, res, d_image=d_image)
+            else:
+                d_image = texel_gather_backward(grad_output, view, res)
+        if ctx.needs_input_grad[1]:
+            pyramid = ctx.saved_tensors[2] if ctx.filter == "mip" else None
+            d_view = texel_gather_dview(image, view, grad_output, filter=ctx.filter, pyramid=pyramid, footprint=ctx.footprint)
+        return d_image, d_view, None, None
 
 
 def texel_gather(image, view, *, filter="bilinear", footprint=1.0, max_aniso=8, plan=None):
@@ -326,13 +399,27 @@ def texel_gather(image, view, *, filter="bilinear", footprint=1.0, max_aniso=8, 
     ``plan``: None (the default) scatters ``image.grad`` with float atomics, whose order of addition varies from run to run.  True, or
     a ``GatherPlan`` made for this view, image size and filter (``view.gather_plan``; any other raises ``ValueError``), leaves the
     forward as it is, bit for bit, and computes ``image.grad`` through the plan (README, "Gather plan"; zdr_amd/plan.py): no atomic,
-    the same bits from run to run.  True builds the plan on first use — one synchronisation — and keeps it on the ``TexelView``."""
+    the same bits from run to run.  True builds the plan on first use — one synchronisation — and keeps it on the ``TexelView``.
+    A view whose ``data`` carries gradient from a camera tensor (``scene.texel_view(..., camera=tensor)``; README, "Camera
+    gradients") also receives gradient, with visibility held fixed: "bilinear" and "mip" only, and without ``plan`` — either
+    raises ``ValueError``.  A leaf tensor passed as the view receives none, as before; ``texel_gather_dview`` computes its cotangent."""
     if filter not in FILTERS:
         raise ValueError(f"filter must be one of {FILTERS}, not {filter!r}")
     footprint_data = getattr(view, "footprint_data", None)
     view_object = view
+    live = view if isinstance(view, torch.Tensor) else getattr(view, "data", None)     # (a tensor's own .data is detached: it would hide the gradient)
     view = _view_data(view)
     _check_image(image, "image", view.device)
+    # A view that a differentiable camera made — its data is the result of an autograd node — gets gradient.  A leaf tensor that merely
+    # has requires_grad set stays on the path it always took and receives none: texel_gather_dview serves it directly.
+    if isinstance(live, torch.Tensor) and live.requires_grad and live.grad_fn is not None and torch.is_grad_enabled():
+        if plan is not None:
+            raise ValueError("a gather plan is tied to a fixed view: plan= cannot be used with a view that carries gradient")
+        if filter == "aniso":
+            raise ValueError('filter="aniso" has no derivative in the view buffer: use "mip" or "bilinear" with a differentiable camera')
+        if filter == "mip":
+            _mip_params(view, (int(image.shape[1]), int(image.shape[0])), 0, footprint)     # (raises on a bad footprint)
+        return TexelGatherViewOperator.apply(image, live, filter, float(footprint))
     if plan is not None:
         from . import plan as GP
         if filter == "aniso":

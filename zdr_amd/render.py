@@ -183,7 +183,8 @@ class TexelView:
     camera, inside its image and the segment to the camera is free; ``cosine``: n . wi towards the camera, signed (a weight, not a test);
     ``pixel`` (H, W, 2): the texel's position (X, Y) in the image, pixel x covering [x, x + 1); ``depth``, ``distance``: along the
     camera's axis and along the segment; ``scale``: the on-screen length of one texel in pixels.  Eight zeros where ``reach`` is 0.
-    No gradient.  ``footprint_data``: the (H, W, 4) footprint buffer (include/zdr.h, zdr_texel_footprint) when the view was made with
+    No gradient, unless the view was made from a camera tensor that requires grad (README, "Camera gradients"): then ``data`` carries
+    gradient to it, ``visible`` held fixed.  ``footprint_data``: the (H, W, 4) footprint buffer (include/zdr.h, zdr_texel_footprint) when the view was made with
     ``footprint=True``, else None; ``footprint`` reads it."""
 
     def __init__(self, data, res, footprint_data=None):
@@ -253,6 +254,34 @@ class TexelProjection:
 
 def _camera_pod(cam: Camera) -> N.CameraPOD:
     return N.CameraPOD(float(cam.fov), (C.c_float * 3)(*cam.origin), (C.c_float * 3)(*cam.target), (C.c_float * 3)(*cam.up))
+
+
+def _camera_arg(camera, default):
+    """``camera`` of the texel-view calls -> (Camera, the camera tensor or None).  A tensor is a differentiable camera: 10 float32
+    values on the CPU in ``Camera.to_tensor``'s order, read on the host — float32 to float32, so the bits are those of the ``Camera``."""
+    if not isinstance(camera, torch.Tensor):
+        return (camera if camera is not None else default), None
+    if camera.device.type != "cpu":
+        raise ValueError(f"a camera tensor must be on the CPU (it is read on the host), not on {camera.device}")
+    if camera.dtype != torch.float32 or camera.numel() != 10:
+        raise ValueError(f"a camera tensor is 10 float32 values (fov, origin, target, up), not {tuple(camera.shape)} {camera.dtype}")
+    return Camera.from_tensor(camera), camera
+
+
+class TexelViewOperator(torch.autograd.Function):
+    """view.data = texel_view(camera tensor): the forward is ``Scene.texel_view_forward`` with the tensor's values, the backward
+    ``Scene.texel_view_backward`` (visibility held fixed) and a copy of its 10 floats to the host — ONE synchronisation per backward."""
+    @staticmethod
+    def forward(ctx, camera, texel_data, scene, res):
+        ctx.scene, ctx.res, ctx.camera, ctx.shape = scene, res, Camera.from_tensor(camera), camera.shape
+        ctx.save_for_backward(texel_data)
+        return scene.texel_view_forward(texel_data, res, camera=ctx.camera)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        texel_data, = ctx.saved_tensors
+        d = ctx.scene.texel_view_backward(texel_data, grad_output.contiguous(), ctx.res, camera=ctx.camera)
+        return d.cpu().reshape(ctx.shape), None, None, None
 
 
 class Scene:
@@ -691,7 +720,9 @@ class Scene:
         of ``camera`` (default: ``scene.camera``) with an image of ``res`` = (width, height), for the surface points of ``texel_data``,
         an (H, W, 16) tensor in the layout of ``texel_aovs_forward`` of which the normal, the texel size, the position and ``reach``
         are read.  ``out`` and ``workspace`` (any tensor of at least ``zdr_texel_view_workspace_bytes`` bytes) are allocated when not
-        given.  Only enqueues, on torch's current stream."""
+        given.  ``camera`` may be a camera tensor (10 float32 values on the CPU, ``Camera.to_tensor``): it is read on the host, without
+        a synchronisation, and gives the bits of the equivalent ``Camera``; this low-level call attaches no gradient (``texel_view``
+        does).  Only enqueues, on torch's current stream."""
         if texel_data.ndim != 3 or texel_data.shape[2] != N.AOV_CHANNELS or texel_data.dtype != torch.float32 or texel_data.device != self.device:
             raise ValueError(f"texel_data must be a float32 (H, W, {N.AOV_CHANNELS}) tensor on {self.device}")
         width, height = int(res[0]), int(res[1])
@@ -704,8 +735,33 @@ class Scene:
         p = N.TexelViewParams()
         p.struct_size = C.sizeof(N.TexelViewParams)
         p.tex_h, p.tex_w, p.width, p.height = H, W, width, height
-        p.camera = _camera_pod(camera if camera is not None else self.camera)
+        p.camera = _camera_pod(_camera_arg(camera, self.camera)[0])
         N.check(N.lib().zdr_scene_texel_view(self._handle, C.byref(p), texel_data.data_ptr(), out.data_ptr(), workspace.data_ptr(), self._stream()))
+        return out
+
+    def texel_view_backward(self, texel_data, d_view, res, *, camera=None, out=None, workspace=None):
+        """zdr_texel_view_backward: the adjoint of ``texel_view_forward`` in the camera, a (10,) device tensor in ``Camera.to_tensor``'s
+        order (fov, origin, target, up), overwritten, from ``d_view`` (H, W, 8), the cotangent of the view buffer of ``texel_data``.
+        ``visible`` is held fixed (float 0 of ``d_view`` is ignored), the rows of texels that are not shaded are not read.  ``camera``:
+        a ``Camera`` or a camera tensor (default: ``scene.camera``).  ``out`` and ``workspace`` (any tensor of at least
+        ``zdr_texel_view_backward_workspace_bytes`` bytes, contents irrelevant) are allocated when not given.  A deterministic
+        reduction without atomics: the same bits from run to run.  Only enqueues, on torch's current stream."""
+        if texel_data.ndim != 3 or texel_data.shape[2] != N.AOV_CHANNELS or texel_data.dtype != torch.float32 or texel_data.device != self.device:
+            raise ValueError(f"texel_data must be a float32 (H, W, {N.AOV_CHANNELS}) tensor on {self.device}")
+        H, W = int(texel_data.shape[0]), int(texel_data.shape[1])
+        if not isinstance(d_view, torch.Tensor) or tuple(d_view.shape) != (H, W, 8) or d_view.dtype != torch.float32 or d_view.device != self.device:
+            raise ValueError(f"d_view must be a float32 {(H, W, 8)} tensor on {self.device}")
+        width, height = int(res[0]), int(res[1])
+        if width < 1 or height < 1:
+            raise ValueError(f"res must be a positive (width, height), not {res}")
+        texel_data, d_view = texel_data.detach().contiguous(), d_view.detach().contiguous()
+        workspace = self._workspace(workspace, int(N.lib().zdr_texel_view_backward_workspace_bytes(H, W)))
+        out = self._out_tensor(out, (10,), False)
+        p = N.TexelViewParams()
+        p.struct_size = C.sizeof(N.TexelViewParams)
+        p.tex_h, p.tex_w, p.width, p.height = H, W, width, height
+        p.camera = _camera_pod(_camera_arg(camera, self.camera)[0])
+        N.check(N.lib().zdr_texel_view_backward(C.byref(p), texel_data.data_ptr(), d_view.data_ptr(), out.data_ptr(), workspace.data_ptr(), self._stream()))
         return out
 
     def texel_view(self, material, index=0, *, res, camera=None, texels=None, footprint=False) -> TexelView:
@@ -713,14 +769,21 @@ class Scene:
         height): a ``TexelView``.  ``material`` and ``index`` are taken as ``texel_aovs`` takes them; ``texels``: a ``TexelAovs``
         already computed for them (without it one is computed here).  ``footprint=True`` also computes the footprint buffer
         (``texel_footprint_forward``) and attaches it as ``view.footprint_data``, which ``gather(..., filter="aniso")`` needs.  No
-        gradient."""
+        gradient, unless ``camera`` is a camera tensor that requires grad (10 float32 values on the CPU, ``Camera.to_tensor``; a device
+        tensor raises ``ValueError``): then ``view.data`` carries gradient to it — through ``view.gather`` ("bilinear", "mip") and
+        ``view.weight()`` — with ``visible`` held fixed, and each backward copies 40 bytes to the host: one synchronisation (README,
+        "Camera gradients").  The forward bits are those of the equivalent ``Camera``."""
         if texels is None:
             texels = self.texel_aovs(material, index)
-        data = self.texel_view_forward(texels.data, res, camera=camera)
+        cam, cam_tensor = _camera_arg(camera, self.camera)
+        if cam_tensor is not None and cam_tensor.requires_grad:
+            data = TexelViewOperator.apply(cam_tensor, texels.data.detach(), self, (int(res[0]), int(res[1])))
+        else:
+            data = self.texel_view_forward(texels.data, res, camera=cam)
         if not footprint:
             return TexelView(data, res)
         from .project import texel_footprint_forward
-        return TexelView(data, res, texel_footprint_forward(texels.data, res, camera if camera is not None else self.camera))
+        return TexelView(data, res, texel_footprint_forward(texels.data, res, cam))
 
     def texel_project(self, views, material, index=0, *, cosine_power=1.0, fill=False, texels=None, filter="bilinear", footprint=1.0, max_aniso=8, plan=None) -> TexelProjection:
         """Photographs into texture space ("bake from photographs"): ``views`` is a list of (camera, image) pairs, each image (h, w, 4)
@@ -735,7 +798,8 @@ class Scene:
         through a gather plan of its own (README, "Gather plan").  The views are made in this call, so the plans are too, EVERY call:
         one build and one synchronisation per view, also where no gradient is asked for.  That buys the bit-stable gradient, not
         speed; a loop over fixed cameras keeps its ``TexelView`` objects and calls ``view.gather(image, plan=True)`` instead, which
-        builds each plan once."""
+        builds each plan once.  A camera may be a camera tensor as ``texel_view`` takes it; one that requires grad receives gradient
+        (visibility held fixed; "bilinear" and "mip" only, and not with ``plan``)."""
         from .pushpull import push_pull
         if plan not in (None, True):
             raise ValueError("texel_project makes its views itself: plan must be None or True")
