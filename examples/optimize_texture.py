@@ -29,7 +29,9 @@ from those by push-pull.  Roughness starts as it would have.  Prints the share o
 first iteration's loss.  --project-filter mip prefilters the photograph for that projection (a mip pyramid, the level taken from each
 texel's on-screen size: scene.texel_project(..., filter="mip")), so that a texel that covers many pixels reads their mean, not one;
 --project-filter aniso takes the level from the short axis of each texel's on-screen ellipse and averages probes along the long one
-(filter="aniso"), which does not over-blur the walls seen at a grazing angle.
+(filter="aniso"), which does not over-blur the walls seen at a grazing angle; --footprint-patch uv lets that ellipse follow the UV
+mapping (the texel as the parallelogram of its UV tangents: scene.texel_project(..., footprint_patch="uv")) where a texture is not
+square or a chart is stretched.
 """
 import argparse
 import math
@@ -77,7 +79,7 @@ def texel_prior_loss(material, f, guides):
 
 def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0, denoise=False,
         texel_prior=0.0, mask_unreached=False, save_lighting=False, fill_unreached=False, fill_param=False, init_from_target=False,
-        project_filter="bilinear"):
+        project_filter="bilinear", footprint_patch="square"):
     scene = Scene([(os.path.join(ASSETS, "cboxuv.obj"), None, float3(0.0)),
                    (os.path.join(ASSETS, "cbox-light.obj"), None, float3(17, 12, 4))], integrator=integrator)
     scene.camera = Camera(fov=50 / 180 * 3.1415926, origin=float3(-0.2, 2.6, 6.0), target=float3(-0.2, 2.6, -2.5), up=float3(0.0, 1.0, 0.0))
@@ -88,11 +90,11 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
     theta = torch.rand((tex, tex, 4), device="cuda", generator=g).requires_grad_()
     opt = torch.optim.Adam([theta], lr=0.02)
     losses = []
-    texels = scene.texel_aovs(theta.detach()) if (texel_prior > 0.0 or mask_unreached or save_lighting or fill_unreached or fill_param or init_from_target) else None   # geometry only: once
+    texels = scene.texel_aovs(theta.detach(), tangents=footprint_patch == "uv") if (texel_prior > 0.0 or mask_unreached or save_lighting or fill_unreached or fill_param or init_from_target) else None   # geometry only: once
     guides = texels.as_guides() if texel_prior > 0.0 else None
     if init_from_target:
         with torch.no_grad():
-            photo = scene.texel_project([(scene.camera, image_gt)], theta.detach(), texels=texels, filter=project_filter)
+            photo = scene.texel_project([(scene.camera, image_gt)], theta.detach(), texels=texels, filter=project_filter, footprint_patch=footprint_patch)
             irradiance = scene.texel_lighting(theta.detach(), spp=max(64, spp), texels=texels).irradiance
             known = (photo.weight > 0) & (irradiance.sum(-1) > 0)
             guess = torch.zeros_like(theta)
@@ -165,7 +167,9 @@ if __name__ == "__main__":
     ap.add_argument("--fill-param", action="store_true")
     ap.add_argument("--init-from-target", action="store_true")
     ap.add_argument("--project-filter", choices=("bilinear", "mip", "aniso"), default="bilinear")
+    ap.add_argument("--footprint-patch", choices=("square", "uv"), default="square")
     a = ap.parse_args()
     run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness, denoise=a.denoise,
         texel_prior=a.texel_prior, mask_unreached=a.mask_unreached, save_lighting=a.save_lighting, fill_unreached=a.fill_unreached,
-        fill_param=a.fill_param, init_from_target=a.init_from_target, project_filter=a.project_filter)
+        fill_param=a.fill_param, init_from_target=a.init_from_target, project_filter=a.project_filter,
+        footprint_patch=a.footprint_patch)

@@ -357,6 +357,33 @@ size_t zdr_texel_aovs_workspace_bytes(int32_t tex_h, int32_t tex_w);   /* 0 = in
 int zdr_scene_texel_aovs(zdr_scene *scene, int32_t material, int32_t tex_h, int32_t tex_w,
                          float *aovs /* DEVICE tex_h x tex_w x 16 */, void *workspace, void *stream);
 
+/* UV tangents: how the texture's pixel lattice lies on the surface.  Per texel of material m, tangents (DEVICE, tex_h x tex_w x 8,
+ * overwritten) holds the world derivatives of the position per texture pixel, of the texel's winner — the very winner of
+ * zdr_scene_texel_aovs: the coverage winner, else the reach winner.  They are constant over a triangle, so a texel that is only reached
+ * takes its reach winner's, as it takes that winner's texel_size.
+ * World corners P0, P1, P2: the winner's, in input order; pixel-space corners (X_i, Y_i): the float32 products of zdr_scene_texel_aovs.
+ * In float32, uncontracted, divisions and roots IEEE, per component c of a vector, dot products from x to z:
+ *   e1 = P1 - P0,  e2 = P2 - P0,  a1 = X1 - X0,  a2 = X2 - X0,  b1 = Y1 - Y0,  b2 = Y2 - Y0,  det = a1 b2 - a2 b1
+ *   Tx.c = (e1.c b2 - e2.c b1) / det        dp/dX: world units per texture pixel to the right
+ *   Ty.c = (e2.c a1 - e1.c a2) / det        dp/dY: per texture pixel DOWNWARDS (Y = (1 - v) (tex_h - 1))
+ *   C = Tx x Ty = (Tx.y Ty.z - Tx.z Ty.y, Tx.z Ty.x - Tx.x Ty.z, Tx.x Ty.y - Tx.y Ty.x),  area = sqrt(C.C),  s = C.n
+ * with n the texel's normal as zdr_scene_texel_aovs wrote it (floats 4..6 of its row).  A row:
+ *   floats 0..2, 3     Tx, area          area: the world area of one texel, texel_size^2 up to rounding
+ *   floats 4..6, 7     Ty, orientation   +1 where s > 0, -1 where s < 0, 0 otherwise (s is 0 or NaN); a mirrored chart has the other sign
+ * Eight zeros where the texel is not reached; where the winner is degenerate by zdr_scene_texel_aovs's rule — the same test on the same
+ * float, so that on reached texels the row is zero exactly where texel_size is 0 (a 1 x 1 texture: all zeros) —; and where any of the
+ * eight results is not finite.  No atomic beyond the rasteriser's atomicMin: the same bits from run to run and between ZDR_ACCEL_BRUTE
+ * and ZDR_ACCEL_BVH.
+ *
+ * The call writes BOTH buffers: aovs by the three launches of zdr_scene_texel_aovs (the same launcher, the same bits), then a fourth
+ * launch reads the keys those left in `workspace` (zdr_texel_aovs_workspace_bytes) and the normals in aovs.  The raster runs once.  It
+ * only enqueues on `stream`, never allocates, never synchronises, and can be captured in a HIP graph without a call before.
+ * Errors as for zdr_scene_texel_aovs; in addition ZDR_E_INVALID: a null or misaligned (16 bytes) tangents, any overlap among aovs,
+ * tangents and the workspace.  ZDR_E_UNSUPPORTED: a library linked without these kernels (zdr_tangent.hip). */
+int zdr_scene_texel_tangents(zdr_scene *scene, int32_t material, int32_t tex_h, int32_t tex_w,
+                             float *aovs /* DEVICE tex_h x tex_w x 16 */, float *tangents /* DEVICE tex_h x tex_w x 8 */,
+                             void *workspace /* zdr_texel_aovs_workspace_bytes */, void *stream);
+
 /* Texture-space lighting: whether any light reaches a texel, where zdr_scene_texel_aovs says where the texel is.  Per texel, the direct
  * irradiance on the normal's side and the open fraction of the hemisphere (sky visibility; with a finite max_distance, ambient
  * occlusion) — a baker's lightmap, and for texture recovery the mask "lit by nothing".
@@ -589,8 +616,18 @@ int zdr_texel_gather_mip_backward(const zdr_texel_gather_mip_params *params, con
  * P >= Q, else (R, 0.5 (Q - P) + d) — no cancellation in the component that carries the length —, divided by sqrt(e.e), (1, 0) if that
  * is 0.  Floats of a row: 0, 1 = major e (pixels), 2 = minor, 3 = major.  Because M M^T = texel_size^2 J (I - n n^T) J^T, the ellipse
  * does not depend on the tangent basis that make_onb returns.  The texel is taken as a SQUARE PATCH of side texel_size in its tangent
- * plane: the texel buffers carry no UV derivatives, so the stretch of the UV mapping itself is not modelled.  No atomic: the same bits
- * from run to run.
+ * plane: that is the default, and it does not model the stretch of the UV mapping itself (a non-square texture, a stretched chart).
+ * zdr_texel_footprint_tangents below follows the mapping.  No atomic: the same bits from run to run.
+ *
+ * Footprint from UV tangents, zdr_texel_footprint_tangents: the same params, the same out, and the tangent buffer of
+ * zdr_scene_texel_tangents in addition.  The texel is the PARALLELOGRAM p + a Tx + b Ty, a, b in [-1/2, 1/2]: its true patch.  The shaded
+ * rule, the camera frame, z, gX and gY are those above.  A texel whose tangent row is eight zeros gets four zeros.  Otherwise
+ *   m00 = gX.Tx,  m01 = gX.Ty,  m10 = gY.Tx,  m11 = gY.Ty
+ * — no texel_size, no make_onb — and P, Q, R, hd, d, major, minor, the direction and the finiteness test follow operation for operation
+ * (one device function, csrc/footprint.h, called by both kernels).  The output feeds zdr_texel_gather_aniso, its adjoint and
+ * zdr_gather_plan_* unchanged: they read a footprint buffer and do not care who wrote it.  With max_aniso = 1 that gather is the mip
+ * gather at the texel's TRUE long axis: the remedy for zdr_texel_gather_mip on non-square textures, whose level comes from the view
+ * buffer's scale (texel_size).  One launch of zdr_tangent.hip; errors as zdr_texel_footprint, tangents counted among the inputs.
  *
  * Probes of a texel.  A = major * footprint, B = minor * footprint (float32 products; footprint: finite, > 0; max_aniso: 1 .. 16).  If not
  * A > 1 (a NaN too): N = 1, s = 1.  Else B' = max(B, A / max_aniso, 1) (a NaN B is passed over), q = ceil(A / B' - 0.125),
@@ -626,6 +663,8 @@ typedef struct {
 } zdr_texel_footprint_params;
 int zdr_texel_footprint(const zdr_texel_footprint_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
                         float *out /* DEVICE tex_h x tex_w x 4 */, void *stream);
+int zdr_texel_footprint_tangents(const zdr_texel_footprint_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
+                                 const float *tangents /* DEVICE tex_h x tex_w x 8 */, float *out /* DEVICE tex_h x tex_w x 4 */, void *stream);
 typedef struct {
     uint32_t struct_size;              /* = sizeof(zdr_texel_gather_aniso_params) */
     int32_t tex_h, tex_w;

@@ -13,7 +13,9 @@ operations into its walk loop, +8 %; it had been A/B-timed on the Cornell box on
     python tools/isa_diff.py --pair-renamed='REGEX=>REPLACEMENT' [rev]        (may be given several times)
         for a kernel that was renamed or folded into another template: a mangled name of rev that is gone from the tree is rewritten with
         re.sub(REGEX, REPLACEMENT) and compared with the kernel of that name, e.g.
-        '_Z19k_path_bwd_emissionI(\w+?Accel)(Lb\dE)E=>_Z10k_path_bwdI\1\2Lb1ELb0ELb1EE'."""
+        '_Z19k_path_bwd_emissionI(\w+?Accel)(Lb\dE)E=>_Z10k_path_bwdI\1\2Lb1ELb0ELb1EE'.
+    python tools/isa_diff.py --source=zdr_texel.hip --flags='-O3 -fno-slp-vectorize -ffp-contract=off' [rev]
+        another translation unit of csrc/, under the options zdr_amd/build.py gives it (default: zdr_kernels.hip and its options)."""
 import os
 import re
 import subprocess
@@ -22,12 +24,14 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["-O3", "-munsafe-fp-atomics", "-fno-slp-vectorize", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only"]
+SOURCE = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--source=")), "zdr_kernels.hip")
+FLAGS = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--flags=")), "-O3 -munsafe-fp-atomics -fno-slp-vectorize").split() + [
+    "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only"]
 
 
 def assemble(tree, out):
     subprocess.run([HIPCC, *FLAGS, "-I" + os.path.join(tree, "include"), "-I" + os.path.join(tree, "zdr_amd", "csrc"),
-                    os.path.join(tree, "zdr_amd", "csrc", "zdr_kernels.hip"), "-o", out], check=True, capture_output=True)
+                    os.path.join(tree, "zdr_amd", "csrc", SOURCE), "-o", out], check=True, capture_output=True)
     kernels, name, res, rname = {}, None, {}, None
     for line in open(out):
         r = re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", line)      # the kernel descriptor: registers, LDS, scratch, the enabled SGPR inputs
@@ -90,7 +94,9 @@ for name in sorted(set(old) | set(new)):
     if name not in old or name not in new:
         print(f"{'ADDED' if name in new else 'REMOVED':10s} {demangle(name)}"); changed += 1
     elif old[name] == new[name]:
-        print(f"identical  {demangle(name)}")
+        a = stats(old[name])
+        vgprs = next((l.split()[-1] for l in old[name] if ".amdhsa_next_free_vgpr" in l), "?")
+        print(f"identical  {demangle(name)}   instructions {a[0]}, VALU {a[1]}, scratch ops {a[2]}, VGPRs {vgprs}")
     else:
         changed += 1
         a, b = stats(old[name]), stats(new[name])

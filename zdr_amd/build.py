@@ -32,6 +32,9 @@ ANISO_LIB = os.path.join(CSRC, "libzdr_aniso.so")
 PLAN_LIB = os.path.join(CSRC, "libzdr_plan.so")
 # Camera gradients — the derivative of a gather in the view buffer and the adjoint of the view buffer in the camera (zdr_viewgrad.hip): a ninth.
 VIEWGRAD_LIB = os.path.join(CSRC, "libzdr_viewgrad.so")
+# UV tangents — the per-texel tangent buffer and the footprint ellipse of a texel's true patch (zdr_tangent.hip): a tenth, so that
+# libzdr_texel.so and libzdr_aniso.so keep exactly their three kernels each.
+TANGENT_LIB = os.path.join(CSRC, "libzdr_tangent.so")
 ARCH = "gfx950"
 
 
@@ -61,7 +64,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB, VIEWGRAD_LIB)):
+    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB, VIEWGRAD_LIB, TANGENT_LIB)):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -114,6 +117,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # camera gradients, linked into libzdr_viewgrad.so, under the flags of zdr_plan.hip (no float atomic here either): the taps and
         # lerps are the gathers' own, and the sums follow the operation order of include/zdr.h
         ("zdr_viewgrad.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
+        # UV tangents, linked into libzdr_tangent.so, under the flags of zdr_aniso.hip without the atomics option (it has no float atomic):
+        # the degenerate test is the rasteriser's and the ellipse the footprint kernel's, float for float (texel_setup.h, footprint.h)
+        ("zdr_tangent.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -127,7 +133,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    viewgrad_obj = objs.pop()                               # (zdr_viewgrad.o: the last job)
+    tangent_obj = objs.pop()                                # (zdr_tangent.o: the last job)
+    viewgrad_obj = objs.pop()                               # (zdr_viewgrad.o: the one before)
     plan_obj = objs.pop()                                   # (zdr_plan.o: the one before)
     aniso_obj = objs.pop()                                  # (zdr_aniso.o: the one before)
     mip_obj = objs.pop()                                    # (zdr_mip.o: the one before)
@@ -143,8 +150,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", ANISO_LIB, aniso_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PLAN_LIB, plan_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", VIEWGRAD_LIB, viewgrad_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", TANGENT_LIB, tangent_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake", "-lzdr_pushpull",
-              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan", "-lzdr_viewgrad",
+              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan", "-lzdr_viewgrad", "-lzdr_tangent",
               "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -6,7 +6,8 @@
 //
 //   k_aniso_footprint  thread = texel: the Jacobian of the view buffer's X, Y with respect to the world position, applied to the texel's
 //                      square patch (side texel_size in the tangent plane of make_onb(n)), and the singular values and the major axis of
-//                      that 2 x 2 matrix in closed form.  No list, no workspace: a texel that is not shaded writes four zeros itself.
+//                      that 2 x 2 matrix in closed form (footprint.h: the Jacobian and the ellipse, shared with k_tan_footprint of
+//                      zdr_tangent.hip).  No list, no workspace: a texel that is not shaded writes four zeros itself.
 //   k_aniso_gather     thread = texel, a run-time loop over the probes: the level split and the places of the two levels are formed once,
 //                      a probe is two bilinear samples and an addition; nothing per probe is kept, so nothing goes to scratch.
 //   k_aniso_scatter    thread = (texel, channel), for the reason given above k_proj_scatter (zdr_project.hip): one float atomic per tap,
@@ -16,6 +17,7 @@
 // bilinear gather, bit for bit.
 #include "scene.h"
 #include "aniso.h"
+#include "footprint.h"
 #include "texel_filter.h"
 
 // --------------------------------------------------------------------------------------------------------------------- the footprint
@@ -28,28 +30,12 @@ __global__ __launch_bounds__(256) void k_aniso_footprint(AnisoFootprintArgs A) {
     const f3 n = mk3(nr.x, nr.y, nr.z), p = mk3(pr.x, pr.y, pr.z);
     float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
     if ((reach == 1.0f) && !any_nan(n) && !any_nan(p)) {         // the view's rule (k_proj_compact)
-        const f3 fwd = ld3(A.cam_fwd), right = ld3(A.cam_right), upp = ld3(A.cam_upp);
-        const f3 v = p - ld3(A.cam_o);
-        const float z = dot(v, fwd), a = dot(v, right), b = dot(v, upp);
-        if (z > 0.0f) {
-            const float zz = z * z;
-            const f3 gX = (right * z - fwd * a) * __fdiv_rn(A.half_w, A.cam_tan * zz);
-            const f3 gY = -((upp * z - fwd * b) * __fdiv_rn(A.half_h, (A.cam_tan * A.aspect) * zz));
+        const fp_jacobian_t J = fp_jacobian(A, p);               // (footprint.h: shared with k_tan_footprint of zdr_tangent.hip)
+        if (J.front) {
             const Onb onb = make_onb(n);
-            const float m00 = ts * dot(gX, onb.tangent), m01 = ts * dot(gX, onb.binormal);
-            const float m10 = ts * dot(gY, onb.tangent), m11 = ts * dot(gY, onb.binormal);
-            const float P = m00 * m00 + m01 * m01, Q = m10 * m10 + m11 * m11, R = m00 * m10 + m01 * m11;
-            const float hd = 0.5f * (P - Q);
-            const float d = __fsqrt_rn(hd * hd + R * R);
-            const float major = __fsqrt_rn(0.5f * (P + Q) + d);
-            const float minor = major == 0.0f ? 0.0f : __fdiv_rn(fabsf(m00 * m11 - m01 * m10), major);
-            float ex, ey;
-            if (P >= Q) { ex = hd + d; ey = R; } else { ex = R; ey = 0.5f * (Q - P) + d; }
-            const float el = __fsqrt_rn(ex * ex + ey * ey);
-            if (el == 0.0f) { ex = 1.0f; ey = 0.0f; } else { ex = __fdiv_rn(ex, el); ey = __fdiv_rn(ey, el); }
-            const float ax = major * ex, ay = major * ey;
-            const float big = 3.402823466e38f;                   // finite: |x| <= FLT_MAX, false for a NaN
-            if (fabsf(ax) <= big && fabsf(ay) <= big && fabsf(minor) <= big && fabsf(major) <= big) out = make_float4(ax, ay, minor, major);
+            const float m00 = ts * dot(J.gX, onb.tangent), m01 = ts * dot(J.gX, onb.binormal);
+            const float m10 = ts * dot(J.gY, onb.tangent), m11 = ts * dot(J.gY, onb.binormal);
+            out = fp_ellipse(m00, m01, m10, m11);
         }
     }
     A.out[t] = out;

@@ -31,6 +31,8 @@
 #include "plan.h"
 #define ZDR_VIEWGRAD_LAUNCHER_REF __attribute__((weak))  // (csrc/viewgrad.h)
 #include "viewgrad.h"
+#define ZDR_TANGENT_LAUNCHER_REF __attribute__((weak))   // (csrc/tangent.h)
+#include "tangent.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1624,6 +1626,33 @@ extern "C" int zdr_scene_texel_aovs(zdr_scene *s, int32_t material, int32_t tex_
     return ZDR_OK;
 }
 
+// zdr_scene_texel_tangents (include/zdr.h): zdr_scene_texel_aovs's checks and three launches, then the tangent resolve of zdr_tangent.hip on
+// the keys they left in the workspace.  Nothing is allocated; capturable without a call before.
+extern "C" int zdr_scene_texel_tangents(zdr_scene *s, int32_t material, int32_t tex_h, int32_t tex_w, float *aovs, float *tangents, void *workspace, void *stream) {
+    const char *name = "zdr_scene_texel_tangents";
+    if (!s || !aovs || !tangents || !workspace) return fail(ZDR_E_INVALID, "null argument");
+    if ((uintptr_t)aovs % 16 || (uintptr_t)tangents % 16 || (uintptr_t)workspace % 16)
+        return fail(ZDR_E_INVALID, std::string(name) + ": aovs, tangents and workspace must be 16-byte aligned");
+    if (material < 0 || material >= ZDR_MAX_MATERIALS)
+        return fail(ZDR_E_INVALID, std::string(name) + ": material " + std::to_string(material) + " outside [0, " + std::to_string(ZDR_MAX_MATERIALS) + ")");
+    if (int rc = texel_check_size(tex_h, tex_w)) return rc;
+    const size_t n = (size_t)tex_h * (size_t)tex_w;
+    if (denoise_overlap(aovs, 64 * n, {{workspace, 8 * n}, {tangents, 32 * n}}) || denoise_overlap(tangents, 32 * n, {{workspace, 8 * n}}))
+        return fail(ZDR_E_INVALID, std::string(name) + ": aovs, tangents and the workspace must not overlap one another");
+    if (!zdr_launch_texel_aovs)                                      // (weak: csrc/texel.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the texture-space kernels (zdr_texel.hip)");
+    if (!zdr_launch_texel_tangents)                                  // (weak: csrc/tangent.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the UV-tangent kernels (zdr_tangent.hip)");
+    HIPCHK(hipSetDevice(s->device));
+    TexelArgs A;
+    A.shade = s->ds.shade; A.slot_of_tri = s->ds.slot_of_tri; A.inst_tri_begin = s->ds.inst_tri_begin; A.inst_slot = s->d_inst_slot;
+    A.ntris = (int32_t)s->ntris; A.material = material; A.tex_h = tex_h; A.tex_w = tex_w;
+    A.keys = (uint2 *)workspace; A.aovs = (float4 *)aovs;
+    if (zdr_launch_texel_aovs(A, (hipStream_t)stream)) return fail(ZDR_E_HIP, "texel feature-buffer launch failed");
+    if (zdr_launch_texel_tangents(A, (float4 *)tangents, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the tangent launch failed");
+    return ZDR_OK;
+}
+
 // ------------------------------------------------------------------- texture-space lighting
 // zdr_scene_texel_lighting (include/zdr.h): argument checks, then the three launches of zdr_bake.hip on the caller's stream.  The handle
 // is only read — the records, the acceleration structure, the light table and the environment tables as they are — so nothing is
@@ -1940,6 +1969,31 @@ extern "C" int zdr_texel_footprint(const zdr_texel_footprint_params *p, const fl
     A.aspect = (float)p->height / (float)p->width;                   // (as zdr_scene_texel_view)
     camera_frame(p->camera, A.cam_o, A.cam_fwd, A.cam_right, A.cam_upp, A.cam_tan);
     if (zdr_launch_texel_footprint(A, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
+    return ZDR_OK;
+}
+
+// zdr_texel_footprint_tangents (include/zdr.h): zdr_texel_footprint's checks, the tangent buffer in addition, one launch of zdr_tangent.hip.
+extern "C" int zdr_texel_footprint_tangents(const zdr_texel_footprint_params *p, const float *texel_aovs, const float *tangents, float *out, void *stream) {
+    const char *name = "zdr_texel_footprint_tangents";
+    if (!p) return fail(ZDR_E_INVALID, "null argument");
+    if (int rc = filter_check_struct("zdr_texel_footprint_params.", p->struct_size, sizeof(zdr_texel_footprint_params))) return rc;
+    if (int rc = filter_check_positive(name, "texture", p->tex_h, p->tex_w)) return rc;
+    if (int rc = filter_check_positive(name, "image", p->width, p->height)) return rc;
+    if (!(p->camera.fov > 0.0f && p->camera.fov < 3.14159265358979323846f))       // (false for a NaN)
+        return fail(ZDR_E_INVALID, std::string(name) + ": camera.fov must be finite and lie in (0, pi)");
+    if (int rc = filter_check_texels(name, p->tex_h, p->tex_w)) return rc;
+    if (int rc = filter_check_pixels(name, p->width, p->height)) return rc;
+    if (int rc = filter_check_pointers(name, {(const void *)texel_aovs, (const void *)tangents, (const void *)out})) return rc;
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w;
+    if (denoise_overlap(out, 16 * n, {{texel_aovs, 64 * n}, {tangents, 32 * n}})) return fail(ZDR_E_INVALID, std::string(name) + ": out must not alias or overlap an input");
+    if (!zdr_launch_texel_footprint_tangents)                        // (weak: csrc/tangent.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the UV-tangent kernels (zdr_tangent.hip)");
+    AnisoFootprintArgs A;
+    A.texels = (const float4 *)texel_aovs; A.out = (float4 *)out; A.ntexels = (uint32_t)n;
+    A.half_w = 0.5f * (float)p->width; A.half_h = 0.5f * (float)p->height;
+    A.aspect = (float)p->height / (float)p->width;                   // (as zdr_texel_footprint)
+    camera_frame(p->camera, A.cam_o, A.cam_fwd, A.cam_right, A.cam_upp, A.cam_tan);
+    if (zdr_launch_texel_footprint_tangents(A, (const float4 *)tangents, (hipStream_t)stream)) return fail(ZDR_E_HIP, std::string(name) + ": the launch failed");
     return ZDR_OK;
 }
 

@@ -191,12 +191,15 @@ def _footprint_data(data, view):
     return data.detach().contiguous()
 
 
-def texel_footprint_forward(texel_data, res, camera, *, out=None):
+def texel_footprint_forward(texel_data, res, camera, *, out=None, tangents=None):
     """zdr_texel_footprint: the (H, W, 4) footprint buffer — the major axis of each texel's on-screen ellipse as a vector in pixels
     (floats 0, 1), the lengths of the minor and of the major axis (floats 2, 3) — of ``camera`` with an image of ``res`` = (width, height),
     for the surface points of ``texel_data``, an (H, W, 16) tensor in the layout of ``Scene.texel_aovs_forward`` of which the normal,
     the texel size, the position and ``reach`` are read.  Four zeros where the texel is not shaded or lies behind the camera.  ``out``
-    is allocated when not given.  No scene, no workspace; only enqueues, on torch's current stream."""
+    is allocated when not given.  Without ``tangents`` a texel is a square patch of side ``texel_size`` (zdr_texel_footprint); with
+    ``tangents``, the (H, W, 8) buffer of ``Scene.texel_tangents_forward`` for the same texels, it is the parallelogram they span
+    (zdr_texel_footprint_tangents), and a texel whose tangent row is zero gets four zeros.  No scene, no workspace; only enqueues, on
+    torch's current stream."""
     from .render import _camera_pod
     if not isinstance(texel_data, torch.Tensor) or texel_data.dim() != 3 or texel_data.shape[2] != N.AOV_CHANNELS or texel_data.dtype != torch.float32 \
             or texel_data.shape[0] < 1 or texel_data.shape[1] < 1:
@@ -207,6 +210,13 @@ def texel_footprint_forward(texel_data, res, camera, *, out=None):
     if width < 1 or height < 1:
         raise ValueError(f"res must be a positive (width, height), not {res}")
     texel_data = texel_data.detach().contiguous()
+    if tangents is not None:
+        want = (int(texel_data.shape[0]), int(texel_data.shape[1]), 8)
+        if not isinstance(tangents, torch.Tensor) or tuple(tangents.shape) != want or tangents.dtype != torch.float32:
+            raise ValueError(f"tangents must be a float32 {want} tensor, the tangent buffer of texel_data's texels")
+        if tangents.device != texel_data.device:
+            raise ValueError(f"tangents must be on texel_data's device {texel_data.device}, not on {tangents.device}")
+        tangents = tangents.detach().contiguous()
     shape = (int(texel_data.shape[0]), int(texel_data.shape[1]), FOOTPRINT_CHANNELS)
     out = _out(out, shape, texel_data.device, "out")
     if out is None:
@@ -217,7 +227,10 @@ def texel_footprint_forward(texel_data, res, camera, *, out=None):
     p.camera = _camera_pod(camera)
     with torch.cuda.device(texel_data.device):
         stream = C.c_void_p(torch.cuda.current_stream(texel_data.device).cuda_stream)
-        N.check(N.lib().zdr_texel_footprint(C.byref(p), texel_data.data_ptr(), out.data_ptr(), stream))
+        if tangents is None:
+            N.check(N.lib().zdr_texel_footprint(C.byref(p), texel_data.data_ptr(), out.data_ptr(), stream))
+        else:
+            N.check(N.lib().zdr_texel_footprint_tangents(C.byref(p), texel_data.data_ptr(), tangents.data_ptr(), out.data_ptr(), stream))
     return out
 
 

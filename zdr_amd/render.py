@@ -138,9 +138,14 @@ class TexelAovs(_ChannelViews):
     bilinear lookup somewhere on a model can read the texel (so it can receive gradient); ``position``, ``normal``: of the surface at
     the texel, or at the closest point of the nearest triangle for a texel that is only reached; ``texel_size``: world length of one
     texel there; ``instance``, ``slot``: the model the texel belongs to and the material index, -1 where ``reach`` is 0.  The buffers
-    depend on the geometry and the slot table only and carry no gradient.  The layout is ``Aovs``'s, so ``denoise`` takes them as guides."""
+    depend on the geometry and the slot table only and carry no gradient.  The layout is ``Aovs``'s, so ``denoise`` takes them as guides.
+    ``tangents``: the ``TexelTangents`` of the same texels when made with ``texel_aovs(..., tangents=True)``, else None."""
     CHANNELS = {"normal": (4, 7), "texel_size": (7, 8), "position": (8, 11), "coverage": (11, 12), "reach": (12, 13),
                 "instance": (14, 15), "slot": (15, 16)}
+
+    def __init__(self, data, tangents=None):
+        super().__init__(data)
+        self.tangents = tangents       # a TexelTangents from texel_aovs(..., tangents=True), else None
 
     def as_guides(self, reached=True):
         """A copy of ``data`` for ``denoise``, which reads channel 11 as its coverage: with ``reached`` that channel holds ``reach``, so
@@ -157,6 +162,28 @@ class TexelAovs(_ChannelViews):
             raise ValueError(f'by must be "coverage" or "reach", not {by!r}')
         from .pushpull import push_pull
         return push_pull(x, getattr(self, by))
+
+
+class TexelTangents:
+    """The UV tangents of ``Scene.texel_aovs(..., tangents=True)`` (include/zdr.h, zdr_scene_texel_tangents): ``data`` is the (H, W, 8)
+    tensor of one material's texels.  ``dpdx``, ``dpdy`` (H, W, 3): the world derivatives of the position per texture pixel to the right
+    and DOWNWARDS (Y = (1 - v)(H - 1)); ``area`` (H, W): the world area of one texel, ``texel_size`` squared up to rounding;
+    ``orientation`` (H, W): +1 or -1, the sign of (dpdx x dpdy) . normal — a mirrored chart has the other sign.  Eight zeros where
+    the texel is not reached or ``texel_size`` is 0.  No gradient."""
+
+    def __init__(self, data):
+        self.data = data
+
+    dpdx = property(lambda self: self.data[..., 0:3])
+    area = property(lambda self: self.data[..., 3])
+    dpdy = property(lambda self: self.data[..., 4:7])
+    orientation = property(lambda self: self.data[..., 7])
+
+    def metric(self):
+        """The first fundamental form of the mapping per texel, (H, W, 3) = (dpdx . dpdx, dpdx . dpdy, dpdy . dpdy): what a
+        metric-aware regulariser weighs texture differences with.  Torch code."""
+        x, y = self.dpdx, self.dpdy
+        return torch.stack([(x * x).sum(-1), (x * y).sum(-1), (y * y).sum(-1)], -1)
 
 
 class TexelLighting:
@@ -185,12 +212,14 @@ class TexelView:
     camera's axis and along the segment; ``scale``: the on-screen length of one texel in pixels.  Eight zeros where ``reach`` is 0.
     No gradient, unless the view was made from a camera tensor that requires grad (README, "Camera gradients"): then ``data`` carries
     gradient to it, ``visible`` held fixed.  ``footprint_data``: the (H, W, 4) footprint buffer (include/zdr.h, zdr_texel_footprint) when the view was made with
-    ``footprint=True``, else None; ``footprint`` reads it."""
+    ``footprint=True``, else None; ``footprint`` reads it.  ``footprint_patch``: what that buffer takes a texel to be — "square" (a
+    square of side ``texel_size``), "uv" (the parallelogram of the texel's UV tangents) — or None without one."""
 
-    def __init__(self, data, res, footprint_data=None):
+    def __init__(self, data, res, footprint_data=None, footprint_patch=None):
         self.data = data
         self.res = (int(res[0]), int(res[1]))
         self.footprint_data = footprint_data
+        self.footprint_patch = footprint_patch if footprint_data is not None else None
 
     visible = property(lambda self: self.data[..., 0])
     cosine = property(lambda self: self.data[..., 1])
@@ -233,7 +262,7 @@ class TexelView:
 
 class TexelFootprint:
     """The footprint buffer of a view (include/zdr.h, zdr_texel_footprint), ``data`` (H, W, 4): the on-screen ellipse of each texel's
-    square patch.  ``major_axis`` (H, W, 2): the long axis as a vector in pixels; ``minor``, ``major`` (H, W): the lengths of the two
+    patch (square, or with ``footprint="uv"`` the parallelogram of its UV tangents).  ``major_axis`` (H, W, 2): the long axis as a vector in pixels; ``minor``, ``major`` (H, W): the lengths of the two
     axes (``major`` = |``major_axis``|).  Zeros where the texel is not shaded or lies behind the camera.  No gradient."""
 
     def __init__(self, data):
@@ -664,14 +693,33 @@ class Scene:
         N.check(N.lib().zdr_scene_texel_aovs(self._handle, int(index), H, W, out.data_ptr(), workspace.data_ptr(), self._stream()))
         return out
 
-    def texel_aovs(self, material, index=0) -> TexelAovs:
+    def texel_tangents_forward(self, index, tex_hw, *, slots=None, out=None, aovs_out=None, workspace=None):
+        """zdr_scene_texel_tangents: ``(aovs, tangents)``, the (H, W, 16) buffers of ``texel_aovs_forward`` — the same bits — and the
+        (H, W, 8) UV tangents (include/zdr.h) of material ``index`` at ``tex_hw`` = (H, W), in one call: the raster runs once.
+        ``slots``: as ``texel_aovs_forward``.  ``out`` (the tangents), ``aovs_out`` and ``workspace`` (any tensor of at least
+        ``zdr_texel_aovs_workspace_bytes`` bytes) are allocated when not given.  Only enqueues, on torch's current stream."""
+        H, W = int(tex_hw[0]), int(tex_hw[1])
+        if slots is not None:
+            self._upload_slots(check_material_slots(slots, self.inst_count))
+        workspace = self._workspace(workspace, int(N.lib().zdr_texel_aovs_workspace_bytes(H, W)))
+        aovs_out = self._out_tensor(aovs_out, (H, W, N.AOV_CHANNELS), False)
+        out = self._out_tensor(out, (H, W, 8), False)
+        N.check(N.lib().zdr_scene_texel_tangents(self._handle, int(index), H, W, aovs_out.data_ptr(), out.data_ptr(), workspace.data_ptr(), self._stream()))
+        return aovs_out, out
+
+    def texel_aovs(self, material, index=0, tangents=False) -> TexelAovs:
         """What each texel of ``material[index]`` is: a ``TexelAovs`` whose ``data`` is the (H, W, 16) tensor of include/zdr.h,
         zdr_scene_texel_aovs, at that material's size — coverage, reach, world position, normal, texel size, instance and slot, with a
         named view for each.  ``material`` is a tensor or a list exactly as ``render_aovs`` takes it; it is used for its sizes and to
-        resolve the slots only (with one tensor and ``material_slots`` unset only model 0 has material 0).  No gradient."""
+        resolve the slots only (with one tensor and ``material_slots`` unset only model 0 has material 0).  ``tangents=True``: one
+        call of ``texel_tangents_forward`` instead, and ``.tangents`` is the ``TexelTangents`` of the same texels (README, "UV
+        tangents"); without it ``.tangents`` is None.  No gradient."""
         _, slots, dims, _ = self._resolve_materials(material, True, pack=False)
         if not 0 <= int(index) < len(dims):
             raise ValueError(f"index {index}: {len(dims)} materials were given")
+        if tangents:
+            data, tan = self.texel_tangents_forward(int(index), dims[int(index)], slots=slots)
+            return TexelAovs(data, TexelTangents(tan))
         return TexelAovs(self.texel_aovs_forward(int(index), dims[int(index)], slots=slots))
 
     # ------------------------------------------------------------- texture-space lighting
@@ -767,25 +815,36 @@ class Scene:
     def texel_view(self, material, index=0, *, res, camera=None, texels=None, footprint=False) -> TexelView:
         """What ``camera`` (default: ``scene.camera``) sees of each texel of ``material[index]`` in an image of ``res`` = (width,
         height): a ``TexelView``.  ``material`` and ``index`` are taken as ``texel_aovs`` takes them; ``texels``: a ``TexelAovs``
-        already computed for them (without it one is computed here).  ``footprint=True`` also computes the footprint buffer
-        (``texel_footprint_forward``) and attaches it as ``view.footprint_data``, which ``gather(..., filter="aniso")`` needs.  No
+        already computed for them (without it one is computed here).  ``footprint=True`` (the same as "square") also computes the footprint buffer
+        (``texel_footprint_forward``) and attaches it as ``view.footprint_data``, which ``gather(..., filter="aniso")`` needs: each
+        texel as a square patch of side ``texel_size``.  ``footprint="uv"``: each texel as the parallelogram of its UV tangents, which
+        follows a non-square texture or a stretched chart (README, "UV tangents"); it takes ``texels.tangents``, computes texels with
+        tangents itself when ``texels`` is not given, and raises ``ValueError`` when ``texels`` was made without them.  No
         gradient, unless ``camera`` is a camera tensor that requires grad (10 float32 values on the CPU, ``Camera.to_tensor``; a device
         tensor raises ``ValueError``): then ``view.data`` carries gradient to it — through ``view.gather`` ("bilinear", "mip") and
         ``view.weight()`` — with ``visible`` held fixed, and each backward copies 40 bytes to the host: one synchronisation (README,
         "Camera gradients").  The forward bits are those of the equivalent ``Camera``."""
+        if footprint and footprint not in (True, "square", "uv"):
+            raise ValueError(f'footprint must be False, True, "square" or "uv", not {footprint!r}')
+        patch = None if not footprint else "uv" if footprint == "uv" else "square"
         if texels is None:
-            texels = self.texel_aovs(material, index)
+            texels = self.texel_aovs(material, index, tangents=patch == "uv")
+        elif patch == "uv" and getattr(texels, "tangents", None) is None:
+            raise ValueError('footprint="uv" needs texels that carry UV tangents: scene.texel_aovs(..., tangents=True)')
         cam, cam_tensor = _camera_arg(camera, self.camera)
         if cam_tensor is not None and cam_tensor.requires_grad:
             data = TexelViewOperator.apply(cam_tensor, texels.data.detach(), self, (int(res[0]), int(res[1])))
         else:
             data = self.texel_view_forward(texels.data, res, camera=cam)
-        if not footprint:
+        if patch is None:
             return TexelView(data, res)
         from .project import texel_footprint_forward
-        return TexelView(data, res, texel_footprint_forward(texels.data, res, cam))
+        if patch == "uv":
+            return TexelView(data, res, texel_footprint_forward(texels.data, res, cam, tangents=texels.tangents.data), "uv")
+        return TexelView(data, res, texel_footprint_forward(texels.data, res, cam), "square")
 
-    def texel_project(self, views, material, index=0, *, cosine_power=1.0, fill=False, texels=None, filter="bilinear", footprint=1.0, max_aniso=8, plan=None) -> TexelProjection:
+    def texel_project(self, views, material, index=0, *, cosine_power=1.0, fill=False, texels=None, filter="bilinear", footprint=1.0, max_aniso=8, plan=None,
+                      footprint_patch="square") -> TexelProjection:
         """Photographs into texture space ("bake from photographs"): ``views`` is a list of (camera, image) pairs, each image (h, w, 4)
         of the size the camera took it at (sizes may differ from view to view).  Every view is gathered through its ``texel_view`` and
         weighted with ``view.weight(cosine_power)``; the result has ``color`` = sum w_i c_i / sum w_i (0 where the sum is 0),
@@ -794,7 +853,8 @@ class Scene:
         bit for bit.  ``material``, ``index``, ``texels``: as ``texel_view`` takes them.  ``filter``, ``footprint``: how each view is
         gathered, as ``texel_gather`` takes them; "mip" prefilters the photographs, so that a texel that covers many pixels reads all
         of them (README, "Prefiltered gather"); "aniso" computes each view's footprint buffer itself and gathers with up to
-        ``max_aniso`` probes along each texel's long axis (README, "Anisotropic gather").  ``plan=True``: every view's gradient goes
+        ``max_aniso`` probes along each texel's long axis (README, "Anisotropic gather"); ``footprint_patch``, "square" or "uv", is what
+        those buffers take a texel to be, as ``texel_view(..., footprint=)`` takes it (read by "aniso" only).  ``plan=True``: every view's gradient goes
         through a gather plan of its own (README, "Gather plan").  The views are made in this call, so the plans are too, EVERY call:
         one build and one synchronisation per view, also where no gradient is asked for.  That buys the bit-stable gradient, not
         speed; a loop over fixed cameras keeps its ``TexelView`` objects and calls ``view.gather(image, plan=True)`` instead, which
@@ -805,13 +865,16 @@ class Scene:
             raise ValueError("texel_project makes its views itself: plan must be None or True")
         if len(views) == 0:
             raise ValueError("texel_project needs at least one (camera, image) pair")
+        if footprint_patch not in ("square", "uv"):
+            raise ValueError(f'footprint_patch must be "square" or "uv", not {footprint_patch!r}')
         if texels is None:
-            texels = self.texel_aovs(material, index)
+            texels = self.texel_aovs(material, index, tangents=filter == "aniso" and footprint_patch == "uv")
         num = weight = count = None
         for camera, image in views:
             if image.dim() != 3 or image.shape[2] != 4:
                 raise ValueError(f"every image must be (height, width, 4), not {tuple(image.shape)}")
-            view = self.texel_view(material, index, res=(int(image.shape[1]), int(image.shape[0])), camera=camera, texels=texels, footprint=filter == "aniso")
+            view = self.texel_view(material, index, res=(int(image.shape[1]), int(image.shape[0])), camera=camera, texels=texels,
+                                   footprint=footprint_patch if filter == "aniso" else False)
             w = view.weight(cosine_power)
             term = w[..., None] * view.gather(image, filter=filter, footprint=footprint, max_aniso=max_aniso, plan=plan)
             num = term if num is None else num + term
