@@ -845,7 +845,9 @@ int zdr_sampler_dump(zdr_scene *scene, int32_t sampler, uint32_t seed, uint32_t 
  * (an index pass + one packed pass for its two strata, csrc/sampler.h cmj_next2_packed) and draw the vertex's numbers one
  * by one; the path kernels draw the pixel's numbers one by one and pack the vertex's (each kernel keeps the form that
  * its register budget pays for: csrc/integrators.h, pixel_ray).  Other arguments and the output
- * layout as zdr_sampler_dump; *batched (HOST, may be NULL) receives 1 when the packed route was taken, 0 for the fallback. */
+ * layout as zdr_sampler_dump; *batched (HOST, may be NULL) receives 0 for the fallback and non-zero when the packed route was
+ * taken: 2 when the path kernels also permute the four strata of a vertex's two 2-D draws in one pass, one per byte (strata
+ * grid of at most 16 x 16, i.e. spp <= 256: csrc/sampler.h, permutation_element4), else 1. */
 int zdr_vertex_sampler_dump(zdr_scene *scene, int32_t integrator, int32_t sampler, uint32_t seed, uint32_t spp,
                             const int32_t *queries, uint32_t n, int32_t nvert, int32_t rr_depth, float *out,
                             int32_t *batched, void *stream);

@@ -79,10 +79,11 @@ ZD f3 collocated_sample(const DScene &S, const RenderCfg &R, const KernelIO &io,
     COUNT(C_SHADED);
     Onb onb = make_onb(it.ns);
     f3 wo = to_local(onb, -d);
-    GgxTerms g = ggx_terms(wo, wo, m.w);
+    const GgxWo gw = ggx_wo(wo, m.w);
+    GgxTerms g = ggx_terms(gw, wo, wo);
     float inv_t = rcp(h.t), li = inv_t * inv_t;
     if (BWD) {
-        float dl_; grad = brdf_grad(wo.z * ZDR_INV_PI, ggx_dfdr_from(g, wo, wo, m.w, dl_), le_grad * li);
+        float dl_; grad = brdf_grad(wo.z * ZDR_INV_PI, ggx_dfdr_from(g, gw, wo, wo, dl_), le_grad * li);
         guv = it.uv;
     }
     return ggx_brdf_from(g, wo, mk3(m.x, m.y, m.z)) * li;
@@ -195,7 +196,8 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
     f3 wo = to_local(onb, -d);
     f3 wil = to_local(onb, light.wi);
     if (!occluded && wil.z > 0.0f) {                                              // direct.py:49
-        GgxTerms g = ggx_terms(wo, wil, roughness);
+        const GgxWo gw = ggx_wo(wo, roughness);
+        GgxTerms g = ggx_terms(gw, wo, wil);
         f3 bsdf = ggx_brdf_from(g, wil, diffuse);
         float pdf_bsdf = ggx_pdf_from(g, wo, wil);
         float mis = balanced_heuristic(light.pdf, pdf_bsdf);
@@ -203,7 +205,7 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
         radiance = radiance + ((bsdf * mis) * light.eval) * inv_dn;
         if (BWD) {
             f3 W = (light.eval * mis) * inv_dn;
-            float dl_; float4 gr = brdf_grad(wil.z * ZDR_INV_PI, ggx_dfdr_from(g, wo, wil, roughness, dl_), W * le_grad);
+            float dl_; float4 gr = brdf_grad(wil.z * ZDR_INV_PI, ggx_dfdr_from(g, gw, wo, wil, dl_), W * le_grad);
             mat_grad.x += gr.x; mat_grad.y += gr.y; mat_grad.z += gr.z; mat_grad.w += gr.w;
         }
         if constexpr (EG) {
@@ -239,7 +241,8 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
             lit = true;
         }
         if (lit && (em.x > 0.0f || em.y > 0.0f || em.z > 0.0f)) {
-            GgxTerms g = ggx_terms(wo, wi_local, roughness);
+            const GgxWo gw = ggx_wo(wo, roughness);
+            GgxTerms g = ggx_terms(gw, wo, wi_local);
             float pdf_bsdf = ggx_pdf_from(g, wo, wi_local);
             float mis = balanced_heuristic(pdf_bsdf, pdf_light);
             float inv_p = rcp(pdf_bsdf);
@@ -250,13 +253,13 @@ ZD f3 direct_sample(const DScene &S, const RenderCfg &R, const SamplerCfg &C, co
                 if (h2.slot >= 0) { l_bsdf->w = beta * mis; l_bsdf->light = emit_light_of(S, hit_inst); }
             }
             if (BWD) {
-                float dl_; float4 gr = brdf_grad(wi_local.z * ZDR_INV_PI, ggx_dfdr_from(g, wo, wi_local, roughness, dl_), (em * (mis * inv_p)) * le_grad);
+                float dl_; float4 gr = brdf_grad(wi_local.z * ZDR_INV_PI, ggx_dfdr_from(g, gw, wo, wi_local, dl_), (em * (mis * inv_p)) * le_grad);
                 mat_grad.x += gr.x; mat_grad.y += gr.y; mat_grad.z += gr.z; mat_grad.w += gr.w;
             }
         }
         if constexpr (EG) {   // an escaping BSDF sample has a gradient even where the map is zero now (the test above skips it)
             if (h2.slot < 0 && S.env_count > 0) {
-                GgxTerms g = ggx_terms(wo, wi_local, roughness);
+                GgxTerms g = ggx_terms(ggx_wo(wo, roughness), wo, wi_local);
                 float pdf_bsdf = ggx_pdf_from(g, wo, wi_local);
                 e_bsdf->w = (ggx_brdf_from(g, wi_local, diffuse) * rcp(pdf_bsdf)) * balanced_heuristic(pdf_bsdf, pdf_light);
                 e_bsdf->uv = direction_to_uv(wi);
@@ -386,9 +389,9 @@ ZD ShadeCtx shade_ctx(const DScene &S, const RenderCfg &R, const SamplerCfg &C, 
 
 // EG (environment-gradient kernels): env_w receives the per-unit weight of the light sample's radiance, beta_in f mis / max(pdf, 1e-4)
 template <bool BWD, bool EG = false>
-ZD NeeTerms nee_terms(const ShadeCtx &x, f3 beta_in, f3 *env_w = nullptr) {       // beta_in: throughput arriving at the vertex
+ZD NeeTerms nee_terms(const ShadeCtx &x, const GgxWo &gw, f3 beta_in, f3 *env_w = nullptr) {       // beta_in: throughput arriving at the vertex; gw: ggx_wo of the vertex
     NeeTerms n; n.dL = n.bW = n.fLW = n.neeM = mk3(0.0f); n.cL = 0.0f; n.dfLdr = 0.0f;
-    GgxTerms g = ggx_terms(x.wo, x.wil, x.roughness);
+    GgxTerms g = ggx_terms(gw, x.wo, x.wil);
     f3 bsdf = ggx_brdf_from(g, x.wil, x.diffuse);
     float pb = ggx_pdf_from(g, x.wo, x.wil);
     float mis = balanced_heuristic(x.light.pdf, pb);
@@ -398,7 +401,7 @@ ZD NeeTerms nee_terms(const ShadeCtx &x, f3 beta_in, f3 *env_w = nullptr) {     
     if (BWD) {
         f3 W = (x.light.eval * mis) * inv_dn;
         float dlnpL;
-        n.bW = beta_in * W; n.cL = x.wil.z * ZDR_INV_PI; n.dfLdr = ggx_dfdr_from(g, x.wo, x.wil, x.roughness, dlnpL);
+        n.bW = beta_in * W; n.cL = x.wil.z * ZDR_INV_PI; n.dfLdr = ggx_dfdr_from(g, gw, x.wo, x.wil, dlnpL);
         n.fLW = bsdf * W;
         float pbf = (x.light.pdf + pb > 1e-4f) ? pb * rcp(x.light.pdf + pb) : 0.0f;   // d w_nee/dr = -w_nee pb/(pl+pb) dln(pb)/dr
         n.neeM = ((beta_in * bsdf) * W) * (pbf * dlnpL);
@@ -413,11 +416,11 @@ ZD void nee_apply(PathState &ps, PathVertex &pv, const NeeTerms &n) {
 
 // BSDF sampling and Russian roulette (prb.py:69-87); true = the path stops here, else (ps.o, ps.d) is the continuation ray
 template <int SK, bool BWD>
-ZD bool sample_bsdf(const RenderCfg &R, const SamplerCfg &C, const ShadeCtx &x, PathState &ps, const Interaction &it, PathVertex &pv) {
+ZD bool sample_bsdf(const RenderCfg &R, const SamplerCfg &C, const ShadeCtx &x, const GgxWo &gw, PathState &ps, const Interaction &it, PathVertex &pv) {
     float u_lobe = x.u_lobe; f2 u_dir = x.u_dir;
     if (!x.pre) { u_lobe = sampler_next<SK>(C, ps.smp); u_dir = sampler_next2<SK>(C, ps.smp); }
     f3 wi_local = ggx_sample(x.wo, x.roughness, u_lobe, u_dir);
-    GgxTerms g = ggx_terms(x.wo, wi_local, x.roughness);
+    GgxTerms g = ggx_terms(gw, x.wo, wi_local);
     ps.pdf_bsdf = ggx_pdf_from(g, x.wo, wi_local);
     f3 wi = to_world(x.onb, wi_local);
     bool stop = (dot(wi, it.ng) < 1e-4f) || (wi_local.z < 1e-4f);             // prb.py:73-74
@@ -441,7 +444,7 @@ ZD bool sample_bsdf(const RenderCfg &R, const SamplerCfg &C, const ShadeCtx &x, 
         }
         if (BWD && !stop) {
             float inv_pq = inv_p * rcp(q);
-            pv.bpq = beta_in * inv_pq; pv.c = wi_local.z * ZDR_INV_PI; pv.dfdr = ggx_dfdr_from(g, x.wo, wi_local, x.roughness, pv.dlnp);
+            pv.bpq = beta_in * inv_pq; pv.c = wi_local.z * ZDR_INV_PI; pv.dfdr = ggx_dfdr_from(g, gw, x.wo, wi_local, pv.dlnp);
             pv.T = f * inv_pq;
             // prb.py:83 has no upper clamp on q: for lum(beta') >= 1 the path survives with certainty and is
             // STILL divided by q = lum(beta'), i.e. beta leaves this vertex with unit luminance.  The forward's
@@ -484,16 +487,17 @@ ZD VertexRays path_vertex_begin(const DScene &S, const RenderCfg &R, const Sampl
     if constexpr (LG) emit_term_clear(*emit);
     COUNT(C_SHADOW);
     vr.shadow = x.wil.z >= 1e-4f;
+    const GgxWo gw = ggx_wo(x.wo, x.roughness);                  // once for the light direction and the sampled one
     if (vr.shadow) {
         if constexpr (LG) {
-            n = nee_terms<BWD, true>(x, ps.beta, &emit->w);
+            n = nee_terms<BWD, true>(x, gw, ps.beta, &emit->w);
             emit->light = mesh_light;
         } else
         if constexpr (EG) {
-            n = nee_terms<BWD, true>(x, ps.beta, &env->w);
+            n = nee_terms<BWD, true>(x, gw, ps.beta, &env->w);
             if (env_uv.x < 0.0f) env->w = mk3(0.0f);
             env->uv = env_uv;
-        } else n = nee_terms<BWD>(x, ps.beta);
+        } else n = nee_terms<BWD>(x, gw, ps.beta);
         bool nothing = (n.dL.x == 0.0f) & (n.dL.y == 0.0f) & (n.dL.z == 0.0f) &&
                        (!BWD || ((n.bW.x == 0.0f) & (n.bW.y == 0.0f) & (n.bW.z == 0.0f) & (n.fLW.x == 0.0f) & (n.fLW.y == 0.0f) & (n.fLW.z == 0.0f) &
                                  (n.neeM.x == 0.0f) & (n.neeM.y == 0.0f) & (n.neeM.z == 0.0f) & (fabsf(n.dfLdr) < 3.0e38f)));
@@ -501,7 +505,7 @@ ZD VertexRays path_vertex_begin(const DScene &S, const RenderCfg &R, const Sampl
         vr.shadow = !nothing;
     }
     if (vr.shadow) COUNT(C_SHADOW_TRACED);                                          // counter 7: shadow rays actually traced
-    vr.stop = sample_bsdf<SK, BWD>(R, C, x, ps, it, pv);
+    vr.stop = sample_bsdf<SK, BWD>(R, C, x, gw, ps, it, pv);
     if (!vr.stop) COUNT(C_CLOSEST);
     return vr;
 }
@@ -526,29 +530,32 @@ ZD bool path_shade(const DScene &S, const RenderCfg &R, const SamplerCfg &C, con
         const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT, true>(S, R, C, io, ps, it, pv, cnt, nullptr, &mesh_light);
         const bool occluded = A::any_shadow(S, lds, it.p, x.light.wi, 1e-4f, x.light.dist);
         emit_term_clear(*emit);
+        const GgxWo gw = ggx_wo(x.wo, x.roughness);
         if (!occluded && x.wil.z >= 1e-4f) {
-            nee_apply<BWD>(ps, pv, nee_terms<BWD, true>(x, ps.beta, &emit->w));
+            nee_apply<BWD>(ps, pv, nee_terms<BWD, true>(x, gw, ps.beta, &emit->w));
             emit->light = mesh_light;
         }
-        return sample_bsdf<SK, BWD>(R, C, x, ps, it, pv);
+        return sample_bsdf<SK, BWD>(R, C, x, gw, ps, it, pv);
     } else if constexpr (EG) {
         f2 env_uv; env_uv.x = -1.0f; env_uv.y = 0.0f;
         const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, cnt, &env_uv);
         const bool occluded = A::any_shadow(S, lds, it.p, x.light.wi, 1e-4f, x.light.dist);
         env_term_clear(*env);
+        const GgxWo gw = ggx_wo(x.wo, x.roughness);
         if (!occluded && x.wil.z >= 1e-4f) {
-            nee_apply<BWD>(ps, pv, nee_terms<BWD, true>(x, ps.beta, &env->w));
+            nee_apply<BWD>(ps, pv, nee_terms<BWD, true>(x, gw, ps.beta, &env->w));
             if (env_uv.x < 0.0f) env->w = mk3(0.0f);
             env->uv = env_uv;
         }
-        return sample_bsdf<SK, BWD>(R, C, x, ps, it, pv);
+        return sample_bsdf<SK, BWD>(R, C, x, gw, ps, it, pv);
     } else {
         const ShadeCtx x = shade_ctx<SK, BWD, STATS, ENV, MT>(S, R, C, io, ps, it, pv, cnt);
         COUNT(C_SHADOW);
         const bool occluded = A::any_shadow(S, lds, it.p, x.light.wi, 1e-4f, x.light.dist);
-        if (!occluded && x.wil.z >= 1e-4f) nee_apply<BWD>(ps, pv, nee_terms<BWD>(x, ps.beta));
+        const GgxWo gw = ggx_wo(x.wo, x.roughness);        // the wo-only terms once for both directions, and only now: nothing more lives through the shadow walk
+        if (!occluded && x.wil.z >= 1e-4f) nee_apply<BWD>(ps, pv, nee_terms<BWD>(x, gw, ps.beta));
         COUNT(C_SHADOW_TRACED);
-        return sample_bsdf<SK, BWD>(R, C, x, ps, it, pv);   // the caller traces the continuation ray (path_continue), after it has put pv away
+        return sample_bsdf<SK, BWD>(R, C, x, gw, ps, it, pv);   // the caller traces the continuation ray (path_continue), after it has put pv away
     }
 }
 

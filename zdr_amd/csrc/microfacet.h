@@ -8,22 +8,49 @@
 
 ZD float pow5(float x) { float x2 = x * x; return x2 * x2 * x; }
 
+// The terms of ggx_terms and ggx_dfdr_from that depend on wo and the roughness alone.  A path vertex evaluates the BRDF twice with the
+// same wo — towards the light sample and towards the sampled direction — and the first evaluation sits under the light sample's
+// condition, where the compiler cannot share it with the second: the integrators compute these once per vertex (integrators.h) and
+// hand them to both.  Same operations in the same order as before, so every value keeps its bits; what a caller does not read
+// (dG1o and r3 outside the backward kernels) is dead code there.
+struct GgxWo {
+    float a2;          // alpha^2 = r^4
+    float nvo;         // max(1e-5, wo.z)
+    float ko, so;      // (1 - nv^2) / nv^2 and sqrt(1 + a2 k) for wo
+    float G1o;
+    float dG1o;        // -k / (s (1 + s)^2)
+    float r3;          // r^3
+};
+
+ZD GgxWo ggx_wo(f3 wo, float roughness) {
+    GgxWo o;
+    float alpha = roughness * roughness;                      // microfacet.py:25
+    o.a2 = alpha * alpha;
+    o.nvo = fmaxf(0.00001f, wo.z);                            // :20
+    o.ko = (1.0f - o.nvo * o.nvo) * rcp(o.nvo * o.nvo);
+    o.so = fsqrt(1.0f + o.a2 * o.ko);
+    float opo = 1.0f + o.so;
+    o.G1o = 2.0f * rcp(opo);                                  // :21
+    o.dG1o = -o.ko * rcp(o.so * (opo * opo));
+    o.r3 = roughness * roughness * roughness;
+    return o;
+}
+
 // Everything the eval, the pdf and the derivative share for one (wo, wi, roughness) triple.
 struct GgxTerms {
     float a2;          // alpha^2 = r^4
     float D, F, G1i, G1o;
     float t;           // nh^2 (a2 - 1) + 1
     float nh2;         // max(1e-5, h.z)^2
-    float ki, ko;      // (1 - nv^2) / nv^2 for wi, wo
-    float si, so;      // sqrt(1 + a2 k)
+    float ki;          // (1 - nv^2) / nv^2 for wi
+    float si;          // sqrt(1 + a2 k)
     float inv4;        // 1 / (4 max(1e-5, wi.z) max(1e-5, wo.z))
     float wo_dot_h;
 };
 
-ZD GgxTerms ggx_terms(f3 wo, f3 wi, float roughness) {
+ZD GgxTerms ggx_terms(const GgxWo &o, f3 wo, f3 wi) {
     GgxTerms g;
-    float alpha = roughness * roughness;                      // microfacet.py:25
-    g.a2 = alpha * alpha;
+    g.a2 = o.a2; g.G1o = o.G1o;
     f3 h = normalize(wi + wo);                                // :26
     float nh = fmaxf(0.00001f, h.z);                          // :10
     g.nh2 = nh * nh;
@@ -32,14 +59,11 @@ ZD GgxTerms ggx_terms(f3 wo, f3 wi, float roughness) {
     g.wo_dot_h = dot(wo, h);
     float c = clampf(g.wo_dot_h, 0.00001f, 1.0f);             // :28
     g.F = ZDR_SPECULAR + (1.0f - ZDR_SPECULAR) * pow5(1.0f - c);  // :15
-    float nvi = fmaxf(0.00001f, wi.z), nvo = fmaxf(0.00001f, wo.z);  // :20
+    float nvi = fmaxf(0.00001f, wi.z);                        // :20
     g.ki = (1.0f - nvi * nvi) * rcp(nvi * nvi);
-    g.ko = (1.0f - nvo * nvo) * rcp(nvo * nvo);
     g.si = fsqrt(1.0f + g.a2 * g.ki);
-    g.so = fsqrt(1.0f + g.a2 * g.ko);
     g.G1i = 2.0f * rcp(1.0f + g.si);                          // :21
-    g.G1o = 2.0f * rcp(1.0f + g.so);
-    g.inv4 = rcp(4.0f * nvi * nvo);                           // :30
+    g.inv4 = rcp(4.0f * nvi * o.nvo);                         // :30
     return g;
 }
 
@@ -62,14 +86,13 @@ ZD float ggx_pdf_from(const GgxTerms &g, f3 wo, f3 wi) {
 //   G1' = -k / (s (1 + s)^2).  d(f cos)_c / d diffuse_c = wi.z / pi.
 // Also returns d ln(ggx_sample_pdf) / d roughness (only the glossy half G1(wo) D / (4 |wo.z|) depends on
 // it): the PRB adjoint needs it where Russian roulette renormalises the throughput (integrators.h).
-ZD float ggx_dfdr_from(const GgxTerms &g, f3 wo, f3 wi, float roughness, float &dlnpdf_dr) {
+ZD float ggx_dfdr_from(const GgxTerms &g, const GgxWo &o, f3 wo, f3 wi, float &dlnpdf_dr) {
     float t3 = g.t * g.t * g.t;
     float dD = (1.0f - g.nh2 * (1.0f + g.a2)) * rcp(ZDR_PI * t3);
-    float opi = 1.0f + g.si, opo = 1.0f + g.so;
+    float opi = 1.0f + g.si;
     float dG1i = -g.ki * rcp(g.si * (opi * opi));
-    float dG1o = -g.ko * rcp(g.so * (opo * opo));
+    float dG1o = o.dG1o, r3 = o.r3;
     float dS = dD * (g.G1i * g.G1o) + g.D * (dG1i * g.G1o + g.G1i * dG1o);
-    float r3 = roughness * roughness * roughness;
     float dglossy = (dG1o * g.D + g.G1o * dD) * rcp(4.0f * fabsf(wo.z));
     dlnpdf_dr = (0.5f * dglossy * 4.0f * r3) * rcp(ggx_pdf_from(g, wo, wi));
     return 4.0f * r3 * (g.F * wi.z * g.inv4) * dS;

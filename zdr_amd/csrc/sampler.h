@@ -162,7 +162,8 @@ ZD f2 sampler_next2(const SamplerCfg &c, Sampler &s) {
 // past that), so for w <= 0xffff the state fits 16 bits and TWO permutations run in the halves of one register: v_pk_mul_lo_u16,
 // v_pk_lshrrev_b16, v_pk_add_u16 and plain logic.  Same values bit for bit (tests/test_gpu_paths.py compares every vertex of
 // every path with the oracle); five passes instead of nine — ten with the Russian-roulette draw, whose permutation shares the fifth.  Valid for the CMJ sampler with power-of-two spp and strata grid
-// (every BASELINE configuration); anything else takes the calls one by one.
+// (every BASELINE configuration); anything else takes the calls one by one.  Where the strata grid is at most 16 x 16 (spp <= 256) the four
+// stratum permutations go into ONE pass, a byte each (permutation_element4): four passes per vertex.
 typedef unsigned short zdr_us2 __attribute__((ext_vector_type(2)));
 ZD uint32_t pk_mul16(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, (zdr_us2)(__builtin_bit_cast(zdr_us2, a) * __builtin_bit_cast(zdr_us2, b))); }
 ZD uint32_t pk_add16(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, (zdr_us2)(__builtin_bit_cast(zdr_us2, a) + __builtin_bit_cast(zdr_us2, b))); }
@@ -182,9 +183,37 @@ ZD uint32_t permutation_element2(uint32_t i, uint32_t w, uint32_t pa, uint32_t p
     return pk_add16(i, P0) & w;
 }
 
+// FOUR permutations per register, one per byte, for masks of at most 4 bits (a strata grid of at most 16 x 16: every spp <= 256):
+// permutation_element(i.byte k, w.byte k + 1, w.byte k, p_k) for (pa, pb, pc, pd) = p_0..3.  A 4-bit state only ever sees its multipliers
+// mod 16 and the low 4 bits of every xor operand; `(i & w) >> 4` and the closing `i >> 5` are zero.  Every field is masked to 4 bits before
+// a multiply, so the product of the low byte of a half (at most 15 * 15) never carries into the byte above it; what the high byte spills
+// leaves the half.  The one per-permutation multiplier, 1 | p >> 27 (at most 15), goes through two multiplies — the even bytes' multipliers
+// in one, the odd bytes' in the other — and a merge.  The seeds are masked with 0x70ffffff: of p >> 23 only bit 23 is left in a 4-bit
+// state, and bit 27 of p >> 27 is clear.  Same values bit for bit (tests/test_gpu_vertex_diet.py).
+ZD uint32_t permutation_element4(uint32_t i, uint32_t w, uint32_t pa, uint32_t pb, uint32_t pc, uint32_t pd) {
+    const uint32_t K = 0x0f0f0f0fu;
+    const uint32_t Lab = __builtin_amdgcn_perm(pb, pa, 0x05010400u), Hab = __builtin_amdgcn_perm(pb, pa, 0x07030602u);   // {a0 b0 a1 b1}, {a2 b2 a3 b3}
+    const uint32_t Lcd = __builtin_amdgcn_perm(pd, pc, 0x05010400u), Hcd = __builtin_amdgcn_perm(pd, pc, 0x07030602u);
+    const uint32_t T0 = __builtin_amdgcn_perm(Lcd, Lab, 0x05040100u), T1 = __builtin_amdgcn_perm(Lcd, Lab, 0x07060302u);  // byte 0 of the four seeds, byte 1
+    const uint32_t T2 = __builtin_amdgcn_perm(Hcd, Hab, 0x05040100u);                                                     // byte 2
+    const uint32_t me = (__builtin_amdgcn_perm(Hcd, Hab, 0x0c060c02u) >> 3) | 0x00010001u;     // {1 | pa >> 27, 1 | pc >> 27}, one per half
+    const uint32_t mo = (__builtin_amdgcn_perm(Hcd, Hab, 0x0c070c03u) >> 3) | 0x00010001u;     // {1 | pb >> 27, 1 | pd >> 27}
+    const uint32_t P0 = T0 & K;
+    i ^= P0; i = pk_mul16(i, 0x000d000du) & K; i ^= (T1 ^ T2) & K;                             // p >> 16 and p >> 8 in one xor
+    i = pk_mul16(i, 0x000f000fu) & K; i ^= (T2 >> 7) & 0x01010101u; i ^= (i & w & 0x0e0e0e0eu) >> 1;
+    i = (pk_mul16(i, me) & 0x000f000fu) | (pk_mul16(i, mo) & 0x0f000f00u);
+    i = pk_mul16(i, 0x000b000bu) & K;                                                          // 0x6935fa69 * 0x74dcb303 mod 16
+    i ^= (i & w & 0x0c0c0c0cu) >> 2;
+    i = pk_mul16(i, 0x00030003u) & K; i ^= (i & w & 0x0c0c0c0cu) >> 2; i = pk_mul16(i, 0x000f000fu) & w;
+    return (i + P0) & w;
+}
+
 struct VertexSamples { float u_pick, u_prim; f2 u_pt; float u_lobe; f2 u_dir; uint32_t i_rr; };   // i_rr: the permuted index of the NEXT 1-D draw (Russian roulette), should the vertex make it
 __host__ ZD bool cmj_can_batch(const SamplerCfg &c) {               // wave-uniform (host: zdr_vertex_sampler_dump reports which route its kernel took)
     return c.spp_pow2 && c.res_pow2 && c.spp <= 65536u && c.w == c.spp - 1u && c.resw_x == c.res_x - 1u && c.resw_y == c.res_y - 1u;
+}
+__host__ ZD bool cmj_can_batch4(const SamplerCfg &c) {              // wave-uniform, under cmj_can_batch: the four strata permutations of a vertex fit one register
+    return (c.resw_x | c.resw_y) <= 15u;
 }
 ZD VertexSamples cmj_vertex_samples(const SamplerCfg &c, Sampler &s) {
     const uint32_t M = 0x70ffffffu;
@@ -196,23 +225,32 @@ ZD VertexSamples cmj_vertex_samples(const SamplerCfg &c, Sampler &s) {
     const uint32_t h23 = permutation_element2(I, W, ((ps + 2u) * 0x51633e2du) & M, ((ps + 4u) * 0x45fbe943u) & M, small_w);
     const uint32_t h45 = permutation_element2(I, W, ((ps + 5u) * 0x51633e2du) & M, ((ps + 7u) * 0x45fbe943u) & M, small_w);   // the fifth goes with the roulette's, which follows at dimension +7 if it is drawn at all
     const uint32_t i_pick = h01 & 0xffffu, i_prim = h01 >> 16, i_pt = h23 & 0xffffu, i_lobe = h23 >> 16, i_dir = h45 & 0xffffu;
-    // the strata of the two 2-D draws (corrmj.py:109-112): x and y permuted in one pass each
-    const uint32_t WR = c.resw_x | (c.resw_y << 16);
-    const bool small_r = (c.resw_x | c.resw_y) < 2048u;
+    // the strata of the two 2-D draws (corrmj.py:109-112): all four permuted in one pass where the grid allows it, else x and y in one pass each
     const uint32_t x_pt = i_pt & (c.res_x - 1u), y_pt = i_pt >> c.res_x_shift, x_dir = i_dir & (c.res_x - 1u), y_dir = i_dir >> c.res_x_shift;
-    const uint32_t s_pt = permutation_element2(x_pt | (y_pt << 16), WR, ((ps + 2u) * 0x68bc21ebu) & M, ((ps + 2u) * 0x02e5be93u) & M, small_r);
-    const uint32_t s_dir = permutation_element2(x_dir | (y_dir << 16), WR, ((ps + 5u) * 0x68bc21ebu) & M, ((ps + 5u) * 0x02e5be93u) & M, small_r);
+    const uint32_t pa = ((ps + 2u) * 0x68bc21ebu) & M, pb = ((ps + 2u) * 0x02e5be93u) & M, pc = ((ps + 5u) * 0x68bc21ebu) & M, pd = ((ps + 5u) * 0x02e5be93u) & M;
+    float sx_pt, sy_pt, sx_dir, sy_dir;
+    if (cmj_can_batch4(c)) {                                          // wave-uniform
+        const uint32_t WR = (c.resw_x | (c.resw_y << 8)) * 0x00010001u;
+        const uint32_t s4 = permutation_element4(x_pt | (y_pt << 8) | (x_dir << 16) | (y_dir << 24), WR, pa, pb, pc, pd);
+        sx_pt = (float)(s4 & 0xffu); sy_pt = (float)((s4 >> 8) & 0xffu); sx_dir = (float)((s4 >> 16) & 0xffu); sy_dir = (float)(s4 >> 24);
+    } else {
+        const uint32_t WR = c.resw_x | (c.resw_y << 16);
+        const bool small_r = (c.resw_x | c.resw_y) < 2048u;
+        const uint32_t s_pt = permutation_element2(x_pt | (y_pt << 16), WR, pa, pb, small_r);
+        const uint32_t s_dir = permutation_element2(x_dir | (y_dir << 16), WR, pc, pd, small_r);
+        sx_pt = (float)(s_pt & 0xffffu); sy_pt = (float)(s_pt >> 16); sx_dir = (float)(s_dir & 0xffffu); sy_dir = (float)(s_dir >> 16);
+    }
     // the jitters, in call order (corrmj.py:88-92)
     const float d_pick = next_lcg(s), d_prim = next_lcg(s), dx_pt = next_lcg(s), dy_pt = next_lcg(s), d_lobe = next_lcg(s), dx_dir = next_lcg(s), dy_dir = next_lcg(s);
     VertexSamples v;
     v.u_pick = strat(c, i_pick, d_pick); v.u_prim = strat(c, i_prim, d_prim); v.u_lobe = strat(c, i_lobe, d_lobe);
     {
-        const float ax = (float)(s_pt >> 16) + dx_pt, ay = (float)(s_pt & 0xffffu) + dy_pt;       // (sy + dx, sx + dy)
+        const float ax = sy_pt + dx_pt, ay = sx_pt + dy_pt;                                       // (sy + dx, sx + dy)
         v.u_pt.x = clampf(((float)x_pt + ax * c.inv_res_y) * c.inv_res_x, 0.0f, ZDR_ONE_MINUS_EPS);
         v.u_pt.y = clampf(((float)y_pt + ay * c.inv_res_x) * c.inv_res_y, 0.0f, ZDR_ONE_MINUS_EPS);
     }
     {
-        const float ax = (float)(s_dir >> 16) + dx_dir, ay = (float)(s_dir & 0xffffu) + dy_dir;
+        const float ax = sy_dir + dx_dir, ay = sx_dir + dy_dir;
         v.u_dir.x = clampf(((float)x_dir + ax * c.inv_res_y) * c.inv_res_x, 0.0f, ZDR_ONE_MINUS_EPS);
         v.u_dir.y = clampf(((float)y_dir + ay * c.inv_res_x) * c.inv_res_y, 0.0f, ZDR_ONE_MINUS_EPS);
     }

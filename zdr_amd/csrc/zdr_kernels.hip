@@ -1392,10 +1392,11 @@ __global__ void k_shading_dump(int mode, const float *in, uint32_t n, float *out
     if (mode == ZDR_SHADING_EVAL) {
         const f3 wo = ld3(a), wi = ld3(a + 3), diffuse = ld3(a + 7), ct = ld3(a + 10);
         const float roughness = a[6];
-        const GgxTerms g = ggx_terms(wo, wi, roughness);
+        const GgxWo gw = ggx_wo(wo, roughness);
+        const GgxTerms g = ggx_terms(gw, wo, wi);
         const f3 f = ggx_brdf_from(g, wi, diffuse);
         float dlnp;
-        const float dfdr = ggx_dfdr_from(g, wo, wi, roughness, dlnp);
+        const float dfdr = ggx_dfdr_from(g, gw, wo, wi, dlnp);
         const float4 gr = brdf_grad(wi.z * ZDR_INV_PI, dfdr, ct);
         r[0] = f.x; r[1] = f.y; r[2] = f.z; r[3] = ggx_pdf_from(g, wo, wi); r[4] = dfdr; r[5] = dlnp; r[6] = g.t; r[7] = g.D;
         r[8] = gr.x; r[9] = gr.y; r[10] = gr.z; r[11] = gr.w;
@@ -1404,13 +1405,14 @@ __global__ void k_shading_dump(int mode, const float *in, uint32_t n, float *out
         const float roughness = a[3], u_lobe = a[7];
         f2 u_dir; u_dir.x = a[8]; u_dir.y = a[9];
         const f3 wi_local = ggx_sample(wo, roughness, u_lobe, u_dir);
-        const GgxTerms g = ggx_terms(wo, wi_local, roughness);
+        const GgxWo gw = ggx_wo(wo, roughness);
+        const GgxTerms g = ggx_terms(gw, wo, wi_local);
         const float pdf = ggx_pdf_from(g, wo, wi_local);
         const f3 f = ggx_brdf_from(g, wi_local, diffuse);
         const float inv_p = rcp(pdf);
         const f3 w = f * inv_p;
         float dlnp;
-        const float dfdr = ggx_dfdr_from(g, wo, wi_local, roughness, dlnp);
+        const float dfdr = ggx_dfdr_from(g, gw, wo, wi_local, dlnp);
         r[0] = wi_local.x; r[1] = wi_local.y; r[2] = wi_local.z; r[3] = pdf; r[4] = w.x; r[5] = w.y; r[6] = w.z;
         r[7] = dfdr; r[8] = dlnp; r[9] = (wi_local.z < 1e-4f) ? 1.0f : 0.0f; r[10] = g.t; r[11] = g.D;
     } else {                                                   // ZDR_SHADING_FRAME
@@ -1599,7 +1601,7 @@ __global__ void k_sampler_dump(SamplerCfg C, const int32_t *q, uint32_t n, int n
 }
 
 // The same numbers drawn THE WAY THE PATH KERNELS DRAW THEM (shade_ctx / sample_bsdf, integrators.h): the pixel's next2f, then per
-// vertex all seven numbers at once through cmj_vertex_samples (two Kensler permutations per register) and the roulette draw through
+// vertex all seven numbers at once through cmj_vertex_samples (two Kensler permutations per register, four for a small strata grid) and the roulette draw through
 // cmj_next_with_index — whenever cmj_can_batch(C), which is every BASELINE configuration — else the calls one by one.
 template <int SK>
 __global__ void k_vertex_sampler_dump(SamplerCfg C, const int32_t *q, uint32_t n, int nvert, int rr_depth, int direct, float *out) {
@@ -1638,7 +1640,9 @@ __global__ void k_vertex_sampler_dump(SamplerCfg C, const int32_t *q, uint32_t n
 // as_kernels: 0 = the calls one by one, 1 = as the path kernels draw, 2 = as the direct kernels draw
 int zdr_launch_sampler_dump(const SamplerCfg &C, const int32_t *queries, uint32_t n, int32_t nvert, int32_t rr_depth, float *out, int as_path_kernels, int *batched, hipStream_t st) {
     const int direct = as_path_kernels == 2;
-    if (batched) *batched = (as_path_kernels && C.kind == ZDR_SAMPLER_CMJ && cmj_can_batch(C)) ? 1 : 0;
+    if (batched) *batched = (as_path_kernels && C.kind == ZDR_SAMPLER_CMJ && cmj_can_batch(C)) ? ((!direct && cmj_can_batch4(C)) ? 2 : 1) : 0;   // 2: a vertex's four strata in one pass.
+    // The kernel does not write its route: cmj_can_batch / cmj_can_batch4 here are the very predicates cmj_vertex_samples and shade_ctx branch on (sampler.h),
+    // so the report holds as long as they stay the only guards of those branches; whoever adds a condition there adds it to the predicate.
     if (n == 0) return 0;
     dim3 grid((n + 63) / 64);
     if (as_path_kernels) {
