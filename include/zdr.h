@@ -412,7 +412,8 @@ int zdr_scene_texel_tangents(zdr_scene *scene, int32_t material, int32_t tex_h, 
  * Determinism.  The same bits from run to run: no float atomic; the any-hit walks are per lane; where several lanes share a texel's
  * samples (lane j of 2^k takes s = begin + j, begin + j + 2^k, ...; k depends on tex_h x tex_w and the length of the range only) each
  * adds its samples in order and the lanes' sums are added in lane order.  Nothing depends on the launch grid.
- * No gradient is defined.
+ * Gradient.  Of the irradiance, in the lights' emissions and in the environment map: zdr_scene_texel_lighting_backward below.  None in
+ * position, normal or geometry, and none of the openness.
  *
  * The caller provides `workspace`, zdr_texel_lighting_workspace_bytes(tex_h, tex_w) bytes (0 = invalid size): a counter and the list of
  * texels to shade.  Three launches on `stream` — clear the counter, compact, shade — that never allocate and never synchronise, with a
@@ -432,6 +433,43 @@ typedef struct {
 size_t zdr_texel_lighting_workspace_bytes(int32_t tex_h, int32_t tex_w);   /* 0 = invalid size */
 int zdr_scene_texel_lighting(zdr_scene *scene, const zdr_texel_lighting_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
                              float *out /* DEVICE tex_h x tex_w x 4 */, void *workspace, void *stream);
+
+/* The adjoint of zdr_scene_texel_lighting's irradiance in the per-model emissions and in the environment map.  With the light list, the
+ * sampling tables and visibility held fixed — as zdr_render_backward_emission and zdr_render_backward_env hold them — the forward is
+ * exactly linear in both, and this is the transpose of that sparse linear map, with no approximation.
+ *
+ * Forward, for reference: for texel t and sample s, L = sample_light(p, u_pick, u_prim, u_pt), c = n . L.wi, w = c * rcp(max(L.pdf, 1e-4)).
+ * The sample is ACCEPTED iff s lies in the sample range, c > 0, L.eval has a positive component, the shadow segment (1e-4, L.dist) is free
+ * and L.eval * w is finite; irradiance[t] = (sum over the accepted samples of L.eval * w) * inv_spp.
+ * Adjoint.  With the cotangent d_out (DEVICE, tex_h x tex_w x 4) every accepted sample of a shaded texel t forms
+ * term[ch] = (d_out[t][ch] * inv_spp) * w, ch = r, g, b.
+ *   Mesh light.  The sample came from the front of mesh light l (the list index sample_light hands out, cos_light > 1e-4):
+ *   d_emission[light_insts[l]][ch] += term[ch].
+ *   Environment map.  The sample came from the map at uv: d_env[y][x][ch] += k * term[ch] on the four taps of the map's bilinear lookup,
+ *   k = (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy, fx fy.  Taps that the clamp puts on one texel receive both weights.  The alpha channel
+ *   is never touched.
+ * Both targets are ADDED INTO, as zdr_render_backward does: rows of models that are not lights keep their bits, and so do texels of the
+ * map that no sample reads.  d_out[..][3] (the openness' cotangent) is ignored.  The cotangent of a texel that is not shaded (reach != 1,
+ * a NaN in position or normal) is never read.  params is the forward's: max_distance plays no part, and the SAME seed is used (no
+ * seed + 1 as for zdr_render_backward).  The acceptance test is replayed with the values the scene holds: the emissions and the map must
+ * be those of the forward.
+ * Held fixed: which models emit, the alias tables and pdfs, visibility and the acceptance test itself.  For one seed the gradient is the
+ * exact derivative as long as no accepted light becomes dark in every component.
+ * Not promised: bit-stability.  The list of shaded texels varies in order from run to run and the sums use float atomics, so two runs
+ * may differ in the last bits.  (The forward's bits stay what they are.)
+ *
+ * d_emission (DEVICE, ninst x 3) and d_env (DEVICE, the map's h x w x 4) may each be NULL, not both; both in one call are allowed.
+ * workspace: zdr_texel_lighting_backward_workspace_bytes(scene, tex_h, tex_w) bytes (0 = invalid) — it takes the handle because the
+ * emission accumulator in it depends on the scene's current light count.  Four launches on `stream` — clear, compact, the adjoint of the
+ * shading kernel, the gather of the accumulator into d_emission — that never allocate and never synchronise: the call can be captured
+ * without a call before.  The scene is only read.
+ * Errors as zdr_scene_texel_lighting's (max_distance is not looked at), and ZDR_E_INVALID for: both targets NULL; d_env on a scene
+ * without a map; a workspace that overlaps an input or a target, targets that overlap the inputs or each other.  d_emission on a scene
+ * without lights is accepted and adds nothing. */
+size_t zdr_texel_lighting_backward_workspace_bytes(zdr_scene *scene, int32_t tex_h, int32_t tex_w);   /* 0 = invalid */
+int zdr_scene_texel_lighting_backward(zdr_scene *scene, const zdr_texel_lighting_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
+                                      const float *d_out /* DEVICE tex_h x tex_w x 4 */, float *d_emission /* DEVICE ninst x 3 or NULL */,
+                                      float *d_env /* DEVICE map h x w x 4 or NULL */, void *workspace, void *stream);
 
 /* Push-pull: fills the texels of a texture that a weight marks as unknown from the ones it marks as known, through a weighted pyramid — a
  * baker's seam padding — and the adjoint of that map with respect to the texture.  No scene handle.  The known texels come out bit for

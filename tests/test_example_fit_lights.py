@@ -1,0 +1,24 @@
+"""-m gpu: examples/fit_lights.py runs — a 32^2 texture, spp 8, 30 Adam steps, with and without --env — and ends with a loss below its
+first iteration's: the gradient of Scene.texel_lighting(emissions=, envmap=) points downhill through the autograd route."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+
+def load_example():
+    spec = importlib.util.spec_from_file_location("fit_lights", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "fit_lights.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("env", [False, True])
+def test_the_example_ends_with_a_loss_below_its_first(env):
+    losses = load_example().run(tex=32, spp=8, iters=30, env=env, verbose=False)
+    print(f"[fit lights] env {env}: loss {losses[0]:.4e} -> {losses[-1]:.4e} over {len(losses)} iterations")
+    assert len(losses) == 30 and np.isfinite(losses).all() and losses[0] > 0
+    assert losses[-1] < losses[0]

@@ -35,6 +35,9 @@ VIEWGRAD_LIB = os.path.join(CSRC, "libzdr_viewgrad.so")
 # UV tangents — the per-texel tangent buffer and the footprint ellipse of a texel's true patch (zdr_tangent.hip): a tenth, so that
 # libzdr_texel.so and libzdr_aniso.so keep exactly their three kernels each.
 TANGENT_LIB = os.path.join(CSRC, "libzdr_tangent.so")
+# The adjoint of the light baker in the emissions and the environment map (zdr_bakegrad.hip): an eleventh, so that libzdr_bake.so keeps
+# exactly its ten kernels.
+BAKEGRAD_LIB = os.path.join(CSRC, "libzdr_bakegrad.so")
 ARCH = "gfx950"
 
 
@@ -64,7 +67,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB, VIEWGRAD_LIB, TANGENT_LIB)):
+    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB, VIEWGRAD_LIB, TANGENT_LIB, BAKEGRAD_LIB)):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -120,6 +123,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # UV tangents, linked into libzdr_tangent.so, under the flags of zdr_aniso.hip without the atomics option (it has no float atomic):
         # the degenerate test is the rasteriser's and the ellipse the footprint kernel's, float for float (texel_setup.h, footprint.h)
         ("zdr_tangent.hip", ["-O3", "-fno-slp-vectorize", "-ffp-contract=off"]),
+        # the adjoint of the light baker, linked into libzdr_bakegrad.so, under the flags of zdr_bake.hip plus the atomics option: its
+        # sums into the emission accumulator and the environment map become global_atomic_add_f32
+        ("zdr_bakegrad.hip", ["-O3", "-fno-slp-vectorize", "-munsafe-fp-atomics"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -133,7 +139,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    tangent_obj = objs.pop()                                # (zdr_tangent.o: the last job)
+    bakegrad_obj = objs.pop()                               # (zdr_bakegrad.o: the last job)
+    tangent_obj = objs.pop()                                # (zdr_tangent.o: the one before)
     viewgrad_obj = objs.pop()                               # (zdr_viewgrad.o: the one before)
     plan_obj = objs.pop()                                   # (zdr_plan.o: the one before)
     aniso_obj = objs.pop()                                  # (zdr_aniso.o: the one before)
@@ -151,8 +158,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", PLAN_LIB, plan_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", VIEWGRAD_LIB, viewgrad_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", TANGENT_LIB, tangent_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BAKEGRAD_LIB, bakegrad_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake", "-lzdr_pushpull",
-              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan", "-lzdr_viewgrad", "-lzdr_tangent",
+              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan", "-lzdr_viewgrad", "-lzdr_tangent", "-lzdr_bakegrad",
               "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)

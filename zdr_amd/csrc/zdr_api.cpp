@@ -33,6 +33,8 @@
 #include "viewgrad.h"
 #define ZDR_TANGENT_LAUNCHER_REF __attribute__((weak))   // (csrc/tangent.h)
 #include "tangent.h"
+#define ZDR_BAKEGRAD_LAUNCHER_REF __attribute__((weak))  // (csrc/bakegrad.h)
+#include "bakegrad.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1695,6 +1697,59 @@ extern "C" int zdr_scene_texel_lighting(zdr_scene *s, const zdr_texel_lighting_p
     B.ntexels = (uint32_t)n; B.tex_w = p->tex_w; B.sample_begin = p->sample_begin; B.sample_end = p->sample_end;
     B.inv_spp = 1.0f / (float)p->spp; B.spp_f = (float)p->spp; B.max_distance = p->max_distance;
     if (zdr_launch_texel_lighting(S, s->accel_is_bvh, C, B, (hipStream_t)stream)) return fail(ZDR_E_HIP, "texel lighting launch failed");
+    return ZDR_OK;
+}
+
+// zdr_scene_texel_lighting_backward (include/zdr.h): the forward's checks, then the launches of zdr_bakegrad.hip on the caller's stream.
+// The handle is only read here too; the emission accumulator lives in the caller's workspace, so nothing is allocated.
+static size_t lgrad_list_bytes(int32_t tex_h, int32_t tex_w) { return ((size_t)tex_h * (size_t)tex_w * sizeof(uint32_t) + 15) & ~(size_t)15; }
+
+extern "C" size_t zdr_texel_lighting_backward_workspace_bytes(zdr_scene *s, int32_t tex_h, int32_t tex_w) {
+    if (!s) { fail(ZDR_E_INVALID, "null argument"); return 0; }
+    if (bake_check_size(tex_h, tex_w)) return 0;
+    const size_t acc = ((size_t)ZDR_LGRAD_COPIES * 3 * (size_t)std::max(s->ds.light_count, 0) * sizeof(float) + 15) & ~(size_t)15;
+    return ZDR_BAKE_HEADER_BYTES + lgrad_list_bytes(tex_h, tex_w) + acc;
+}
+
+extern "C" int zdr_scene_texel_lighting_backward(zdr_scene *s, const zdr_texel_lighting_params *p, const float *texel_aovs, const float *d_out,
+                                                 float *d_emission, float *d_env, void *workspace, void *stream) {
+    if (!s || !p || !texel_aovs || !d_out || !workspace) return fail(ZDR_E_INVALID, "null argument");
+    if (p->struct_size != sizeof(zdr_texel_lighting_params))
+        return fail(ZDR_E_INVALID, "zdr_texel_lighting_params.struct_size is " + std::to_string(p->struct_size) + ", this library expects " + std::to_string(sizeof(zdr_texel_lighting_params)));
+    if (!d_emission && !d_env) return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting_backward: neither d_emission nor d_env is given");
+    if (d_env && s->ds.env_count <= 0) return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting_backward: d_env is given, but the scene has no environment map");
+    if ((uintptr_t)texel_aovs % 16 || (uintptr_t)d_out % 16 || (uintptr_t)workspace % 16 || (uintptr_t)d_env % 16 || (uintptr_t)d_emission % 4)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting_backward: texel_aovs, d_out, d_env and workspace must be 16-byte aligned, d_emission 4-byte aligned");
+    if (int rc = bake_check_size(p->tex_h, p->tex_w)) return rc;
+    if (p->spp == 0) return fail(ZDR_E_INVALID, "spp must be positive");
+    if (p->sample_begin >= p->sample_end || p->sample_end > p->spp)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting_backward: the sample range [" + std::to_string(p->sample_begin) + ", " + std::to_string(p->sample_end) + ") is empty or not within [0, spp)");
+    const size_t n = (size_t)p->tex_h * (size_t)p->tex_w, wbytes = zdr_texel_lighting_backward_workspace_bytes(s, p->tex_h, p->tex_w);
+    const size_t ebytes = d_emission ? 3 * (size_t)s->ninst * sizeof(float) : 0;
+    const size_t mbytes = d_env ? 16 * (size_t)s->ds.env_h * (size_t)s->ds.env_w : 0;
+    if (denoise_overlap(workspace, wbytes, {{texel_aovs, 64 * n}, {d_out, 16 * n}, {d_emission, ebytes}, {d_env, mbytes}}))
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting_backward: the workspace must not overlap texel_aovs, d_out, d_emission or d_env");
+    if (d_emission && denoise_overlap(d_emission, ebytes, {{texel_aovs, 64 * n}, {d_out, 16 * n}, {d_env, mbytes}}))
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting_backward: d_emission must not overlap texel_aovs, d_out or d_env");
+    if (d_env && denoise_overlap(d_env, mbytes, {{texel_aovs, 64 * n}, {d_out, 16 * n}}))
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_lighting_backward: d_env must not overlap texel_aovs or d_out");
+    SamplerCfg C;
+    if (int rc = make_sampler_cfg(s, p->sampler, p->seed, p->spp, C)) return rc;
+    if (!zdr_launch_texel_lighting_backward)                         // (weak: csrc/bakegrad.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the texture-space lighting gradient kernels (zdr_bakegrad.hip)");
+    const bool emit = d_emission && s->ds.light_count > 0;           // a scene without lights: accepted, nothing to add
+    if (!emit && !d_env) return ZDR_OK;
+    HIPCHK(hipSetDevice(s->device));
+    DScene S = s->ds;
+    S.shadow_pairs = ~0ull;      // every pair, as the forward
+    LgradArgs G;
+    G.texels = (const float4 *)texel_aovs; G.d_out = (const float4 *)d_out; G.d_env = d_env; G.d_emission = emit ? d_emission : nullptr;
+    G.count = (uint32_t *)workspace; G.list = (uint32_t *)((char *)workspace + ZDR_BAKE_HEADER_BYTES);
+    G.acc = emit ? (float *)((char *)workspace + ZDR_BAKE_HEADER_BYTES + lgrad_list_bytes(p->tex_h, p->tex_w)) : nullptr;
+    G.ntexels = (uint32_t)n; G.tex_w = p->tex_w; G.sample_begin = p->sample_begin; G.sample_end = p->sample_end;
+    G.inv_spp = 1.0f / (float)p->spp;
+    if (int rc = zdr_launch_texel_lighting_backward(S, s->accel_is_bvh, C, G, (hipStream_t)stream))
+        return fail(ZDR_E_HIP, "texel lighting backward: launch " + std::to_string(rc / 256) + " of 4 failed: " + hipGetErrorString((hipError_t)(rc % 256)));
     return ZDR_OK;
 }
 

@@ -190,7 +190,8 @@ class TexelLighting:
     """Texture-space lighting of ``Scene.texel_lighting`` (include/zdr.h, zdr_scene_texel_lighting): ``data`` is the (H, W, 4) tensor of
     one material's texels, the shape of a material, so ``denoise`` filters it with ``TexelAovs.as_guides()``.  ``irradiance`` (H, W, 3):
     direct irradiance on the side the texel's normal points to; ``openness`` (H, W): the open fraction of the cosine-weighted hemisphere,
-    up to ``max_distance``.  Four zeros where ``reach`` is 0.  No gradient."""
+    up to ``max_distance``.  Four zeros where ``reach`` is 0.  ``irradiance`` carries a gradient in the emissions and the environment
+    map when ``texel_lighting`` was given ``emissions=`` or ``envmap=``; ``openness`` never does."""
 
     def __init__(self, data):
         self.data = data
@@ -752,15 +753,100 @@ class Scene:
         N.check(N.lib().zdr_scene_texel_lighting(self._handle, C.byref(p), texel_data.data_ptr(), out.data_ptr(), workspace.data_ptr(), self._stream()))
         return out
 
-    def texel_lighting(self, material, index=0, *, spp=16, seed=0, samples=None, max_distance=None, texels=None) -> TexelLighting:
+    def texel_lighting_backward(self, texel_data, d_out, *, spp, seed=0, samples=None, sampler=None, d_emission=None, d_env=None, workspace=None):
+        """The adjoint of ``texel_lighting_forward``'s irradiance (include/zdr.h, zdr_scene_texel_lighting_backward): with the cotangent
+        ``d_out`` (H, W, 4) — float 3, the openness', is ignored — ADDS the gradient of the lights' emissions into ``d_emission``, a
+        float32 (ninst, 3) tensor, and that of the environment map into ``d_env``, a prepared float32 tensor of the map's size; one of
+        the two at least, both in one call are allowed.  ``spp``, ``seed``, ``samples`` and ``sampler`` are the forward's (the same
+        seed), and the scene must hold the forward's emissions and map: the acceptance test is replayed with them.  Not bit-stable
+        from run to run (float atomics).  Only enqueues, on torch's current stream.  Returns (d_emission, d_env)."""
+        if texel_data.ndim != 3 or texel_data.shape[2] != N.AOV_CHANNELS or texel_data.dtype != torch.float32 or texel_data.device != self.device:
+            raise ValueError(f"texel_data must be a float32 (H, W, {N.AOV_CHANNELS}) tensor on {self.device}")
+        texel_data = texel_data.detach().contiguous()
+        H, W = int(texel_data.shape[0]), int(texel_data.shape[1])
+        if not isinstance(d_out, torch.Tensor) or tuple(d_out.shape) != (H, W, 4) or d_out.dtype != torch.float32 or d_out.device != self.device:
+            raise ValueError(f"d_out must be a float32 ({H}, {W}, 4) tensor on {self.device}")
+        d_out = d_out.detach().contiguous()
+        if d_emission is None and d_env is None:
+            raise ValueError("texel_lighting_backward needs d_emission, d_env or both")
+        if d_emission is not None:
+            self._check_d_emission(d_emission, None)
+        if d_env is not None:
+            self._check_d_env(d_env)
+        sampler = self.sampler if sampler is None else sampler
+        if sampler not in N.SAMPLERS:
+            raise ValueError(f"unknown sampler {sampler!r}")
+        if sampler == "pmj02bn":
+            self._ensure_pmj_tables()
+        begin, end = (0, int(spp)) if samples is None else (int(samples[0]), int(samples[1]))
+        if not 0 <= begin < end <= int(spp):
+            raise ValueError(f"samples {(begin, end)} must be a non-empty subrange of [0, {int(spp)})")
+        workspace = self._workspace(workspace, int(N.lib().zdr_texel_lighting_backward_workspace_bytes(self._handle, H, W)))
+        p = N.TexelLightingParams()
+        p.struct_size = C.sizeof(N.TexelLightingParams)
+        p.tex_h, p.tex_w, p.spp, p.seed, p.sampler = H, W, int(spp), int(seed) & 0xFFFFFFFF, N.SAMPLERS[sampler]
+        p.sample_begin, p.sample_end = begin, end
+        p.max_distance = 1e30                              # (not looked at)
+        N.check(N.lib().zdr_scene_texel_lighting_backward(self._handle, C.byref(p), texel_data.data_ptr(), d_out.data_ptr(),
+                                                          None if d_emission is None else d_emission.data_ptr(),
+                                                          None if d_env is None else d_env.data_ptr(), workspace.data_ptr(), self._stream()))
+        return d_emission, d_env
+
+    class TexelLightingOperator(torch.autograd.Function):
+        """texel_lighting() with ``emissions=`` and / or ``envmap=``, modelled on RenderOperator: detached copies become the scene's
+        values in the forward, and the backward applies that snapshot again before the native call."""
+        @staticmethod
+        def forward(ctx, emissions, env, self, texel_data, spp, seed, samples, max_distance):
+            if env is not None:
+                env = env.detach().clone()
+                self.set_envmap_texture(env)
+            if emissions is not None:
+                self.set_emission_values(emissions.detach().clone())
+            ctx.env = env
+            ctx.with_emissions = emissions is not None
+            ctx.scene = weakref.ref(self)
+            ctx.texel_data = texel_data.detach()
+            ctx.args = (spp, seed, samples, self.sampler)
+            ctx.emissions = self.emissions
+            return self.texel_lighting_forward(texel_data, spp=spp, seed=seed, samples=samples, max_distance=max_distance)
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            scene = ctx.scene()
+            if scene.emissions is not ctx.emissions:       # the light list, then its values: the forward's snapshot
+                scene.update_lights(ctx.emissions)
+            spp, seed, samples, sampler = ctx.args
+            d_emission = d_env = None
+            if ctx.with_emissions:
+                scene._apply_emission_values(ctx.emissions.values)
+                d_emission = torch.zeros_like(ctx.emissions.values)
+            if ctx.env is not None:
+                scene.set_envmap_texture(ctx.env)
+                d_env = torch.zeros_like(ctx.env)
+            g = grad_output.to(device=scene.device, dtype=torch.float32).contiguous()
+            scene.texel_lighting_backward(ctx.texel_data, g, spp=spp, seed=seed, samples=samples, sampler=sampler, d_emission=d_emission, d_env=d_env)
+            return d_emission, d_env, None, None, None, None, None, None
+
+    def texel_lighting(self, material, index=0, *, spp=16, seed=0, samples=None, max_distance=None, texels=None, emissions=None, envmap=None) -> TexelLighting:
         """Whether any light reaches each texel of ``material[index]``: a ``TexelLighting`` whose ``data`` is the (H, W, 4) tensor of
         include/zdr.h, zdr_scene_texel_lighting, at that material's size — ``irradiance`` and ``openness``.  ``material`` and ``index``
         are taken as ``texel_aovs`` takes them; ``texels``: a ``TexelAovs`` already computed for them (without it one is computed
         here).  The lights are the scene's current ones (``update_lights``, ``set_emission_values``), the environment map included.
-        No gradient."""
+
+        ``emissions``: a float32 (ninst, 3) tensor on the GPU, ``envmap``: a float32 (H, 2H, 3|4) or (H, H, 3|4) tensor on the GPU, as
+        ``render`` takes them — here both may be given in one call.  They become the scene's values, and ``irradiance`` is then
+        differentiable in them (include/zdr.h, zdr_scene_texel_lighting_backward): the light list, the sampling tables and visibility
+        are held fixed, so for one seed the gradient is exact; its sums use float atomics and may differ in the last bits from run to
+        run.  ``openness`` has no gradient.  Without either keyword the call builds no autograd node and returns the bits of
+        ``texel_lighting_forward``."""
+        if emissions is not None:
+            check_emissions(emissions, self.inst_count, self.device)
+        env = None if envmap is None else self._prepare_envmap(envmap)
         if texels is None:
             texels = self.texel_aovs(material, index)
-        return TexelLighting(self.texel_lighting_forward(texels.data, spp=spp, seed=seed, samples=samples, max_distance=max_distance))
+        if emissions is None and env is None:
+            return TexelLighting(self.texel_lighting_forward(texels.data, spp=spp, seed=seed, samples=samples, max_distance=max_distance))
+        return TexelLighting(Scene.TexelLightingOperator.apply(emissions, env, self, texels.data, spp, seed, samples, max_distance))
 
     # ------------------------------------------------------------- texture-space views
     def texel_view_forward(self, texel_data, res, *, camera=None, out=None, workspace=None):
