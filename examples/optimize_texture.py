@@ -32,6 +32,10 @@ texel's on-screen size: scene.texel_project(..., filter="mip")), so that a texel
 (filter="aniso"), which does not over-blur the walls seen at a grazing angle; --footprint-patch uv lets that ellipse follow the UV
 mapping (the texel as the parallelogram of its UV tangents: scene.texel_project(..., footprint_patch="uv")) where a texture is not
 square or a chart is stretched.
+--init-bounces K (with --init-from-target) divides by the direct PLUS the bounced irradiance instead: albedo = pi * color / (direct +
+bounced(albedo)), the bounced term being scene.texel_bounce with K Lambertian bounces.  It depends on the albedo, so the division is
+iterated --init-rounds J times from a grey albedo.  With --save-lighting it also writes bounced.png and prints the share of the reached
+texels without any light before and after the bounced term.
 """
 import argparse
 import math
@@ -79,7 +83,7 @@ def texel_prior_loss(material, f, guides):
 
 def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0, verbose=True, albedo_smoothness=0.0, denoise=False,
         texel_prior=0.0, mask_unreached=False, save_lighting=False, fill_unreached=False, fill_param=False, init_from_target=False,
-        project_filter="bilinear", footprint_patch="square"):
+        project_filter="bilinear", footprint_patch="square", init_bounces=0, init_rounds=2):
     scene = Scene([(os.path.join(ASSETS, "cboxuv.obj"), None, float3(0.0)),
                    (os.path.join(ASSETS, "cbox-light.obj"), None, float3(17, 12, 4))], integrator=integrator)
     scene.camera = Camera(fov=50 / 180 * 3.1415926, origin=float3(-0.2, 2.6, 6.0), target=float3(-0.2, 2.6, -2.5), up=float3(0.0, 1.0, 0.0))
@@ -96,10 +100,15 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
         with torch.no_grad():
             photo = scene.texel_project([(scene.camera, image_gt)], theta.detach(), texels=texels, filter=project_filter, footprint_patch=footprint_patch)
             irradiance = scene.texel_lighting(theta.detach(), spp=max(64, spp), texels=texels).irradiance
-            known = (photo.weight > 0) & (irradiance.sum(-1) > 0)
-            guess = torch.zeros_like(theta)
-            guess[..., :3] = (math.pi * photo.color[..., :3] / irradiance.clamp_min(1e-8)).clamp(1e-3, 1.0)
-            theta[..., :3] = push_pull(guess, known)[..., :3].clamp(1e-3, 1.0)
+            albedo = theta.detach().clone()
+            albedo[..., :3] = 0.5                                  # the bounced light depends on the albedo: start grey, iterate
+            for _ in range(max(int(init_rounds), 1) if init_bounces > 0 else 1):
+                total = irradiance if init_bounces <= 0 else irradiance + scene.texel_bounce(albedo, spp=max(64, spp), bounces=init_bounces, texels=texels).irradiance
+                known = (photo.weight > 0) & (total.sum(-1) > 0)
+                guess = torch.zeros_like(theta)
+                guess[..., :3] = (math.pi * photo.color[..., :3] / total.clamp_min(1e-8)).clamp(1e-3, 1.0)
+                albedo[..., :3] = push_pull(guess, known)[..., :3].clamp(1e-3, 1.0)
+            theta[..., :3] = albedo[..., :3]
             reached = texels.reach == 1
             if verbose:
                 print(f"initialised from the target: the camera sees {int((reached & (photo.weight > 0)).sum())} of {int(reached.sum())} reached texels "
@@ -133,6 +142,11 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
         if verbose:
             print(f"texture-space lighting: {int(unlit.sum())} of {int(reached.sum())} reached texels ({float(unlit.sum()) / max(int(reached.sum()), 1):.1%}) "
                   "were reached by no light sample")
+        bounce = scene.texel_bounce(material.detach(), spp=max(64, spp), bounces=init_bounces, texels=texels) if init_bounces > 0 else None
+        if bounce is not None and verbose:
+            dark = unlit & (bounce.irradiance.sum(-1) == 0)
+            print(f"with {init_bounces} bounces: {int(dark.sum())} of {int(reached.sum())} reached texels ({float(dark.sum()) / max(int(reached.sum()), 1):.1%}) "
+                  f"receive no light at all (before the bounced term: {float(unlit.sum()) / max(int(reached.sum()), 1):.1%})")
     if out:
         os.makedirs(out, exist_ok=True)
         save_png(os.path.join(out, "target.png"), image_gt)
@@ -144,6 +158,8 @@ def run(iters=200, res=256, spp=16, tex=256, out=None, integrator="path", seed=0
         if save_lighting:
             save_png(os.path.join(out, "irradiance.png"), light.irradiance / light.irradiance.max().clamp_min(1e-8))
             save_png(os.path.join(out, "openness.png"), light.openness[..., None].expand(-1, -1, 3))
+            if bounce is not None:
+                save_png(os.path.join(out, "bounced.png"), bounce.irradiance / light.irradiance.max().clamp_min(1e-8))
         duvdxy = scene.render_duvdxy(material.detach(), res=(res, res), spp=16)            # screen -> texture Jacobian (example.py)
         footprint = torch.det(duvdxy.reshape(res, res, 2, 2)).abs() * tex * tex
         Image.fromarray((footprint.clamp(0, 1) ** 0.454 * 255).to(torch.uint8).cpu().numpy()).save(os.path.join(out, "footprints.png"))
@@ -168,8 +184,10 @@ if __name__ == "__main__":
     ap.add_argument("--init-from-target", action="store_true")
     ap.add_argument("--project-filter", choices=("bilinear", "mip", "aniso"), default="bilinear")
     ap.add_argument("--footprint-patch", choices=("square", "uv"), default="square")
+    ap.add_argument("--init-bounces", type=int, default=0)
+    ap.add_argument("--init-rounds", type=int, default=2)
     a = ap.parse_args()
     run(a.iters, a.res, a.spp, a.tex, a.out, a.integrator, albedo_smoothness=a.albedo_smoothness, denoise=a.denoise,
         texel_prior=a.texel_prior, mask_unreached=a.mask_unreached, save_lighting=a.save_lighting, fill_unreached=a.fill_unreached,
         fill_param=a.fill_param, init_from_target=a.init_from_target, project_filter=a.project_filter,
-        footprint_patch=a.footprint_patch)
+        footprint_patch=a.footprint_patch, init_bounces=a.init_bounces, init_rounds=a.init_rounds)

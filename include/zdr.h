@@ -471,6 +471,83 @@ int zdr_scene_texel_lighting_backward(zdr_scene *scene, const zdr_texel_lighting
                                       const float *d_out /* DEVICE tex_h x tex_w x 4 */, float *d_emission /* DEVICE ninst x 3 or NULL */,
                                       float *d_env /* DEVICE map h x w x 4 or NULL */, void *workspace, void *stream);
 
+/* Bounced light: the irradiance that reaches a texel after at least one bounce, and the share of its hemisphere that can bounce light at
+ * all — a Lambertian random walk of `bounces` = K vertices from every texel.  albedo / pi x (zdr_scene_texel_lighting's irradiance + this
+ * irradiance) is the Lambertian radiosity of the texel.  Forward only: nothing here has a gradient.
+ *
+ * Inputs.  texel_aovs (DEVICE, tex_h x tex_w x 16) has the layout of zdr_scene_texel_aovs; floats 4..6 (normal n), 8..10 (position p) and
+ * 12 (reach) are read.  A texel is shaded iff reach == 1 and neither n nor p holds a NaN; every other texel is four zeros.  The materials
+ * are a packed buffer with dims and nmat as zdr_render_aovs takes them; the slot table is the one the scene holds
+ * (zdr_scene_set_material_slots).  ALL materials are read, at the bounce vertices.  The lights are the scene's current ones, the
+ * environment map included.
+ * Draws.  For texel (x, y) and sample s the sampler state is the baker's: sampler_make(cfg, x, y, perm_seed, s) with perm_seed =
+ * xxhash32_4(x, y, seed, 0) for CMJ and 0 for pmj02bn.  u_ao = next2 comes first — the very openness direction of zdr_scene_texel_lighting
+ * for the same seed.  Vertex k = 1 .. K then draws u_pick = next, u_prim = next, u_pt = next2, u_lobe = next, u_dir = next2; u_lobe is
+ * drawn and ignored.  These are floats 2 + 7 (k - 1) .. of zdr_sampler_dump with nvert = K and rr_depth >= K.  The last vertex draws
+ * neither u_lobe nor u_dir.  There is no Russian roulette; 1 <= bounces <= 8.
+ * Walk of one sample.  beta = (1, 1, 1), dir = to_world(make_onb(n), lobe(u_ao)) with lobe(u) = (r cos phi, r sin phi, sqrt(1 - u.x)),
+ * r = sqrt(u.x), phi = 2 pi u.y.  The first segment leaves p over (1e-4, 1e30): the openness ray.  Later segments leave
+ * offset_ray_origin(p_k, ng_k) over (0, 1e30), as the direct integrator sends its BSDF ray.  For k = 1 .. K:
+ *   1. a NaN in dir ends the walk;
+ *   2. h = the closest hit of the segment; a miss ends the walk.  Light that a segment sees directly, the environment included, is the
+ *      previous vertex's direct light and is counted by the light samples only;
+ *   3. it = surface_interact(h); the walk ends if dot(-dir, it.ng) < 1e-4 or dot(-dir, it.ns) < 1e-4 (the integrators' one-sidedness);
+ *   4. the walk ends if the model has no material (slot < 0: a light or a blocker);
+ *   5. if k = 1 the sample counts for `surface`;
+ *   6. beta *= read_bsdf(material of the slot, it.uv).rgb.  Roughness is ignored: with cosine sampling a Lambertian bounce's
+ *      f cos / pdf is the albedo, so no pi appears anywhere;
+ *   7. one light sample: L = sample_light(it.p, u_pick, u_prim, u_pt), c = it.ns . L.wi.  It is accepted iff c > 0, L.eval has a positive
+ *      component, the segment from it.p towards L.wi over (1e-4, L.dist) is free and add = (beta * L.eval) * (c * rcp(max(L.pdf, 1e-4)))
+ *      is finite.  An accepted sample gives E += add;
+ *   8. dir = to_world(make_onb(it.ns), lobe(u_dir)); the walk ends if dot(dir, it.ng) < 1e-4 or the lobe's z is below 1e-4.
+ * Vertex k's add does not depend on K (prefix property).
+ * Output.  out (DEVICE, tex_h x tex_w x 4):
+ *   floats 0..2        irradiance         (sum over s of E_s) / spp: the irradiance arriving after 1 .. K bounces
+ *   float 3            surface            first segments that landed on the front of a model with a material, over spp
+ * Sample range.  [sample_begin, sample_end) is a subrange of [0, spp), and the outputs of disjoint ranges add up.
+ * Determinism.  Lanes per texel follow the rule of zdr_scene_texel_lighting — 2^k lanes, k = zdr_texel_bounce_lanes_shift(tex_h, tex_w,
+ * sample_begin, sample_end), from the texture's size and the length of the range alone; lane j takes s = begin + j, begin + j + 2^k, ... —
+ * and a lane adds every accepted add into one accumulator, s ascending and, within s, k ascending.  Lane 0 of a texel then adds the lanes'
+ * sums in lane order and multiplies by 1 / spp (IEEE division); surface is a count divided by spp, correctly rounded.  The same bits
+ * from run to run, whatever the grid and the order of the list: no float atomic, and the walks are per lane.
+ * Limits.  Lambertian bounces only — GGX is ignored, so on glossy materials this is not zdr_render_forward's radiance.  K truncates: the
+ * result is biased low by the bounces beyond it.  With the same seed the walk shares u_ao with the openness ray, and vertex 1 shares
+ * its light draws with zdr_scene_texel_lighting's own sample: either output is unbiased, but the two are correlated.
+ *
+ * workspace: zdr_texel_bounce_workspace_bytes(tex_h, tex_w) bytes (0 = invalid size): a counter and the list of texels to shade.  Three
+ * launches on `stream` — clear the counter, compact (one returning atomic per workgroup), shade — that never allocate and never
+ * synchronise; the material table travels as a kernel argument, so the call can be captured in a HIP graph without a call before (on a
+ * scene whose slot table has been set: a table that was never set would have to be created, which a capture refuses).
+ * ZDR_E_INVALID: a null or misaligned (16 bytes) pointer, struct_size other than sizeof(zdr_texel_bounce_params), a size <= 0, spp = 0,
+ * a sample range that is empty or not within [0, spp), bounces outside [1, 8], nmat outside [1, ZDR_MAX_MATERIALS], a slot beyond nmat,
+ * an unknown sampler, an output that overlaps the workspace or an input, a workspace that overlaps an input.  ZDR_E_UNSUPPORTED: more
+ * than 2^26 texels; pmj02bn without tables; a library linked without these kernels (zdr_bounce.hip).
+ *
+ * zdr_texel_bounce_dump serves the tests, in the tradition of zdr_path_dump: queries (DEVICE, n x 3 int32 {x, y, s}), one lane per query,
+ * the same walk with a recorder.  A row of out is 4 + 12 K floats: the header {bits(nvert), surface, 0, 0}, then per vertex
+ * {bits(inst), bits(prim), u, v, bits(flags), beta.rgb after the vertex, add.rgb, 0} — instance, input triangle and barycentrics as
+ * zdr_trace_closest reports a hit.  Flag bits: 0 shaded (front and has a material), 1 the light sample is lit (c > 0 and eval positive),
+ * 2 the shadow segment is free, 3 add accepted, 4 the walk goes on to a next vertex (never set at vertex K).  A vertex where the walk
+ * ends is recorded with its flags; nvert counts the recorded vertices (the segments that hit).  A query outside the texture or the
+ * sample range, or of a texel that is not shaded, is a row of zeros. */
+typedef struct {
+    uint32_t struct_size;              /* = sizeof(zdr_texel_bounce_params) */
+    int32_t tex_h, tex_w;
+    uint32_t spp;
+    uint32_t seed;
+    int32_t sampler;                   /* ZDR_SAMPLER_* */
+    uint32_t sample_begin, sample_end;
+    int32_t bounces;                   /* K, 1 .. 8 */
+} zdr_texel_bounce_params;
+size_t zdr_texel_bounce_workspace_bytes(int32_t tex_h, int32_t tex_w);   /* 0 = invalid size */
+int zdr_texel_bounce_lanes_shift(int32_t tex_h, int32_t tex_w, uint32_t sample_begin, uint32_t sample_end);   /* k of 2^k lanes per texel; -1 = invalid */
+int zdr_scene_texel_bounce(zdr_scene *scene, const zdr_texel_bounce_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
+                           const float *materials /* DEVICE packed */, const int32_t *dims /* HOST nmat x {h, w} */, uint32_t nmat,
+                           float *out /* DEVICE tex_h x tex_w x 4 */, void *workspace, void *stream);
+int zdr_texel_bounce_dump(zdr_scene *scene, const zdr_texel_bounce_params *params, const float *texel_aovs, const float *materials,
+                          const int32_t *dims, uint32_t nmat, const int32_t *queries /* DEVICE n x 3 */, uint32_t n,
+                          float *out /* DEVICE n x (4 + 12 bounces) */, void *stream);
+
 /* Push-pull: fills the texels of a texture that a weight marks as unknown from the ones it marks as known, through a weighted pyramid — a
  * baker's seam padding — and the adjoint of that map with respect to the texture.  No scene handle.  The known texels come out bit for
  * bit as they went in; with the weights held fixed the map is linear in the texture, so y = K x is also a reparameterisation of a

@@ -7,8 +7,8 @@ from .project import (texel_footprint_forward, texel_gather, texel_gather_aniso_
 from .plan import GatherPlan, gather_plan
 from .pushpull import push_pull
 from .mathtypes import Camera, float3, float4x4
-from .render import Aovs, Scene, TexelAovs, TexelFootprint, TexelLighting, TexelProjection, TexelTangents, TexelView
+from .render import Aovs, Scene, TexelAovs, TexelBounce, TexelFootprint, TexelLighting, TexelProjection, TexelTangents, TexelView
 
 __all__ = ["Scene", "Aovs", "TexelAovs", "TexelLighting", "Camera", "float3", "float4x4", "denoise", "push_pull",
            "TexelView", "TexelProjection", "texel_gather", "texel_gather_forward", "texel_gather_backward",
-           "GatherPlan", "gather_plan", "texel_gather_dview", "TexelTangents"]
+           "GatherPlan", "gather_plan", "texel_gather_dview", "TexelTangents", "TexelBounce"]

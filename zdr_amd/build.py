@@ -38,6 +38,8 @@ TANGENT_LIB = os.path.join(CSRC, "libzdr_tangent.so")
 # The adjoint of the light baker in the emissions and the environment map (zdr_bakegrad.hip): an eleventh, so that libzdr_bake.so keeps
 # exactly its ten kernels.
 BAKEGRAD_LIB = os.path.join(CSRC, "libzdr_bakegrad.so")
+# The bounced-light baker (zdr_bounce.hip): a twelfth, so that libzdr_bake.so keeps exactly its ten kernels too.
+BOUNCE_LIB = os.path.join(CSRC, "libzdr_bounce.so")
 ARCH = "gfx950"
 
 
@@ -67,7 +69,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB, VIEWGRAD_LIB, TANGENT_LIB, BAKEGRAD_LIB)):
+    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB, VIEWGRAD_LIB, TANGENT_LIB, BAKEGRAD_LIB, BOUNCE_LIB)):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -126,6 +128,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # the adjoint of the light baker, linked into libzdr_bakegrad.so, under the flags of zdr_bake.hip plus the atomics option: its
         # sums into the emission accumulator and the environment map become global_atomic_add_f32
         ("zdr_bakegrad.hip", ["-O3", "-fno-slp-vectorize", "-munsafe-fp-atomics"]),
+        # the bounced-light baker, linked into libzdr_bounce.so, under the flags of zdr_bake.hip (no float atomic here either): the
+        # closest-hit and any-hit walks, surface_interact, the material lookup and sample_light of the path kernels
+        ("zdr_bounce.hip", ["-O3", "-fno-slp-vectorize"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -139,7 +144,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    bakegrad_obj = objs.pop()                               # (zdr_bakegrad.o: the last job)
+    bounce_obj = objs.pop()                                 # (zdr_bounce.o: the last job)
+    bakegrad_obj = objs.pop()                               # (zdr_bakegrad.o: the one before)
     tangent_obj = objs.pop()                                # (zdr_tangent.o: the one before)
     viewgrad_obj = objs.pop()                               # (zdr_viewgrad.o: the one before)
     plan_obj = objs.pop()                                   # (zdr_plan.o: the one before)
@@ -159,8 +165,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", VIEWGRAD_LIB, viewgrad_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", TANGENT_LIB, tangent_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BAKEGRAD_LIB, bakegrad_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BOUNCE_LIB, bounce_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake", "-lzdr_pushpull",
-              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan", "-lzdr_viewgrad", "-lzdr_tangent", "-lzdr_bakegrad",
+              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan", "-lzdr_viewgrad", "-lzdr_tangent", "-lzdr_bakegrad", "-lzdr_bounce",
               "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -35,6 +35,8 @@
 #include "tangent.h"
 #define ZDR_BAKEGRAD_LAUNCHER_REF __attribute__((weak))  // (csrc/bakegrad.h)
 #include "bakegrad.h"
+#define ZDR_BOUNCE_LAUNCHER_REF __attribute__((weak))    // (csrc/bounce.h)
+#include "bounce.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1750,6 +1752,92 @@ extern "C" int zdr_scene_texel_lighting_backward(zdr_scene *s, const zdr_texel_l
     G.inv_spp = 1.0f / (float)p->spp;
     if (int rc = zdr_launch_texel_lighting_backward(S, s->accel_is_bvh, C, G, (hipStream_t)stream))
         return fail(ZDR_E_HIP, "texel lighting backward: launch " + std::to_string(rc / 256) + " of 4 failed: " + hipGetErrorString((hipError_t)(rc % 256)));
+    return ZDR_OK;
+}
+
+// ------------------------------------------------------------------- bounced light
+// zdr_scene_texel_bounce (include/zdr.h): argument checks, then the three launches of zdr_bounce.hip on the caller's stream.  The handle
+// is only read — the records, the acceleration structure, the light table, the environment tables and the slot table as they are — and
+// the material table travels as a kernel argument, so nothing is allocated and the call can be captured without a call before.  A scene
+// whose slot table was never set has no material anywhere: every walk ends at its first vertex, and only then would the table have to
+// be created — refused while capturing, as everywhere.
+static int bounce_check_size(int32_t tex_h, int32_t tex_w) {
+    if (tex_h <= 0 || tex_w <= 0) return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce: the texture size must be positive");
+    if ((uint64_t)tex_h * (uint64_t)tex_w > ZDR_BOUNCE_MAX_TEXELS) return fail(ZDR_E_UNSUPPORTED, "zdr_scene_texel_bounce: more than 2^26 texels");
+    return ZDR_OK;
+}
+
+extern "C" size_t zdr_texel_bounce_workspace_bytes(int32_t tex_h, int32_t tex_w) {
+    if (bounce_check_size(tex_h, tex_w)) return 0;
+    return ZDR_BOUNCE_HEADER_BYTES + (((size_t)tex_h * (size_t)tex_w * sizeof(uint32_t) + 15) & ~(size_t)15);
+}
+
+extern "C" int zdr_texel_bounce_lanes_shift(int32_t tex_h, int32_t tex_w, uint32_t sample_begin, uint32_t sample_end) {
+    if (bounce_check_size(tex_h, tex_w)) return -1;
+    if (sample_begin >= sample_end) { fail(ZDR_E_INVALID, "zdr_texel_bounce_lanes_shift: the sample range is empty"); return -1; }
+    return zdr_bounce_lanes_shift((uint32_t)tex_h * (uint32_t)tex_w, sample_end - sample_begin);
+}
+
+// the checks and the arguments both entry points share
+static int bounce_prepare(zdr_scene *s, const zdr_texel_bounce_params *p, const float *texel_aovs, const float *materials, const int32_t *dims, uint32_t nmat,
+                          hipStream_t st, SamplerCfg &C, BounceArgs &B, MaterialTable &mt) {
+    if (!s || !p || !texel_aovs) return fail(ZDR_E_INVALID, "null argument");
+    if (p->struct_size != sizeof(zdr_texel_bounce_params))
+        return fail(ZDR_E_INVALID, "zdr_texel_bounce_params.struct_size is " + std::to_string(p->struct_size) + ", this library expects " + std::to_string(sizeof(zdr_texel_bounce_params)));
+    if (int rc = check_table_args(materials != nullptr, dims, nmat)) return rc;
+    if ((uintptr_t)texel_aovs % 16 || (uintptr_t)materials % 16) return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce: texel_aovs and materials must be 16-byte aligned");
+    if (int rc = bounce_check_size(p->tex_h, p->tex_w)) return rc;
+    if (p->spp == 0) return fail(ZDR_E_INVALID, "spp must be positive");
+    if (p->sample_begin >= p->sample_end || p->sample_end > p->spp)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce: the sample range [" + std::to_string(p->sample_begin) + ", " + std::to_string(p->sample_end) + ") is empty or not within [0, spp)");
+    if (p->bounces < 1 || p->bounces > ZDR_BOUNCE_MAX_BOUNCES)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce: bounces is " + std::to_string(p->bounces) + ", must lie in [1, " + std::to_string(ZDR_BOUNCE_MAX_BOUNCES) + "]");
+    if (int rc = make_sampler_cfg(s, p->sampler, p->seed, p->spp, C)) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    if (int rc = make_material_table(s, dims, nmat, stream_is_capturing(st), st, mt)) return rc;
+    memset(&B, 0, sizeof B);
+    B.texels = (const float4 *)texel_aovs; B.materials = (const float4 *)materials;
+    B.ntexels = (uint32_t)((size_t)p->tex_h * (size_t)p->tex_w); B.tex_w = p->tex_w; B.sample_begin = p->sample_begin; B.sample_end = p->sample_end;
+    B.inv_spp = 1.0f / (float)p->spp; B.spp_f = (float)p->spp; B.bounces = p->bounces;
+    size_t texels = 0;
+    for (uint32_t k = 0; k < nmat; k++) texels += (size_t)dims[2 * k] * (size_t)dims[2 * k + 1];
+    B.wide_offsets = wide_offsets_for(texels, 0);
+    return ZDR_OK;
+}
+
+extern "C" int zdr_scene_texel_bounce(zdr_scene *s, const zdr_texel_bounce_params *p, const float *texel_aovs, const float *materials, const int32_t *dims,
+                                      uint32_t nmat, float *out, void *workspace, void *stream) {
+    if (!out || !workspace) return fail(ZDR_E_INVALID, "null argument");
+    if ((uintptr_t)out % 16 || (uintptr_t)workspace % 16) return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce: out and workspace must be 16-byte aligned");
+    if (!zdr_launch_texel_bounce)                                    // (weak: csrc/bounce.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the bounced-light kernels (zdr_bounce.hip)");
+    SamplerCfg C; BounceArgs B; MaterialTable mt;
+    if (int rc = bounce_prepare(s, p, texel_aovs, materials, dims, nmat, (hipStream_t)stream, C, B, mt)) return rc;
+    const size_t n = B.ntexels, wbytes = zdr_texel_bounce_workspace_bytes(p->tex_h, p->tex_w);
+    size_t mbytes = 0;
+    for (uint32_t k = 0; k < nmat; k++) mbytes += 16 * (size_t)dims[2 * k] * (size_t)dims[2 * k + 1];
+    if (denoise_overlap(out, 16 * n, {{workspace, wbytes}, {texel_aovs, 64 * n}, {materials, mbytes}})) return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce: out must not overlap the workspace, texel_aovs or the materials");
+    if (denoise_overlap(workspace, wbytes, {{texel_aovs, 64 * n}, {materials, mbytes}})) return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce: the workspace must not overlap texel_aovs or the materials");
+    DScene S = s->ds;
+    S.shadow_pairs = ~0ull;      // every pair (BruteAccel::any_shadow then gives any()'s answer, which the mask of never-occluders equals bit for bit)
+    B.out = (float4 *)out;
+    B.count = (uint32_t *)workspace; B.list = (uint32_t *)((char *)workspace + ZDR_BOUNCE_HEADER_BYTES);
+    if (zdr_launch_texel_bounce(S, s->accel_is_bvh, C, B, mt, (hipStream_t)stream)) return fail(ZDR_E_HIP, "texel bounce launch failed");
+    return ZDR_OK;
+}
+
+extern "C" int zdr_texel_bounce_dump(zdr_scene *s, const zdr_texel_bounce_params *p, const float *texel_aovs, const float *materials, const int32_t *dims,
+                                     uint32_t nmat, const int32_t *queries, uint32_t n, float *out, void *stream) {
+    if (n == 0) return ZDR_OK;
+    if (!queries || !out) return fail(ZDR_E_INVALID, "null argument");
+    if ((uintptr_t)out % 16) return fail(ZDR_E_INVALID, "zdr_texel_bounce_dump: out must be 16-byte aligned");
+    if (!zdr_launch_texel_bounce_dump)                               // (weak: csrc/bounce.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the bounced-light kernels (zdr_bounce.hip)");
+    SamplerCfg C; BounceArgs B; MaterialTable mt;
+    if (int rc = bounce_prepare(s, p, texel_aovs, materials, dims, nmat, (hipStream_t)stream, C, B, mt)) return rc;
+    DScene S = s->ds;
+    S.shadow_pairs = ~0ull;
+    if (zdr_launch_texel_bounce_dump(S, s->accel_is_bvh, C, B, mt, queries, n, out, (hipStream_t)stream)) return fail(ZDR_E_HIP, "texel bounce dump launch failed");
     return ZDR_OK;
 }
 

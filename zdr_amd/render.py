@@ -205,6 +205,24 @@ class TexelLighting:
         return self.data[..., 3]
 
 
+class TexelBounce:
+    """Bounced light of ``Scene.texel_bounce`` (include/zdr.h, zdr_scene_texel_bounce): ``data`` is the (H, W, 4) tensor of one material's
+    texels.  ``irradiance`` (H, W, 3): the irradiance that arrives after at least one Lambertian bounce, up to ``bounces`` of them;
+    ``surface`` (H, W): the share of the cosine-weighted hemisphere that ends on the front of a model with a material — what can bounce
+    light at all.  Four zeros where ``reach`` is 0.  No gradient."""
+
+    def __init__(self, data):
+        self.data = data
+
+    @property
+    def irradiance(self):
+        return self.data[..., 0:3]
+
+    @property
+    def surface(self):
+        return self.data[..., 3]
+
+
 class TexelView:
     """What a camera sees of each texel, from ``Scene.texel_view`` (include/zdr.h, zdr_scene_texel_view): ``data`` is the (H, W, 8) view
     buffer of one material's texels for an image of ``res`` = (width, height).  ``visible`` (H, W): 1 where the texel lies in front of the
@@ -847,6 +865,71 @@ class Scene:
         if emissions is None and env is None:
             return TexelLighting(self.texel_lighting_forward(texels.data, spp=spp, seed=seed, samples=samples, max_distance=max_distance))
         return TexelLighting(Scene.TexelLightingOperator.apply(emissions, env, self, texels.data, spp, seed, samples, max_distance))
+
+    # ------------------------------------------------------------------- bounced light
+    def _bounce_call(self, texel_data, materials, spp, bounces, seed, samples, sampler, dims, slots):
+        """(texel_data, packed materials, dims array, params) of a bounced-light call, checked"""
+        if (not isinstance(texel_data, torch.Tensor) or texel_data.ndim != 3 or texel_data.shape[2] != N.AOV_CHANNELS or texel_data.dtype != torch.float32
+                or texel_data.device != self.device):
+            raise ValueError(f"texel_data must be a float32 (H, W, {N.AOV_CHANNELS}) tensor on {self.device}")
+        texel_data = texel_data.detach().contiguous()
+        if not 1 <= int(bounces) <= 8:
+            raise ValueError(f"bounces is {bounces}, must lie in [1, 8]")
+        begin, end = (0, int(spp)) if samples is None else (int(samples[0]), int(samples[1]))
+        if not 0 <= begin < end <= int(spp):
+            raise ValueError(f"samples {(begin, end)} must be a non-empty subrange of [0, {int(spp)})")
+        sampler = self.sampler if sampler is None else sampler
+        if sampler not in N.SAMPLERS:
+            raise ValueError(f"unknown sampler {sampler!r}")
+        if sampler == "pmj02bn":
+            self._ensure_pmj_tables()
+        packed, d, _ = self._aov_call(materials, dims, slots)
+        p = N.TexelBounceParams()
+        p.struct_size = C.sizeof(N.TexelBounceParams)
+        p.tex_h, p.tex_w, p.spp, p.seed, p.sampler = int(texel_data.shape[0]), int(texel_data.shape[1]), int(spp), int(seed) & 0xFFFFFFFF, N.SAMPLERS[sampler]
+        p.sample_begin, p.sample_end, p.bounces = begin, end, int(bounces)
+        return texel_data, packed, d, p
+
+    def texel_bounce_forward(self, texel_data, materials, *, spp, bounces=1, seed=0, samples=None, sampler=None, dims=None, slots=None, out=None,
+                             workspace=None):
+        """The (H, W, 4) buffer of include/zdr.h, zdr_scene_texel_bounce — the irradiance that arrives after 1 .. ``bounces`` Lambertian
+        bounces (floats 0..2) and ``surface`` (float 3) — for the surface points of ``texel_data``, an (H, W, 16) tensor in the layout of
+        ``texel_aovs_forward``.  ``materials``, ``dims``, ``slots``: as ``render_aovs_forward`` takes them; every material is read, at
+        the bounce vertices.  ``samples`` = (begin, end): a subrange of [0, spp) (the outputs of disjoint ranges add up).  ``sampler``:
+        "cmj" or "pmj02bn" (default: the scene's).  ``out`` and ``workspace`` (any tensor of at least
+        ``zdr_texel_bounce_workspace_bytes`` bytes) are allocated when not given.  No gradient.  Only enqueues, on torch's current stream."""
+        texel_data, packed, d, p = self._bounce_call(texel_data, materials, spp, bounces, seed, samples, sampler, dims, slots)
+        workspace = self._workspace(workspace, int(N.lib().zdr_texel_bounce_workspace_bytes(p.tex_h, p.tex_w)))
+        out = self._out_tensor(out, (p.tex_h, p.tex_w, 4), False)
+        N.check(N.lib().zdr_scene_texel_bounce(self._handle, C.byref(p), texel_data.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
+                                               out.data_ptr(), workspace.data_ptr(), self._stream()))
+        return out
+
+    def texel_bounce_dump(self, texel_data, materials, queries, *, spp, bounces=1, seed=0, samples=None, sampler=None, dims=None, slots=None):
+        """zdr_texel_bounce_dump: the walks of ``queries`` (n, 3) int {x, y, s} vertex by vertex, (n, 4 + 12 ``bounces``) float32 in the
+        layout of include/zdr.h.  The other arguments are ``texel_bounce_forward``'s.  A test hook."""
+        texel_data, packed, d, p = self._bounce_call(texel_data, materials, spp, bounces, seed, samples, sampler, dims, slots)
+        q = self._queries(queries)
+        out = torch.zeros((q.shape[0], 4 + 12 * p.bounces), dtype=torch.float32, device=self.device)
+        N.check(N.lib().zdr_texel_bounce_dump(self._handle, C.byref(p), texel_data.data_ptr(), packed.data_ptr(), d.ctypes.data, d.shape[0],
+                                              q.data_ptr(), q.shape[0], out.data_ptr(), self._stream()))
+        return out
+
+    def texel_bounce(self, material, index=0, *, spp=16, bounces=1, seed=0, samples=None, texels=None) -> TexelBounce:
+        """The light that reaches each texel of ``material[index]`` after at least one bounce: a ``TexelBounce`` whose ``data`` is the
+        (H, W, 4) tensor of include/zdr.h, zdr_scene_texel_bounce, at that material's size — ``irradiance``, the irradiance arriving
+        after 1 .. ``bounces`` Lambertian bounces, and ``surface``, the share of the hemisphere that can bounce light at all.
+        ``material`` is a tensor or a list exactly as ``render_aovs`` takes it and ``index`` picks the texture that is baked; ALL
+        materials are read, at the bounce vertices.  ``texels``: a ``TexelAovs`` already computed for them.  The lights are the
+        scene's current ones, the environment map included.  ``albedo / pi * (texel_lighting(...).irradiance + irradiance)`` is the
+        Lambertian radiosity of a texel.  Roughness is ignored, and ``bounces`` truncates the walk.  Nothing carries a gradient: the
+        materials are read detached."""
+        mats, slots, dims, _ = self._resolve_materials(material, True, pack=False)
+        if not 0 <= int(index) < len(dims):
+            raise ValueError(f"index {index}: {len(dims)} materials were given")
+        if texels is None:
+            texels = self.texel_aovs(material, index)
+        return TexelBounce(self.texel_bounce_forward(texels.data, mats, spp=spp, bounces=bounces, seed=seed, samples=samples, slots=slots))
 
     # ------------------------------------------------------------- texture-space views
     def texel_view_forward(self, texel_data, res, *, camera=None, out=None, workspace=None):
