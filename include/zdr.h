@@ -473,7 +473,8 @@ int zdr_scene_texel_lighting_backward(zdr_scene *scene, const zdr_texel_lighting
 
 /* Bounced light: the irradiance that reaches a texel after at least one bounce, and the share of its hemisphere that can bounce light at
  * all — a Lambertian random walk of `bounces` = K vertices from every texel.  albedo / pi x (zdr_scene_texel_lighting's irradiance + this
- * irradiance) is the Lambertian radiosity of the texel.  Forward only: nothing here has a gradient.
+ * irradiance) is the Lambertian radiosity of the texel.  The irradiance has an adjoint in the materials and the emissions,
+ * zdr_scene_texel_bounce_backward below; `surface` has no gradient.
  *
  * Inputs.  texel_aovs (DEVICE, tex_h x tex_w x 16) has the layout of zdr_scene_texel_aovs; floats 4..6 (normal n), 8..10 (position p) and
  * 12 (reach) are read.  A texel is shaded iff reach == 1 and neither n nor p holds a NaN; every other texel is four zeros.  The materials
@@ -547,6 +548,56 @@ int zdr_scene_texel_bounce(zdr_scene *scene, const zdr_texel_bounce_params *para
 int zdr_texel_bounce_dump(zdr_scene *scene, const zdr_texel_bounce_params *params, const float *texel_aovs, const float *materials,
                           const int32_t *dims, uint32_t nmat, const int32_t *queries /* DEVICE n x 3 */, uint32_t n,
                           float *out /* DEVICE n x (4 + 12 bounces) */, void *stream);
+
+/* The adjoint of zdr_scene_texel_bounce's irradiance: the gradient in the rgb of the material texels and in the lights' emissions.  The
+ * walk's directions come from cosine lobes about the normals, so neither the hits nor the draws depend on the materials: for one seed the
+ * bake is a polynomial in the material texels, of degree <= bounces per channel and exactly linear for bounces = 1, and exactly linear
+ * in the emissions.  Both gradients are exact transposes, not approximations.
+ *
+ * Definition.  Consider one shaded texel t and one sample s of the range.  The walk of zdr_scene_texel_bounce visits shaded vertices
+ * k = 1 .. n, n <= bounces.  Vertex k has the albedo a_k (rgb) = read_bsdf(material of the vertex's slot, it.uv).rgb, beta_k = the product
+ * of a_i over i <= k with beta_0 = 1, the weight w_k = L.eval x c x rcp(max(L.pdf, 1e-4)) and the forward's acceptance bit A_k (step 7 of
+ * the walk, with the forward's beta).  The forward is out[t].rgb = inv_spp x sum over s and k of A_k beta_k w_k.  With the cotangent
+ * gamma = d_out[t].rgb x inv_spp, all per channel:
+ *     Q_{n+1} = 0,   Q_k = A_k w_k + a_{k+1} Q_{k+1}
+ *     d a_k   = gamma x beta_{k-1} x Q_k
+ * Materials.  d a_k goes to the four taps of the bilinear lookup of vertex k, in the material of the vertex's slot, with the weights of
+ * read_bsdf; taps that the clamp puts on one texel receive both weights.  Only rgb is written: the roughness channel is never touched.
+ * The rule is division free: the gradient is correct where an albedo component is 0, and an all-black material still receives the
+ * gradient of its first vertex.  A term that is not finite is dropped, as the forward drops a non-finite add.
+ * Emissions.  An accepted vertex whose sample came from the front of mesh light l adds gamma x beta_k x c x rcp(max(L.pdf, 1e-4)) to
+ * d_emission[light_insts[l]]: the rule of zdr_scene_texel_lighting_backward with beta_k in front.
+ * Both targets are ADDED INTO: texels that no vertex reads keep their bits, and so do the rows of models that are not lights.
+ * d_out[..., 3], the cotangent of `surface`, is ignored; the cotangent of a texel that is not shaded is never read.  The seed is the
+ * forward's own, and the scene must hold the forward's emissions and map.
+ * Held fixed: the walks, the light list, the sampling tables, visibility and the acceptance bits.
+ * Not differentiated: the environment map through the bounce, the geometry, the GGX lobe (which the forward ignores too).
+ * Not promised: bit-stability.  The list of shaded texels varies in order from run to run and the sums use float atomics, so two runs
+ * may differ in the last bits.  (The forward's bits stay what they are.)
+ * Operation order.  Lanes, trips and draws are the forward's (zdr_texel_bounce_lanes_shift).  Per trip a lane (1) replays the walk and
+ * records per vertex {uv, slot, A_k w_k, a_k} — A_k is decided on add = (beta_k * L.eval) * (c * rcp(max(L.pdf, 1e-4))) as in the forward;
+ * the emission term (gamma * beta_k) * (c * rcp(...)) is added here —, (2) forms Q_k = A_k w_k + a_{k+1} * Q_{k+1} from the last vertex
+ * to the first, (3) forms d a_k = (gamma * beta_{k-1}) * Q_k from the first vertex to the last, with beta_0 = 1 and beta_k = beta_{k-1} *
+ * a_k, and hands each to the gradient scatter of the material-table backward calls: k_m * d a_k added to tap m's staging cell, the cells
+ * and their copies summed per texel (in float64 where a material has copies), then added to d_materials.
+ *
+ * d_materials (DEVICE, packed like materials) and d_emission (DEVICE, ninst x 3) may each be NULL, not both.
+ * workspace: zdr_texel_bounce_backward_workspace_bytes(scene, tex_h, tex_w, dims, nmat) bytes (0 = invalid) — the handle because the
+ * emission accumulator depends on the scene's current light count, the material dims because the staging cells and their copies (those
+ * of every material-table backward call: a 1 x 1 material is replicated, not an atomic hot spot) depend on them.  It needs no
+ * initialisation.  Up to five launches on `stream` — clear (a kernel), compact, the adjoint of the shading kernel, the gather of the
+ * cells into d_materials, the gather of the accumulator into d_emission — that never allocate and never synchronise: the call can be
+ * captured without a call before, as the forward.
+ * Errors as zdr_scene_texel_bounce's, and ZDR_E_INVALID for: both targets NULL; a misaligned target (d_materials 16 bytes, d_emission 4);
+ * a workspace that overlaps an input or a target, targets that overlap the inputs or each other.  ZDR_E_UNSUPPORTED: a library linked
+ * without these kernels (zdr_bouncegrad.hip).  d_emission on a scene without lights is accepted and adds nothing. */
+size_t zdr_texel_bounce_backward_workspace_bytes(zdr_scene *scene, int32_t tex_h, int32_t tex_w, const int32_t *dims /* HOST nmat x {h, w} */,
+                                                 uint32_t nmat);   /* 0 = invalid */
+int zdr_scene_texel_bounce_backward(zdr_scene *scene, const zdr_texel_bounce_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
+                                    const float *d_out /* DEVICE tex_h x tex_w x 4 */, const float *materials /* DEVICE packed */,
+                                    const int32_t *dims /* HOST nmat x {h, w} */, uint32_t nmat,
+                                    float *d_materials /* DEVICE packed like materials, +=, or NULL */,
+                                    float *d_emission /* DEVICE ninst x 3, +=, or NULL */, void *workspace, void *stream);
 
 /* Push-pull: fills the texels of a texture that a weight marks as unknown from the ones it marks as known, through a weighted pyramid — a
  * baker's seam padding — and the adjoint of that map with respect to the texture.  No scene handle.  The known texels come out bit for

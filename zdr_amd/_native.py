@@ -20,6 +20,7 @@ VIEWGRAD_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_viewgrad.so")   # camera 
 TANGENT_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_tangent.so")     # UV tangents: likewise
 BAKEGRAD_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_bakegrad.so")   # the light baker's adjoint: likewise
 BOUNCE_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_bounce.so")       # the bounced-light baker: likewise
+BOUNCEGRAD_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_bouncegrad.so")   # the bounced-light baker's adjoint: likewise
 TEXEL_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_texel.so")   # the texture-space kernels: a dependency of libzdr_hip.so, found beside it
 
 COLLOCATED, DIRECT, PATH, UVGRAD = 0, 1, 2, 3
@@ -55,7 +56,8 @@ EXPORTS = ("zdr_version", "zdr_abi_version", "zdr_last_error", "zdr_scene_create
            "zdr_texel_gather_dview", "zdr_texel_view_backward_workspace_bytes", "zdr_texel_view_backward",
            "zdr_scene_texel_tangents", "zdr_texel_footprint_tangents",
            "zdr_texel_lighting_backward_workspace_bytes", "zdr_scene_texel_lighting_backward",
-           "zdr_texel_bounce_workspace_bytes", "zdr_texel_bounce_lanes_shift", "zdr_scene_texel_bounce", "zdr_texel_bounce_dump")
+           "zdr_texel_bounce_workspace_bytes", "zdr_texel_bounce_lanes_shift", "zdr_scene_texel_bounce", "zdr_texel_bounce_dump",
+           "zdr_texel_bounce_backward_workspace_bytes", "zdr_scene_texel_bounce_backward")
 
 
 class CameraPOD(C.Structure):
@@ -152,7 +154,7 @@ def lib():
     from . import build as _build
     if _build.stale():
         _build.build()
-    for path in (LIB_PATH, TEXEL_LIB_PATH, BAKE_LIB_PATH, PUSHPULL_LIB_PATH, PROJECT_LIB_PATH, MIP_LIB_PATH, ANISO_LIB_PATH, PLAN_LIB_PATH, VIEWGRAD_LIB_PATH, TANGENT_LIB_PATH, BAKEGRAD_LIB_PATH, BOUNCE_LIB_PATH):
+    for path in (LIB_PATH, TEXEL_LIB_PATH, BAKE_LIB_PATH, PUSHPULL_LIB_PATH, PROJECT_LIB_PATH, MIP_LIB_PATH, ANISO_LIB_PATH, PLAN_LIB_PATH, VIEWGRAD_LIB_PATH, TANGENT_LIB_PATH, BAKEGRAD_LIB_PATH, BOUNCE_LIB_PATH, BOUNCEGRAD_LIB_PATH):
         if not os.path.exists(path):
             raise ZdrError(f"{path} is missing: the zdr HIP back end was not built (python -m zdr_amd.build)")
     L = C.CDLL(LIB_PATH)
@@ -198,6 +200,9 @@ def lib():
     L.zdr_texel_bounce_lanes_shift.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.c_uint32]
     L.zdr_scene_texel_bounce.argtypes = [vp, C.POINTER(TexelBounceParams), fp, fp, ip, C.c_uint32, fp, vp, vp]
     L.zdr_texel_bounce_dump.argtypes = [vp, C.POINTER(TexelBounceParams), fp, fp, ip, C.c_uint32, ip, C.c_uint32, fp, vp]
+    L.zdr_texel_bounce_backward_workspace_bytes.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_uint32]
+    L.zdr_texel_bounce_backward_workspace_bytes.restype = C.c_size_t
+    L.zdr_scene_texel_bounce_backward.argtypes = [vp, C.POINTER(TexelBounceParams), fp, fp, fp, ip, C.c_uint32, fp, fp, vp, vp]
     L.zdr_push_pull_workspace_bytes.argtypes = [C.POINTER(PushPullParams)]
     L.zdr_push_pull_workspace_bytes.restype = C.c_size_t
     L.zdr_push_pull.argtypes = [C.POINTER(PushPullParams), fp, fp, fp, vp, vp]

@@ -37,6 +37,8 @@
 #include "bakegrad.h"
 #define ZDR_BOUNCE_LAUNCHER_REF __attribute__((weak))    // (csrc/bounce.h)
 #include "bounce.h"
+#define ZDR_BOUNCEGRAD_LAUNCHER_REF __attribute__((weak))   // (csrc/bouncegrad.h)
+#include "bouncegrad.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1838,6 +1840,75 @@ extern "C" int zdr_texel_bounce_dump(zdr_scene *s, const zdr_texel_bounce_params
     DScene S = s->ds;
     S.shadow_pairs = ~0ull;
     if (zdr_launch_texel_bounce_dump(S, s->accel_is_bvh, C, B, mt, queries, n, out, (hipStream_t)stream)) return fail(ZDR_E_HIP, "texel bounce dump launch failed");
+    return ZDR_OK;
+}
+
+// zdr_scene_texel_bounce_backward (include/zdr.h): the forward's checks, then the launches of zdr_bouncegrad.hip on the caller's stream.  The
+// handle is only read here too.  The materials' staging cells, their copies and strides follow material_cell_layout — the rule of every
+// material-table backward call, so a 1 x 1 material keeps its copies and the few-texel LDS path —, but they live in the caller's
+// workspace behind the list and the emission accumulator: nothing is allocated, and the call can be captured without a call before.
+static int bgrad_cell_layout(const int32_t *dims, uint32_t nmat, MaterialTable &mt, int32_t &cell_copies, size_t &cells) {
+    if (int rc = pack_material_table(dims, nmat, mt)) return rc;
+    RenderCfg R; memset(&R, 0, sizeof R);
+    material_cell_layout(mt, R);
+    cell_copies = R.cell_copies;
+    cells = (size_t)R.cell_copies * (size_t)mt.ncells;
+    return ZDR_OK;
+}
+static size_t bgrad_list_bytes(int32_t tex_h, int32_t tex_w) { return ((size_t)tex_h * (size_t)tex_w * sizeof(uint32_t) + 15) & ~(size_t)15; }
+static size_t bgrad_acc_bytes(const zdr_scene *s) { return ((size_t)ZDR_BGRAD_COPIES * 3 * (size_t)std::max(s->ds.light_count, 0) * sizeof(float) + 15) & ~(size_t)15; }
+
+extern "C" size_t zdr_texel_bounce_backward_workspace_bytes(zdr_scene *s, int32_t tex_h, int32_t tex_w, const int32_t *dims, uint32_t nmat) {
+    if (!s) { fail(ZDR_E_INVALID, "null argument"); return 0; }
+    if (check_table_args(true, dims, nmat)) return 0;
+    if (bounce_check_size(tex_h, tex_w)) return 0;
+    MaterialTable mt; int32_t copies = 1; size_t cells = 0;
+    if (bgrad_cell_layout(dims, nmat, mt, copies, cells)) return 0;
+    return ZDR_BOUNCE_HEADER_BYTES + bgrad_list_bytes(tex_h, tex_w) + bgrad_acc_bytes(s) + 64 * cells;
+}
+
+extern "C" int zdr_scene_texel_bounce_backward(zdr_scene *s, const zdr_texel_bounce_params *p, const float *texel_aovs, const float *d_out, const float *materials,
+                                               const int32_t *dims, uint32_t nmat, float *d_materials, float *d_emission, void *workspace, void *stream) {
+    if (!d_out || !workspace) return fail(ZDR_E_INVALID, "null argument");
+    if (!d_materials && !d_emission) return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce_backward: neither d_materials nor d_emission is given");
+    if ((uintptr_t)d_out % 16 || (uintptr_t)workspace % 16 || (uintptr_t)d_materials % 16 || (uintptr_t)d_emission % 4)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce_backward: d_out, d_materials and workspace must be 16-byte aligned, d_emission 4-byte aligned");
+    if (!zdr_launch_texel_bounce_backward)                           // (weak: csrc/bouncegrad.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the bounced-light gradient kernels (zdr_bouncegrad.hip)");
+    SamplerCfg C; BounceArgs B; MaterialTable mt;
+    if (int rc = bounce_prepare(s, p, texel_aovs, materials, dims, nmat, (hipStream_t)stream, C, B, mt)) return rc;
+    int32_t cell_copies = 1; size_t cells = 0;
+    {   // the cells of the table bounce_prepare made: the same entries, laid out for a backward call
+        RenderCfg R; memset(&R, 0, sizeof R);
+        material_cell_layout(mt, R);
+        cell_copies = R.cell_copies; cells = (size_t)R.cell_copies * (size_t)mt.ncells;
+    }
+    const size_t n = B.ntexels, lbytes = bgrad_list_bytes(p->tex_h, p->tex_w), abytes = bgrad_acc_bytes(s);
+    const size_t wbytes = ZDR_BOUNCE_HEADER_BYTES + lbytes + abytes + 64 * cells;
+    size_t mbytes = 0;
+    for (uint32_t k = 0; k < nmat; k++) mbytes += 16 * (size_t)dims[2 * k] * (size_t)dims[2 * k + 1];
+    const size_t ebytes = d_emission ? 3 * (size_t)s->ninst * sizeof(float) : 0, dmbytes = d_materials ? mbytes : 0;
+    if (denoise_overlap(workspace, wbytes, {{texel_aovs, 64 * n}, {d_out, 16 * n}, {materials, mbytes}, {d_materials, dmbytes}, {d_emission, ebytes}}))
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce_backward: the workspace must not overlap texel_aovs, d_out, the materials, d_materials or d_emission");
+    if (d_materials && denoise_overlap(d_materials, dmbytes, {{texel_aovs, 64 * n}, {d_out, 16 * n}, {materials, mbytes}, {d_emission, ebytes}}))
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce_backward: d_materials must not overlap texel_aovs, d_out, the materials or d_emission");
+    if (d_emission && denoise_overlap(d_emission, ebytes, {{texel_aovs, 64 * n}, {d_out, 16 * n}, {materials, mbytes}}))
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce_backward: d_emission must not overlap texel_aovs, d_out or the materials");
+    const bool emit = d_emission && s->ds.light_count > 0;           // a scene without lights: accepted, nothing to add
+    if (!emit && !d_materials) return ZDR_OK;
+    DScene S = s->ds;
+    S.shadow_pairs = ~0ull;      // every pair, as the forward
+    BgradArgs G; memset(&G, 0, sizeof G);
+    G.texels = B.texels; G.d_out = (const float4 *)d_out; G.materials = B.materials;
+    G.d_materials = d_materials; G.d_emission = emit ? d_emission : nullptr;
+    G.count = (uint32_t *)workspace; G.list = (uint32_t *)((char *)workspace + ZDR_BOUNCE_HEADER_BYTES);
+    G.acc = emit ? (float *)((char *)workspace + ZDR_BOUNCE_HEADER_BYTES + lbytes) : nullptr;
+    G.cells = d_materials ? (float *)((char *)workspace + ZDR_BOUNCE_HEADER_BYTES + lbytes + abytes) : nullptr;
+    G.ntexels = B.ntexels; G.tex_w = B.tex_w; G.sample_begin = B.sample_begin; G.sample_end = B.sample_end;
+    G.inv_spp = B.inv_spp; G.bounces = B.bounces; G.wide_offsets = B.wide_offsets;
+    G.cell_copies = cell_copies; G.ncell_words = (uint32_t)(4 * cells);
+    if (int rc = zdr_launch_texel_bounce_backward(S, s->accel_is_bvh, C, G, mt, (hipStream_t)stream))
+        return fail(ZDR_E_HIP, "texel bounce backward: launch " + std::to_string(rc / 256) + " of 5 failed: " + hipGetErrorString((hipError_t)(rc % 256)));
     return ZDR_OK;
 }
 

@@ -209,7 +209,8 @@ class TexelBounce:
     """Bounced light of ``Scene.texel_bounce`` (include/zdr.h, zdr_scene_texel_bounce): ``data`` is the (H, W, 4) tensor of one material's
     texels.  ``irradiance`` (H, W, 3): the irradiance that arrives after at least one Lambertian bounce, up to ``bounces`` of them;
     ``surface`` (H, W): the share of the cosine-weighted hemisphere that ends on the front of a model with a material — what can bounce
-    light at all.  Four zeros where ``reach`` is 0.  No gradient."""
+    light at all.  Four zeros where ``reach`` is 0.  ``irradiance`` carries a gradient in the materials that require grad and in the
+    emissions when ``texel_bounce`` was given ``emissions=``; ``surface`` never does."""
 
     def __init__(self, data):
         self.data = data
@@ -897,7 +898,8 @@ class Scene:
         ``texel_aovs_forward``.  ``materials``, ``dims``, ``slots``: as ``render_aovs_forward`` takes them; every material is read, at
         the bounce vertices.  ``samples`` = (begin, end): a subrange of [0, spp) (the outputs of disjoint ranges add up).  ``sampler``:
         "cmj" or "pmj02bn" (default: the scene's).  ``out`` and ``workspace`` (any tensor of at least
-        ``zdr_texel_bounce_workspace_bytes`` bytes) are allocated when not given.  No gradient.  Only enqueues, on torch's current stream."""
+        ``zdr_texel_bounce_workspace_bytes`` bytes) are allocated when not given.  This low-level call attaches no gradient
+        (``texel_bounce_backward`` is its adjoint, ``texel_bounce`` the differentiable call).  Only enqueues, on torch's current stream."""
         texel_data, packed, d, p = self._bounce_call(texel_data, materials, spp, bounces, seed, samples, sampler, dims, slots)
         workspace = self._workspace(workspace, int(N.lib().zdr_texel_bounce_workspace_bytes(p.tex_h, p.tex_w)))
         out = self._out_tensor(out, (p.tex_h, p.tex_w, 4), False)
@@ -915,21 +917,99 @@ class Scene:
                                               q.data_ptr(), q.shape[0], out.data_ptr(), self._stream()))
         return out
 
-    def texel_bounce(self, material, index=0, *, spp=16, bounces=1, seed=0, samples=None, texels=None) -> TexelBounce:
+    def texel_bounce_backward(self, texel_data, d_out, materials, *, spp, bounces=1, seed=0, samples=None, sampler=None, dims=None, slots=None,
+                              d_materials=None, d_emission=None, workspace=None):
+        """The adjoint of ``texel_bounce_forward``'s irradiance (include/zdr.h, zdr_scene_texel_bounce_backward): with the cotangent
+        ``d_out`` (H, W, 4) — float 3, that of ``surface``, is ignored, and so is every texel that is not shaded — ADDS the gradient of
+        the material texels' rgb into ``d_materials`` (a list shaped like ``materials``, or the packed buffer; roughness is never
+        written) and that of the lights' emissions into ``d_emission``, a float32 (ninst, 3) tensor; one of the two at least.  The
+        other arguments are the forward's (the same seed), and the scene must hold the forward's emissions and map.  The walks, the
+        light list, the sampling tables, visibility and the acceptance bits are held fixed: for one seed the gradient is the exact
+        transpose, also where an albedo is 0.  Not bit-stable from run to run (float atomics).  ``workspace``: any tensor of at least
+        ``zdr_texel_bounce_backward_workspace_bytes`` bytes, allocated when not given; it needs no initialisation.  Only enqueues, on
+        torch's current stream.  Returns (d_materials, d_emission)."""
+        texel_data, packed, d, p = self._bounce_call(texel_data, materials, spp, bounces, seed, samples, sampler, dims, slots)
+        H, W = p.tex_h, p.tex_w
+        if not isinstance(d_out, torch.Tensor) or tuple(d_out.shape) != (H, W, 4) or d_out.dtype != torch.float32 or d_out.device != self.device:
+            raise ValueError(f"d_out must be a float32 ({H}, {W}, 4) tensor on {self.device}")
+        d_out = d_out.detach().contiguous()
+        if d_materials is None and d_emission is None:
+            raise ValueError("texel_bounce_backward needs d_materials, d_emission or both")
+        dpacked = None
+        if d_materials is not None:
+            if isinstance(d_materials, (list, tuple)):
+                mats = materials if isinstance(materials, (list, tuple)) else [materials]
+                if len(d_materials) != len(mats) or (dims is None and any(tuple(g.shape) != tuple(m.shape) for g, m in zip(d_materials, mats))):
+                    raise ValueError("d_materials must be a list shaped like the materials")
+            dpacked = self._pack_grads(d_materials, packed)
+        if d_emission is not None:
+            self._check_d_emission(d_emission, None)
+        workspace = self._workspace(workspace, int(N.lib().zdr_texel_bounce_backward_workspace_bytes(self._handle, H, W, d.ctypes.data, d.shape[0])))
+        N.check(N.lib().zdr_scene_texel_bounce_backward(self._handle, C.byref(p), texel_data.data_ptr(), d_out.data_ptr(), packed.data_ptr(), d.ctypes.data,
+                                                        d.shape[0], None if dpacked is None else dpacked.data_ptr(),
+                                                        None if d_emission is None else d_emission.data_ptr(), workspace.data_ptr(), self._stream()))
+        if dpacked is not None:
+            self._unpack_grads(dpacked, d_materials)
+        return d_materials, d_emission
+
+    class TexelBounceOperator(torch.autograd.Function):
+        """texel_bounce() of materials that require grad and / or with ``emissions=``, modelled on TexelLightingOperator: a detached
+        copy of the emissions becomes the scene's values in the forward, and the backward applies the forward's light list and values
+        again before the native call.  The forward is texel_bounce_forward, unchanged."""
+        @staticmethod
+        def forward(ctx, emissions, self, texel_data, spp, bounces, seed, samples, slots, *mats):
+            if emissions is not None:
+                self.set_emission_values(emissions.detach().clone())
+            ctx.with_emissions = emissions is not None
+            ctx.scene = weakref.ref(self)
+            ctx.texel_data = texel_data.detach()
+            ctx.args = (spp, bounces, seed, samples, self.sampler, slots)
+            ctx.emissions = self.emissions
+            ctx.save_for_backward(*mats)
+            return self.texel_bounce_forward(texel_data, [m.detach() for m in mats], spp=spp, bounces=bounces, seed=seed, samples=samples, slots=slots)
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            scene = ctx.scene()
+            if scene.emissions is not ctx.emissions:       # the light list, then its values: the forward's snapshot
+                scene.update_lights(ctx.emissions)
+            spp, bounces, seed, samples, sampler, slots = ctx.args
+            mats = [m.detach() for m in ctx.saved_tensors]
+            d_emission = None
+            if ctx.with_emissions:
+                scene._apply_emission_values(ctx.emissions.values)
+                d_emission = torch.zeros_like(ctx.emissions.values)
+            d_mats = [torch.zeros_like(m) for m in mats] if any(ctx.needs_input_grad[8:]) else None
+            g = grad_output.to(device=scene.device, dtype=torch.float32).contiguous()
+            scene.texel_bounce_backward(ctx.texel_data, g, mats, spp=spp, bounces=bounces, seed=seed, samples=samples, sampler=sampler, slots=slots,
+                                        d_materials=d_mats, d_emission=d_emission)
+            return (d_emission, None, None, None, None, None, None, None) + (tuple(d_mats) if d_mats is not None else (None,) * len(mats))
+
+    def texel_bounce(self, material, index=0, *, spp=16, bounces=1, seed=0, samples=None, texels=None, emissions=None) -> TexelBounce:
         """The light that reaches each texel of ``material[index]`` after at least one bounce: a ``TexelBounce`` whose ``data`` is the
         (H, W, 4) tensor of include/zdr.h, zdr_scene_texel_bounce, at that material's size — ``irradiance``, the irradiance arriving
         after 1 .. ``bounces`` Lambertian bounces, and ``surface``, the share of the hemisphere that can bounce light at all.
         ``material`` is a tensor or a list exactly as ``render_aovs`` takes it and ``index`` picks the texture that is baked; ALL
         materials are read, at the bounce vertices.  ``texels``: a ``TexelAovs`` already computed for them.  The lights are the
         scene's current ones, the environment map included.  ``albedo / pi * (texel_lighting(...).irradiance + irradiance)`` is the
-        Lambertian radiosity of a texel.  Roughness is ignored, and ``bounces`` truncates the walk.  Nothing carries a gradient: the
-        materials are read detached."""
+        Lambertian radiosity of a texel.  Roughness is ignored, and ``bounces`` truncates the walk.
+
+        ``irradiance`` is differentiable in the rgb of every material tensor that requires grad (each receives a gradient of its own
+        shape) and in ``emissions``, a float32 (ninst, 3) tensor on the GPU that becomes the scene's values as in ``texel_lighting``
+        (include/zdr.h, zdr_scene_texel_bounce_backward): the walks, the light list, the sampling tables and visibility are held
+        fixed, so for one seed the gradient is exact; its sums use float atomics and may differ in the last bits from run to run.
+        ``surface`` has no gradient, nor have the roughness, the geometry and the environment map.  With plain tensors and without
+        ``emissions`` the call builds no autograd node and returns the bits of ``texel_bounce_forward``."""
+        if emissions is not None:
+            check_emissions(emissions, self.inst_count, self.device)
         mats, slots, dims, _ = self._resolve_materials(material, True, pack=False)
         if not 0 <= int(index) < len(dims):
             raise ValueError(f"index {index}: {len(dims)} materials were given")
         if texels is None:
             texels = self.texel_aovs(material, index)
-        return TexelBounce(self.texel_bounce_forward(texels.data, mats, spp=spp, bounces=bounces, seed=seed, samples=samples, slots=slots))
+        if emissions is None and not (torch.is_grad_enabled() and any(m.requires_grad for m in mats)):
+            return TexelBounce(self.texel_bounce_forward(texels.data, mats, spp=spp, bounces=bounces, seed=seed, samples=samples, slots=slots))
+        return TexelBounce(Scene.TexelBounceOperator.apply(emissions, self, texels.data, spp, bounces, seed, samples, slots, *mats))
 
     # ------------------------------------------------------------- texture-space views
     def texel_view_forward(self, texel_data, res, *, camera=None, out=None, workspace=None):
