@@ -1,5 +1,6 @@
 """Scenes with more lights than the emission-gradient kernels' on-chip table holds (ZDR_EMIT_LDS_LIGHTS = 10, zdr_kernels.hip), and the
-oracle-side measurement both the host preconditions (test_many_lights_host.py) and the GPU tests (test_gpu_many_lights.py) rest on.
+oracle-side measurement both the host preconditions (test_many_lights_host.py) and the GPU tests (test_gpu_many_lights.py) rest on;
+and the hall, with more lights than the table of the texture-space adjoints holds (32; test_gpu_texel_bake_edges.py).
 Importable without a GPU; built from the repository's own assets and zdr_amd.scenes."""
 from math import acos, cos, pi, sin
 
@@ -40,6 +41,26 @@ def chandelier_arrays(base=None):
         if i == BLOCKER_BEFORE_PANEL:
             add(*panel_mesh(1, 1), BLOCKER_XFORM, (0, 0, 0))
         add(*panel_mesh(1 + i % 3, 1 + i % 2), [[0.2, 0, 0, x], [0, -1, 0, 4.9], [0, 0, -0.2, z], [0, 0, 0, 1]], e)
+    return geometry.from_arrays(np.concatenate(V), np.concatenate(T), begin, np.stack(X), np.stack(E))
+
+
+HALL_X, HALL_Z = np.linspace(-2.2, 1.8, 6), np.linspace(-4.8, 0.4, 7)
+HALL_PANELS = HALL_X.size * HALL_Z.size
+TEXEL_LDS_LIGHTS = 32                                            # ZDR_BGRAD_LDS_LIGHTS = ZDR_LGRAD_LDS_LIGHTS: the texture-space adjoints' table
+
+
+def hall_arrays():
+    """The Cornell box with a 6 x 7 grid of small panels of different triangle counts facing down at y = 4.9 (z-major), each with its
+    own rgb: 44 instances, 43 lights with list indices 0 ... 42 (list index = instance - 1) — more than the 32 the adjoints of the
+    texture-space bakes sum on chip (zdr_bouncegrad.hip, zdr_bakegrad.hip)."""
+    base = geometry.assemble(cbox_models())
+    V = [base.verts]; T = [base.tris]; begin = list(base.inst_tri_begin); X = list(base.inst_xform); E = list(base.inst_emission)
+    em = np.random.default_rng(7).uniform(5.0, 40.0, (HALL_PANELS, 3)).astype(np.float32)
+    for n, (z, x) in enumerate((z, x) for z in HALL_Z for x in HALL_X):
+        verts, tris = panel_mesh(1 + n % 3, 1 + n % 2)
+        nv = sum(v.shape[0] for v in V)
+        V.append(verts); T.append(tris + nv); begin.append(begin[-1] + tris.shape[0])
+        X.append(np.array([[0.15, 0, 0, x], [0, -1, 0, 4.9], [0, 0, -0.15, z], [0, 0, 0, 1]], np.float32).reshape(16)); E.append(em[n])
     return geometry.from_arrays(np.concatenate(V), np.concatenate(T), begin, np.stack(X), np.stack(E))
 
 

@@ -30,8 +30,8 @@ pytestmark = pytest.mark.gpu
 def sum_of_dump(name, q, dump, samples=None, vertices=None):
     """The texel buffer from the dumped adds, in float32 and in the order of include/zdr.h: lane j of 2^shift takes the samples begin + j,
     begin + j + lanes, ... and adds the accepted adds of each, vertices ascending; the lanes' sums are added in lane order, times 1 / spp."""
-    H, W = BC.CASES[name][2]
-    spp = BC.CASES[name][4]
+    H, W = BC.case(name)[2]
+    spp = BC.case(name)[4]
     begin, end = samples if samples is not None else (BC.RANGES.get(name) or (0, spp))
     shift = N.lib().zdr_texel_bounce_lanes_shift(H, W, begin, end)
     assert shift >= 0

@@ -33,7 +33,7 @@ def set_case_envmap(scene, env):
 
 
 def new_scene(name, accel):
-    make, env = GC.CASES[name][0], GC.CASES[name][4]
+    make, env = GC.case(name)[0], GC.case(name)[4]
     scene = Scene(make(), integrator="direct", accel=accel)
     if name in GC.SAMPLERS:
         scene.set_pmj02bn_tables(*GC.pmj_tables(name))
@@ -44,7 +44,7 @@ def new_scene(name, accel):
 
 
 def case_scene(name, accel):
-    key = (GC.CASES[name][0], GC.CASES[name][4], accel, GC.SAMPLERS.get(name))
+    key = (GC.case(name)[0], GC.case(name)[4], accel, GC.SAMPLERS.get(name))
     if key not in _scenes:
         _scenes[key] = new_scene(name, accel)
     return _scenes[key]
@@ -52,7 +52,7 @@ def case_scene(name, accel):
 
 def case_kw(name, **kw):
     kw.setdefault("samples", GC.RANGES.get(name))
-    return dict(spp=GC.CASES[name][3], seed=GC.SEED, sampler="pmj02bn" if name in GC.SAMPLERS else None, **kw)
+    return dict(spp=GC.case(name)[3], seed=GC.SEED, sampler="pmj02bn" if name in GC.SAMPLERS else None, **kw)
 
 
 def zeros(name, scene, target):

@@ -74,8 +74,49 @@ CASES = {
     "cbox_pmj02bn_k2": (TC.cbox_arrays, (0, None), (16, 16), None, 4, 2, None, "cbox_16x16"),
     "cbox_k3_range": (TC.cbox_arrays, (0, None), (16, 16), None, 4, 3, None, "cbox_16x16"),
 }
-SAMPLERS = {"cbox_pmj02bn_k2": (5, 256)}            # pmj02bn from seeded tables of (sets, samples per set); every other case draws with CMJ
-RANGES = {"cbox_k3_range": (1, 4)}                  # the sample range of a case that does not take all of [0, spp)
+
+
+@functools.lru_cache(None)
+def hall_arrays():
+    import many_lights as ML
+    return ML.hall_arrays()
+
+
+def _lit_panel_arrays():
+    import texel_lighting_grad_cases as GC
+    return GC.env_panel_lit_arrays()
+
+
+HALL_SLOTS = (0,) + (None,) * 43
+
+# The cases at the edges of the launch shapes (tests/test_gpu_texel_bake_edges.py, tests/test_texel_bake_edges_host.py): the same
+# tuples, looked up by ``case(name)`` like the others, but in a table of their own so that the parametrised tests over CASES keep their
+# size.  hall: 43 lights, past the 32 the adjoint sums on chip.  cbox_k8: the documented maximum of bounces, with CMJ and with pmj02bn.
+# cbox_wave*: 64 texels, so a whole wave per texel at spp 64, one lane for a single sample, 32 lanes in two trips (the second ragged) for
+# the 37 samples [3, 40).  cbox_wide: more live workgroups than the emission accumulator has rows and than its 64 x 64 material has
+# copies of its cells.  tiny_*: material tables of 4, 28, 30 and 12 + 6 staging cells (MATERIAL_SIZES) around ZDR_LDS_CELLS = 28.
+# cbox_k3_nan: NaNs in two sample points (NAN_POINTS).  env_lit_k2: an environment map and a mesh light in one light list.
+EDGE_CASES = {
+    "hall_k2": (hall_arrays, HALL_SLOTS, (16, 16), None, 4, 2, None, None),
+    "cbox_k8": (TC.cbox_arrays, (0, None), (8, 8), None, 4, 8, None, None),
+    "cbox_k8_pmj02bn": (TC.cbox_arrays, (0, None), (8, 8), None, 4, 8, None, None),
+    "cbox_wave": (TC.cbox_arrays, (0, None), (8, 8), None, 64, 2, None, None),
+    "cbox_wave_one": (TC.cbox_arrays, (0, None), (8, 8), None, 64, 2, None, None),
+    "cbox_wave_ragged": (TC.cbox_arrays, (0, None), (8, 8), None, 64, 2, None, None),
+    "cbox_wide": (TC.cbox_arrays, (0, None), (40, 40), None, 16, 2, None, None),
+    "tiny_1x1": (TC.cbox_arrays, (0, None), (16, 16), None, 4, 3, None, "cbox_16x16"),
+    "tiny_3x6": (TC.cbox_arrays, (0, None), (16, 16), None, 4, 3, None, "cbox_16x16"),
+    "tiny_4x5": (TC.cbox_arrays, (0, None), (16, 16), None, 4, 3, None, "cbox_16x16"),
+    "tiny_multi": (LC.multi_arrays, MULTI_SLOTS, (16, 16), None, 9, 3, None, None),
+    "cbox_k3_nan": (TC.cbox_arrays, (0, None), (16, 16), None, 4, 3, None, "cbox_16x16"),
+    "env_lit_k2": (_lit_panel_arrays, ENV_SLOTS, (16, 16), (3, 4), 4, 2, LC.sun_env, None),
+}
+MATERIAL_SIZES = {"cbox_wide": ((64, 64),), "tiny_1x1": ((1, 1),), "tiny_3x6": ((3, 6),), "tiny_4x5": ((4, 5),), "tiny_multi": ((2, 3), (1, 2))}   # materials that are not sized by the sample points
+# (row-major index of a reached texel's rank, float of its row): a NaN in a position and, 100 reached texels on, one in a normal
+NAN_POINTS = {"cbox_k3_nan": ((20, 9), (120, 5))}
+
+SAMPLERS = {"cbox_pmj02bn_k2": (5, 256), "cbox_k8_pmj02bn": (5, 256)}   # pmj02bn from seeded tables of (sets, samples per set); every other case draws with CMJ
+RANGES = {"cbox_k3_range": (1, 4), "cbox_wave_one": (0, 1), "cbox_wave_ragged": (3, 40)}   # the sample range of a case that does not take all of [0, spp)
 
 # largest |float32 reference - float64 reference| of a vertex's add over the samples whose signatures agree
 # (python tests/texel_bounce_cases.py; profiles/texel_bounce_margins.txt), rounded up in the third digit
@@ -86,27 +127,65 @@ MARGINS = {
     "env_k2": 5.19e-05,
     "cbox_pmj02bn_k2": 2.86e-06,
     "cbox_k3_range": 4.67e-06,
+    # EDGE_CASES
+    "hall_k2": 3.80e-05,
+    "cbox_k8": 9.20e-07,
+    "cbox_k8_pmj02bn": 8.99e-07,
+    "cbox_wave": 2.32e-05,
+    "cbox_wave_one": 1.45e-06,
+    "cbox_wave_ragged": 2.53e-06,
+    "cbox_wide": 7.00e-05,
+    "tiny_1x1": 3.35e-06,
+    "tiny_3x6": 3.80e-06,
+    "tiny_4x5": 2.40e-06,
+    "tiny_multi": 3.84e-05,
+    "cbox_k3_nan": 4.67e-06,
+    "env_lit_k2": 2.30e-05,
 }
 
 
+def case(name):
+    """the tuple of a case of CASES or of EDGE_CASES"""
+    return CASES[name] if name in CASES else EDGE_CASES[name]
+
+
 def bounces(name):
-    return CASES[name][5]
+    return case(name)[5]
+
+
+def nan_texels(name):
+    """[(y, x, float), ...]: the floats of the case's sample points that hold a NaN (NAN_POINTS), as texels of the buffer"""
+    make, slots, hw = case(name)[:3]
+    clean = LC.points(case(name)[7])
+    ys, xs = np.nonzero(clean[..., 12] == 1)
+    return [(int(ys[rank]), int(xs[rank]), f) for rank, f in NAN_POINTS.get(name, ())]
 
 
 @functools.lru_cache(None)
 def points(name):
     """(H, W, 16) float32: the sample points of a case"""
-    make, slots, hw = CASES[name][:3]
-    if CASES[name][7] is not None:
-        return LC.points(CASES[name][7])
+    make, slots, hw = case(name)[:3]
+    if name in NAN_POINTS:
+        pts = LC.points(case(name)[7]).copy()
+        for y, x, f in nan_texels(name):
+            pts[y, x, f] = np.nan
+        return pts
+    if case(name)[7] is not None:
+        return LC.points(case(name)[7])
     return np.ascontiguousarray(R.texel_aovs_ref(make(), slots, 0, hw, np.float32)["data"], np.float32)
+
+
+def material_sizes(name):
+    if name in MATERIAL_SIZES:
+        return list(MATERIAL_SIZES[name])
+    return [case(name)[2]] + ([case(name)[3]] if case(name)[3] else [])
 
 
 @functools.lru_cache(None)
 def materials(name):
     """the case's materials, float32 (h, w, 4): a seeded random albedo in [0.2, 0.9] and a roughness the walk ignores"""
     rng = np.random.default_rng(11)
-    sizes = [CASES[name][2]] + ([CASES[name][3]] if CASES[name][3] else [])
+    sizes = material_sizes(name)
     return tuple(np.ascontiguousarray(np.concatenate([rng.uniform(0.2, 0.9, (h, w, 3)), rng.uniform(0.1, 0.9, (h, w, 1))], -1), np.float32) for h, w in sizes)
 
 
@@ -118,7 +197,7 @@ def pmj_tables(name):
 
 
 def run_reference(name, dtype="float64", samples=None, mats=None, K=None, hits=None, oscene=None, spp=None, seed=SEED):
-    make, slots, hw, _, case_spp, case_K, env, _ = CASES[name]
+    make, slots, hw, _, case_spp, case_K, env, _ = case(name)
     pmj = name in SAMPLERS
     return BR.texel_bounce_ref(make(), LC.oracle_scene(make) if oscene is None else oscene, points(name), materials(name) if mats is None else mats, slots,
                                spp=case_spp if spp is None else spp, bounces=case_K if K is None else K, seed=seed,
@@ -177,11 +256,13 @@ def perturbed_signature_changes(name, pattern):
     return int((~BR.signature_equal(ref, moved)).sum()), int(ref["nvert"].size)
 
 
-def table_lines():
-    """the host part of profiles/texel_bounce_margins.txt (tools/texel_bounce_margins.py adds the kernels' walks on a GPU)"""
+def table_lines(names=None):
+    """the host part of profiles/texel_bounce_margins.txt (tools/texel_bounce_margins.py adds the kernels' walks on a GPU) for the cases
+    ``names`` (None: CASES)"""
+    names = list(CASES) if names is None else list(names)
     lines = [f"float32 reference against the float64 reference (tests/texel_bounce_ref.py; no GPU involved), seed {SEED}: largest absolute error of a "
              "vertex's add over the samples whose signatures (nvert, triangle and flags per vertex) agree"]
-    for name in CASES:
+    for name in names:
         ref = reference(name)
         e, same, total = margin(name)
         s = scale(name)
@@ -189,8 +270,9 @@ def table_lines():
         lines.append(f"  {name:16s} samples {total:5d}  signatures agree {same:5d}  near {near:4d}  vertices {int(ref['nvert'].sum()):6d}  accepted {int(((ref['flags'] & BR.F_ADDED) != 0).sum()):6d}"
                      f"  largest add {s:.4e}  error {e:.3e} ({e / s:.2e} of it)  floor ({FLOOR_ULPS} ulps) {FLOOR_ULPS * EPS32 * s:.3e}"
                      f"  mean bounced irradiance {float(ref['data'][..., :3][reached(name)].mean()):.4f}")
-    lines.append(f"share of the bounce vertices of env_k2 that accept an environment sample: {env_accept_share('env_k2'):.3f}")
-    for name in CASES:
+    if "env_k2" in names:
+        lines.append(f"share of the bounce vertices of env_k2 that accept an environment sample: {env_accept_share('env_k2'):.3f}")
+    for name in names:
         changes = [perturbed_signature_changes(name, k)[0] for k in range(4)]
         lines.append(f"  {name:16s} samples that change signature under +-{BARY_EPS:g} on every barycentric, four sign patterns: {changes} of {reference(name)['nvert'].size}")
     return lines

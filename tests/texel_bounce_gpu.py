@@ -14,7 +14,7 @@ _scenes = {}
 
 
 def case_scene(name, accel):
-    make, env = BC.CASES[name][0], BC.CASES[name][6]
+    make, env = BC.case(name)[0], BC.case(name)[6]
     key = (make, env, accel, BC.SAMPLERS.get(name))
     if key not in _scenes:
         scene = Scene(make(), integrator="direct", accel=accel)
@@ -38,7 +38,7 @@ def case_args(name, mats=None):
 def case_kw(name, **kw):
     kw.setdefault("samples", BC.RANGES.get(name))
     kw.setdefault("bounces", BC.bounces(name))
-    return dict(spp=BC.CASES[name][4], seed=BC.SEED, sampler="pmj02bn" if name in BC.SAMPLERS else None, slots=BC.CASES[name][1], **kw)
+    return dict(spp=BC.case(name)[4], seed=BC.SEED, sampler="pmj02bn" if name in BC.SAMPLERS else None, slots=BC.case(name)[1], **kw)
 
 
 def run_forward(name, accel, mats=None, **kw):

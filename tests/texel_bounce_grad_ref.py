@@ -34,6 +34,20 @@ MARGINS = {
     "env_k2": (1.23e-05, 0.0),
     "cbox_pmj02bn_k2": (1.36e-06, 7.92e-08),
     "cbox_k3_range": (7.26e-07, 4.51e-08),
+    # BC.EDGE_CASES
+    "hall_k2": (7.27e-06, 1.48e-07),
+    "cbox_k8": (6.36e-07, 5.33e-08),
+    "cbox_k8_pmj02bn": (8.31e-07, 4.99e-08),
+    "cbox_wave": (1.70e-07, 6.42e-08),
+    "cbox_wave_one": (6.12e-09, 3.15e-10),
+    "cbox_wave_ragged": (8.35e-08, 1.05e-08),
+    "cbox_wide": (3.80e-06, 7.76e-07),
+    "tiny_1x1": (1.34e-05, 1.22e-07),
+    "tiny_3x6": (1.57e-06, 1.68e-07),
+    "tiny_4x5": (1.29e-06, 7.45e-08),
+    "tiny_multi": (4.37e-06, 2.13e-07),
+    "cbox_k3_nan": (8.31e-07, 1.13e-07),
+    "env_lit_k2": (8.50e-06, 2.02e-07),
 }
 
 
@@ -228,7 +242,7 @@ def texel_bounce_grad_ref(rec, materials, d_out, *, emissions=None, order=None):
 # ------------------------------------------------------------------------------------ the cases of tests/texel_bounce_cases.py
 def cotangent(name):
     """the case's seeded cotangent (H, W, 4) float32, uniform in [-1, 1): NaN in channel 3 and in every texel that is not shaded"""
-    H, W = BC.CASES[name][2]
+    H, W = BC.case(name)[2]
     rng = np.random.default_rng(COT_SEED)
     g = rng.uniform(-1.0, 1.0, (H, W, 4)).astype(np.float32)
     g[..., 3] = np.nan
@@ -237,7 +251,7 @@ def cotangent(name):
 
 
 def case_records(name, hits, dtype="float64", K=None, samples=None):
-    make, slots, _, _, spp, case_K, env, _ = BC.CASES[name]
+    make, slots, _, _, spp, case_K, env, _ = BC.case(name)
     pmj = name in BC.SAMPLERS
     return records(make(), BC.points(name), slots, hits, spp=spp, bounces=case_K if K is None else K, seed=BC.SEED,
                    samples=BC.RANGES.get(name) if samples is None else samples, sampler="pmj02bn" if pmj else "cmj", env=env() if env else None,
@@ -257,7 +271,7 @@ def reference_grad(name):
 
 
 def light_rows(name):
-    return LG.light_instances(BC.CASES[name][0]())
+    return LG.light_instances(BC.case(name)[0]())
 
 
 def margin(name):
@@ -283,10 +297,10 @@ def bars(name, grad=None):
     return max(4.0 * MARGINS[name][0], FLOOR_ULPS * EPS32 * sm), max(4.0 * MARGINS[name][1], FLOOR_ULPS * EPS32 * se)
 
 
-def table_lines():
+def table_lines(names=None):
     lines = [f"float32 reference of the adjoint against the float64 reference (tests/texel_bounce_grad_ref.py; no GPU involved), seed {BC.SEED}, "
              f"cotangent seed {COT_SEED}: the larger error of ascending and descending summation per target"]
-    for name in BC.CASES:
+    for name in (BC.CASES if names is None else names):
         (em, ee), (sm, se) = margin(name)
         lines.append(f"  {name:16s} terms {reference_grad(name)['n_terms']:7d}  d_materials: largest entry {sm:.4e} error {em:.3e} ({em / sm:.2e} of it)  "
                      f"d_emission: largest entry {se:.4e} error {ee:.3e}" + (f" ({ee / se:.2e} of it)" if se > 0 else ""))

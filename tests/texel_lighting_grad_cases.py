@@ -45,6 +45,11 @@ def chandelier_arrays():
 
 
 @functools.lru_cache(None)
+def hall_arrays():
+    return ML.hall_arrays()
+
+
+@functools.lru_cache(None)
 def env_panel_lit_arrays():
     """the panel and blocker of texel_lighting_cases.env_panel_arrays, the blocker (it faces the panel) emitting (4, 2, 1)"""
     a = LC.env_panel_arrays()
@@ -64,6 +69,20 @@ CASES = {
 SAMPLERS = {"cbox_16x16_pmj_tail": (1, 16)}         # pmj02bn from seeded tables of (sets, samples per set); every other case draws with CMJ
 RANGES = {"cbox_16x16_pmj_tail": (1, 16)}           # the sample range of a case that does not take all of [0, spp)
 
+# The cases at the edges of the launch shapes (tests/test_gpu_texel_bake_edges.py, tests/test_texel_bake_edges_host.py), looked up by
+# ``case(name)`` like the others, in a table of their own so that the parametrised tests over CASES keep their size.  hall_16: 43 lights,
+# past the 32 k_lgrad_shade sums on chip.  cbox_wide_40: more live workgroups than the emission accumulator has rows.
+EDGE_CASES = {
+    "hall_16": (hall_arrays, (0,) + (None,) * 43, (16, 16), 4, None),
+    "cbox_wide_40": (TC.cbox_arrays, (0, None), (40, 40), 16, None),
+}
+
+
+def case(name):
+    """the tuple of a case of CASES or of EDGE_CASES"""
+    return CASES[name] if name in CASES else EDGE_CASES[name]
+
+
 # largest |float32 reference - float64 reference| over the entries of each target
 # (python tests/texel_lighting_grad_cases.py; profiles/texel_lighting_grad_margins.txt), rounded up in the third digit
 MARGINS = {
@@ -74,13 +93,16 @@ MARGINS = {
     "env_panel_8x8": {"env": 8.76e-07},
     "env_panel_lit_16": {"emission": 6.17e-06, "env": 1.25e-06},
     "cbox_16x16_pmj_tail": {"emission": 5.05e-07},
+    # EDGE_CASES
+    "hall_16": {"emission": 2.00e-07},
+    "cbox_wide_40": {"emission": 7.09e-07},
 }
 
 
 @functools.lru_cache(None)
 def points(name):
     """(H, W, 16) float32: the sample points of a case"""
-    make, slots, hw = CASES[name][:3]
+    make, slots, hw = case(name)[:3]
     return np.ascontiguousarray(R.texel_aovs_ref(make(), slots, 0, hw, np.float32)["data"], np.float32)
 
 
@@ -96,7 +118,7 @@ def pmj_tables(name):
 
 
 def _common(name, samples):
-    make, _, _, spp, env = CASES[name]
+    make, _, _, spp, env = case(name)
     pmj = name in SAMPLERS
     return dict(spp=spp, seed=SEED, samples=RANGES.get(name) if samples is None else samples, sampler="pmj02bn" if pmj else "cmj",
                 tables=pmj_tables(name) if pmj else None), make, env
@@ -105,7 +127,7 @@ def _common(name, samples):
 @functools.lru_cache(None)
 def raw_cotangent(name):
     """(H, W, 4) float32 seeded normals, before the uncertain texels are cleared"""
-    h, w = CASES[name][2]
+    h, w = case(name)[2]
     return np.random.default_rng(COTANGENT_SEED).standard_normal((h, w, 4)).astype(np.float32)
 
 
@@ -145,11 +167,11 @@ def forward(name, emissions=None, env_tex=None):
 
 def lights(name):
     """the instances that emit"""
-    return GR.light_instances(CASES[name][0]())
+    return GR.light_instances(case(name)[0]())
 
 
 def targets(name):
-    return (("emission",) if lights(name) else ()) + (("env",) if CASES[name][4] else ())
+    return (("emission",) if lights(name) else ()) + (("env",) if case(name)[4] else ())
 
 
 def entries(ref, target):
@@ -180,10 +202,11 @@ def failing(name, target, got, ref=None):
     return np.abs((got if target == "emission" else got[..., :3]) - want) > bar(name, target, ref)
 
 
-if __name__ == "__main__":      # the table of profiles/texel_lighting_grad_margins.txt
-    print(f"float32 reference against the float64 reference (tests/texel_lighting_grad_ref.py; no GPU involved), seed {SEED}, cotangent seed "
-          f"{COTANGENT_SEED}: largest absolute error over the entries of each target")
-    for name in CASES:
+def table_lines(names=None):
+    """the table of profiles/texel_lighting_grad_margins.txt for the cases ``names`` (None: CASES)"""
+    lines = [f"float32 reference against the float64 reference (tests/texel_lighting_grad_ref.py; no GPU involved), seed {SEED}, cotangent seed "
+             f"{COTANGENT_SEED}: largest absolute error over the entries of each target"]
+    for name in (CASES if names is None else names):
         ref, r32 = reference(name), reference(name, "float32")
         rch = reached(name)
         line = f"  {name:19s} reached {int(rch.sum()):4d}  uncertain {int((rch & ref['uncertain']).sum()):3d}  lights {len(lights(name)):2d}"
@@ -199,4 +222,24 @@ if __name__ == "__main__":      # the table of profiles/texel_lighting_grad_marg
             line += f"  | terms per light {int(n.min())} .. {int(n.max())}"
         if "env" in targets(name):
             line += f"  | texels lit by the map {int((ref['lit_env'] > 0).sum())}, by a mesh light {int((ref['lit_mesh'] > 0).sum())}, map texels with a term {int((ref['n_env'] > 0).sum())}"
-        print(line)
+        lines.append(line)
+    return lines
+
+
+def kernel_lines(names):
+    """from a GPU: the kernels' own distance to their bars (the figures tests/test_gpu_texel_lighting_grad.py prints)"""
+    import test_gpu_texel_lighting_grad as T
+    lines = ["the kernels against the float64 reference, on an MI355X: largest error per target and its largest share of an entry's bar"]
+    for name in names:
+        for accel in ("brute", "bvh"):
+            got = T.run_case(name, accel, targets(name))
+            for target, g in got.items():
+                want, _ = entries(reference(name), target)
+                err = np.abs((g if target == "emission" else g[..., :3]).astype(np.float64) - want)
+                lines.append(f"  [texel lighting grad] {name} {accel} {target}: largest error {err.max():.3e}, {(err / np.maximum(bar(name, target), 1e-300)).max():.3f} of its bar")
+    return lines
+
+
+if __name__ == "__main__":      # the table of profiles/texel_lighting_grad_margins.txt; --edges: of EDGE_CASES; --gpu: the kernels' lines for them
+    names = list(EDGE_CASES) if "--edges" in sys.argv else None
+    print("\n".join(kernel_lines(names or list(CASES)) if "--gpu" in sys.argv else table_lines(names)))

@@ -63,6 +63,26 @@ ZD f3 bgrad_cosine_lobe(f2 u) {
     return mk3(r * cs, r * sn, fsqrt(1.0f - u.x));
 }
 
+// surface_interact (scene.h) with the rounding of zdr_bounce.hip's kernels spelled out.  The replay must decide every acceptance bit as
+// the forward did, and a light sample whose shadow ray leaves its own surface at a grazing angle is decided by the last bit of it.p.  The
+// interpolation a w0 + b w1 + c w2 is left to the compiler's contraction in scene.h: every kernel of zdr_bounce.hip rounds b w1 and fuses
+// the other two products, fma(c, w2, fma(a, w0, b w1)), and so do this unit's BvhAccel kernels — its BruteAccel kernels rounded a w0 in
+// it.p.x instead, and one sample of 19,520 of a Cornell-box bake lost the light sample of its first vertex (tests/test_gpu_texel_bake_edges.py,
+// cbox_wide).  An explicit fma is the same in every kernel it is inlined into.
+ZD Interaction bgrad_interact(const DScene &S, const Hit &h) {
+    Interaction it = surface_interact(S, h);
+    const uint32_t r = 128u * (uint32_t)h.slot;
+    const float4 r0 = load_at<float4>(S.shade, r, 0), r1 = load_at<float4>(S.shade, r, 16), r2 = load_at<float4>(S.shade, r, 32),
+                 r3 = load_at<float4>(S.shade, r, 48), r4 = load_at<float4>(S.shade, r, 64), r5 = load_at<float4>(S.shade, r, 80);
+    const float w0 = 1.0f - h.u - h.v, w1 = h.u, w2 = h.v;
+    auto mix = [&](float a, float b, float c) { return __builtin_fmaf(c, w2, __builtin_fmaf(a, w0, b * w1)); };
+    it.p = mk3(mix(r0.x, r1.x, r2.x), mix(r0.y, r1.y, r2.y), mix(r0.z, r1.z, r2.z));
+    it.uv.x = mix(r0.w, r2.w, r4.w);
+    it.uv.y = mix(r1.w, r3.w, r5.w);
+    it.ns = normalize(mk3(mix(r3.x, r4.x, r5.x), mix(r3.y, r4.y, r5.y), mix(r3.z, r4.z, r5.z)));
+    return it;
+}
+
 // what read_bsdf_in needs of a table entry; chosen per lane from the wave-uniform table (BounceMat of zdr_bounce.hip)
 struct BgradMat { int32_t texel, h, w; };
 
@@ -119,7 +139,7 @@ __global__ __launch_bounds__(BGRAD_WAVE) void k_bgrad_shade(DScene S, SamplerCfg
             const bool hit = alive;
             Hit hs = h;
             if (!hit) { hs.slot = 0; hs.u = 0.0f; hs.v = 0.0f; }    // (a lane without a hit reads the first record: any valid address)
-            const Interaction it = surface_interact(S, hs);
+            const Interaction it = bgrad_interact(S, hs);
             const bool front = !(dot(-dir, it.ng) < 1e-4f || dot(-dir, it.ns) < 1e-4f);
             int slot = -1;
             if (hit) slot = load_at<int32_t>(mt.inst_slot, 4u * (uint32_t)it.inst);
