@@ -474,7 +474,7 @@ int zdr_scene_texel_lighting_backward(zdr_scene *scene, const zdr_texel_lighting
 /* Bounced light: the irradiance that reaches a texel after at least one bounce, and the share of its hemisphere that can bounce light at
  * all — a Lambertian random walk of `bounces` = K vertices from every texel.  albedo / pi x (zdr_scene_texel_lighting's irradiance + this
  * irradiance) is the Lambertian radiosity of the texel.  The irradiance has an adjoint in the materials and the emissions,
- * zdr_scene_texel_bounce_backward below; `surface` has no gradient.
+ * zdr_scene_texel_bounce_backward below, and one in the environment map, zdr_scene_texel_bounce_backward_env; `surface` has no gradient.
  *
  * Inputs.  texel_aovs (DEVICE, tex_h x tex_w x 16) has the layout of zdr_scene_texel_aovs; floats 4..6 (normal n), 8..10 (position p) and
  * 12 (reach) are read.  A texel is shaded iff reach == 1 and neither n nor p holds a NaN; every other texel is four zeros.  The materials
@@ -571,7 +571,8 @@ int zdr_texel_bounce_dump(zdr_scene *scene, const zdr_texel_bounce_params *param
  * d_out[..., 3], the cotangent of `surface`, is ignored; the cotangent of a texel that is not shaded is never read.  The seed is the
  * forward's own, and the scene must hold the forward's emissions and map.
  * Held fixed: the walks, the light list, the sampling tables, visibility and the acceptance bits.
- * Not differentiated: the environment map through the bounce, the geometry, the GGX lobe (which the forward ignores too).
+ * Not differentiated: the geometry, the GGX lobe (which the forward ignores too).  The environment map through the bounce has a call of
+ * its own, zdr_scene_texel_bounce_backward_env below.
  * Not promised: bit-stability.  The list of shaded texels varies in order from run to run and the sums use float atomics, so two runs
  * may differ in the last bits.  (The forward's bits stay what they are.)
  * Operation order.  Lanes, trips and draws are the forward's (zdr_texel_bounce_lanes_shift).  Per trip a lane (1) replays the walk and
@@ -598,6 +599,44 @@ int zdr_scene_texel_bounce_backward(zdr_scene *scene, const zdr_texel_bounce_par
                                     const int32_t *dims /* HOST nmat x {h, w} */, uint32_t nmat,
                                     float *d_materials /* DEVICE packed like materials, +=, or NULL */,
                                     float *d_emission /* DEVICE ninst x 3, +=, or NULL */, void *workspace, void *stream);
+
+/* The adjoint of zdr_scene_texel_bounce's irradiance in the environment map.  The forward reads the map at every bounce vertex whose light
+ * sample falls on it, and the bake is exactly linear in the map's texels: this is the transpose of that sparse linear map, with no
+ * approximation.
+ *
+ * Held fixed: everything zdr_scene_texel_bounce_backward holds fixed — the walks, the light list, the sampling tables, visibility and the
+ * acceptance bits.
+ * Definition.  Consider one shaded texel t and one sample s of the range.  Vertex k of the forward's walk has beta_k (the forward's, the
+ * materials included), ws = c * rcp(max(L.pdf, 1e-4)) and the forward's acceptance bit A_k, decided on add = (beta_k * L.eval) * ws as in
+ * the forward.  With gamma = d_out[t].rgb * inv_spp, an accepted vertex whose light sample came from the environment map at uv (the
+ * env_uv of sample_light: uv.x >= 0) forms
+ *     term[ch] = (gamma[ch] * beta_k[ch]) * ws,   ch = r, g, b
+ * and d_env[y][x][ch] += k_m * term[ch] on the four taps of the map's bilinear lookup (env_lookup), k_m = (1 - fx)(1 - fy), fx (1 - fy),
+ * (1 - fx) fy, fx fy.  Taps that the clamp puts on one texel receive both weights.  This is zdr_scene_texel_lighting_backward's rule with
+ * beta_k in front.  A term that is not finite is dropped.  The alpha channel is never touched.
+ * d_env is ADDED INTO: texels of the map that no sample reads keep their bits.  d_out[..., 3], the cotangent of `surface`, is ignored; the
+ * cotangent of a texel that is not shaded is never read.  The seed is the forward's own, and the scene must hold the forward's emissions
+ * and map: the acceptance test is replayed with them.
+ * Not promised: bit-stability.  The list of shaded texels varies in order from run to run and the sums use float atomics, so two runs
+ * may differ in the last bits.  (The forward's bits stay what they are.)
+ * Operation order.  Lanes, trips and draws are the forward's (zdr_texel_bounce_lanes_shift); a lane replays the walk vertex by vertex and
+ * carries beta_k.  Per vertex index the accepted environment samples of a wave are merged by map cell — the merge of
+ * zdr_scene_texel_lighting_backward: up to four cells per vertex index are summed on chip and added as 12 floats each, the samples of
+ * further cells add their 12 floats one by one.  This is a replay of its own: a caller who wants the materials' or the emissions'
+ * gradient too calls zdr_scene_texel_bounce_backward as well.
+ *
+ * workspace: zdr_texel_bounce_backward_env_workspace_bytes(tex_h, tex_w) bytes (0 = invalid size): a header — word 0 the shaded texels,
+ * word 1 the accepted environment samples, word 2 the groups of 12 floats that went to memory after the merge — and the list of texels.
+ * It needs no initialisation.  Three launches on `stream` — clear (a kernel), compact, the replay — that never allocate and never
+ * synchronise: the call can be captured without a call before, as the forward.
+ * Errors as zdr_scene_texel_bounce_backward's, and ZDR_E_INVALID for: a NULL or misaligned (16 bytes) d_env; a d_env that overlaps an
+ * input or the workspace; a scene without an environment map ("d_env given, but the scene has no environment map", as
+ * zdr_render_backward_env).  ZDR_E_UNSUPPORTED: a library linked without these kernels (zdr_bounceenv.hip). */
+size_t zdr_texel_bounce_backward_env_workspace_bytes(int32_t tex_h, int32_t tex_w);   /* 0 = invalid size */
+int zdr_scene_texel_bounce_backward_env(zdr_scene *scene, const zdr_texel_bounce_params *params, const float *texel_aovs /* DEVICE tex_h x tex_w x 16 */,
+                                        const float *d_out /* DEVICE tex_h x tex_w x 4 */, const float *materials /* DEVICE packed */,
+                                        const int32_t *dims /* HOST nmat x {h, w} */, uint32_t nmat,
+                                        float *d_env /* DEVICE map h x w x 4, += */, void *workspace, void *stream);
 
 /* Push-pull: fills the texels of a texture that a weight marks as unknown from the ones it marks as known, through a weighted pyramid — a
  * baker's seam padding — and the adjoint of that map with respect to the texture.  No scene handle.  The known texels come out bit for

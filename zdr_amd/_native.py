@@ -21,6 +21,7 @@ TANGENT_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_tangent.so")     # UV tang
 BAKEGRAD_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_bakegrad.so")   # the light baker's adjoint: likewise
 BOUNCE_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_bounce.so")       # the bounced-light baker: likewise
 BOUNCEGRAD_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_bouncegrad.so")   # the bounced-light baker's adjoint: likewise
+BOUNCEENV_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_bounceenv.so")     # its adjoint in the environment map: likewise
 TEXEL_LIB_PATH = os.path.join(HERE, "csrc", "libzdr_texel.so")   # the texture-space kernels: a dependency of libzdr_hip.so, found beside it
 
 COLLOCATED, DIRECT, PATH, UVGRAD = 0, 1, 2, 3
@@ -57,7 +58,8 @@ EXPORTS = ("zdr_version", "zdr_abi_version", "zdr_last_error", "zdr_scene_create
            "zdr_scene_texel_tangents", "zdr_texel_footprint_tangents",
            "zdr_texel_lighting_backward_workspace_bytes", "zdr_scene_texel_lighting_backward",
            "zdr_texel_bounce_workspace_bytes", "zdr_texel_bounce_lanes_shift", "zdr_scene_texel_bounce", "zdr_texel_bounce_dump",
-           "zdr_texel_bounce_backward_workspace_bytes", "zdr_scene_texel_bounce_backward")
+           "zdr_texel_bounce_backward_workspace_bytes", "zdr_scene_texel_bounce_backward",
+           "zdr_texel_bounce_backward_env_workspace_bytes", "zdr_scene_texel_bounce_backward_env")
 
 
 class CameraPOD(C.Structure):
@@ -203,6 +205,9 @@ def lib():
     L.zdr_texel_bounce_backward_workspace_bytes.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_uint32]
     L.zdr_texel_bounce_backward_workspace_bytes.restype = C.c_size_t
     L.zdr_scene_texel_bounce_backward.argtypes = [vp, C.POINTER(TexelBounceParams), fp, fp, fp, ip, C.c_uint32, fp, fp, vp, vp]
+    L.zdr_texel_bounce_backward_env_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.zdr_texel_bounce_backward_env_workspace_bytes.restype = C.c_size_t
+    L.zdr_scene_texel_bounce_backward_env.argtypes = [vp, C.POINTER(TexelBounceParams), fp, fp, fp, ip, C.c_uint32, fp, vp, vp]
     L.zdr_push_pull_workspace_bytes.argtypes = [C.POINTER(PushPullParams)]
     L.zdr_push_pull_workspace_bytes.restype = C.c_size_t
     L.zdr_push_pull.argtypes = [C.POINTER(PushPullParams), fp, fp, fp, vp, vp]

@@ -43,6 +43,9 @@ BOUNCE_LIB = os.path.join(CSRC, "libzdr_bounce.so")
 # The adjoint of the bounced-light baker in the materials and the emissions (zdr_bouncegrad.hip): a thirteenth, so that libzdr_bounce.so
 # keeps exactly its kernels.
 BOUNCEGRAD_LIB = os.path.join(CSRC, "libzdr_bouncegrad.so")
+# The adjoint of the bounced-light baker in the environment map (zdr_bounceenv.hip): a fourteenth, so that libzdr_bounce.so and
+# libzdr_bouncegrad.so keep exactly their kernels.
+BOUNCEENV_LIB = os.path.join(CSRC, "libzdr_bounceenv.so")
 ARCH = "gfx950"
 
 
@@ -72,7 +75,7 @@ def source_hash() -> str:
 
 
 def stale() -> bool:
-    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB, VIEWGRAD_LIB, TANGENT_LIB, BAKEGRAD_LIB, BOUNCE_LIB, BOUNCEGRAD_LIB)):
+    if not all(os.path.exists(p) for p in (LIB, TEXEL_LIB, BAKE_LIB, PUSHPULL_LIB, PROJECT_LIB, MIP_LIB, ANISO_LIB, PLAN_LIB, VIEWGRAD_LIB, TANGENT_LIB, BAKEGRAD_LIB, BOUNCE_LIB, BOUNCEGRAD_LIB, BOUNCEENV_LIB)):
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(s) > t for s in _sources())
@@ -137,6 +140,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         # the adjoint of the bounced-light baker, linked into libzdr_bouncegrad.so, under the flags of zdr_bakegrad.hip: the walk of
         # zdr_bounce.hip once more, and its sums into the staging cells and the emission accumulator become global_atomic_add_f32
         ("zdr_bouncegrad.hip", ["-O3", "-fno-slp-vectorize", "-munsafe-fp-atomics"]),
+        # the adjoint of the bounced-light baker in the environment map, linked into libzdr_bounceenv.so, under the flags of
+        # zdr_bouncegrad.hip: the walk once more, and its sums into the map become global_atomic_add_f32
+        ("zdr_bounceenv.hip", ["-O3", "-fno-slp-vectorize", "-munsafe-fp-atomics"]),
     ]
     procs = []
     for src, extra in jobs:
@@ -150,7 +156,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-    bouncegrad_obj = objs.pop()                             # (zdr_bouncegrad.o: the last job)
+    bounceenv_obj = objs.pop()                              # (zdr_bounceenv.o: the last job)
+    bouncegrad_obj = objs.pop()                             # (zdr_bouncegrad.o: the one before)
     bounce_obj = objs.pop()                                 # (zdr_bounce.o: the one before)
     bakegrad_obj = objs.pop()                               # (zdr_bakegrad.o: the one before)
     tangent_obj = objs.pop()                                # (zdr_tangent.o: the one before)
@@ -174,8 +181,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BAKEGRAD_LIB, bakegrad_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BOUNCE_LIB, bounce_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BOUNCEGRAD_LIB, bouncegrad_obj],
+             [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", BOUNCEENV_LIB, bounceenv_obj],
              [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs, "-Wl,--no-as-needed", "-L" + CSRC, "-lzdr_texel", "-lzdr_bake", "-lzdr_pushpull",
-              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan", "-lzdr_viewgrad", "-lzdr_tangent", "-lzdr_bakegrad", "-lzdr_bounce", "-lzdr_bouncegrad",
+              "-lzdr_project", "-lzdr_mip", "-lzdr_aniso", "-lzdr_plan", "-lzdr_viewgrad", "-lzdr_tangent", "-lzdr_bakegrad", "-lzdr_bounce", "-lzdr_bouncegrad", "-lzdr_bounceenv",
               "-Wl,-rpath,$ORIGIN"]]
     for cmd in links:
         r = subprocess.run(cmd, capture_output=True, text=True)

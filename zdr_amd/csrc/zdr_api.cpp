@@ -39,6 +39,8 @@
 #include "bounce.h"
 #define ZDR_BOUNCEGRAD_LAUNCHER_REF __attribute__((weak))   // (csrc/bouncegrad.h)
 #include "bouncegrad.h"
+#define ZDR_BOUNCEENV_LAUNCHER_REF __attribute__((weak))    // (csrc/bounceenv.h)
+#include "bounceenv.h"
 #include "internal.h"
 #include "zdr.h"
 
@@ -1909,6 +1911,45 @@ extern "C" int zdr_scene_texel_bounce_backward(zdr_scene *s, const zdr_texel_bou
     G.cell_copies = cell_copies; G.ncell_words = (uint32_t)(4 * cells);
     if (int rc = zdr_launch_texel_bounce_backward(S, s->accel_is_bvh, C, G, mt, (hipStream_t)stream))
         return fail(ZDR_E_HIP, "texel bounce backward: launch " + std::to_string(rc / 256) + " of 5 failed: " + hipGetErrorString((hipError_t)(rc % 256)));
+    return ZDR_OK;
+}
+
+// zdr_scene_texel_bounce_backward_env (include/zdr.h): the forward's checks, then the three launches of zdr_bounceenv.hip on the caller's
+// stream.  The handle is only read; the workspace is the forward's (a header and the list), so nothing is allocated and the call can be
+// captured without a call before.
+extern "C" size_t zdr_texel_bounce_backward_env_workspace_bytes(int32_t tex_h, int32_t tex_w) {
+    if (bounce_check_size(tex_h, tex_w)) return 0;
+    return ZDR_BOUNCE_HEADER_BYTES + bgrad_list_bytes(tex_h, tex_w);
+}
+
+extern "C" int zdr_scene_texel_bounce_backward_env(zdr_scene *s, const zdr_texel_bounce_params *p, const float *texel_aovs, const float *d_out, const float *materials,
+                                                   const int32_t *dims, uint32_t nmat, float *d_env, void *workspace, void *stream) {
+    if (!d_out || !workspace) return fail(ZDR_E_INVALID, "null argument");
+    if (!d_env) return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce_backward_env: d_env is NULL");
+    if ((uintptr_t)d_out % 16 || (uintptr_t)workspace % 16 || (uintptr_t)d_env % 16)
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce_backward_env: d_out, d_env and workspace must be 16-byte aligned");
+    if (s && s->ds.env_count <= 0) return fail(ZDR_E_INVALID, "d_env given, but the scene has no environment map");
+    if (!zdr_launch_texel_bounce_backward_env)                       // (weak: csrc/bounceenv.h)
+        return fail(ZDR_E_UNSUPPORTED, "this library was linked without the bounced-light environment gradient kernels (zdr_bounceenv.hip)");
+    SamplerCfg C; BounceArgs B; MaterialTable mt;
+    if (int rc = bounce_prepare(s, p, texel_aovs, materials, dims, nmat, (hipStream_t)stream, C, B, mt)) return rc;
+    const size_t n = B.ntexels, wbytes = ZDR_BOUNCE_HEADER_BYTES + bgrad_list_bytes(p->tex_h, p->tex_w);
+    size_t mbytes = 0;
+    for (uint32_t k = 0; k < nmat; k++) mbytes += 16 * (size_t)dims[2 * k] * (size_t)dims[2 * k + 1];
+    const size_t ebytes = 16 * (size_t)s->ds.env_h * (size_t)s->ds.env_w;
+    if (denoise_overlap(workspace, wbytes, {{texel_aovs, 64 * n}, {d_out, 16 * n}, {materials, mbytes}, {d_env, ebytes}}))
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce_backward_env: the workspace must not overlap texel_aovs, d_out, the materials or d_env");
+    if (denoise_overlap(d_env, ebytes, {{texel_aovs, 64 * n}, {d_out, 16 * n}, {materials, mbytes}}))
+        return fail(ZDR_E_INVALID, "zdr_scene_texel_bounce_backward_env: d_env must not overlap texel_aovs, d_out or the materials");
+    DScene S = s->ds;
+    S.shadow_pairs = ~0ull;      // every pair, as the forward
+    BenvArgs G; memset(&G, 0, sizeof G);
+    G.texels = B.texels; G.d_out = (const float4 *)d_out; G.materials = B.materials; G.d_env = d_env;
+    G.count = (uint32_t *)workspace; G.list = (uint32_t *)((char *)workspace + ZDR_BOUNCE_HEADER_BYTES);
+    G.ntexels = B.ntexels; G.tex_w = B.tex_w; G.sample_begin = B.sample_begin; G.sample_end = B.sample_end;
+    G.inv_spp = B.inv_spp; G.bounces = B.bounces; G.wide_offsets = B.wide_offsets;
+    if (int rc = zdr_launch_texel_bounce_backward_env(S, s->accel_is_bvh, C, G, mt, (hipStream_t)stream))
+        return fail(ZDR_E_HIP, "texel bounce backward (environment): launch " + std::to_string(rc / 256) + " of 3 failed: " + hipGetErrorString((hipError_t)(rc % 256)));
     return ZDR_OK;
 }
 

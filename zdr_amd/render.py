@@ -952,14 +952,43 @@ class Scene:
             self._unpack_grads(dpacked, d_materials)
         return d_materials, d_emission
 
+    def texel_bounce_backward_env(self, texel_data, d_out, materials, *, spp, bounces=1, seed=0, samples=None, sampler=None, dims=None, slots=None,
+                                  d_env, workspace=None):
+        """The adjoint of ``texel_bounce_forward``'s irradiance in the environment map (include/zdr.h,
+        zdr_scene_texel_bounce_backward_env): with the cotangent ``d_out`` (H, W, 4) — float 3 and every texel that is not shaded are
+        ignored — ADDS the gradient of the map's rgb into ``d_env``, a prepared float32 tensor of the map's size (alpha is never
+        touched, and texels that no bounce vertex samples keep their bits).  The other arguments are the forward's (the same seed),
+        and the scene must hold the forward's emissions and map.  The bake is linear in the map: with the walks, the sampling tables,
+        visibility and the acceptance bits held fixed this is the exact transpose.  A replay of the walk of its own, beside
+        ``texel_bounce_backward``'s.  Not bit-stable from run to run (float atomics).  ``workspace``: any tensor of at least
+        ``zdr_texel_bounce_backward_env_workspace_bytes`` bytes, allocated when not given; it needs no initialisation.  Only enqueues,
+        on torch's current stream.  Returns ``d_env``."""
+        texel_data, packed, d, p = self._bounce_call(texel_data, materials, spp, bounces, seed, samples, sampler, dims, slots)
+        H, W = p.tex_h, p.tex_w
+        if not isinstance(d_out, torch.Tensor) or tuple(d_out.shape) != (H, W, 4) or d_out.dtype != torch.float32 or d_out.device != self.device:
+            raise ValueError(f"d_out must be a float32 ({H}, {W}, 4) tensor on {self.device}")
+        d_out = d_out.detach().contiguous()
+        if not isinstance(d_env, torch.Tensor):
+            raise ValueError("texel_bounce_backward_env needs d_env, a prepared float32 tensor of the map's size")
+        self._check_d_env(d_env)
+        workspace = self._workspace(workspace, int(N.lib().zdr_texel_bounce_backward_env_workspace_bytes(H, W)))
+        N.check(N.lib().zdr_scene_texel_bounce_backward_env(self._handle, C.byref(p), texel_data.data_ptr(), d_out.data_ptr(), packed.data_ptr(),
+                                                            d.ctypes.data, d.shape[0], d_env.data_ptr(), workspace.data_ptr(), self._stream()))
+        return d_env
+
     class TexelBounceOperator(torch.autograd.Function):
-        """texel_bounce() of materials that require grad and / or with ``emissions=``, modelled on TexelLightingOperator: a detached
-        copy of the emissions becomes the scene's values in the forward, and the backward applies the forward's light list and values
-        again before the native call.  The forward is texel_bounce_forward, unchanged."""
+        """texel_bounce() of materials that require grad and / or with ``emissions=`` and / or ``envmap=``, modelled on
+        TexelLightingOperator: detached copies of the emissions and of the prepared map become the scene's values in the forward, and
+        the backward applies the forward's light list, values and map again before the native calls.  The forward is
+        texel_bounce_forward, unchanged."""
         @staticmethod
-        def forward(ctx, emissions, self, texel_data, spp, bounces, seed, samples, slots, *mats):
+        def forward(ctx, emissions, self, texel_data, spp, bounces, seed, samples, slots, env, *mats):
+            if env is not None:
+                env = env.detach().clone()
+                self.set_envmap_texture(env)
             if emissions is not None:
                 self.set_emission_values(emissions.detach().clone())
+            ctx.env = env
             ctx.with_emissions = emissions is not None
             ctx.scene = weakref.ref(self)
             ctx.texel_data = texel_data.detach()
@@ -975,17 +1004,23 @@ class Scene:
                 scene.update_lights(ctx.emissions)
             spp, bounces, seed, samples, sampler, slots = ctx.args
             mats = [m.detach() for m in ctx.saved_tensors]
-            d_emission = None
+            d_emission = d_env = None
             if ctx.with_emissions:
                 scene._apply_emission_values(ctx.emissions.values)
                 d_emission = torch.zeros_like(ctx.emissions.values)
-            d_mats = [torch.zeros_like(m) for m in mats] if any(ctx.needs_input_grad[8:]) else None
+            if ctx.env is not None:
+                scene.set_envmap_texture(ctx.env)
+            d_mats = [torch.zeros_like(m) for m in mats] if any(ctx.needs_input_grad[9:]) else None
             g = grad_output.to(device=scene.device, dtype=torch.float32).contiguous()
-            scene.texel_bounce_backward(ctx.texel_data, g, mats, spp=spp, bounces=bounces, seed=seed, samples=samples, sampler=sampler, slots=slots,
-                                        d_materials=d_mats, d_emission=d_emission)
-            return (d_emission, None, None, None, None, None, None, None) + (tuple(d_mats) if d_mats is not None else (None,) * len(mats))
+            if d_mats is not None or d_emission is not None:
+                scene.texel_bounce_backward(ctx.texel_data, g, mats, spp=spp, bounces=bounces, seed=seed, samples=samples, sampler=sampler, slots=slots,
+                                            d_materials=d_mats, d_emission=d_emission)
+            if ctx.env is not None and ctx.needs_input_grad[8]:
+                d_env = scene.texel_bounce_backward_env(ctx.texel_data, g, mats, spp=spp, bounces=bounces, seed=seed, samples=samples, sampler=sampler,
+                                                        slots=slots, d_env=torch.zeros_like(ctx.env))
+            return (d_emission, None, None, None, None, None, None, None, d_env) + (tuple(d_mats) if d_mats is not None else (None,) * len(mats))
 
-    def texel_bounce(self, material, index=0, *, spp=16, bounces=1, seed=0, samples=None, texels=None, emissions=None) -> TexelBounce:
+    def texel_bounce(self, material, index=0, *, spp=16, bounces=1, seed=0, samples=None, texels=None, emissions=None, envmap=None) -> TexelBounce:
         """The light that reaches each texel of ``material[index]`` after at least one bounce: a ``TexelBounce`` whose ``data`` is the
         (H, W, 4) tensor of include/zdr.h, zdr_scene_texel_bounce, at that material's size — ``irradiance``, the irradiance arriving
         after 1 .. ``bounces`` Lambertian bounces, and ``surface``, the share of the hemisphere that can bounce light at all.
@@ -995,21 +1030,24 @@ class Scene:
         Lambertian radiosity of a texel.  Roughness is ignored, and ``bounces`` truncates the walk.
 
         ``irradiance`` is differentiable in the rgb of every material tensor that requires grad (each receives a gradient of its own
-        shape) and in ``emissions``, a float32 (ninst, 3) tensor on the GPU that becomes the scene's values as in ``texel_lighting``
-        (include/zdr.h, zdr_scene_texel_bounce_backward): the walks, the light list, the sampling tables and visibility are held
-        fixed, so for one seed the gradient is exact; its sums use float atomics and may differ in the last bits from run to run.
-        ``surface`` has no gradient, nor have the roughness, the geometry and the environment map.  With plain tensors and without
-        ``emissions`` the call builds no autograd node and returns the bits of ``texel_bounce_forward``."""
+        shape), in ``emissions``, a float32 (ninst, 3) tensor on the GPU that becomes the scene's values as in ``texel_lighting``
+        (include/zdr.h, zdr_scene_texel_bounce_backward), and in ``envmap``, a float32 (H, 2H, 3|4) or (H, H, 3|4) tensor on the GPU
+        that becomes the scene's map as in ``texel_lighting`` (zdr_scene_texel_bounce_backward_env; its gradient comes back in the
+        caller's shape, from a second replay of the walk — ``texel_bounce_backward_env``): the walks, the light list, the sampling
+        tables and visibility are held fixed, so for one seed the gradient is exact; its sums use float atomics and may differ in the
+        last bits from run to run.  ``surface`` has no gradient, nor have the roughness and the geometry.  With plain tensors and
+        without ``emissions`` and ``envmap`` the call builds no autograd node and returns the bits of ``texel_bounce_forward``."""
         if emissions is not None:
             check_emissions(emissions, self.inst_count, self.device)
+        env = None if envmap is None else self._prepare_envmap(envmap)
         mats, slots, dims, _ = self._resolve_materials(material, True, pack=False)
         if not 0 <= int(index) < len(dims):
             raise ValueError(f"index {index}: {len(dims)} materials were given")
         if texels is None:
             texels = self.texel_aovs(material, index)
-        if emissions is None and not (torch.is_grad_enabled() and any(m.requires_grad for m in mats)):
+        if emissions is None and env is None and not (torch.is_grad_enabled() and any(m.requires_grad for m in mats)):
             return TexelBounce(self.texel_bounce_forward(texels.data, mats, spp=spp, bounces=bounces, seed=seed, samples=samples, slots=slots))
-        return TexelBounce(Scene.TexelBounceOperator.apply(emissions, self, texels.data, spp, bounces, seed, samples, slots, *mats))
+        return TexelBounce(Scene.TexelBounceOperator.apply(emissions, self, texels.data, spp, bounces, seed, samples, slots, env, *mats))
 
     # ------------------------------------------------------------- texture-space views
     def texel_view_forward(self, texel_data, res, *, camera=None, out=None, workspace=None):
