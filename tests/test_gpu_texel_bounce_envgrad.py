@@ -234,9 +234,8 @@ def test_bvh_and_brute_force_agree():
 
 
 # ------------------------------------------------------------------------------------ 7. linearity: a dot-product test
-@pytest.mark.parametrize("accel", ACCELS)
-def test_the_bake_is_linear_in_the_map_a_dot_product_test_against_the_gpu_forward(accel):
-    name = "env_k2"
+def dot_product_against_the_gpu_forward(name, accel):
+    """<d_out, F(env + d) - F(env)> of two GPU bakes against <d_env, d> of the adjoint, for a case that tests/texel_bounce_cases.py shares"""
     scene = case_scene(name, accel)
     ref = dump_reference(name, accel)
     bar_g = ER.bar(name, ref)
@@ -264,6 +263,11 @@ def test_the_bake_is_linear_in_the_map_a_dot_product_test_against_the_gpu_forwar
     print(f"[texel bounce envgrad] {name} {accel}: sum d_out (F(env + d) - F(env)) = {lhs:.9e}, sum d_env d = {rhs:.9e}, differ by {abs(lhs - rhs):.3e} (bar {bar:.3e})")
     assert abs(rhs) > 0 and abs(lhs) > 0
     assert abs(lhs - rhs) <= bar
+
+
+@pytest.mark.parametrize("accel", ACCELS)
+def test_the_bake_is_linear_in_the_map_a_dot_product_test_against_the_gpu_forward(accel):
+    dot_product_against_the_gpu_forward("env_k2", accel)
 
 
 # ------------------------------------------------------- 8. one bounce under unit albedos is the lighting adjoint at the first vertices

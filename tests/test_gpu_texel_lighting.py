@@ -25,7 +25,7 @@ _scenes = {}
 
 
 def case_scene(name, accel):
-    make, env = LC.CASES[name][0], LC.CASES[name][5]
+    make, env = LC.case(name)[0], LC.case(name)[5]
     key = (make, env, accel, LC.SAMPLERS.get(name))
     if key not in _scenes:
         scene = Scene(make(), integrator="direct", accel=accel)
@@ -47,7 +47,7 @@ def case_points(name):
 
 
 def run_case(name, accel, **kw):
-    _, _, _, spp, max_distance, _ = LC.CASES[name]
+    _, _, _, spp, max_distance, _ = LC.case(name)
     kw.setdefault("samples", LC.RANGES.get(name))
     out = case_scene(name, accel).texel_lighting_forward(case_points(name), spp=spp, seed=LC.SEED, max_distance=max_distance,
                                                          sampler="pmj02bn" if name in LC.SAMPLERS else None, **kw)

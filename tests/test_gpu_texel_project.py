@@ -37,7 +37,7 @@ def camera(name):
 
 
 def case_scene(name, accel):
-    make = LC.CASES[PC.CASES[name][0]][0]
+    make = LC.case(PC.case(name)[0])[0]
     if (make, accel) not in _scenes:
         scene = Scene(make(), integrator="direct", accel=accel)
         assert scene.info()["accel"] == accel
@@ -50,7 +50,7 @@ def case_points(name):
 
 
 def run_case(name, accel, **kw):
-    _, cam, res = PC.CASES[name]
+    _, cam, res = PC.case(name)
     out = case_scene(name, accel).texel_view_forward(case_points(name), res, camera=camera(cam), **kw)
     torch.cuda.synchronize()
     return out

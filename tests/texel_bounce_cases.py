@@ -25,6 +25,7 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):       # (run as a 
 
 import texel_bounce_ref as BR                                    # noqa: E402
 import texel_cases as TC                                         # noqa: E402
+import texel_deep_cases as DC                                    # noqa: E402
 import texel_lighting_cases as LC                                # noqa: E402
 import texel_ref as R                                            # noqa: E402
 from zdr_amd import geometry, scenes                             # noqa: E402
@@ -115,7 +116,11 @@ MATERIAL_SIZES = {"cbox_wide": ((64, 64),), "tiny_1x1": ((1, 1),), "tiny_3x6": (
 # (row-major index of a reached texel's rank, float of its row): a NaN in a position and, 100 reached texels on, one in a normal
 NAN_POINTS = {"cbox_k3_nan": ((20, 9), (120, 5))}
 
-SAMPLERS = {"cbox_pmj02bn_k2": (5, 256), "cbox_k8_pmj02bn": (5, 256)}   # pmj02bn from seeded tables of (sets, samples per set); every other case draws with CMJ
+# The cases on a BVH deeper than the LDS part of the traversal stack (tests/texel_deep_cases.py; tests/test_gpu_texel_deep_stack.py,
+# tests/test_texel_deep_stack_host.py): the same tuples, in a table of their own like EDGE_CASES.
+DEEP_CASES = DC.BOUNCE
+
+SAMPLERS = {"cbox_pmj02bn_k2": (5, 256), "cbox_k8_pmj02bn": (5, 256), **DC.BOUNCE_SAMPLERS}   # pmj02bn from seeded tables of (sets, samples per set); every other case draws with CMJ
 RANGES = {"cbox_k3_range": (1, 4), "cbox_wave_one": (0, 1), "cbox_wave_ragged": (3, 40)}   # the sample range of a case that does not take all of [0, spp)
 
 # largest |float32 reference - float64 reference| of a vertex's add over the samples whose signatures agree
@@ -141,12 +146,13 @@ MARGINS = {
     "tiny_multi": 3.84e-05,
     "cbox_k3_nan": 4.67e-06,
     "env_lit_k2": 2.30e-05,
+    **DC.BOUNCE_MARGINS,                                              # DEEP_CASES
 }
 
 
 def case(name):
-    """the tuple of a case of CASES or of EDGE_CASES"""
-    return CASES[name] if name in CASES else EDGE_CASES[name]
+    """the tuple of a case of CASES, of EDGE_CASES or of DEEP_CASES"""
+    return CASES[name] if name in CASES else EDGE_CASES[name] if name in EDGE_CASES else DEEP_CASES[name]
 
 
 def bounces(name):

@@ -27,6 +27,7 @@ import numpy as np
 import envmap_tables as ET
 import texel_bounce_cases as BC
 import texel_bounce_ref as BR
+import texel_deep_cases as DC
 import texel_lighting_cases as LC
 import texel_ref as R
 from zdr_amd import envmap as E
@@ -65,11 +66,14 @@ CASES = {
     "env_wave_ragged": _case(BC.env_bounce_arrays, BC.ENV_SLOTS, (5, 5), (3, 4), 64, 2, LC.sun_env, samples=(3, 40)),
     "env_sky": _case(BC.env_bounce_arrays, BC.ENV_SLOTS, (5, 5), (3, 4), 64, 2, sky_env),
 }
+# the cases on a BVH deeper than the LDS part of the traversal stack (tests/texel_deep_cases.py): those of BC.DEEP_CASES that have a map,
+# shared with tests/texel_bounce_cases.py as env_k2 is, in a table of their own so that the parametrised tests over CASES keep their size
+DEEP_CASES = {n: _case(*BC.case(n)[:7], shared=n) for n in DC.BOUNCE_ENV}
 VERTEX_OF_CONDITION_1 = {"env_lit_k2": 1}      # the vertex index (0-based) that must accept 8 environment samples; every other case: 0
 
 
 def case(name):
-    return CASES[name]
+    return CASES[name] if name in CASES else DEEP_CASES[name]
 
 
 @functools.lru_cache(None)

@@ -17,6 +17,7 @@ import numpy as np
 import texel_bounce_env_cases as EC
 import texel_bounce_grad_ref as GR
 import texel_bounce_ref as BR
+import texel_deep_cases as DC
 import texel_lighting_grad_ref as LG
 import texel_lighting_ref as LR
 
@@ -37,6 +38,12 @@ MARGINS = {
     "env_wave_ragged": 5.02e-09,
     "env_sky": 1.76e-07,
 }
+DEEP_MARGINS = DC.BOUNCE_ENVGRAD_MARGINS      # the same for EC.DEEP_CASES (tests/texel_deep_cases.py): a table of its own, as the cases are
+
+
+def margin_of(name):
+    """the table's margin of a case of EC.CASES or of EC.DEEP_CASES"""
+    return MARGINS[name] if name in MARGINS else DEEP_MARGINS[name]
 
 
 def env_records(arrays, texel_data, slots, hits, *, spp, bounces, seed=0, samples=None, sampler="cmj", env, tables=None, dtype=np.float64):
@@ -239,7 +246,7 @@ def scale(grad):
 
 def bar(name, grad=None):
     """max(4 x margin, 4 float32 ulps of the case's largest entry): the rule of texel_bounce_grad_ref.bars"""
-    return max(4.0 * MARGINS[name], FLOOR_ULPS * EPS32 * scale(reference_grad(name) if grad is None else grad))
+    return max(4.0 * margin_of(name), FLOOR_ULPS * EPS32 * scale(reference_grad(name) if grad is None else grad))
 
 
 def table_lines(names=None):

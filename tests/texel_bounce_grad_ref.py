@@ -17,6 +17,7 @@ import numpy as np
 
 import texel_bounce_cases as BC
 import texel_bounce_ref as BR
+import texel_deep_cases as DC
 import texel_lighting_grad_ref as LG
 import texel_lighting_ref as LR
 
@@ -48,6 +49,7 @@ MARGINS = {
     "tiny_multi": (4.37e-06, 2.13e-07),
     "cbox_k3_nan": (8.31e-07, 1.13e-07),
     "env_lit_k2": (8.50e-06, 2.02e-07),
+    **DC.BOUNCE_GRAD_MARGINS,                                         # BC.DEEP_CASES
 }
 
 

@@ -23,6 +23,7 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):       # (run as a 
 
 import envmap_tables as ET                                       # noqa: E402
 import texel_cases as TC                                         # noqa: E402
+import texel_deep_cases as DC                                    # noqa: E402
 import texel_lighting_ref as LR                                  # noqa: E402
 import texel_ref as R                                            # noqa: E402
 from oracle import OracleScene                                   # noqa: E402
@@ -96,13 +97,23 @@ MARGINS = {
     "cbox_16x16_ao": 4.14e-07,
     "cbox_16x16_pmj02bn": 2.36e-07,
     "cbox_16x16_pmj_tail": 1.76e-07,
+    **DC.LIGHTING_MARGINS,                                            # DEEP_CASES
 }
+
+# The cases on a BVH deeper than the LDS part of the traversal stack (tests/texel_deep_cases.py), and the sample points of its view
+# case: the same tuples, looked up by ``case(name)``, in a table of their own so that the parametrised tests over CASES keep their size.
+DEEP_CASES = {**DC.LIGHTING, **DC.LIGHTING_POINTS}
+
+
+def case(name):
+    """the tuple of a case of CASES or of DEEP_CASES"""
+    return CASES[name] if name in CASES else DEEP_CASES[name]
 
 
 @functools.lru_cache(None)
 def points(name):
     """(H, W, 16) float32: the sample points of a case"""
-    make, slots, hw = CASES[name][:3]
+    make, slots, hw = case(name)[:3]
     return np.ascontiguousarray(R.texel_aovs_ref(make(), slots, 0, hw, np.float32)["data"], np.float32)
 
 
@@ -121,7 +132,7 @@ def pmj_tables(name):
 
 @functools.lru_cache(None)
 def reference(name, dtype="float64", samples=None):
-    make, slots, hw, spp, max_distance, env = CASES[name]
+    make, slots, hw, spp, max_distance, env = case(name)
     pmj = name in SAMPLERS
     return LR.texel_lighting_ref(make(), oracle_scene(make), points(name), spp=spp, seed=SEED, samples=RANGES.get(name) if samples is None else samples,
                                  max_distance=max_distance, sampler="pmj02bn" if pmj else "cmj", env=env() if env else None,

@@ -26,6 +26,7 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):       # (run as a 
 
 import many_lights as ML                                         # noqa: E402
 import texel_cases as TC                                         # noqa: E402
+import texel_deep_cases as DC                                    # noqa: E402
 import texel_lighting_cases as LC                                # noqa: E402
 import texel_lighting_grad_ref as GR                             # noqa: E402
 import texel_lighting_ref as LR                                  # noqa: E402
@@ -78,9 +79,13 @@ EDGE_CASES = {
 }
 
 
+# the cases on a BVH deeper than the LDS part of the traversal stack (tests/texel_deep_cases.py), by the same convention
+DEEP_CASES = DC.LIGHTING_GRAD
+
+
 def case(name):
-    """the tuple of a case of CASES or of EDGE_CASES"""
-    return CASES[name] if name in CASES else EDGE_CASES[name]
+    """the tuple of a case of CASES, of EDGE_CASES or of DEEP_CASES"""
+    return CASES[name] if name in CASES else EDGE_CASES[name] if name in EDGE_CASES else DEEP_CASES[name]
 
 
 # largest |float32 reference - float64 reference| over the entries of each target
@@ -96,6 +101,7 @@ MARGINS = {
     # EDGE_CASES
     "hall_16": {"emission": 2.00e-07},
     "cbox_wide_40": {"emission": 7.09e-07},
+    **DC.LIGHTING_GRAD_MARGINS,                                       # DEEP_CASES
 }
 
 
@@ -240,6 +246,6 @@ def kernel_lines(names):
     return lines
 
 
-if __name__ == "__main__":      # the table of profiles/texel_lighting_grad_margins.txt; --edges: of EDGE_CASES; --gpu: the kernels' lines for them
-    names = list(EDGE_CASES) if "--edges" in sys.argv else None
+if __name__ == "__main__":      # the table of profiles/texel_lighting_grad_margins.txt; --edges: of EDGE_CASES; --deep: of DEEP_CASES; --gpu: the kernels' lines for them
+    names = list(EDGE_CASES) if "--edges" in sys.argv else list(DEEP_CASES) if "--deep" in sys.argv else None
     print("\n".join(kernel_lines(names or list(CASES)) if "--gpu" in sys.argv else table_lines(names)))

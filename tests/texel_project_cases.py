@@ -23,6 +23,7 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):       # (run as a 
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import texel_deep_cases as DC                                    # noqa: E402
 import texel_lighting_cases as LC                                # noqa: E402
 import texel_project_ref as PR                                   # noqa: E402
 from zdr_amd.scenes import CBOX_CAMERA                           # noqa: E402
@@ -36,6 +37,7 @@ CHANNELS = ("cosine", "pixel_x", "pixel_y", "depth", "distance", "scale")      #
 CAMERAS = {
     "standard": (CBOX_CAMERA[0], (-0.2, 2.6, 6.0), (-0.2, 2.6, -2.5), (0.0, 1.0, 0.0)),
     "inside": (CBOX_CAMERA[0], (0.3, 2.0, 0.5), (2.5, 1.0, -1.5), (0.0, 1.0, 0.0)),
+    **DC.cameras(),
 }
 
 # name: (points of texel_lighting_cases, camera, (width, height))
@@ -67,20 +69,29 @@ MARGINS = {
     "cbox_16x16_inside": (1.25e-07, 4.06e-03, 9.70e-04, 5.14e-07, 4.82e-07, 1.03e-03),
     "cbox_64x64_inside": (1.51e-07, 5.09e-01, 2.18e-01, 5.81e-07, 5.35e-07, 3.24e-02),
     "cbox_64x64_inside_1x1": (1.51e-07, 2.12e-02, 9.06e-03, 5.81e-07, 5.35e-07, 1.35e-03),
+    **DC.VIEW_MARGINS,                                                # DEEP_CASES
 }
+
+# the view down a shaft whose BVH is deeper than the LDS part of the traversal stack (tests/texel_deep_cases.py): the same tuples,
+# looked up by ``case(name)``, in a table of their own so that the parametrised tests over CASES keep their size
+DEEP_CASES = DC.VIEW
+
+
+def case(name):
+    return CASES[name] if name in CASES else DEEP_CASES[name]
 
 
 def points(name):
-    return LC.points(CASES[name][0])
+    return LC.points(case(name)[0])
 
 
 def oracle_scene(name):
-    return LC.oracle_scene(LC.CASES[CASES[name][0]][0])
+    return LC.oracle_scene(LC.case(case(name)[0])[0])
 
 
 @functools.lru_cache(None)
 def reference(name, dtype="float64"):
-    _, cam, res = CASES[name]
+    _, cam, res = case(name)
     return PR.view_ref(points(name), CAMERAS[cam], res, oracle_scene(name), np.dtype(dtype).type)
 
 

@@ -3,7 +3,8 @@
 tests/texel_bounce_env_cases.py the float32 reference of the bounced light's adjoint in the environment map, every map texel's terms added
 in ascending and in descending order, against the float64 reference on the same walks and decisions.  No GPU involved.
     python tools/texel_bounce_envgrad_margins.py [--out profiles/texel_bounce_envgrad_margins.txt]
---gpu APPENDS, from a GPU, the kernels' own distance to their bars against the float64 reference on the dump's own walks."""
+--gpu APPENDS, from a GPU, the kernels' own distance to their bars against the float64 reference on the dump's own walks.
+--deep does either for EC.DEEP_CASES (tests/test_gpu_texel_deep_stack.py) and appends to profiles/texel_deep_stack.txt."""
 import argparse
 import os
 import sys
@@ -32,12 +33,15 @@ def kernel_lines(names):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "texel_bounce_envgrad_margins.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--gpu", action="store_true")
+    ap.add_argument("--deep", action="store_true")
     args = ap.parse_args()
-    lines = kernel_lines(list(EC.CASES)) if args.gpu else ER.table_lines()
+    out = args.out or os.path.join(ROOT, "profiles", "texel_deep_stack.txt" if args.deep else "texel_bounce_envgrad_margins.txt")
+    names = list(EC.DEEP_CASES) if args.deep else list(EC.CASES)
+    lines = kernel_lines(names) if args.gpu else ([""] if args.deep else []) + ER.table_lines(names)
     print("\n".join(lines))
-    with open(args.out, "a" if args.gpu else "w") as f:
+    with open(out, "a" if args.gpu or args.deep else "w") as f:
         f.write("\n".join(lines) + "\n")
 
 

@@ -5,7 +5,8 @@ descending order, against the float64 reference on the same walks and decisions.
     python tools/texel_bounce_grad_margins.py [--out profiles/texel_bounce_grad_margins.txt]
 --edges APPENDS the same for BC.EDGE_CASES (tests/test_gpu_texel_bake_edges.py) and, from a GPU, the kernels' own distance to their bars
 against the float64 reference on the dump's own walks; --edges --host-only appends the host table alone, --edges --gpu-only the kernels'
-lines alone."""
+lines alone.
+--deep does what --edges does for BC.DEEP_CASES (tests/test_gpu_texel_deep_stack.py) and appends to profiles/texel_deep_stack.txt."""
 import argparse
 import os
 import sys
@@ -38,20 +39,23 @@ def kernel_lines(names):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "texel_bounce_grad_margins.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--edges", action="store_true")
+    ap.add_argument("--deep", action="store_true")
     ap.add_argument("--host-only", action="store_true")
     ap.add_argument("--gpu-only", action="store_true")
     args = ap.parse_args()
-    if not args.edges:
+    out = args.out or os.path.join(ROOT, "profiles", "texel_deep_stack.txt" if args.deep else "texel_bounce_grad_margins.txt")
+    append = args.edges or args.deep
+    if not append:
         lines = GR.table_lines()
     else:
-        names = list(BC.EDGE_CASES)
+        names = list(BC.DEEP_CASES) if args.deep else list(BC.EDGE_CASES)
         lines = [] if args.gpu_only else [""] + GR.table_lines(names)
         if not args.host_only:
             lines += kernel_lines(names)
     print("\n".join(lines))
-    with open(args.out, "a" if args.edges else "w") as f:
+    with open(out, "a" if append else "w") as f:
         f.write("\n".join(lines) + "\n")
 
 

@@ -5,7 +5,8 @@ walks against the free-running float64 reference — the lines tests/test_gpu_te
 triangles, and the largest |u, v| differences per vertex index.  Recorded, not held to a bar.
     python tools/texel_bounce_margins.py [--out profiles/texel_bounce_margins.txt]
 --edges APPENDS the same for BC.EDGE_CASES (tests/test_gpu_texel_bake_edges.py), with the kernels' own distance to the estimator's bar;
---edges --host-only appends the host table alone, --edges --gpu-only the kernels' lines alone."""
+--edges --host-only appends the host table alone, --edges --gpu-only the kernels' lines alone.
+--deep does what --edges does for BC.DEEP_CASES (tests/test_gpu_texel_deep_stack.py) and appends to profiles/texel_deep_stack.txt."""
 import argparse
 import os
 import sys
@@ -33,23 +34,26 @@ def estimator_line(BG, name, accel):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "texel_bounce_margins.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--edges", action="store_true")
+    ap.add_argument("--deep", action="store_true")
     ap.add_argument("--host-only", action="store_true")
     ap.add_argument("--gpu-only", action="store_true")
     args = ap.parse_args()
-    names = list(BC.EDGE_CASES) if args.edges else list(BC.CASES)
+    names = list(BC.DEEP_CASES) if args.deep else list(BC.EDGE_CASES) if args.edges else list(BC.CASES)
+    out = args.out or os.path.join(ROOT, "profiles", "texel_deep_stack.txt" if args.deep else "texel_bounce_margins.txt")
+    append = args.edges or args.deep
     lines = []
     if not args.gpu_only:
-        lines += ([""] if args.edges else []) + BC.table_lines(names)
+        lines += ([""] if append else []) + BC.table_lines(names)
     if not args.host_only:
         import texel_bounce_gpu as BG
         lines += ["", "the kernels' walks against the free-running float64 reference, on an MI355X: recorded, not held to a bar"]
         lines += ["  " + BG.walk_differences(name, accel)[1] for name in names for accel in BG.ACCELS]
-        if args.edges:
+        if append:
             lines += ["  " + estimator_line(BG, name, accel) for name in names for accel in BG.ACCELS]
     print("\n".join(lines))
-    with open(args.out, "a" if args.edges else "w") as f:
+    with open(out, "a" if append else "w") as f:
         f.write("\n".join(lines) + "\n")
 
 
