@@ -115,7 +115,16 @@ const char *zdr_last_error(void);
  *   inst_xform      ninst x 16 float32  row-major object->world 4x4 (NULL = identity)
  *   inst_emission   ninst x 3 float32   (render.py:85-91; a light is any emission component > 0)
  * zdr_render_forward / zdr_render_backward texture instance 0 only; every other instance is an emitter or a blocker (prb.py:45).
- * To shade several instances, each with a material of its own, see zdr_scene_set_material_slots and zdr_render_*_materials. */
+ * To shade several instances, each with a material of its own, see zdr_scene_set_material_slots and zdr_render_*_materials.
+ * Positions: every WORLD-space position (inst_xform x v, in float32) of a vertex a triangle uses must be finite and at most
+ * ZDR_MAX_COORD = 2^30 in each coordinate's magnitude — the largest power of two for which nothing the host derives from the
+ * positions (plane records, normals, areas, the BVH's boxes and costs) can overflow float32; the derivation is at position_ok in
+ * csrc/zdr_api.cpp.  Otherwise ZDR_E_INVALID, before any device is touched, and zdr_last_error() names the first offending instance
+ * and vertex.  The limit keeps the arithmetic finite, not accurate: the error of a hit distance grows with |position|, that of a
+ * barycentric with |position| / edge length ("Ray queries away from the origin"), so keep scenes near the origin.
+ * A triangle without area (three equal or collinear corners) is legal and is never hit by any ray query; as part of a light it is
+ * not supported. */
+#define ZDR_MAX_COORD 1073741824.0f    /* 2^30 */
 int zdr_scene_create(const float *verts8, uint32_t nverts, const int32_t *tris, uint32_t ntris,
                      const int32_t *inst_tri_begin, const float *inst_xform, const float *inst_emission,
                      uint32_t ninst, int device, int accel, zdr_scene **out);
@@ -1185,7 +1194,8 @@ int zdr_texture_scatter(zdr_scene *scene, int32_t form, const int32_t *dims, uin
  * *stack_entries receives how many of the quads are parallelograms (they come first; the walk tests them in pairs with
  * the first triangle's u, v and 1 - u, 1 - v) (tests/test_brute_quads.py).  (zdr_scene_create additionally orders the
  * primitives WITHIN each of these groups so that those a shadow segment can meet come first — zdr_debug_never_occluders —
- * which needs the lights and is not reproduced here.) */
+ * which needs the lights and is not reproduced here.)  A corner that is not finite or beyond ZDR_MAX_COORD is refused as
+ * zdr_scene_create refuses it: ZDR_E_INVALID, the message names the triangle and which of its three corners. */
 int zdr_debug_build_accel(const float *tri_xyz, uint32_t ntris, int accel, float *nodes_out, uint32_t nodes_cap,
                           uint32_t *nnodes, uint32_t *stack_entries, int32_t *order_out, float *isect_out);
 

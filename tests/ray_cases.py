@@ -27,6 +27,33 @@ no share of the rays is exempt.
                where no margin below 1/2 can change the verdict.  The margin is therefore taken from the pairs with
                |u64|, |v64| <= NEAR = 2, the only ones it can decide, and the host test asserts that the error over ALL pairs
                stays below 1e-3 — far from the 1/2 by which a pair beyond NEAR is outside.
+
+PER-PAIR BOUNDS (Case(..., per_pair=True): the scenes of tests/geometry_cases.py, away from the origin, of mixed scale, transformed).
+Both rules above are rules of thumb for a scene of unit-sized triangles around the origin; the plane form's error follows the RECORD:
+t = (N.w - N.o) / (N.d) cancels numbers of the size |N.w| + sum |N_k o_k|, and u = U.p + U.w numbers of the size |coordinate| / edge.
+In this mode every pair carries bounds of its own, computed in float64 from the float32 record the builder made (pair_bounds); a pair
+is a decided hit / miss when t is outside its bound of (tmin, tmax) and u, v, w are outside theirs, no grazing rule, no share exempt.
+The constants are operation counts of tri_test / pair_test / hit_barycentrics (csrc/accel.h), to first order in g = 2^-24 (the unit
+roundoff of float32, half an ulp; the reference's own error, 2^-53 of the same sums, is a 5e8-th of it):
+  t    |t - t64| <= g (CA (|N.w| + sum |N_k o_k|) + |t64| CD sum |N_k d_k|) / |N.d| + g CM |t64|
+       CA = 4  each N_k: 1 rounding of the float64 record to float32; the term N.x o.x then passes a product and two fma: 3 more (N.y: 2,
+               N.z: 1).  N.w: its rounding to float32, 1.  The subtraction is counted under CM.
+       CD = 4  the same four for N.d.  Where the ray grazes the plane the sum cancels and the error of the denominator is an ulp of
+               sum |N_k d_k|, not of |N.d|: a shorthand "4 |t64|" for the relative part is this term with the ratio sum |N_k d_k| / |N.d| taken as 1,
+               its least value.  A pair with 2 CD g sum |N_k d_k| >= |N.d| has no bound (the sign of the float32 denominator is open).
+       CM = 4  the subtraction N.w - no: 1; v_rcp_f32: one ulp = 2 g; the product with it: 1.
+  u    |u - u64| <= g (C1 (sum |U_k p_k| + |U.w|) + C2 sum |U_k| (|o_k| + 2 |d_k t|)) + |U.d| x the t bound, v likewise
+       C1 = 5  U_k: the record's rounding, 1; U.x p.x then a product, two more terms and the sum with U.w: 4.  (U.w: 2.)
+       C2 = 1  on a sum that already counts p = o + t d both ways: one fma (|p_k| <= |o_k| + |d_k t|) or a product and a sum.
+       the last term: the float32 point is o + t32 d, the float64 one o + t64 d.
+  w    1 - (u + v) (tri_test), or a record of its own (the third edge of the brute-force walk's single triangles, the outer edges of a
+       quad's partner; a rotated slot's u is the input triangle's w): |w - w64| <= Bu + Bv + g (5 + |u + v| + |w|) =: M covers both,
+       and M >= Bu, Bv is the margin all three barycentrics are decided with — it holds for a slot the brute-force builder rotated.
+       A barycentric REPORTED for a rotated slot is 1 - u' - v' of two computed ones: check_closest(rotated=True) allows 2 M + 4 g.
+  quads  the brute-force walk tests the second triangle of a merged quad with the plane of the first (Case.brute_planes): Ref(brute=True)
+       bounds such a pair with the first triangle's N and adds the distance between the two planes, over |n.d|, to its t bound.
+The mirror (mirror32, IEEE division instead of v_rcp_f32, no fma) stays within these on every pair of every case
+(tests/test_geometry_cases_host.py, profiles/geometry_cases_margins.txt); nothing here comes from what a GPU returned.
 """
 import functools
 import os
@@ -46,6 +73,8 @@ T_REL, T_ABS = 1e-5, 5e-6
 C0 = 0.1                       # |n.d| (unit n, unit d) below which a pair counts as grazing
 BARY_MARGIN = 1.9e-5           # 4 x 4.71e-6 measured (profiles/ray_cases_margins.txt), rounded up; test_ray_cases_host.py holds it to the measurement
 NEAR = 2.0                     # the margin is measured on pairs with |u64|, |v64| <= NEAR (see BARY_MARGIN above)
+G32 = 2.0 ** -24                # unit roundoff of float32
+CA, CD, CM, C1, C2 = 4.0, 4.0, 4.0, 5.0, 1.0      # per-pair bounds: the operation counts of the module docstring
 MISS, OPEN, HIT = 0, 1, 2
 FAMILIES = ("axis", "in_plane", "features", "intervals", "tower", "nonfinite")
 
@@ -64,10 +93,13 @@ def tower_arrays(n):
 
 
 class Case:
-    def __init__(self, name, A, accels):
-        self.name, self.A, self.accels = name, A, accels
-        assert (A.inst_xform == np.eye(4, dtype=np.float32).reshape(16)).all()      # world corners = the float32 vertices as they are
-        self.tri = np.ascontiguousarray(A.verts[A.tris][:, :, :3])
+    def __init__(self, name, A, accels, per_pair=False):
+        self.name, self.A, self.accels, self.per_pair = name, A, accels, per_pair
+        if per_pair:               # world corners as the scene holds them: M v in float32, left to right (zdr_api.cpp, xform_point)
+            self.tri = np.ascontiguousarray(emu.world_triangles(A))
+        else:
+            assert (A.inst_xform == np.eye(4, dtype=np.float32).reshape(16)).all()      # world corners = the float32 vertices as they are
+            self.tri = np.ascontiguousarray(A.verts[A.tris][:, :, :3])
         self.t_abs = T_ABS * max(1.0, float(np.abs(self.tri).max()) / 10.0)
         self.lo, self.hi = self.tri.reshape(-1, 3).min(0).astype(np.float64), self.tri.reshape(-1, 3).max(0).astype(np.float64)
         self.tri_inst = np.repeat(np.arange(A.ninst), np.diff(A.inst_tri_begin))
@@ -77,6 +109,31 @@ class Case:
         ip = np.asarray(inst_prim)
         hit = ip[:, 0] >= 0
         return np.where(hit, self.A.inst_tri_begin[np.where(hit, ip[:, 0], 0)] + ip[:, 1], -1)
+
+    @functools.cached_property
+    def rec_in(self):
+        """(T, 12) float64: the builder's float32 plane records {N, U, V} in INPUT triangle order (unrotated corners: the BVH builder's)"""
+        _, order, isect, _ = self.records
+        out = np.empty(isect.shape, np.float64)
+        out[order] = isect
+        return out
+
+    @functools.cached_property
+    def brute_planes(self):
+        """(rec_in with the plane N of a quad's SECOND triangle replaced by the first one's, (T,) how far the second triangle's corners lie
+        off that plane): the brute-force walk tests a quad — two triangles the builder found in one plane to 5e-7 of the quad's size,
+        zdr_api.cpp, find_quads — with ONE plane, so t of the second triangle is the float32 answer for the plane of the first.  Inside the
+        second triangle the two planes are apart by at most the largest distance at its corners (linear in the point): in t that is
+        dev / |n.d|, n the unit normal; it is added to the t bound of these triangles, for the brute-force walk only."""
+        import test_brute_quads as bq
+        nq, order, isect = bq.build(self.tri)
+        rec, dev = self.rec_in.copy(), np.zeros(len(self.tri))
+        for q in range(nq):
+            a, b = order[2 * q], order[2 * q + 1]
+            N = isect[2 * q, 0:4].astype(np.float64)
+            rec[a, 0:4] = rec[b, 0:4] = N
+            dev[b] = np.abs(self.tri[b].astype(np.float64) @ N[:3] - N[3]).max() / np.linalg.norm(N[:3])
+        return rec, dev
 
     @functools.cached_property
     def records(self):
@@ -138,16 +195,48 @@ def any64(tri, rays):
     return k >= 0, pairs
 
 
+def pair_bounds(rec, r, t, u, v, dev=None):
+    """Per-pair error bounds of the plane form (module docstring) -> (Bt, Bu, Bv, M), each (n, T) float64.  rec: (T, 12) float64 holding
+    the float32 records; r: (n, 8) float64 rays; t, u, v: the float64 facts of pairs64; dev: (T,) distance by which the plane of rec
+    is not the triangle's own (Case.brute_planes).  Infinite where nothing can be bounded."""
+    o, d = r[:, None, 0:3], r[:, None, 4:7]
+    N, Nw = rec[None, :, 0:3], np.abs(rec[None, :, 3])
+    with np.errstate(all="ignore"):
+        nd = np.abs((N * d).sum(-1)); snd = np.abs(N * d).sum(-1); sno = np.abs(N * o).sum(-1)
+        at = np.abs(t)
+        Bt = G32 * (CA * (Nw + sno) + at * CD * snd) / nd + G32 * CM * at
+        if dev is not None:
+            Bt = Bt + dev[None, :] * np.sqrt((N * N).sum(-1)) / nd
+        Bt = np.where(2.0 * CD * G32 * snd >= nd, np.inf, Bt)
+        tt = np.where(np.isfinite(t), t, 0.0)[..., None]
+        p = np.abs(o + tt * d); q = np.abs(o) + 2.0 * np.abs(tt * d)
+        out = []
+        for a in (4, 8):
+            U = rec[None, :, a:a + 3]
+            s1 = (np.abs(U) * p).sum(-1) + np.abs(rec[None, :, a + 3]); s2 = (np.abs(U) * q).sum(-1)
+            out.append(G32 * (C1 * s1 + C2 * s2) + np.abs((U * d).sum(-1)) * Bt)
+        Bu, Bv = out
+        M = Bu + Bv + G32 * (5.0 + np.abs(u + v) + np.abs(1.0 - u - v))
+        bad = ~np.isfinite(Bt) | ~np.isfinite(M)
+        Bt, Bu, Bv, M = (np.where(bad, np.inf, x) for x in (Bt, Bu, Bv, M))
+    return Bt, Bu, Bv, M
+
+
 class Ref:
     """The float64 facts of a batch of rays against a scene, pair by pair."""
 
-    def __init__(self, c, rays, margin=None, chunk=256):
+    def __init__(self, c, rays, margin=None, chunk=256, brute=False):
+        """brute (per-pair bounds only): judge the brute-force walk, whose quads test their second triangle with the plane of the first"""
         margin = BARY_MARGIN if margin is None else margin
         rays = np.ascontiguousarray(rays, np.float32)
         n, T = rays.shape[0], c.tri.shape[0]
         self.case, self.rays = c, rays
         self.t = np.empty((n, T)); self.u = np.empty((n, T), np.float32); self.v = np.empty((n, T), np.float32); self.c = np.empty((n, T), np.float32)   # (u, v, c kept in float32: 6e-8 of a barycentric, against a margin of 2e-5)
         self.state = np.empty((n, T), np.int8)
+        if c.per_pair:
+            self.B, self.bu, self.bv, self.m = (np.empty((n, T), np.float32) for _ in range(4))     # (kept in float32, rounded UP: a bound may only grow)
+            rec, dev = c.brute_planes if brute else (c.rec_in, None)
+            flat =(rec[:, 0:3] == 0).all(1)                     # a zero-area triangle: N = 0, t = 0 x inf = NaN, never hit
         for a in range(0, n, chunk):
             r = rays[a:a + chunk].astype(np.float64)
             t, u, v, nd = pairs64(c.tri, r)
@@ -156,16 +245,27 @@ class Ref:
                 cc = np.abs(nd) / np.sqrt((r[:, 4:7] ** 2).sum(1))[:, None]
                 k = np.where(cc < C0, C0 / cc, 1.0)                      # grazing pairs: both margins grow with 1 / |n.d|
                 inside = np.minimum(np.minimum(u, v), 1.0 - u - v)
-                B = (T_REL * np.abs(t) + c.t_abs) * k
-                mb = margin * k
-                hit = (nd != 0) & (inside > mb) & (t - tmin > B) & (tmax - t > B)
-                miss = (nd == 0) | (inside < -mb) | (t < tmin - B) | (t > tmax + B)
+                if c.per_pair:
+                    B, Bu, Bv, mb = pair_bounds(rec, r, t, u, v, dev)
+                    up = lambda x: np.nextafter(x.astype(np.float32), np.float32(np.inf))
+                    s = slice(a, a + chunk)
+                    self.B[s], self.bu[s], self.bv[s], self.m[s] = up(B), up(Bu), up(Bv), up(mb)
+                    zero = flat[None, :] | ((rec[None, :, 0:3] * r[:, None, 4:7]) == 0).all(-1)      # every product of N.d exactly zero: t is infinite or NaN
+                    hit = ~zero & (inside > mb) & (t - tmin > B) & (tmax - t > B)
+                    miss = zero | (inside < -mb) | (t < tmin - B) | (t > tmax + B)
+                else:
+                    B = (T_REL * np.abs(t) + c.t_abs) * k
+                    mb = margin * k
+                    hit = (nd != 0) & (inside > mb) & (t - tmin > B) & (tmax - t > B)
+                    miss = (nd == 0) | (inside < -mb) | (t < tmin - B) | (t > tmax + B)
             dead = ~np.isfinite(r[:, 0:3]).all(1) | ~np.isfinite(r[:, 4:7]).all(1) | (r[:, 4:7] == 0).all(1) | ~(r[:, 3] < r[:, 7])
             miss |= dead[:, None]                     # a ray of NaNs or infinities, without a direction or with an empty interval hits nothing
             st = np.where(miss, MISS, np.where(hit, HIT, OPEN)).astype(np.int8)
             s = slice(a, a + chunk)
             self.t[s], self.u[s], self.v[s], self.c[s], self.state[s] = t, u, v, cc, st
         self.dec_t = np.where(self.state == HIT, self.t, np.inf).min(1)          # the nearest decided hit
+        if c.per_pair:                                                           # ... and the largest float32 t the nearest decided hit may come out with
+            self.dec_hi = np.where(self.state == HIT, self.t + self.B, np.inf).min(1)
         live_t = np.where(self.state != MISS, self.t, np.inf)
         first = live_t.argmin(1)
         rows = np.arange(n)
@@ -174,9 +274,10 @@ class Ref:
         self.decided_hit = (self.state[rows, first] == HIT) & ~self.decided_miss   # the nearest pair that is not a miss is a decided hit
         self.grazing = ((self.c < C0) & (self.state != MISS)).any(1)               # a grazing pair that may count: the ray is not kept
 
-    def check_closest(self, tri_idx, t, uv=None, rows=None):
+    def check_closest(self, tri_idx, t, uv=None, rows=None, rotated=False):
         """-> [(answer, reason, ray)] for the answers that a decided fact contradicts.  rows: the ray of this Ref each answer belongs to
-        (default: answer i to ray i)."""
+        (default: answer i to ray i).  rotated (per-pair bounds only): the barycentrics come from slots the brute-force builder may have
+        rotated (module docstring)."""
         tri_idx = np.asarray(tri_idx); t = np.asarray(t, np.float64)
         rows = np.arange(self.rays.shape[0]) if rows is None else np.asarray(rows)
         assert len(tri_idx) == len(t) == len(rows)
@@ -184,15 +285,23 @@ class Ref:
         st, t64, dec = self.state[rows, k], self.t[rows, k], self.dec_t[rows]
         u64, v64 = self.u[rows, k], self.v[rows, k]
         with np.errstate(all="ignore"):
-            b = T_REL * np.abs(t64) + self.case.t_abs
+            if self.case.per_pair:
+                b = self.B[rows, k].astype(np.float64)
+                m2 = 2.0 * self.m[rows, k].astype(np.float64) + 4.0 * G32
+                bu, bv = (m2, m2) if rotated else (self.bu[rows, k], self.bv[rows, k])
+                nearer = self.dec_hi[rows] < t64 - b
+            else:
+                b = T_REL * np.abs(t64) + self.case.t_abs
+                bu = bv = BARY_MARGIN
+                nearer = dec < t64 - b
             hit = tri_idx >= 0
             why = np.zeros(len(t), np.int8)
             why[~hit & np.isfinite(dec)] = 1
             why[hit & (why == 0) & (st == MISS)] = 2
             why[hit & (why == 0) & ~(np.abs(t - t64) <= b)] = 3
-            why[hit & (why == 0) & (dec < t64 - b)] = 4
+            why[hit & (why == 0) & nearer] = 4
             if uv is not None:
-                why[hit & (why == 0) & (st == HIT) & ~((np.abs(uv[:, 0] - u64) <= BARY_MARGIN) & (np.abs(uv[:, 1] - v64) <= BARY_MARGIN))] = 5
+                why[hit & (why == 0) & (st == HIT) & ~((np.abs(uv[:, 0] - u64) <= bu) & (np.abs(uv[:, 1] - v64) <= bv))] = 5
         text = {1: "miss, but a triangle is hit for certain at t = {dec:.9g}",
                 2: "hit on triangle {k}, which is missed for certain (t64 {t64:.9g}, u {u:.3g}, v {v:.3g})",
                 3: "t = {t:.9g} on triangle {k}, float64 {t64:.9g}: off by more than {b:.3g}",
@@ -211,7 +320,7 @@ class Ref:
     def take(self, keep):
         r = object.__new__(Ref)
         r.case = self.case
-        for name in ("rays", "t", "u", "v", "c", "state", "dec_t", "has_open", "decided_miss", "decided_hit", "grazing"):
+        for name in ("rays", "t", "u", "v", "c", "state", "dec_t", "has_open", "decided_miss", "decided_hit", "grazing") + (("B", "bu", "bv", "m", "dec_hi") if self.case.per_pair else ()):
             setattr(r, name, getattr(self, name)[keep])
         return r
 

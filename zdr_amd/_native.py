@@ -29,6 +29,7 @@ SAMPLER_CMJ, SAMPLER_PMJ02BN = 0, 1
 ACCEL_AUTO, ACCEL_BRUTE, ACCEL_BVH = 0, 1, 2
 ABI_VERSION = 4                # ZDR_ABI_VERSION of the include/zdr.h this binding mirrors
 MAX_MATERIALS = 16             # ZDR_MAX_MATERIALS
+MAX_COORD = 2.0 ** 30          # ZDR_MAX_COORD: the largest magnitude of a world-space coordinate zdr_scene_create accepts
 AOV_CHANNELS = 16              # ZDR_AOV_CHANNELS
 DENOISE_MAX_LEVELS = 6         # ZDR_DENOISE_MAX_LEVELS
 PRB_MODES = {"expectation": 0, "detached": 1, "literal": 2}

@@ -796,6 +796,27 @@ static int upload_scene(zdr_scene *s, const SceneBuild &B) {
     return upload_light_table(s, lights, light_count, nullptr);
 }
 
+// ---- the caller's mesh: every world-space position finite and no larger than ZDR_MAX_COORD (include/zdr.h) = 2^30.
+// Why 2^30: the largest power of two L for which nothing the host derives from positions |x|, |y|, |z| <= L can overflow float32
+// (FLT_MAX = 2^128 (1 - 2^-24)); an edge component is at most 2 L.
+//   plane_record     n = e1 x e2: |n_k| <= 2 (2 L)^2 = 8 L^2;  |N.w| = |n . p0| = |det(p0, p1, p2)| <= (sqrt(3) L)^3 = 5.2 L^3 (Hadamard):
+//                    finite up to L = 2^41.  |U| = 1 / (the triangle's height) and U.w = -U . p0 follow the triangle's shape, not L:
+//                    a triangle without area has them infinite or NaN at any L, and is never hit (N = 0).
+//   build_accel      diag^2 <= 3 (2 L)^2 = 12 L^2: up to 2^62.  SAH cost = area x count <= 24 L^2 x 2^25: up to 2^49.
+//   world_records    the FLOAT32 cross product c of two edges, |c_k| <= 8 L^2, and c . c <= 192 L^4 for the area and the geometric
+//                    normal: 192 x 2^120 = 1.5 x 2^127 is finite, 192 x 2^124 is not.  This is the one that binds: L = 2^30.
+// (A soup scaled by 1e15 built, and then lost every ray to N.w = inf; a coordinate of 1e30 ended in "BVH box quantisation is not
+// conservative"; a NaN went through unnoticed.)
+static bool position_ok(h3 p) {
+    return std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z) && fabsf(p.x) <= ZDR_MAX_COORD && fabsf(p.y) <= ZDR_MAX_COORD && fabsf(p.z) <= ZDR_MAX_COORD;
+}
+static int bad_position(h3 p, const std::string &who) {       // ZDR_E_INVALID, the message names whose position it is
+    char buf[160];
+    snprintf(buf, sizeof buf, ": world-space position (%g, %g, %g) %s", (double)p.x, (double)p.y, (double)p.z,
+             std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z) ? "exceeds ZDR_MAX_COORD = 2^30 in magnitude" : "is not finite");
+    return fail(ZDR_E_INVALID, who + buf);
+}
+
 extern "C" int zdr_scene_create(const float *verts8, uint32_t nverts, const int32_t *tris, uint32_t ntris,
                                 const int32_t *inst_tri_begin, const float *inst_xform, const float *inst_emission,
                                 uint32_t ninst, int device, int accel, zdr_scene **out) {
@@ -806,6 +827,16 @@ extern "C" int zdr_scene_create(const float *verts8, uint32_t nverts, const int3
     if (inst_tri_begin[0] != 0 || (uint32_t)inst_tri_begin[ninst] != ntris) return fail(ZDR_E_INVALID, "inst_tri_begin must span [0, ntris]");
     for (uint32_t i = 0; i < ninst; i++) if (inst_tri_begin[i + 1] < inst_tri_begin[i]) return fail(ZDR_E_INVALID, "inst_tri_begin must be non-decreasing");
     for (size_t i = 0; i < (size_t)ntris * 3; i++) if (tris[i] < 0 || (uint32_t)tris[i] >= nverts) return fail(ZDR_E_INVALID, "triangle index out of range");
+    for (uint32_t i = 0; i < ninst; i++) {          // the positions as world_records will make them, before any device is touched
+        static const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        const float *m = inst_xform ? inst_xform + 16 * (size_t)i : ident;
+        for (size_t c = 3 * (size_t)inst_tri_begin[i]; c < 3 * (size_t)inst_tri_begin[i + 1]; c++) {
+            const float *v = verts8 + 8 * (size_t)tris[c];
+            const h3 p = xform_point(m, H3(v[0], v[1], v[2]));
+            if (position_ok(p)) continue;
+            return bad_position(p, "instance " + std::to_string(i) + ", vertex " + std::to_string(tris[c]) + " (triangle " + std::to_string(c / 3 - (size_t)inst_tri_begin[i]) + " of the instance)");
+        }
+    }
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(ZDR_E_INVALID, "no such HIP device");
@@ -830,6 +861,8 @@ extern "C" int zdr_debug_build_accel(const float *tri_xyz, uint32_t ntris, int a
                                      uint32_t *nnodes, uint32_t *stack_entries, int32_t *order_out, float *isect_out) {
     if (!tri_xyz || !ntris || !nnodes || !order_out || !isect_out) return fail(ZDR_E_INVALID, "null argument");
     const std::vector<h3> pos = triangle_corners(tri_xyz, ntris, 3, 9);
+    for (size_t c = 0; c < pos.size(); c++)          // as zdr_scene_create refuses them (no instances here: the triangle and its corner)
+        if (!position_ok(pos[c])) return bad_position(pos[c], "triangle " + std::to_string(c / 3) + ", vertex " + std::to_string(c % 3));
     std::vector<int> order; std::vector<float4> nodes; uint32_t nn = 0, depth = 0, se = 8;
     const bool use_bvh = wants_bvh(accel, ntris);
     int rc = build_accel(pos, ntris, use_bvh, order, nodes, nn, depth, se); if (rc) return rc;
